@@ -9,6 +9,12 @@ shape with random-init weights. For N>1 it runs one rank per GPU: either under
 ranks itself (``self_launch``). W untimed warmup steps, then EXACTLY K timed steps between a
 barrier + device sync on both sides; the per-rank time is MAX-reduced over ranks and
 rank 0 prints one JSON line. ``value`` = N * batch * K / max_time (weak scaling).
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last step computed (losses,
+updated parameters and BN state, generated batch, logits) as ``DIR/<name>.npy``; with the same
+arguments the inputs (seeded images, weights, z) are the same from run to run, so two builds
+can be compared output for output. ``--full`` is accepted and adds nothing: the plain run is
+already only set-up, warm-up, the timed steps and the result line.
 """
 from __future__ import annotations
 
@@ -40,7 +46,66 @@ def parse():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--force_ddp", action="store_true",
                    help="run the data-parallel step (process group + RCCL collectives) even at N=1")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last step computed as DIR/<name>.npy")
+    # a plain run already does only what the headline figure needs (set up, warm up, time the
+    # steps, print the line); every other measurement of the project is a tool of its own under
+    # benchmarks/, so --full has nothing further to switch on
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's secondary measurements (none: accepted, changes nothing)")
     return p.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much array data in all
+
+
+def step_outputs(eng):
+    """What a caller of ``train_step()`` holds after the last step, as named tensors: the four
+    losses, the updated fp32 parameters and BN moving averages of both networks, and (HIP engine)
+    the generated batch and D's logits on [real | fake]."""
+    from collections import OrderedDict
+    losses = eng.last_losses()
+    out = OrderedDict()
+    out["losses"] = torch.tensor([losses[k] for k in ("d_loss_real", "d_loss_fake", "g_loss", "d_loss")],
+                                 dtype=torch.float64)
+    out["g_params"] = eng.model.g.flat
+    out["d_params"] = eng.model.d.flat
+    out["g_bn_state"] = eng.model.g_bn.flat
+    out["d_bn_state"] = eng.model.d_bn.flat
+    for name, attr in (("generated", "fake"), ("logits", "logits")):
+        t = getattr(eng, attr, None)
+        if torch.is_tensor(t):
+            out[name] = t
+    return out
+
+
+def dump_outputs(eng, out_dir: str, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """Write ``step_outputs`` as ``out_dir/<name>.npy`` (float32; the losses float64). When the
+    arrays exceed ``budget`` bytes in all, the largest are cut to a common element count and
+    written as a fixed sample (sorted indices drawn without replacement from a generator seeded
+    with 0, so two builds sample the same elements); smaller arrays are written whole."""
+    import numpy as np
+    arrays = []
+    for name, t in step_outputs(eng).items():
+        t = t.detach().reshape(-1).cpu()
+        arrays.append((name, t.numpy() if t.dtype == torch.float64 else t.to(torch.float32).numpy()))
+    # water-filling: the largest cap (bytes per array) under which the total fits the budget
+    sizes = sorted(a.nbytes for _, a in arrays)
+    cap, left = max(sizes), budget
+    if sum(sizes) > budget:
+        for i, s in enumerate(sizes):
+            share = left // (len(sizes) - i)
+            if s > share:
+                cap = share
+                break
+            left -= s
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays:
+        if a.nbytes > cap:
+            keep = cap // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def self_launch(args) -> int:
@@ -115,6 +180,11 @@ def main():
     dt = time.perf_counter() - t0
     dt = D.max_over_ranks(dt, device)
     losses = eng.last_losses()
+    if args.dump_outputs:
+        if hasattr(eng, "gather_sharded_state"):
+            eng.gather_sharded_state()  # collective; a no-op unless the updates were sharded over ranks
+        if rank == 0:
+            dump_outputs(eng, args.dump_outputs)
     # self-verifying multi-GPU record: which backend the process group used, how many ranks it
     # saw, and every rank's HIP device (all-gathered), so "RCCL saw N distinct GPUs" is checkable
     backend, world_seen, devices = "none", 1, [torch.cuda.current_device() if device.type == "cuda" else -1]
