@@ -34,7 +34,8 @@ def main():
     dev = torch.device("cuda", 0)
     cfg = DCGANConfig(output_size=a.output_size, c_dim=a.c_dim)
     for B in [int(s) for s in a.sizes.split(",") if s]:
-        eng = HipEngine(cfg, B, dev, graph=False, dtype=a.dtype)
+        # (no weight EMA: its sampler is the same Program over the shadow buffers, same launches)
+        eng = HipEngine(cfg, B, dev, graph=False, dtype=a.dtype, g_ema_decay=0.0)
         real = torch.rand(B, cfg.output_size, cfg.output_size, cfg.c_dim, device=dev) * 2 - 1
         eng.set_synthetic_batch(real)
         for _ in range(3):  # populate the BN moving averages

@@ -889,6 +889,17 @@ class Program {
     }, AccList().r(x, (size_t)B * Hi * Wi * C * es_).r(w, (size_t)25 * N * C * es_).r(bias, (size_t)N * 4)
            .w(y, (size_t)B * Ho * Wo * N * es_).v);
   }
+  // generator weight EMA (ema_kernel): s -= (1 - d_t) (s - w), d_t from the device step counter
+  // (+ step_bias); sbf = optional elem_t mirror of s; ls = fp16 loss-scale state (skip on overflow)
+  int ema(std::string name, uintptr_t s, uintptr_t sbf, uintptr_t w, size_t n, float decay, uintptr_t step,
+          int step_bias, uintptr_t ls, int stream) {
+    if (!(decay >= 0.f && decay < 1.f)) throw std::runtime_error("ema: decay must be in [0, 1)");
+    if (!s || !w || !step) throw std::runtime_error("ema: s, w and step must be non-null");
+    return add(name, stream, [=](hipStream_t st) {
+      return KF(dcg_ema)(P<float>(s), P<elem_t>(sbf), P<const float>(w), n, decay, P<const unsigned long long>(step),
+                         step_bias, P<const float>(ls), st);
+    }, AccList().w(s, n * 4).w(sbf, n * es_).r(w, n * 4).r(step, 8).r(ls, 12).v);
+  }
   // dynamic loss scaling: flag ls[1] if any gradient is non-finite
   int nonfinite_check(std::string name, uintptr_t g, size_t n, uintptr_t ls, int stream) {
     return add(name, stream, [=](hipStream_t s) { return KF(dcg_nonfinite_check)(P<const float>(g), n, P<float>(ls), s); },
@@ -1018,6 +1029,7 @@ PYBIND11_MODULE(_dcgan_hip, m) {
   m.def("wgrad_tile", &wgrad_tile);
   m.def("device_arch", &device_arch);
   m.attr("built_for") = "gfx950";
+  m.attr("EMA_MAX_BLOCKS") = (unsigned)dcg::EMA_MAX_BLOCKS;
   m.attr("OP_LAUNCH") = (int)OP_LAUNCH;
   m.attr("OP_RECORD") = (int)OP_RECORD;
   m.attr("OP_WAIT") = (int)OP_WAIT;
@@ -1098,6 +1110,8 @@ PYBIND11_MODULE(_dcgan_hip, m) {
            py::arg("b2d"), py::arg("b1g"), py::arg("b2g"), py::arg("step"), py::arg("stream"), py::arg("ls") = 0,
            py::arg("growth_interval") = 2000)
       .def("adam2", &Program::adam2)
+      .def("ema", &Program::ema, py::arg("name"), py::arg("s"), py::arg("sbf"), py::arg("w"), py::arg("n"),
+           py::arg("decay"), py::arg("step"), py::arg("step_bias"), py::arg("ls"), py::arg("stream"))
       .def("nonfinite_check", &Program::nonfinite_check)
       .def("narrow_deconv", &Program::narrow_deconv)
       .def("nconv", &Program::nconv)

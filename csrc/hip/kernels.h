@@ -88,6 +88,10 @@ struct WGrad3Args {                 // wgrad3.hip: 25-tap gather GEMM, in-kernel
   int lhw, lw;                         // log2(Hd*Wd), log2(Wd) when both are powers of two, else -1
 };
 
+// grid cap of the streaming generator-EMA kernel (misc.hip ema_kernel): 256 CUs x 8 resident
+// workgroups; larger buffers grid-stride
+constexpr unsigned EMA_MAX_BLOCKS = 2048;
+
 }  // namespace dcg
 
 extern "C" {

@@ -51,6 +51,8 @@ int DCG_API(dcg_adam)(float* w, elem_t* wbf, const float* g, float* m, float* v,
                      const void* g_bf16, hipStream_t s);
 int DCG_API(dcg_step_end)(float* pd, float* pg, float b1d, float b2d, float b1g, float b2g,
                           unsigned long long* step, float* ls, int growth_interval, hipStream_t s);
+int DCG_API(dcg_ema)(float* s, elem_t* sbf, const float* w, size_t n, float decay, const unsigned long long* step,
+                     int step_bias, const float* ls, hipStream_t st);
 int DCG_API(dcg_nonfinite_check)(const float* g, size_t n, float* ls, hipStream_t s);
 int DCG_API(dcg_pack)(const float* src, int T, int A, int Bd, elem_t* nat, elem_t* tr, int st, int sb, int sa, hipStream_t s);
 int DCG_API(dcg_philox_uniform)(float* out, size_t n, uint64_t seed, const unsigned long long* step, uint64_t stream_id,

@@ -651,6 +651,39 @@ __global__ void step_end_kernel(float* __restrict__ pd, float* __restrict__ pg, 
   }
 }
 
+// ---------------------------------------------------------------- generator weight EMA
+// tf.train.ExponentialMovingAverage(decay, num_updates = global step): after Adam(G) wrote w,
+//   d_t = min(decay, (1 + t) / (10 + t)),  s -= (1 - d_t) * (s - w)   (one fma),
+// t = step[0] + step_bias read on the device (graph replays see the live counter; step_bias = 1
+// where the counter is advanced by a later launch). sbf (optional): elem_t mirror of s in the
+// same flat layout, the copy the sampler's conv kernels read. ls: fp16 dynamic loss scaling --
+// an overflowed step leaves s and its mirror untouched, as Adam leaves the weights.
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ s, elem_t* __restrict__ sbf,
+                                                  const float* __restrict__ w, size_t n, float decay,
+                                                  const unsigned long long* __restrict__ step, int step_bias,
+                                                  const float* __restrict__ ls) {
+  if (ls && ls[1] != 0.f) return;
+  const float t = (float)(step[0] + (unsigned long long)step_bias);
+  const float c = -(1.f - fminf(decay, (1.f + t) / (10.f + t)));
+  const size_t n4 = n / 4;
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    f32x4 sv = reinterpret_cast<f32x4*>(s)[i];
+    const f32x4 wv = reinterpret_cast<const f32x4*>(w)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sv[k] = __builtin_fmaf(c, sv[k] - wv[k], sv[k]);
+    reinterpret_cast<f32x4*>(s)[i] = sv;
+    if (sbf) {
+      const elem4 o = {(elem_t)sv[0], (elem_t)sv[1], (elem_t)sv[2], (elem_t)sv[3]};
+      reinterpret_cast<elem4*>(sbf)[i] = o;
+    }
+  }
+  for (size_t i = n4 * 4 + blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float sv = __builtin_fmaf(c, s[i] - w[i], s[i]);
+    s[i] = sv;
+    if (sbf) sbf[i] = (elem_t)sv;
+  }
+}
+
 // overflow detection for dynamic loss scaling: any non-finite gradient sets ls[1]
 __global__ __launch_bounds__(256) void nonfinite_check_kernel(const float* __restrict__ g, size_t n,
                                                               float* __restrict__ ls) {
@@ -909,6 +942,14 @@ extern "C" int DCG_API(dcg_step_end)(float* pd, float* pg, float b1d, float b2d,
                                       unsigned long long* step, float* ls, int growth_interval, hipStream_t s) {
   hipLaunchKernelGGL(step_end_kernel, dim3(1), dim3(64), 0, s, pd, pg, b1d, b2d, b1g, b2g, step, ls,
                      growth_interval);
+  return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_ema)(float* s, elem_t* sbf, const float* w, size_t n, float decay,
+                                 const unsigned long long* step, int step_bias, const float* ls, hipStream_t st) {
+  size_t b = (n / 4 + 255) / 256;  // memory-bound: one float4 per thread, capped grid, grid-stride the rest
+  if (b > EMA_MAX_BLOCKS) b = EMA_MAX_BLOCKS;
+  hipLaunchKernelGGL(ema_kernel, dim3((unsigned)(b ? b : 1)), dim3(256), 0, st, s, sbf, w, n, decay, step, step_bias, ls);
   return (int)hipGetLastError();
 }
 

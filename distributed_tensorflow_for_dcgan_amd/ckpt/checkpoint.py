@@ -84,6 +84,9 @@ def latest_checkpoint(ckpt_dir: str) -> Optional[str]:
 BN_STEPS_KEYS = ("g_bn/ExponentialMovingAverage/local_step", "d_bn/ExponentialMovingAverage/local_step")
 
 
+G_EMA_SUFFIX = "/ExponentialMovingAverage"  # shadow of a G variable (never a BN ".../moments/..." key)
+
+
 def collect_state(engine) -> "OrderedDict[str, np.ndarray]":
     """TF-named numpy tensors of everything a resume needs."""
     engine.sync_state_for_checkpoint()
@@ -106,6 +109,10 @@ def collect_state(engine) -> "OrderedDict[str, np.ndarray]":
         for k, v in opt.tf_slot_tensors().items():
             a = v.detach().cpu().numpy().astype(np.float32)
             out[k] = a.reshape(()) if k.startswith("beta") else a
+    ema = getattr(engine, "g_ema", None)
+    if ema is not None:  # tf.train.ExponentialMovingAverage shadow names
+        for k, v in ema.tensors.items():
+            out[k + G_EMA_SUFFIX] = v.detach().cpu().numpy().astype(np.float32)
     return out
 
 
@@ -133,6 +140,18 @@ def apply_state(engine, sd: Dict[str, np.ndarray], strict: bool = True) -> Dict[
     if "Variable" in tsd:
         engine.global_step = int(np.asarray(sd["Variable"]).reshape(-1)[0])
     info["global_step"] = int(engine.global_step)
+    ema = getattr(engine, "g_ema", None)
+    if ema is not None:
+        # the moving average of G's weights: the saved shadows when all are there, else it
+        # restarts from the loaded weights (a checkpoint written with the average off)
+        keys = {k: k + G_EMA_SUFFIX for k in ema.tensors}
+        with torch.no_grad():
+            if all(v in tsd for v in keys.values()):
+                ema.load_state_dict({k: tsd[v] for k, v in keys.items()})
+                info["g_ema"] = "loaded"
+            else:
+                ema.flat.copy_(m.g.flat)
+                info["g_ema"] = "initialised from the loaded weights (the checkpoint has no shadow variables)"
     if hasattr(engine, "after_state_load"):
         engine.after_state_load()
     return info

@@ -7,6 +7,7 @@ Both expose the same small interface used by the trainer and ``bench.py``:
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
@@ -25,7 +26,7 @@ class ReferenceEngine:
 
     def __init__(self, cfg: DCGANConfig, batch_size: int, device: torch.device, seed: int = 0,
                  lr: float = 2e-4, beta1: float = 0.5, zero_debias: bool = False, rank: int = 0,
-                 world: int = 1, z_seed: Optional[int] = None, **_):
+                 world: int = 1, z_seed: Optional[int] = None, g_ema_decay: Optional[float] = None, **_):
         self.cfg = cfg
         self.batch_size = batch_size
         self.device = device
@@ -34,7 +35,11 @@ class ReferenceEngine:
         if world > 1:
             D.broadcast_tensors([self.model.g.flat, self.model.d.flat, self.model.g_bn.flat,
                                  self.model.d_bn.flat])
-        self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None)
+        if g_ema_decay is None:  # (the HIP engine's switch, so both engines follow one environment)
+            g_ema_decay = float(os.environ.get("DCGAN_G_EMA_DECAY") or 0.0)
+        self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None,
+                                       g_ema_decay=g_ema_decay)
+        self.g_ema_decay = self.step_impl.g_ema_decay
         self.opt_d, self.opt_g = self.step_impl.opt_d, self.step_impl.opt_g
         self.z_gen = torch.Generator(device=device if device.type == "cuda" else "cpu")
         self.z_gen.manual_seed((z_seed if z_seed is not None else seed) + 7919 * rank + 1)
@@ -92,8 +97,13 @@ class ReferenceEngine:
     def last_losses(self) -> Dict[str, float]:
         return dict(self._losses)
 
-    def sampler(self, z: torch.Tensor) -> torch.Tensor:
-        return self.model.sampler(z.to(self.device))
+    @property
+    def g_ema(self):
+        """Moving average of G's weights (a ParamSet laid out like model.g), None when off."""
+        return self.model.g_ema
+
+    def sampler(self, z: torch.Tensor, ema: Optional[bool] = None) -> torch.Tensor:
+        return self.model.sampler(z.to(self.device), ema=ema)
 
     def eval_losses(self, real: torch.Tensor, z: torch.Tensor) -> Dict[str, float]:
         """Sample-time d_loss/g_loss (image_train.py:181-184) without mutating BN EMAs."""
@@ -116,15 +126,15 @@ class ReferenceEngine:
 def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine: str = "auto",
                  dtype: str = "bf16", seed: int = 0, rank: int = 0, world: int = 1, graph: bool = True,
                  allreduce_dtype: str = "fp32", lr: float = 2e-4, beta1: float = 0.5,
-                 zero_debias: bool = False, bucket_mb: float = 32.0):
+                 zero_debias: bool = False, bucket_mb: float = 32.0, g_ema_decay: Optional[float] = None):
     if engine == "auto":  # every dtype (bf16 / fp16 / fp32) runs on the HIP kernels on an MI355X
         engine = "hip" if device.type == "cuda" else "reference"
     if engine == "reference":
         return ReferenceEngine(cfg, batch_size, device, seed=seed, lr=lr, beta1=beta1,
-                               zero_debias=zero_debias, rank=rank, world=world)
+                               zero_debias=zero_debias, rank=rank, world=world, g_ema_decay=g_ema_decay)
     if engine == "hip":
         from .hip_engine import HipEngine
         return HipEngine(cfg, batch_size, device, dtype=dtype, seed=seed, lr=lr, beta1=beta1,
                          zero_debias=zero_debias, rank=rank, world=world, graph=graph,
-                         allreduce_dtype=allreduce_dtype, bucket_mb=bucket_mb)
+                         allreduce_dtype=allreduce_dtype, bucket_mb=bucket_mb, g_ema_decay=g_ema_decay)
     raise ValueError("unknown engine %r" % engine)

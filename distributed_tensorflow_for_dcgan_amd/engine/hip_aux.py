@@ -6,7 +6,7 @@ of it runs inside the training step."""
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 
@@ -74,29 +74,41 @@ class HipEngineAux:
         return OrderedDict(zip(self._sum_names, rows))
 
     # ------------------------------------------------------------------ sampling / eval
-    def sampler(self, z: torch.Tensor) -> torch.Tensor:
+    def sampler(self, z: torch.Tensor, ema: Optional[bool] = None) -> torch.Tensor:
         """G with inference-mode BN (moving averages) -- distriubted_model.py:131-153. With
         --bn_zero_debias the moving averages are divided by 1 - decay^t (t = EMA updates so far,
-        as in the reference engine's BNState.averages)."""
-        if self.progS is None:
-            self._build_sampler()
+        as in the reference engine's BNState.averages). ema: sample from the moving average of G's
+        weights (``g_ema_decay`` > 0) instead of the last iterate; None = the average when kept."""
+        use_ema = self.g_ema is not None if ema is None else bool(ema)
+        if use_ema and self.g_ema is None:
+            raise ValueError("sampler(ema=True) needs an engine built with g_ema_decay > 0")
+        if use_ema:
+            if self.progS_ema is None:
+                self.progS_ema, self._s_out_ema = self._build_sampler(self.g_ema, self.wbf_g_ema)
+            prog, out = self.progS_ema, self._s_out_ema
+        else:
+            if self.progS is None:
+                self.progS, self._s_out = self._build_sampler(self.model.g, self.wbf_g)
+            prog, out = self.progS, self._s_out
         bn = self.model.g_bn
         t = float(bn.steps[0])
         corr = 1.0 - bn.decay ** t if (bn.zero_debias and t > 0) else 1.0
         self._debias.fill_(1.0 / corr)
         self.sample_z.copy_(z.to(self.device, torch.float32))
-        H.run(self.progS)
-        return self._s_out.float().clone()
+        H.run(prog)
+        return out.float().clone()
 
-    def _build_sampler(self):
+    def _build_sampler(self, Pg, Wg):
+        """Sampler program over the fp32 parameter views Pg (projection, biases, BN scale / offset)
+        and the conv kernels Wg the GEMMs read (16-bit mirror; fp32: Pg itself) -- G's weights, or
+        their moving average. The BN moving averages and the debias scalar are shared."""
         cfg, B = self.cfg, self.B
         prog = self._prog()
-        Pg = self.model.g
         t = self._t
         h0p, h0 = t(B, cfg.g_lin_out), t(B, cfg.g_lin_out)
-        self._s_out = t(B, cfg.output_size, cfg.output_size, cfg.c_dim)
+        s_out = t(B, cfg.output_size, cfg.output_size, cfg.c_dim)
         sc = {name: (t(C, dtype=torch.float32), t(C, dtype=torch.float32)) for name, C in cfg.g_bn_layers()}
-        self._s_keep = [h0p, h0, sc]
+        keep = [h0p, h0, sc]
         bnst = self.model.g_bn
         prog.linear_fwd("s.lin", _p(self.sample_z), _p(Pg["g_h0_lin/Matrix"]), _p(Pg["g_h0_lin/bias"]), _p(h0p), B,
                         cfg.z_dim, cfg.g_lin_out, 0)
@@ -112,11 +124,11 @@ class HipEngineAux:
                           B * cfg.g_base_hw ** 2, C0, B * cfg.g_base_hw ** 2, RELU, 0.0, 0)
         prev = h0
         for L in self.gl:
-            nat = self.wbf_g[L.name + "/w"]
+            nat = Wg[L.name + "/w"]
             pad = same_pads(L.out_hw)[0]
             if L.bn:
                 xb, ab = t(B, L.out_hw, L.out_hw, L.cout), t(B, L.out_hw, L.out_hw, L.cout)
-                self._s_keep += [xb, ab]
+                keep += [xb, ab]
                 self._igemm(prog, "s." + L.name, 1, prev, nat, xb, B, L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw,
                             L.cout, pad, bias=Pg[L.name + "/biases"])
                 coef(L.bn, L.cout)
@@ -125,8 +137,9 @@ class HipEngineAux:
                                   RELU, 0.0, 0)
                 prev = ab
             else:
-                self._deconv_out(prog, "s." + L.name, prev, nat, self._s_out, B, L, pad, Pg[L.name + "/biases"], TANH)
-        self.progS = prog
+                self._deconv_out(prog, "s." + L.name, prev, nat, s_out, B, L, pad, Pg[L.name + "/biases"], TANH)
+        self._s_keep = getattr(self, "_s_keep", []) + keep
+        return prog, s_out
 
     def eval_losses(self, real: torch.Tensor, z: torch.Tensor) -> Dict[str, float]:
         """Sample-time d_loss / g_loss (image_train.py:181-184) in train-mode BN but WITHOUT

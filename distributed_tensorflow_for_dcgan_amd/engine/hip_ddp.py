@@ -153,7 +153,7 @@ class HipDDPMixin:
         updates, where each rank's conv-kernel masters are current only on its shard -- the 16-bit
         mirrors plus the masters of the all-reduced slices."""
         if self._shards is None or not self._sharded():
-            return [self.model.g.flat, self.model.d.flat]
+            return [self.model.g.flat, self.model.d.flat] + ([self.g_ema.flat] if self.g_ema is not None else [])
         out = [self.wbf_g.flat, self.wbf_d.flat]
         for name, m, a, b in self._small:
             out.append((self.model.d if m == "d" else self.model.g).flat[a:b])
@@ -208,6 +208,7 @@ class HipDDPMixin:
         else:
             self._c_split_a = self._c_split
             adam_g("adam_g", 0, n)
+        self._ema_g(prog, 1, ls)  # after the last Adam launch over G, before the step counter moves
         prog.step_end("step_end", _p(od.powers), _p(og.powers), od.beta1, od.beta2, og.beta1, og.beta2,
                       _p(self.step_counter), 0, ls, self.LOSS_SCALE_GROWTH)
 

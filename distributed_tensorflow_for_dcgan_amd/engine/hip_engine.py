@@ -9,7 +9,9 @@ every step from C++ (eager, the default) or as hipGraphs:
   progA[a_fwd:]  the g_loss chain back through D(fake) and G's data gradients  -- "G chain"
   progW          G's weight gradients, each tied to the progA position that produces its operand
   progB          D's backward of d_loss, both halves (D grads final)            -- "D chain"
-  progC          TF-Adam(G), TF-Adam(D), beta powers, global step (+ 16-bit weight mirrors)
+  progC          TF-Adam(G), TF-Adam(D), beta powers, global step (+ 16-bit weight mirrors);
+                 with ``g_ema_decay`` > 0 also ``ema_g``, the moving average of G's weights, after
+                 the last Adam launch over G
 
 Schedules (``_schedule``), all proven free of cross-stream overlaps by ``schedule_check.py``:
   "fused"       one process: both chains on two streams, G weight gradients on a third, one
@@ -35,6 +37,7 @@ from ..models.config import DCGANConfig, same_pads
 from ..models.dcgan import DCGAN
 from ..optim.adam import TFAdam
 from ..ops import hip as H
+from ..ops import reference as R
 from ..parallel import dist as D
 from .hip_aux import HipEngineAux
 from .hip_ddp import HipDDPMixin
@@ -123,7 +126,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  seed: int = 0, lr: float = 2e-4, beta1: float = 0.5, zero_debias: bool = False, rank: int = 0,
                  world: int = 1, graph: bool = True, allreduce_dtype: str = "fp32", bucket_mb: float = 32.0,
                  rank_seeded_z: bool = True, schedule: Optional[str] = None, dry_run: bool = False,
-                 ddp: Optional[bool] = None, **_):
+                 ddp: Optional[bool] = None, g_ema_decay: Optional[float] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -144,6 +147,14 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.seed = int(seed)
         self.rank_seeded_z = bool(rank_seeded_z)  # False only in equivalence tests
         self.lr, self.beta1 = float(lr), float(beta1)
+        # moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates = the
+        # global step); 0 = off: no buffers, no op. None: DCGAN_G_EMA_DECAY (A/B of its cost)
+        if g_ema_decay is None:
+            g_ema_decay = float(os.environ.get("DCGAN_G_EMA_DECAY") or 0.0)
+        self.g_ema_decay = R.check_ema_decay(g_ema_decay)
+        if self.g_ema_decay > 0 and os.environ.get("DCGAN_DDP_SHARD", "0") == "1":
+            raise ValueError("g_ema_decay > 0 is not supported with DCGAN_DDP_SHARD=1: under the sharded update "
+                             "each rank holds only 1/W of G's fp32 masters when the average would be taken")
         if schedule is None and os.environ.get("DCGAN_SERIAL_DBWD") == "1":
             schedule = "serial"
         if schedule is not None and schedule not in SCHEDULES:
@@ -257,6 +268,14 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         else:
             self.wbf_d = self.model.d.like(self.edt)
             self.wbf_g = self.model.g.like(self.edt)
+        # moving average of G's weights (same flat layout, padding included) + the 16-bit mirror of
+        # it that the sampler's conv GEMMs read (fp32: they read the average itself)
+        self.g_ema = self.wbf_g_ema = None
+        if self.g_ema_decay > 0:
+            self.g_ema = self.model.g.like()
+            self.g_ema.flat.copy_(self.model.g.flat)
+            self.wbf_g_ema = self.g_ema if self.f32 else self.model.g.like(self.edt)
+            self.model.g_ema = self.g_ema  # (what DCGAN.sampler(ema=True) and the checkpoints see)
         # fp16: dynamic loss scale state [scale, overflow flag, good steps] (device-resident, so
         # the whole step incl. skip / halve / grow stays inside the captured graphs)
         self.loss_scale = (torch.tensor([self.INIT_LOSS_SCALE, 0.0, 0.0], dtype=torch.float32, device=self.device)
@@ -302,9 +321,12 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                                             1.0, 0.0, 0)
         self.progCast = self._prog()  # fp32 masters -> 16-bit mirrors (init / checkpoint load)
         if not self.f32:
-            for ps, pb in ((self.model.d, self.wbf_d), (self.model.g, self.wbf_g)):
+            pairs = [(self.model.d, self.wbf_d), (self.model.g, self.wbf_g)]
+            if self.g_ema is not None:
+                pairs.append((self.g_ema, self.wbf_g_ema))
+            for ps, pb in pairs:
                 self.progCast.cast_to_bf16("mirror", _p(ps.flat), 0, _p(pb.flat), ps.flat.numel(), 1.0, 0.0, 0)
-        self.progS = None  # sampler program, built lazily
+        self.progS = self.progS_ema = None  # sampler programs (weights / their moving average), built lazily
         self.progEval = None
         self.progSum = None
 
@@ -905,6 +927,15 @@ class HipEngine(HipDDPMixin, HipEngineAux):
 
 
     # ---- optimiser (+ 16-bit weight mirrors)
+    def _ema_g(self, prog, step_bias: int, ls: int = 0) -> None:
+        """The moving average of G's weights (+ its 16-bit mirror): one launch on the stream of,
+        and after, the last Adam launch that writes G. step_bias = 1 where the step counter is
+        advanced by a later launch (step_end), 0 where it already was (adam2)."""
+        if self.g_ema is None:
+            return
+        prog.ema("ema_g", _p(self.g_ema.flat), 0 if self.f32 else _p(self.wbf_g_ema.flat), _p(self.model.g.flat),
+                 self.model.g.flat.numel(), self.g_ema_decay, _p(self.step_counter), step_bias, ls, 0)
+
     def _build_update(self, prog, first: bool):
         """TF-Adam for G (first part) and D + the step counter (last part); each Adam also
         writes the 16-bit mirror the conv GEMMs read (fp32: none, the GEMMs read the masters).
@@ -925,6 +956,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             prog.adam_bf("adam_g", _p(self.model.g.flat), mg, _p(self.grad_g.flat), _p(og.m.flat),
                          _p(og.v.flat), _p(og.powers), self.model.g.flat.numel(), og.lr, og.beta1, og.beta2, og.eps,
                          gs, 0, ls)
+            self._ema_g(prog, 1, ls)
         if do_d:
             prog.adam_bf("adam_d", _p(self.model.d.flat), md, _p(self.grad_d.flat), _p(od.m.flat),
                          _p(od.v.flat), _p(od.powers), self.model.d.flat.numel(), od.lr, od.beta1, od.beta2, od.eps,
@@ -941,6 +973,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                    _p(og.powers), G.flat.numel(), og.lr, og.beta1, og.beta2, og.eps, _p(Dm.flat), _p(self.wbf_d.flat),
                    _p(self.grad_d.flat), _p(od.m.flat), _p(od.v.flat), _p(od.powers), Dm.flat.numel(), od.lr,
                    od.beta1, od.beta2, od.eps, 1.0 / self.world, _p(self.step_counter), 0)
+        self._ema_g(prog, 0)
 
     def _repack_weights_now(self):
         if self.progCast.size():
@@ -1234,5 +1267,6 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         D.all_reduce_mean_(self.model.d_bn.flat)
 
     def after_state_load(self) -> None:
-        """Call after loading weights/slots from a checkpoint: refresh the 16-bit weight mirrors."""
+        """Call after loading weights/slots from a checkpoint: refresh the 16-bit weight mirrors
+        (the moving average's too)."""
         self._repack_weights_now()

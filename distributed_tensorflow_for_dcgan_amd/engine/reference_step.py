@@ -22,8 +22,13 @@ from ..optim.adam import TFAdam
 
 class ReferenceStep:
     def __init__(self, model: DCGAN, lr: float = 2e-4, beta1: float = 0.5,
-                 grad_hook: Optional[Callable[[str, torch.Tensor], None]] = None):
+                 grad_hook: Optional[Callable[[str, torch.Tensor], None]] = None, g_ema_decay: float = 0.0):
         self.model = model
+        # moving average of G's weights (model.g_ema; ops.reference.ema_update_), 0 = none kept
+        self.g_ema_decay = R.check_ema_decay(g_ema_decay)
+        if self.g_ema_decay > 0:
+            model.g_ema = model.g.like()
+            model.g_ema.flat.copy_(model.g.flat)
         self.opt_d = TFAdam(model.d, lr, beta1, power_suffix="")
         self.opt_g = TFAdam(model.g, lr, beta1, power_suffix="_1")
         self.global_step = 0
@@ -74,5 +79,8 @@ class ReferenceStep:
         self.opt_d.step(gd)
         self.opt_g.step(gg)
         self.global_step += 1
+        if self.g_ema_decay > 0:  # after Adam(G), with the step count after its increment
+            with torch.no_grad():
+                R.ema_update_(self.model.g_ema.flat, self.model.g.flat, self.g_ema_decay, self.global_step)
         self.last = out
         return {k: float(out[k].detach()) for k in ("d_loss_real", "d_loss_fake", "g_loss", "d_loss")}

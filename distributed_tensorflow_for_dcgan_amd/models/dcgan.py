@@ -224,6 +224,9 @@ class DCGAN:
                             decay=cfg.bn_momentum, zero_debias=zero_debias)
         self.d_bn = BNState(cfg.d_bn_layers(), slots=2, device=self.device,
                             decay=cfg.bn_momentum, zero_debias=zero_debias)
+        # moving average of G's weights (tf.train.ExponentialMovingAverage shadows, same layout
+        # as g); None unless an engine keeps one (g_ema_decay > 0)
+        self.g_ema: Optional[ParamSet] = None
 
     # ---------------------------------------------------------------- reference G
     def generator(self, z: torch.Tensor, train: bool = True, P: Optional[Dict[str, torch.Tensor]] = None,
@@ -250,10 +253,15 @@ class DCGAN:
                 record[L.name] = h
         return h
 
-    def sampler(self, z: torch.Tensor) -> torch.Tensor:
-        """Generator with BN in inference mode (``distriubted_model.py:131-153``)."""
+    def sampler(self, z: torch.Tensor, ema: Optional[bool] = None) -> torch.Tensor:
+        """Generator with BN in inference mode (``distriubted_model.py:131-153``). ema: use the
+        moving average of G's weights (``g_ema``) instead of the last iterate; None = the average
+        when one is kept."""
+        use_ema = self.g_ema is not None if ema is None else bool(ema)
+        if use_ema and self.g_ema is None:
+            raise ValueError("sampler(ema=True) needs a moving average of G's weights (g_ema_decay > 0)")
         with torch.no_grad():
-            return self.generator(z, train=False, update_ema=False)
+            return self.generator(z, train=False, P=self.g_ema.tensors if use_ema else None, update_ema=False)
 
     # ---------------------------------------------------------------- reference D
     def discriminator(self, x: torch.Tensor, groups: int = 1, slots: Sequence[int] = (0,),

@@ -631,3 +631,27 @@ def adam_(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, po
     if advance_powers:
         prog.step_end("powers", _p(powers), 0, beta1, beta2, 0.0, 0.0, 0, 0)
     run(prog)
+
+
+def ema_max_blocks() -> int:
+    """Grid cap of the streaming EMA kernel (larger buffers grid-stride)."""
+    return int(ext().EMA_MAX_BLOCKS)
+
+
+def ema_(s: torch.Tensor, sbf: Optional[torch.Tensor], w: torch.Tensor, decay: float, step: torch.Tensor,
+         step_bias: int = 0, ls: Optional[torch.Tensor] = None) -> None:
+    """In place s -= (1 - d_t)(s - w), d_t = min(decay, (1 + t) / (10 + t)), t = step[0] + step_bias
+    (device int64 counter); sbf (optional) receives s in its 16-bit dtype; ls = fp16 loss-scale
+    state [scale, overflow, good steps]: a set overflow flag leaves s and sbf untouched."""
+    if s.dtype != torch.float32 or w.dtype != torch.float32 or step.dtype != torch.int64:
+        raise TypeError("ema_: s, w must be float32 and step int64")
+    if w.numel() != s.numel() or (sbf is not None and sbf.numel() != s.numel()):
+        raise ValueError("ema_: s, sbf and w must have the same number of elements")
+    dt = 0
+    if sbf is not None:
+        if sbf.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError("ema_: the mirror must be bfloat16 or float16")
+        dt = int(sbf.dtype == torch.float16)
+    prog = ext().Program(dt)
+    prog.ema("ema", _p(s), _p(sbf), _p(w), s.numel(), float(decay), _p(step), int(step_bias), _p(ls), 0)
+    run(prog)

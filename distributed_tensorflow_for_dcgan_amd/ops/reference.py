@@ -111,3 +111,27 @@ def tf_adam_update(param: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: 
 def zero_fraction(x: torch.Tensor) -> torch.Tensor:
     """tf.nn.zero_fraction (sparsity summary, distriubted_model.py:80)."""
     return (x == 0).float().mean()
+
+
+def ema_decay_t(decay: float, t: int) -> float:
+    """Effective decay of tf.train.ExponentialMovingAverage(decay, num_updates=t), in fp32:
+    min(decay, (1 + t) / (10 + t)); t = the global step after this step's increment."""
+    f = torch.float32
+    d = torch.minimum(torch.tensor(float(decay), dtype=f),
+                      (1 + torch.tensor(float(t), dtype=f)) / (10 + torch.tensor(float(t), dtype=f)))
+    return float(d)
+
+
+def ema_update_(s: torch.Tensor, w: torch.Tensor, decay: float, t: int) -> torch.Tensor:
+    """TF assign_moving_average (in place, fp32): s -= (1 - d_t) * (s - w)."""
+    one_minus = float(torch.tensor(1.0, dtype=torch.float32) - torch.tensor(ema_decay_t(decay, t), dtype=torch.float32))
+    s.sub_((s - w.to(s.dtype)) * one_minus)
+    return s
+
+
+def check_ema_decay(decay) -> float:
+    """Validated weight-EMA decay: 0 <= decay < 1 (0 = no moving average is kept)."""
+    d = float(decay)
+    if not 0.0 <= d < 1.0:
+        raise ValueError("g_ema_decay must satisfy 0 <= decay < 1, got %r" % (decay,))
+    return d

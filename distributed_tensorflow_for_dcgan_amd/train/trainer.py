@@ -156,7 +156,8 @@ def run(flags: Flags, out=None) -> int:
     engine = build_engine(cfg, B, device, engine=flags.engine, dtype=flags.dtype, seed=int(flags.seed), rank=rank,
                           world=world, graph=bool(flags.graph), allreduce_dtype=flags.allreduce_dtype,
                           lr=float(flags.learning_rate), beta1=float(flags.beta1),
-                          zero_debias=bool(flags.bn_zero_debias), bucket_mb=float(flags.bucket_mb))
+                          zero_debias=bool(flags.bn_zero_debias), bucket_mb=float(flags.bucket_mb),
+                          g_ema_decay=float(flags.g_ema_decay))
     if flags.log_device_placement:
         for line in placement_report(engine, device, rank, world):
             print(line, file=out, flush=True)
@@ -169,6 +170,8 @@ def run(flags: Flags, out=None) -> int:
               else "load failed!!", file=out)
         if info and not (info.get("adam_d") and info.get("adam_g")):
             print("note: checkpoint has no optimiser state (reference-style); Adam restarts at t=0", file=out)
+        if info and "g_ema" in info:
+            print("generator weight EMA: %s" % info["g_ema"], file=out)
 
     if flags.explicitly_set("is_train") and not flags.is_train:
         try:
@@ -297,6 +300,11 @@ def run(flags: Flags, out=None) -> int:
     return 0
 
 
+def _sample_ema(engine, flags) -> bool:
+    """Sample from the moving average of G's weights: --sample_ema and an engine that keeps one."""
+    return bool(flags.sample_ema) and float(getattr(engine, "g_ema_decay", 0.0)) > 0
+
+
 def _test_mode(engine, flags, cfg, B, device, info, chief, out) -> int:
     """``--nois_train``: sample-only mode (the flag the reference defines but never reads,
     ``image_train.py:23``). Restores the newest checkpoint, writes ``num_samples`` images from
@@ -310,10 +318,11 @@ def _test_mode(engine, flags, cfg, B, device, info, chief, out) -> int:
     gen = torch.Generator().manual_seed(int(flags.seed) + 31337)
     step = int(engine.global_step)
     n = max(1, int(flags.num_samples))
+    ema = _sample_ema(engine, flags)
     imgs = []
     while sum(x.shape[0] for x in imgs) < n:
         z = (torch.rand(B, cfg.z_dim, generator=gen) * 2 - 1).to(device)
-        imgs.append(engine.sampler(z).detach().float().cpu().numpy())
+        imgs.append(engine.sampler(z, ema=ema).detach().float().cpu().numpy())
     arr = np.concatenate(imgs, 0)[:n]
     path = os.path.join(flags.sample_dir, "test_%06d.png" % step)
     IM.save_images(arr, (8, 8) if n == 64 else IM.grid_size(n), path)
@@ -324,12 +333,12 @@ def _test_mode(engine, flags, cfg, B, device, info, chief, out) -> int:
         for d in range(min(cfg.z_dim, 8)):
             z = base.clone()
             z[:, d] = sweep
-            x = engine.sampler(z.to(device)).detach().float().cpu().numpy()
+            x = engine.sampler(z.to(device), ema=ema).detach().float().cpu().numpy()
             IM.save_images(x, IM.grid_size(B), os.path.join(flags.sample_dir, "test_arange_%d.png" % d))
         z0 = torch.rand(1, cfg.z_dim, generator=gen) * 2 - 1
         z1 = torch.rand(1, cfg.z_dim, generator=gen) * 2 - 1
         t = torch.linspace(0.0, 1.0, B).unsqueeze(1)
-        x = engine.sampler(((1 - t) * z0 + t * z1).to(device)).detach().float().cpu().numpy()
+        x = engine.sampler(((1 - t) * z0 + t * z1).to(device), ema=ema).detach().float().cpu().numpy()
         IM.save_images(x, IM.grid_size(B), os.path.join(flags.sample_dir, "test_interp.png"))
         print("[Visualize] wrote z sweeps and interpolation to %s" % flags.sample_dir, file=out, flush=True)
     return 0
@@ -338,7 +347,7 @@ def _test_mode(engine, flags, cfg, B, device, info, chief, out) -> int:
 def _sample(engine, flags, sample_source, source, sample_z, step, step_per_epoch, out) -> None:
     """Chief sampling side path (image_train.py:179-192): EMA-BN sampler grid + sample losses."""
     batch = (sample_source or source).next()
-    samples = engine.sampler(sample_z)
+    samples = engine.sampler(sample_z, ema=_sample_ema(engine, flags))
     losses = engine.eval_losses(batch, sample_z)
     n = samples.shape[0]
     grid = (8, 8) if n == 64 else IM.grid_size(n)

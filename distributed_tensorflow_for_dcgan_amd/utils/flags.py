@@ -75,6 +75,11 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
     ("cache_on_device", "bool", False, "decode the whole TFRecord dataset once into GPU memory (288 GB HBM)"),
     ("collective_timeout", "float", 600.0, "seconds before a hung collective is an error (RCCL watchdog)"),
     ("num_samples", "int", 64, "images per grid in sample-only mode (--nois_train)"),
+    ("g_ema_decay", "float", 0.0, "keep an exponential moving average of the generator's weights with this decay "
+                                  "(tf.train.ExponentialMovingAverage with num_updates = global step, e.g. 0.999; "
+                                  "0 = off); saved in checkpoints as <var>/ExponentialMovingAverage"),
+    ("sample_ema", "bool", True, "sample grids / --nois_train / --visualize draw from the generator's moving "
+                                 "average when --g_ema_decay keeps one (--nosample_ema: the last iterate)"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -153,6 +158,8 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
     parser = build_parser(defaults_override)
     argv = list(argv) if argv is not None else sys.argv[1:]
     ns = parser.parse_args(argv)
+    if not 0.0 <= float(ns.g_ema_decay) < 1.0:
+        parser.error("--g_ema_decay must satisfy 0 <= decay < 1, got %r" % (ns.g_ema_decay,))
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
