@@ -681,11 +681,25 @@ class Program {
   }
 
   // ------------------------------------------------------------------ heads, losses, optimiser
+  // D's real target 1 - label_smooth of a valid (objective, label_smooth) pair: GAN_BCE | GAN_LSGAN |
+  // GAN_HINGE, 0 <= label_smooth < 0.5 (NaN fails), no smoothing with hinge
+  static float gan_real_target(const char* op, int objective, double label_smooth) {
+    if (objective != GAN_BCE && objective != GAN_LSGAN && objective != GAN_HINGE)
+      throw std::runtime_error(std::string(op) + ": objective must be 0 (bce), 1 (lsgan) or 2 (hinge), got " +
+                               std::to_string(objective));
+    if (!(label_smooth >= 0.0 && label_smooth < 0.5))
+      throw std::runtime_error(std::string(op) + ": label_smooth must satisfy 0 <= s < 0.5, got " +
+                               std::to_string(label_smooth));
+    if (objective == GAN_HINGE && label_smooth > 0.0)
+      throw std::runtime_error(std::string(op) + ": label_smooth > 0 is not defined for the hinge objective");
+    return (float)(1.0 - label_smooth);
+  }
   int gan_loss(std::string name, uintptr_t logits, int B, uintptr_t out, uintptr_t dl_d, uintptr_t dl_g,
-               uintptr_t prob, int stream, uintptr_t ls) {
+               uintptr_t prob, int stream, uintptr_t ls, int objective, double label_smooth) {
+    const float t = gan_real_target("gan_loss", objective, label_smooth);
     return add(name, stream, [=](hipStream_t s) {
       return KF(dcg_gan_loss)(P<const float>(logits), B, P<float>(out), P<float>(dl_d), P<float>(dl_g),
-                          P<float>(prob), P<const float>(ls), s);
+                          P<float>(prob), P<const float>(ls), objective, t, s);
     }, AccList().r(logits, (size_t)B * 8).w(out, 16).w(dl_d, (size_t)B * 8).w(dl_g, (size_t)B * 4)
            .w(prob, (size_t)B * 8).r(ls, 12).v);
   }
@@ -711,9 +725,11 @@ class Program {
       return KF(dcg_linear_wgrad)(P<const float>(z), P<const elem_t>(dh), P<float>(dW), P<float>(db), B, K, N, s);
     }, AccList().r(z, (size_t)B * K * 4).r(dh, (size_t)B * N * es_).w(dW, (size_t)K * N * 4).w(db, (size_t)N * 4).v);
   }
-  // loss_out != 0: the 3-loss BCE (gan_loss) runs in the GEMV's last-arriving block
+  // loss_out != 0: the 3 losses of the objective (gan_loss) run in the GEMV's last-arriving block
   int gemv_head(std::string name, uintptr_t x, uintptr_t w, uintptr_t b, uintptr_t out, int R, int K, int stream,
-                uintptr_t loss_out, uintptr_t dl_d, uintptr_t dl_g, uintptr_t prob, uintptr_t ls) {
+                uintptr_t loss_out, uintptr_t dl_d, uintptr_t dl_g, uintptr_t prob, uintptr_t ls, int objective,
+                double label_smooth) {
+    const float t = gan_real_target("gemv_head", objective, label_smooth);
     unsigned* ctr = nullptr;
     AccList acc;
     acc.r(x, (size_t)R * K * es_).r(w, (size_t)K * 4).r(b, 4).w(out, (size_t)R * 4);
@@ -725,15 +741,17 @@ class Program {
     return add(name, stream, [=](hipStream_t s) {
       return KF(dcg_gemv_head)(P<const elem_t>(x), P<const float>(w), P<const float>(b), P<float>(out), R, K, ctr,
                                P<float>(loss_out), P<float>(dl_d), P<float>(dl_g), P<float>(prob), P<const float>(ls),
-                               s);
+                               objective, t, s);
     }, acc.v);
   }
   // the head with the top BN layer's apply + activation fused: x = that layer's pre-BN input,
   // y = its activation (written here), scale / shift [groups][C] from its BN finalize
   int gemv_head_bn(std::string name, uintptr_t x, uintptr_t w, uintptr_t b, uintptr_t out, int R, int K, int stream,
                    uintptr_t loss_out, uintptr_t dl_d, uintptr_t dl_g, uintptr_t prob, uintptr_t ls, uintptr_t scale,
-                   uintptr_t shift, int C, int rpg, int act, float leak, uintptr_t y) {
+                   uintptr_t shift, int C, int rpg, int act, float leak, uintptr_t y, int objective,
+                   double label_smooth) {
     if (dt_ == 2) throw std::runtime_error("gemv_head_bn: 16-bit builds only");
+    const float t = gan_real_target("gemv_head_bn", objective, label_smooth);
     unsigned* ctr = nullptr;
     AccList acc;
     const size_t groups = (size_t)((R + rpg - 1) / rpg);
@@ -748,7 +766,7 @@ class Program {
       return KF(dcg_gemv_head_bn)(P<const elem_t>(x), P<const float>(w), P<const float>(b), P<float>(out), R, K, ctr,
                                   P<float>(loss_out), P<float>(dl_d), P<float>(dl_g), P<float>(prob),
                                   P<const float>(ls), P<const float>(scale), P<const float>(shift), C, rpg, act, leak,
-                                  P<elem_t>(y), s);
+                                  P<elem_t>(y), objective, t, s);
     }, acc.v);
   }
   int head_dgrad(std::string name, uintptr_t dl, uintptr_t w, uintptr_t dx, int R, int K, int stream) {
@@ -1092,14 +1110,16 @@ PYBIND11_MODULE(_dcgan_hip, m) {
            py::arg("act") = 0, py::arg("leak") = 0.f, py::arg("part") = 0)
       .def("colsum_small", &Program::colsum_small)
       .def("gan_loss", &Program::gan_loss, py::arg("name"), py::arg("logits"), py::arg("B"), py::arg("out"),
-           py::arg("dl_d"), py::arg("dl_g"), py::arg("prob"), py::arg("stream"), py::arg("ls") = 0)
+           py::arg("dl_d"), py::arg("dl_g"), py::arg("prob"), py::arg("stream"), py::arg("ls") = 0,
+           py::arg("objective") = 0, py::arg("label_smooth") = 0.0)
       .def("linear_fwd", &Program::linear_fwd, py::arg("name"), py::arg("z"), py::arg("W"), py::arg("b"),
            py::arg("out"), py::arg("B"), py::arg("K"), py::arg("N"), py::arg("stream"), py::arg("stats") = 0,
            py::arg("C") = 0, py::arg("gen_step") = 0, py::arg("gen_seed") = 0)
       .def("linear_wgrad", &Program::linear_wgrad)
       .def("gemv_head", &Program::gemv_head, py::arg("name"), py::arg("x"), py::arg("w"), py::arg("b"), py::arg("out"),
            py::arg("R"), py::arg("K"), py::arg("stream"), py::arg("loss_out") = 0, py::arg("dl_d") = 0,
-           py::arg("dl_g") = 0, py::arg("prob") = 0, py::arg("ls") = 0)
+           py::arg("dl_g") = 0, py::arg("prob") = 0, py::arg("ls") = 0, py::arg("objective") = 0,
+           py::arg("label_smooth") = 0.0)
       .def("head_dgrad", &Program::head_dgrad)
       .def("head_wgrad", &Program::head_wgrad)
       .def("adam", &Program::adam)
@@ -1117,7 +1137,11 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("nconv", &Program::nconv)
       .def("nconv_tiles", &Program::nconv_tiles)
       .def("narrow_deconv_dact", &Program::narrow_deconv_dact)
-      .def("gemv_head_bn", &Program::gemv_head_bn)
+      .def("gemv_head_bn", &Program::gemv_head_bn, py::arg("name"), py::arg("x"), py::arg("w"), py::arg("b"),
+           py::arg("out"), py::arg("R"), py::arg("K"), py::arg("stream"), py::arg("loss_out"), py::arg("dl_d"),
+           py::arg("dl_g"), py::arg("prob"), py::arg("ls"), py::arg("scale"), py::arg("shift"), py::arg("C"),
+           py::arg("rpg"), py::arg("act"), py::arg("leak"), py::arg("y"), py::arg("objective") = 0,
+           py::arg("label_smooth") = 0.0)
       .def("head_bwd_rs", &Program::head_bwd_rs)
       .def("narrow_deconv_bnin", &Program::narrow_deconv_bnin)
       .def("nwgrad_ok", &Program::nwgrad_ok)

@@ -92,6 +92,11 @@ struct WGrad3Args {                 // wgrad3.hip: 25-tap gather GEMM, in-kernel
 // workgroups; larger buffers grid-stride
 constexpr unsigned EMA_MAX_BLOCKS = 2048;
 
+// GAN objectives of the loss / head kernels (misc.hip gan_loss_block). The first three are the
+// ids of the launchers and bindings; GAN_BCE_T is the kernel instance of bce with a smoothed
+// real target, which the launchers pick themselves (real_target != 1).
+enum GanObjective : int { GAN_BCE = 0, GAN_LSGAN = 1, GAN_HINGE = 2, GAN_BCE_T = 3 };
+
 }  // namespace dcg
 
 extern "C" {

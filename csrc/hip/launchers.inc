@@ -36,13 +36,15 @@ int DCG_API(dcg_head_bwd)(const elem_t* x, const float* dl, const float* w, elem
                           int rpg, int act, float leak, float* part, hipStream_t s);
 int DCG_API(dcg_colsum_small)(const elem_t* x, int R, int C, float* part, int blocks, hipStream_t s);
 
+// objective = GAN_BCE | GAN_LSGAN | GAN_HINGE, real_target = 1 - label_smooth (1 for hinge); -2 otherwise
 int DCG_API(dcg_gan_loss)(const float* logits, int B, float* out, float* dl_d, float* dl_g, float* prob,
-                          const float* ls, hipStream_t s);
+                          const float* ls, int objective, float real_target, hipStream_t s);
 int DCG_API(dcg_linear_fwd)(float* z, const float* W, const float* b, elem_t* out, int B, int K, int N, float* stats,
                             int C, const unsigned long long* gen_step, uint64_t gen_seed, hipStream_t s);
 int DCG_API(dcg_linear_wgrad)(const float* z, const elem_t* dh, float* dW, float* db, int B, int K, int N, hipStream_t s);
 int DCG_API(dcg_gemv_head)(const elem_t* x, const float* w, const float* b, float* out, int R, int K, unsigned* counter,
-                           float* loss_out, float* dl_d, float* dl_g, float* prob, const float* ls, hipStream_t s);
+                           float* loss_out, float* dl_d, float* dl_g, float* prob, const float* ls, int objective,
+                           float real_target, hipStream_t s);
 int DCG_API(dcg_head_dgrad)(const float* dl, const float* w, elem_t* dx, int R, int K, hipStream_t s);
 int DCG_API(dcg_head_wgrad)(const elem_t* x, const float* dl, float* part, int R, int K, int splits, hipStream_t s);
 int DCG_API(dcg_sum_vec)(const float* v, int n, float* out, hipStream_t s);

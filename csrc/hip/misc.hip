@@ -1,6 +1,7 @@
 // dcg-variants: bf16 f16 f32
 // Small fused kernels of the DCGAN step for gfx950:
-//   * BCE-with-logits, all 3 reference losses + both logit gradients in ONE kernel (K15/K16)
+//   * the GAN objective (BCE-with-logits as the reference, least squares or hinge), all 3
+//     losses + both logit gradients in ONE kernel (K15/K16)
 //   * linear layers: G projection z->h0 (K1), its weight gradient (K2), D's 1-output head
 //     (GEMV) and its gradients
 //   * TF-form Adam over a flat fp32 buffer + device-side beta powers (K17, graph-capturable)
@@ -8,6 +9,7 @@
 //   * Philox-4x32-10 z ~ U(-1,1) keyed by a device step counter (K19, graph-capturable)
 //   * stride-2 TF-SAME im2col for 3-channel tensors, dtype casts
 #include <algorithm>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -17,11 +19,17 @@ namespace dcg {
 // logits: [2B] (real rows first). out[0..3] = d_loss_real, d_loss_fake, g_loss, d_loss;
 // dl_d[2B] = d d_loss / d logit; dl_g[B] = d g_loss / d logit_fake; prob[2B] = sigmoid.
 // The block-wide body, shared by the standalone kernel and the head GEMV's last-arriving block;
-// logit(i) fetches logit i.
-template <typename F>
-__device__ __forceinline__ void gan_loss_block(F logit, int B, float* __restrict__ out, float* __restrict__ dl_d,
-                                               float* __restrict__ dl_g, float* __restrict__ prob,
-                                               const float* __restrict__ ls) {
+// logit(i) fetches logit i. OBJ (compile time) selects the objective; t = D's real target (1 -
+// label_smooth, one-sided: the fake target and G's target never move), read by GAN_BCE_T and
+// GAN_LSGAN only. GAN_BCE is the reference's losses with every target a literal: the default
+// instance carries nothing of the others.
+//   GAN_BCE / GAN_BCE_T  sigmoid cross-entropy: real vs t, fake vs 0, G vs 1 (non-saturating)
+//   GAN_LSGAN            0.5 (x_r - t)^2, 0.5 x_f^2, G: 0.5 (x_f - 1)^2
+//   GAN_HINGE            relu(1 - x_r), relu(1 + x_f), G: -x_f; subgradient 0 at the kinks (torch's)
+template <int OBJ, typename F>
+__device__ __forceinline__ void gan_loss_block(F logit, int B, float t, float* __restrict__ out,
+                                               float* __restrict__ dl_d, float* __restrict__ dl_g,
+                                               float* __restrict__ prob, const float* __restrict__ ls) {
   __shared__ float red[3][256];
   float lr = 0.f, lf = 0.f, lg = 0.f;
   const float invB = 1.f / (float)B;
@@ -29,17 +37,51 @@ __device__ __forceinline__ void gan_loss_block(F logit, int B, float* __restrict
   const float gB = ls ? ls[0] * invB : invB;
   for (int i = threadIdx.x; i < 2 * B; i += 256) {
     const float x = logit(i);
-    const float sp = log1pf(expf(-fabsf(x)));
     const float sg = 1.f / (1.f + expf(-x));
     if (prob) prob[i] = sg;
-    if (i < B) {
-      lr += fmaxf(x, 0.f) - x + sp;          // target 1
-      dl_d[i] = (sg - 1.f) * gB;
+    if constexpr (OBJ == GAN_BCE) {
+      const float sp = log1pf(expf(-fabsf(x)));
+      if (i < B) {
+        lr += fmaxf(x, 0.f) - x + sp;          // target 1
+        dl_d[i] = (sg - 1.f) * gB;
+      } else {
+        lf += fmaxf(x, 0.f) + sp;              // target 0
+        lg += fmaxf(x, 0.f) - x + sp;          // target 1 (non-saturating G loss)
+        dl_d[i] = sg * gB;
+        dl_g[i - B] = (sg - 1.f) * gB;
+      }
+    } else if constexpr (OBJ == GAN_BCE_T) {
+      const float sp = log1pf(expf(-fabsf(x)));
+      if (i < B) {
+        lr += fmaxf(x, 0.f) - x * t + sp;      // target t
+        dl_d[i] = (sg - t) * gB;
+      } else {
+        lf += fmaxf(x, 0.f) + sp;
+        lg += fmaxf(x, 0.f) - x + sp;
+        dl_d[i] = sg * gB;
+        dl_g[i - B] = (sg - 1.f) * gB;
+      }
+    } else if constexpr (OBJ == GAN_LSGAN) {
+      if (i < B) {
+        lr += 0.5f * (x - t) * (x - t);
+        dl_d[i] = (x - t) * gB;
+      } else {
+        lf += 0.5f * x * x;
+        lg += 0.5f * (x - 1.f) * (x - 1.f);
+        dl_d[i] = x * gB;
+        dl_g[i - B] = (x - 1.f) * gB;
+      }
     } else {
-      lf += fmaxf(x, 0.f) + sp;              // target 0
-      lg += fmaxf(x, 0.f) - x + sp;          // target 1 (non-saturating G loss)
-      dl_d[i] = sg * gB;
-      dl_g[i - B] = (sg - 1.f) * gB;
+      static_assert(OBJ == GAN_HINGE, "unknown objective");
+      if (i < B) {
+        lr += fmaxf(1.f - x, 0.f);
+        dl_d[i] = x < 1.f ? -gB : 0.f;
+      } else {
+        lf += fmaxf(1.f + x, 0.f);
+        lg -= x;
+        dl_d[i] = x > -1.f ? gB : 0.f;
+        dl_g[i - B] = -gB;
+      }
     }
   }
   red[0][threadIdx.x] = lr;
@@ -57,11 +99,12 @@ __device__ __forceinline__ void gan_loss_block(F logit, int B, float* __restrict
   }
 }
 
-__global__ __launch_bounds__(256) void gan_loss_kernel(const float* __restrict__ logits, int B,
+template <int OBJ>
+__global__ __launch_bounds__(256) void gan_loss_kernel(const float* __restrict__ logits, int B, float t,
                                                        float* __restrict__ out, float* __restrict__ dl_d,
                                                        float* __restrict__ dl_g, float* __restrict__ prob,
                                                        const float* __restrict__ ls) {
-  gan_loss_block([&](int i) { return logits[i]; }, B, out, dl_d, dl_g, prob, ls);
+  gan_loss_block<OBJ>([&](int i) { return logits[i]; }, B, t, out, dl_d, dl_g, prob, ls);
 }
 
 // ---------------------------------------------------------------- Philox z ~ U(-1, 1)
@@ -225,6 +268,7 @@ struct HeadLossArgs {  // fused gan loss (counter == nullptr: plain GEMV)
   float* dl_g;
   float* prob;
   const float* ls;
+  float t;  // D's real target (GAN_BCE_T, GAN_LSGAN)
 };
 
 // BNA (optional): x is the top BN layer's PRE-BN input; the head applies that BN + activation on
@@ -235,7 +279,7 @@ struct HeadBnArgs {
   const float* scale; const float* shift; int C, rpg, act; float leak; elem_t* y;
 };
 
-template <bool BNA>
+template <bool BNA, int OBJ>
 __global__ __launch_bounds__(256) void gemv_head_kernel(const elem_t* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ b, float* __restrict__ out, int R,
                                                         int K, HeadLossArgs L, HeadBnArgs bn) {
@@ -288,8 +332,8 @@ __global__ __launch_bounds__(256) void gemv_head_kernel(const elem_t* __restrict
     if (threadIdx.x == 0) out[row] = logit;
     return;
   }
-  // fused 3-loss BCE: the logit is written through (sc1), the last row's block computes the
-  // losses and seeds from `sc1` loads of all 2B logits (one launch less per step)
+  // fused 3 losses of objective OBJ: the logit is written through (sc1), the last row's block
+  // computes the losses and seeds from `sc1` loads of all 2B logits (one launch less per step)
   const __amdgpu_buffer_rsrc_t rl = make_rsrc(out, (uint32_t)(R * 4));
   if (threadIdx.x == 0)
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, logit), rl, (uint32_t)row * 4u, 0, 16);
@@ -303,8 +347,8 @@ __global__ __launch_bounds__(256) void gemv_head_kernel(const elem_t* __restrict
   }
   __syncthreads();
   if (!last) return;
-  gan_loss_block([&](int i) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, (uint32_t)i * 4u, 0, 16)); },
-                 R / 2, L.out, L.dl_d, L.dl_g, L.prob, L.ls);
+  gan_loss_block<OBJ>([&](int i) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, (uint32_t)i * 4u, 0, 16)); },
+                      R / 2, L.t, L.out, L.dl_d, L.dl_g, L.prob, L.ls);
 }
 
 // dx[r][k] = dl[r] * w[k] (elem_t), 8 per thread
@@ -858,10 +902,35 @@ static inline unsigned grid_for(size_t n, size_t per = 256) {
   return (unsigned)(b ? b : 1);
 }
 
-extern "C" int DCG_API(dcg_gan_loss)(const float* logits, int B, float* out, float* dl_d, float* dl_g, float* prob,
-                                      const float* ls, hipStream_t s) {
-  hipLaunchKernelGGL(gan_loss_kernel, dim3(1), dim3(256), 0, s, logits, B, out, dl_d, dl_g, prob, ls);
+// kernel instance of (objective id GAN_BCE | GAN_LSGAN | GAN_HINGE, real target t), -1 = not one:
+// bce with t == 1 is the default instance, a smoothed bce target has its own
+static inline int gan_instance(int objective, float t) {
+  if (!(t > 0.5f && t <= 1.f)) return -1;
+  if (objective == GAN_BCE) return t == 1.f ? GAN_BCE : GAN_BCE_T;
+  if (objective == GAN_LSGAN) return GAN_LSGAN;
+  if (objective == GAN_HINGE && t == 1.f) return GAN_HINGE;
+  return -1;
+}
+
+// runs `launch(std::integral_constant<int, OBJ>)` for the instance of (objective, t)
+template <typename L>
+static inline int gan_dispatch(int objective, float t, L launch) {
+  switch (gan_instance(objective, t)) {
+    case GAN_BCE: launch(std::integral_constant<int, GAN_BCE>{}); break;
+    case GAN_BCE_T: launch(std::integral_constant<int, GAN_BCE_T>{}); break;
+    case GAN_LSGAN: launch(std::integral_constant<int, GAN_LSGAN>{}); break;
+    case GAN_HINGE: launch(std::integral_constant<int, GAN_HINGE>{}); break;
+    default: return -2;
+  }
   return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_gan_loss)(const float* logits, int B, float* out, float* dl_d, float* dl_g, float* prob,
+                                      const float* ls, int objective, float real_target, hipStream_t s) {
+  return gan_dispatch(objective, real_target, [&](auto obj) {
+    hipLaunchKernelGGL(gan_loss_kernel<decltype(obj)::value>, dim3(1), dim3(256), 0, s, logits, B, real_target, out,
+                       dl_d, dl_g, prob, ls);
+  });
 }
 
 extern "C" int DCG_API(dcg_linear_fwd)(float* z, const float* W, const float* b, elem_t* out, int B, int K, int N,
@@ -886,24 +955,31 @@ extern "C" int DCG_API(dcg_linear_wgrad)(const float* z, const elem_t* dh, float
 
 extern "C" int DCG_API(dcg_gemv_head)(const elem_t* x, const float* w, const float* b, float* out, int R, int K,
                                       unsigned* counter, float* loss_out, float* dl_d, float* dl_g, float* prob,
-                                      const float* ls, hipStream_t s) {
+                                      const float* ls, int objective, float real_target, hipStream_t s) {
   if (K % 32 || (counter && (R % 2 || !loss_out || !dl_d || !dl_g))) return -2;
-  const dcg::HeadLossArgs L{counter, loss_out, dl_d, dl_g, prob, ls};
-  hipLaunchKernelGGL(gemv_head_kernel<false>, dim3(R), dim3(256), 0, s, x, w, b, out, R, K, L, dcg::HeadBnArgs{});
-  return (int)hipGetLastError();
+  if (!counter) objective = GAN_BCE, real_target = 1.f;  // plain GEMV: the loss block never runs
+  const dcg::HeadLossArgs L{counter, loss_out, dl_d, dl_g, prob, ls, real_target};
+  return gan_dispatch(objective, real_target, [&](auto obj) {
+    hipLaunchKernelGGL((gemv_head_kernel<false, decltype(obj)::value>), dim3(R), dim3(256), 0, s, x, w, b, out, R, K,
+                       L, dcg::HeadBnArgs{});
+  });
 }
 
 // the head with the top BN layer's apply + activation fused (x = pre-BN input, y = activation out)
 extern "C" int DCG_API(dcg_gemv_head_bn)(const elem_t* x, const float* w, const float* b, float* out, int R, int K,
                                          unsigned* counter, float* loss_out, float* dl_d, float* dl_g, float* prob,
                                          const float* ls, const float* scale, const float* shift, int C, int rpg,
-                                         int act, float leak, elem_t* y, hipStream_t s) {
+                                         int act, float leak, elem_t* y, int objective, float real_target,
+                                         hipStream_t s) {
   if (K % 2048 || C % 8 || 512 % C || (counter && (R % 2 || !loss_out || !dl_d || !dl_g)) || !scale || !shift || !y)
     return -2;  // (every 8-element chunk of a lane then holds channels lane * 8 % C ..: loaded once)
-  const dcg::HeadLossArgs L{counter, loss_out, dl_d, dl_g, prob, ls};
+  if (!counter) objective = GAN_BCE, real_target = 1.f;
+  const dcg::HeadLossArgs L{counter, loss_out, dl_d, dl_g, prob, ls, real_target};
   const dcg::HeadBnArgs bn{scale, shift, C, rpg, act, leak, y};
-  hipLaunchKernelGGL(gemv_head_kernel<true>, dim3(R), dim3(256), 0, s, x, w, b, out, R, K, L, bn);
-  return (int)hipGetLastError();
+  return gan_dispatch(objective, real_target, [&](auto obj) {
+    hipLaunchKernelGGL((gemv_head_kernel<true, decltype(obj)::value>), dim3(R), dim3(256), 0, s, x, w, b, out, R, K,
+                       L, bn);
+  });
 }
 
 extern "C" int DCG_API(dcg_head_dgrad)(const float* dl, const float* w, elem_t* dx, int R, int K, hipStream_t s) {

@@ -15,11 +15,11 @@ int DCG_API(dcg_narrow_deconv_dact)(const elem_t* x, const elem_t* w, elem_t* y,
 int DCG_API(dcg_narrow_deconv_tiles)(int B, int Ho, int Wo);
 // wgrad3.hip: taps per tile of a wgrad3 cfg (2 for the two-tap tiles 320..339)
 int DCG_API(dcg_wgrad3_taps_per_tile)(int cfg);
-// misc.hip: the D head GEMV (+ fused 3-loss BCE) with the top BN layer's apply + activation fused
+// misc.hip: the D head GEMV (+ the fused 3 losses of the objective) with the top BN layer's apply + activation fused
 int DCG_API(dcg_gemv_head_bn)(const elem_t* x, const float* w, const float* b, float* out, int R, int K,
                               unsigned* counter, float* loss_out, float* dl_d, float* dl_g, float* prob,
                               const float* ls, const float* scale, const float* shift, int C, int rpg, int act,
-                              float leak, elem_t* y, hipStream_t s);
+                              float leak, elem_t* y, int objective, float real_target, hipStream_t s);
 // narrow.hip: G's RGB layer forward with the lower layer's BN apply + activation fused into its staging
 int DCG_API(dcg_narrow_deconv_bnin)(const elem_t* x, const elem_t* w, const float* bias, elem_t* y, int B, int Hi,
                                     int Wi, int C, int Ho, int Wo, int N, int pad, int act, float leak,

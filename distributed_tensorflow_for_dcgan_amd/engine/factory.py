@@ -26,7 +26,8 @@ class ReferenceEngine:
 
     def __init__(self, cfg: DCGANConfig, batch_size: int, device: torch.device, seed: int = 0,
                  lr: float = 2e-4, beta1: float = 0.5, zero_debias: bool = False, rank: int = 0,
-                 world: int = 1, z_seed: Optional[int] = None, g_ema_decay: Optional[float] = None, **_):
+                 world: int = 1, z_seed: Optional[int] = None, g_ema_decay: Optional[float] = None,
+                 gan_loss: Optional[str] = None, label_smooth: Optional[float] = None, **_):
         self.cfg = cfg
         self.batch_size = batch_size
         self.device = device
@@ -37,9 +38,14 @@ class ReferenceEngine:
                                  self.model.d_bn.flat])
         if g_ema_decay is None:  # (the HIP engine's switch, so both engines follow one environment)
             g_ema_decay = float(os.environ.get("DCGAN_G_EMA_DECAY") or 0.0)
+        if gan_loss is None:
+            gan_loss = os.environ.get("DCGAN_GAN_LOSS") or "bce"
+        if label_smooth is None:
+            label_smooth = float(os.environ.get("DCGAN_LABEL_SMOOTH") or 0.0)
         self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None,
-                                       g_ema_decay=g_ema_decay)
+                                       g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth)
         self.g_ema_decay = self.step_impl.g_ema_decay
+        self.gan_loss, self.label_smooth = self.step_impl.gan_loss, self.step_impl.label_smooth
         self.opt_d, self.opt_g = self.step_impl.opt_d, self.step_impl.opt_g
         self.z_gen = torch.Generator(device=device if device.type == "cuda" else "cpu")
         self.z_gen.manual_seed((z_seed if z_seed is not None else seed) + 7919 * rank + 1)
@@ -126,15 +132,18 @@ class ReferenceEngine:
 def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine: str = "auto",
                  dtype: str = "bf16", seed: int = 0, rank: int = 0, world: int = 1, graph: bool = True,
                  allreduce_dtype: str = "fp32", lr: float = 2e-4, beta1: float = 0.5,
-                 zero_debias: bool = False, bucket_mb: float = 32.0, g_ema_decay: Optional[float] = None):
+                 zero_debias: bool = False, bucket_mb: float = 32.0, g_ema_decay: Optional[float] = None,
+                 gan_loss: Optional[str] = None, label_smooth: Optional[float] = None):
     if engine == "auto":  # every dtype (bf16 / fp16 / fp32) runs on the HIP kernels on an MI355X
         engine = "hip" if device.type == "cuda" else "reference"
     if engine == "reference":
         return ReferenceEngine(cfg, batch_size, device, seed=seed, lr=lr, beta1=beta1,
-                               zero_debias=zero_debias, rank=rank, world=world, g_ema_decay=g_ema_decay)
+                               zero_debias=zero_debias, rank=rank, world=world, g_ema_decay=g_ema_decay,
+                               gan_loss=gan_loss, label_smooth=label_smooth)
     if engine == "hip":
         from .hip_engine import HipEngine
         return HipEngine(cfg, batch_size, device, dtype=dtype, seed=seed, lr=lr, beta1=beta1,
                          zero_debias=zero_debias, rank=rank, world=world, graph=graph,
-                         allreduce_dtype=allreduce_dtype, bucket_mb=bucket_mb, g_ema_decay=g_ema_decay)
+                         allreduce_dtype=allreduce_dtype, bucket_mb=bucket_mb, g_ema_decay=g_ema_decay,
+                         gan_loss=gan_loss, label_smooth=label_smooth)
     raise ValueError("unknown engine %r" % engine)

@@ -5,7 +5,8 @@ native ``Program`` objects (``csrc/bindings.cpp``) over statically allocated buf
 every step from C++ (eager, the default) or as hipGraphs:
 
   progA[:a_fwd]  z ~ U(-1,1) (Philox, device step counter) -> G forward -> D forward on the 2B
-                 batch [real | fake] with per-half BN statistics -> fused 3-loss BCE
+                 batch [real | fake] with per-half BN statistics -> the 3 losses of the objective
+                 (``gan_loss``: bce | lsgan | hinge) + both seeds, fused into the head GEMV
   progA[a_fwd:]  the g_loss chain back through D(fake) and G's data gradients  -- "G chain"
   progW          G's weight gradients, each tied to the progA position that produces its operand
   progB          D's backward of d_loss, both halves (D grads final)            -- "D chain"
@@ -126,7 +127,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  seed: int = 0, lr: float = 2e-4, beta1: float = 0.5, zero_debias: bool = False, rank: int = 0,
                  world: int = 1, graph: bool = True, allreduce_dtype: str = "fp32", bucket_mb: float = 32.0,
                  rank_seeded_z: bool = True, schedule: Optional[str] = None, dry_run: bool = False,
-                 ddp: Optional[bool] = None, g_ema_decay: Optional[float] = None, **_):
+                 ddp: Optional[bool] = None, g_ema_decay: Optional[float] = None, gan_loss: Optional[str] = None,
+                 label_smooth: Optional[float] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -155,6 +157,13 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         if self.g_ema_decay > 0 and os.environ.get("DCGAN_DDP_SHARD", "0") == "1":
             raise ValueError("g_ema_decay > 0 is not supported with DCGAN_DDP_SHARD=1: under the sharded update "
                              "each rank holds only 1/W of G's fp32 masters when the average would be taken")
+        # objective of the fused head / loss kernel: bce | lsgan | hinge, D's real target = 1 -
+        # label_smooth. None: DCGAN_GAN_LOSS / DCGAN_LABEL_SMOOTH (A/B on the benchmark)
+        if gan_loss is None:
+            gan_loss = os.environ.get("DCGAN_GAN_LOSS") or "bce"
+        if label_smooth is None:
+            label_smooth = float(os.environ.get("DCGAN_LABEL_SMOOTH") or 0.0)
+        self.gan_loss, self.label_smooth = R.check_gan_loss(gan_loss, label_smooth)
         if schedule is None and os.environ.get("DCGAN_SERIAL_DBWD") == "1":
             schedule = "serial"
         if schedule is not None and schedule not in SCHEDULES:
@@ -587,19 +596,21 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             prev = self.d_a[L.name]
         lin = cfg.d_lin_name
         last = self.dl[-1]
+        obj = H.GAN_LOSS_IDS[self.gan_loss]
         if last.bn and self._head_applies_bn():
             # head GEMV with the top BN layer's apply + LeakyReLU fused (writes its activation) + the
-            # fused 3-loss BCE in its last-arriving block
+            # fused 3 losses of the objective in its last-arriving block
             st = self.bn[last.bn]
             prog.gemv_head_bn("d_head+bn_apply+loss", _p(self.d_x[last.name]), _p(Pd[lin + "/Matrix"]),
                               _p(Pd[lin + "/bias"]), _p(self.logits), B2, cfg.d_lin_in, 0, _p(self.losses),
                               _p(self.dl_d), _p(self.dl_g), _p(self.prob), _p(self.loss_scale), _p(st["scale"]),
-                              _p(st["shift"]), last.cout, B, LRELU, cfg.lrelu_leak, _p(self.d_a[last.name]))
+                              _p(st["shift"]), last.cout, B, LRELU, cfg.lrelu_leak, _p(self.d_a[last.name]),
+                              obj, self.label_smooth)
         else:
-            # head GEMV + the fused 3-loss BCE in its last-arriving block
+            # head GEMV + the fused 3 losses of the objective in its last-arriving block
             prog.gemv_head("d_head+loss", _p(prev), _p(Pd[lin + "/Matrix"]), _p(Pd[lin + "/bias"]), _p(self.logits),
                            B2, cfg.d_lin_in, 0, _p(self.losses), _p(self.dl_d), _p(self.dl_g), _p(self.prob),
-                           _p(self.loss_scale))
+                           _p(self.loss_scale), obj, self.label_smooth)
 
     # ---- D backward for d_loss (2B rows, both groups) -> all D gradients
     def _build_d_backward_dloss(self, prog):

@@ -22,8 +22,11 @@ from ..optim.adam import TFAdam
 
 class ReferenceStep:
     def __init__(self, model: DCGAN, lr: float = 2e-4, beta1: float = 0.5,
-                 grad_hook: Optional[Callable[[str, torch.Tensor], None]] = None, g_ema_decay: float = 0.0):
+                 grad_hook: Optional[Callable[[str, torch.Tensor], None]] = None, g_ema_decay: float = 0.0,
+                 gan_loss: str = "bce", label_smooth: float = 0.0):
         self.model = model
+        # objective (ops.reference.gan_losses): bce | lsgan | hinge, D's real target = 1 - label_smooth
+        self.gan_loss, self.label_smooth = R.check_gan_loss(gan_loss, label_smooth)
         # moving average of G's weights (model.g_ema; ops.reference.ema_update_), 0 = none kept
         self.g_ema_decay = R.check_ema_decay(g_ema_decay)
         if self.g_ema_decay > 0:
@@ -44,7 +47,7 @@ class ReferenceStep:
         _, logits = m.discriminator(both, groups=2, slots=(0, 1), train=True, P=Pd,
                                     update_ema=update_ema, record=record)
         lr_, lf = logits[:B], logits[B:]
-        d_real, d_fake, g_loss, d_loss = R.gan_losses(lr_, lf)
+        d_real, d_fake, g_loss, d_loss = R.gan_losses(lr_, lf, self.gan_loss, self.label_smooth)
         return {"fake": fake, "logits_real": lr_, "logits_fake": lf, "d_loss_real": d_real,
                 "d_loss_fake": d_fake, "g_loss": g_loss, "d_loss": d_loss}
 

@@ -22,6 +22,8 @@ from ..models.config import same_out, same_pads
 _EXT = None
 
 ACT = {None: 0, "none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
+# objective ids of gan_loss / gemv_head / gemv_head_bn (kernels.h GAN_BCE, GAN_LSGAN, GAN_HINGE)
+GAN_LOSS_IDS = {"bce": 0, "lsgan": 1, "hinge": 2}
 
 
 class HipUnavailable(RuntimeError):
@@ -631,6 +633,29 @@ def adam_(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, po
     if advance_powers:
         prog.step_end("powers", _p(powers), 0, beta1, beta2, 0.0, 0.0, 0, 0)
     run(prog)
+
+
+def gan_loss_id(kind: str, label_smooth: float = 0.0) -> int:
+    """Objective id of the loss / head kernels for a validated (name, label_smooth) pair."""
+    from .reference import check_gan_loss
+    return GAN_LOSS_IDS[check_gan_loss(kind, label_smooth)[0]]
+
+
+def gan_loss(logits: torch.Tensor, kind: str = "bce", label_smooth: float = 0.0,
+             ls: Optional[torch.Tensor] = None):
+    """The stand-alone loss kernel on fp32 logits [2B] (real rows first): (losses[4] = d_loss_real,
+    d_loss_fake, g_loss, d_loss; dl_d[2B]; dl_g[B]; prob[2B] = sigmoid). ls = fp16 loss-scale state:
+    the seeds carry ls[0], the losses do not."""
+    if logits.dtype != torch.float32 or logits.dim() != 1 or logits.numel() % 2 or not logits.numel():
+        raise TypeError("gan_loss: logits must be a float32 vector of 2B elements")
+    obj = gan_loss_id(kind, label_smooth)
+    B = logits.numel() // 2
+    out, dl_d, dl_g, prob = (torch.empty(n, device=logits.device, dtype=torch.float32) for n in (4, 2 * B, B, 2 * B))
+    prog = ext().Program()
+    prog.gan_loss("gan_loss", _p(logits), B, _p(out), _p(dl_d), _p(dl_g), _p(prob), 0, _p(ls), obj,
+                  float(label_smooth))
+    run(prog)
+    return out, dl_d, dl_g, prob
 
 
 def ema_max_blocks() -> int:

@@ -89,11 +89,42 @@ def sigmoid_cross_entropy_with_logits(logits: torch.Tensor, targets: torch.Tenso
     return logits.clamp(min=0) - logits * targets + torch.log1p(torch.exp(-logits.abs()))
 
 
-def gan_losses(d_logits_real: torch.Tensor, d_logits_fake: torch.Tensor):
-    """(d_loss_real, d_loss_fake, g_loss, d_loss) exactly as image_train.py:91-96."""
-    d_real = sigmoid_cross_entropy_with_logits(d_logits_real, torch.ones_like(d_logits_real)).mean()
-    d_fake = sigmoid_cross_entropy_with_logits(d_logits_fake, torch.zeros_like(d_logits_fake)).mean()
-    g = sigmoid_cross_entropy_with_logits(d_logits_fake, torch.ones_like(d_logits_fake)).mean()
+GAN_LOSSES = ("bce", "lsgan", "hinge")  # (the position is the kernel's objective id, ops.hip.GAN_LOSS_IDS)
+
+
+def check_gan_loss(kind, label_smooth=0.0):
+    """Validated (objective name, one-sided label smoothing s): a known name, 0 <= s < 0.5, and no
+    smoothing with hinge (its real-side margin is not a target that could be smoothed)."""
+    if not isinstance(kind, str) or kind not in GAN_LOSSES:
+        raise ValueError("gan_loss must be one of %s, got %r" % ("|".join(GAN_LOSSES), kind))
+    s = float(label_smooth)
+    if not 0.0 <= s < 0.5:
+        raise ValueError("label_smooth must satisfy 0 <= s < 0.5, got %r" % (label_smooth,))
+    if kind == "hinge" and s > 0:
+        raise ValueError("label_smooth > 0 is not defined for gan_loss=hinge (got %r)" % (label_smooth,))
+    return kind, s
+
+
+def gan_losses(d_logits_real: torch.Tensor, d_logits_fake: torch.Tensor, kind: str = "bce",
+               label_smooth: float = 0.0):
+    """(d_loss_real, d_loss_fake, g_loss, d_loss). ``bce`` (default) is image_train.py:91-96 exactly;
+    ``lsgan`` the least-squares and ``hinge`` the hinge objective. ``label_smooth`` s lowers D's
+    real target to t = 1 - s (one-sided: neither the fake target nor G's target moves)."""
+    kind, s = check_gan_loss(kind, label_smooth)
+    xr, xf = d_logits_real, d_logits_fake
+    t = 1.0 - s
+    if kind == "bce":
+        d_real = sigmoid_cross_entropy_with_logits(xr, torch.full_like(xr, t)).mean()
+        d_fake = sigmoid_cross_entropy_with_logits(xf, torch.zeros_like(xf)).mean()
+        g = sigmoid_cross_entropy_with_logits(xf, torch.ones_like(xf)).mean()
+    elif kind == "lsgan":
+        d_real = 0.5 * (xr - t).pow(2).mean()
+        d_fake = 0.5 * xf.pow(2).mean()
+        g = 0.5 * (xf - 1.0).pow(2).mean()
+    else:
+        d_real = torch.relu(1.0 - xr).mean()
+        d_fake = torch.relu(1.0 + xf).mean()
+        g = -xf.mean()
     return d_real, d_fake, g, d_real + d_fake
 
 

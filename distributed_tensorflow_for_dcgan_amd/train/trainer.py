@@ -157,7 +157,11 @@ def run(flags: Flags, out=None) -> int:
                           world=world, graph=bool(flags.graph), allreduce_dtype=flags.allreduce_dtype,
                           lr=float(flags.learning_rate), beta1=float(flags.beta1),
                           zero_debias=bool(flags.bn_zero_debias), bucket_mb=float(flags.bucket_mb),
-                          g_ema_decay=float(flags.g_ema_decay))
+                          g_ema_decay=float(flags.g_ema_decay), gan_loss=str(flags.gan_loss),
+                          label_smooth=float(flags.label_smooth))
+    if chief:
+        print("GAN objective: %s, label_smooth %g (D's real target %g)" % (
+            engine.gan_loss, engine.label_smooth, 1.0 - engine.label_smooth), file=out, flush=True)
     if flags.log_device_placement:
         for line in placement_report(engine, device, rank, world):
             print(line, file=out, flush=True)

@@ -80,6 +80,10 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                                   "0 = off); saved in checkpoints as <var>/ExponentialMovingAverage"),
     ("sample_ema", "bool", True, "sample grids / --nois_train / --visualize draw from the generator's moving "
                                  "average when --g_ema_decay keeps one (--nosample_ema: the last iterate)"),
+    ("gan_loss", "str", "bce", "GAN objective: bce (the reference's sigmoid cross-entropy losses) | lsgan "
+                               "(least squares) | hinge"),
+    ("label_smooth", "float", 0.0, "one-sided label smoothing s, 0 <= s < 0.5: D's real target becomes 1 - s "
+                                   "(bce and lsgan; the fake target and G's target do not move)"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -160,6 +164,11 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
     ns = parser.parse_args(argv)
     if not 0.0 <= float(ns.g_ema_decay) < 1.0:
         parser.error("--g_ema_decay must satisfy 0 <= decay < 1, got %r" % (ns.g_ema_decay,))
+    from ..ops.reference import check_gan_loss
+    try:
+        check_gan_loss(ns.gan_loss, ns.label_smooth)
+    except ValueError as e:
+        parser.error("--gan_loss / --label_smooth: %s" % e)
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
