@@ -918,6 +918,88 @@ class Program {
                          step_bias, P<const float>(ls), st);
     }, AccList().w(s, n * 4).w(sbf, n * es_).r(w, n * 4).r(step, 8).r(ls, 12).v);
   }
+  // ---- spectral normalisation of D's weights (specnorm.hip). mats: one tuple per weight
+  // (W, u, v, sigma, ws, hat, hat_f32, grad, K, Cout): fp32 master [K, Cout], state, workspace of
+  // sn_plan(K, Cout) floats, the normalised copy (elem_t mirror slice, or fp32 when hat_f32) and,
+  // for the projection, the gradient slice
+  using SNTuple = std::tuple<uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t, int, uintptr_t, long, long>;
+  SNTable sn_table(const char* what, const std::vector<SNTuple>& mats, bool need_hat, bool need_grad) const {
+    const std::string w(what);
+    if (mats.empty() || mats.size() > (size_t)SN_MAX_MATS)
+      throw std::runtime_error(w + ": 1.." + std::to_string(SN_MAX_MATS) + " matrices per call");
+    SNTable t;
+    t.n = (int)mats.size();
+    for (int i = 0; i < t.n; ++i) {
+      uintptr_t W, u, v, sg, ws, hat, grad; int hf; long K, C;
+      std::tie(W, u, v, sg, ws, hat, hf, grad, K, C) = mats[i];
+      if (K <= 0 || C <= 0) throw std::runtime_error(w + ": K and Cout must be positive");
+      const SNPlan p = sn_plan(K, C);
+      if (!p.nrb) throw std::runtime_error(w + ": matrix shape out of range");
+      if (!W || !u || !v || !sg || !ws) throw std::runtime_error(w + ": W, u, v, sigma and ws must be non-null");
+      if (need_hat && !hat) throw std::runtime_error(w + ": the normalised copy must be non-null");
+      if (need_grad && !grad) throw std::runtime_error(w + ": the gradient must be non-null");
+      const size_t hes = (hf || es_ == 4) ? 4 : 2;
+      if (W % 16 || u % 16 || grad % 16 || hat % (4 * hes) || v % 4 || sg % 4 || ws % 4)
+        throw std::runtime_error(w + ": misaligned slice (W, u, grad: 16 bytes; copy: 4 elements; v, sigma, ws: 4 bytes)");
+      SNMat& m = t.m[i];
+      m.W = P<const float>(W); m.u = P<float>(u); m.v = P<float>(v); m.sigma = P<float>(sg); m.ws = P<float>(ws);
+      m.hat = P<void>(hat); m.grad = P<float>(grad); m.K = (int)K; m.Cout = (int)C;
+      m.nrb = p.nrb; m.rpb = p.rpb; m.nct = p.nct; m.ncb = p.ncb; m.hat_f32 = hf ? 1 : 0;
+    }
+    return t;
+  }
+  static uintptr_t U(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+  // write of the normalised copies: from the power step's partials (from_state = 0: also sigma, u)
+  // or from the stored sigma
+  int sn_apply_op(const std::string& name, const SNTable& t, int from_state, uintptr_t ls, int stream) {
+    AccList a;
+    for (int i = 0; i < t.n; ++i) {
+      const SNMat& m = t.m[i];
+      const size_t n = (size_t)m.K * m.Cout;
+      a.r(U(m.W), n * 4).w(U(m.hat), n * ((m.hat_f32 || es_ == 4) ? 4 : 2));
+      if (from_state) a.r(U(m.sigma), 4);
+      else a.r(U(m.ws + SN_WS_SPART), (size_t)m.nct * 4).w(U(m.u), (size_t)m.Cout * 4).w(U(m.sigma), 4);
+    }
+    a.r(ls, 12);
+    return add(name, stream, [this, t, from_state, ls](hipStream_t s) {
+      return KF(dcg_sn_apply)(&t, from_state, P<const float>(ls), s);
+    }, a.v);
+  }
+  // one power-iteration step from the stored u + the normalised copies: 4 launches over all mats
+  int sn_power(std::string name, std::vector<SNTuple> mats, uintptr_t ls, int stream) {
+    const SNTable t = sn_table("sn_power", mats, true, false);
+    AccList a1, a2, a3;
+    for (int i = 0; i < t.n; ++i) {
+      const SNMat& m = t.m[i];
+      const size_t n = (size_t)m.K * m.Cout, cp = (size_t)m.nrb * m.Cout * 4;
+      a1.r(U(m.W), n * 4).r(U(m.u), (size_t)m.Cout * 4).w(U(m.v), (size_t)m.K * 4).w(U(m.ws + SN_WS_TPART), (size_t)m.nrb * 4);
+      a2.r(U(m.W), n * 4).r(U(m.ws + SN_WS_TPART), (size_t)m.nrb * 4).w(U(m.v), (size_t)m.K * 4).w(U(m.ws + SN_WS_CPART), cp);
+      a3.r(U(m.ws + SN_WS_CPART), cp).w(U(m.u), (size_t)m.Cout * 4).w(U(m.ws + SN_WS_SPART), (size_t)m.nct * 4);
+    }
+    a1.r(ls, 12); a2.r(ls, 12); a3.r(ls, 12);
+    add(name + ".wu", stream, [this, t, ls](hipStream_t s) { return KF(dcg_sn_wu)(&t, P<const float>(ls), s); }, a1.v);
+    add(name + ".wtv", stream, [this, t, ls](hipStream_t s) { return KF(dcg_sn_wtv)(&t, P<const float>(ls), s); }, a2.v);
+    add(name + ".colsum", stream, [this, t, ls](hipStream_t s) { return KF(dcg_sn_colsum)(&t, P<const float>(ls), s); }, a3.v);
+    return sn_apply_op(name + ".apply", t, 0, ls, stream);
+  }
+  // the normalised copies from the stored sigma (init / checkpoint load): 1 launch
+  int sn_apply(std::string name, std::vector<SNTuple> mats, int stream) {
+    return sn_apply_op(name, sn_table("sn_apply", mats, true, false), 1, 0, stream);
+  }
+  // gradient projection, in place on each grad slice: 2 launches over all mats
+  int sn_project(std::string name, std::vector<SNTuple> mats, int stream) {
+    const SNTable t = sn_table("sn_project", mats, false, true);
+    AccList a1, a2;
+    for (int i = 0; i < t.n; ++i) {
+      const SNMat& m = t.m[i];
+      const size_t n = (size_t)m.K * m.Cout;
+      a1.r(U(m.grad), n * 4).r(U(m.W), n * 4).w(U(m.ws + SN_WS_DPART), (size_t)m.ncb * 4);
+      a2.r(U(m.ws + SN_WS_DPART), (size_t)m.ncb * 4).r(U(m.sigma), 4).r(U(m.u), (size_t)m.Cout * 4)
+          .r(U(m.v), (size_t)m.K * 4).w(U(m.grad), n * 4);
+    }
+    add(name + ".dot", stream, [this, t](hipStream_t s) { return KF(dcg_sn_dot)(&t, s); }, a1.v);
+    return add(name + ".project", stream, [this, t](hipStream_t s) { return KF(dcg_sn_project)(&t, s); }, a2.v);
+  }
   // dynamic loss scaling: flag ls[1] if any gradient is non-finite
   int nonfinite_check(std::string name, uintptr_t g, size_t n, uintptr_t ls, int stream) {
     return add(name, stream, [=](hipStream_t s) { return KF(dcg_nonfinite_check)(P<const float>(g), n, P<float>(ls), s); },
@@ -1048,6 +1130,13 @@ PYBIND11_MODULE(_dcgan_hip, m) {
   m.def("device_arch", &device_arch);
   m.attr("built_for") = "gfx950";
   m.attr("EMA_MAX_BLOCKS") = (unsigned)dcg::EMA_MAX_BLOCKS;
+  m.attr("SN_MAX_MATS") = (int)dcg::SN_MAX_MATS;
+  // (row blocks, rows per block, column tiles, streaming blocks, workspace floats) of a [K, Cout] matrix
+  m.def("sn_plan", [](long K, long Cout) {
+    const dcg::SNPlan p = dcg::sn_plan(K, Cout);
+    if (!p.nrb) throw std::runtime_error("sn_plan: matrix shape out of range");
+    return py::make_tuple(p.nrb, p.rpb, p.nct, p.ncb, p.ws_floats);
+  });
   m.attr("OP_LAUNCH") = (int)OP_LAUNCH;
   m.attr("OP_RECORD") = (int)OP_RECORD;
   m.attr("OP_WAIT") = (int)OP_WAIT;
@@ -1132,6 +1221,9 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("adam2", &Program::adam2)
       .def("ema", &Program::ema, py::arg("name"), py::arg("s"), py::arg("sbf"), py::arg("w"), py::arg("n"),
            py::arg("decay"), py::arg("step"), py::arg("step_bias"), py::arg("ls"), py::arg("stream"))
+      .def("sn_power", &Program::sn_power, py::arg("name"), py::arg("mats"), py::arg("ls"), py::arg("stream"))
+      .def("sn_apply", &Program::sn_apply, py::arg("name"), py::arg("mats"), py::arg("stream"))
+      .def("sn_project", &Program::sn_project, py::arg("name"), py::arg("mats"), py::arg("stream"))
       .def("nonfinite_check", &Program::nonfinite_check)
       .def("narrow_deconv", &Program::narrow_deconv)
       .def("nconv", &Program::nconv)

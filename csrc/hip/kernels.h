@@ -97,6 +97,59 @@ constexpr unsigned EMA_MAX_BLOCKS = 2048;
 // real target, which the launchers pick themselves (real_target != 1).
 enum GanObjective : int { GAN_BCE = 0, GAN_LSGAN = 1, GAN_HINGE = 2, GAN_BCE_T = 3 };
 
+// ---- spectral normalisation of D's weights (specnorm.hip). One descriptor per normalised
+// weight, viewed as W [K, Cout] row-major (TF's reshape(w, [-1, Cout]); the head is [K, 1]); a table
+// of up to SN_MAX_MATS of them rides in the kernel arguments so one grid covers them all.
+constexpr int SN_MAX_MATS = 8;
+constexpr int SN_MAX_ROW_BLOCKS = 256;        // row blocks per matrix (power step, launches 1 and 2)
+constexpr int SN_MAX_ROWS_PER_BLOCK = 1024;   // v rows a block stages in LDS -> K <= 262144
+constexpr int SN_MAX_STREAM_BLOCKS = 512;     // streaming blocks per matrix (copy write, dot, project)
+constexpr int SN_MAX_COL_TILES = 64;          // 256-column tiles -> Cout <= 16384
+// workspace layout (floats): [tpart 256 | spart 64 | dpart 512 | cpart nrb * Cout]
+constexpr int SN_WS_TPART = 0, SN_WS_SPART = 256, SN_WS_DPART = 320, SN_WS_CPART = 832;
+
+struct SNMat {
+  const float* W;   // fp32 master [K, Cout]
+  float* u;         // [Cout]
+  float* v;         // [K]
+  float* sigma;     // [1]
+  float* ws;        // workspace, sn_plan().ws_floats floats
+  void* hat;        // normalised copy W / sigma: elem_t [K * Cout] (mirror slice), or float (hat_f32)
+  float* grad;      // dL/d(W / sigma) -> dL/dW in place (projection only)
+  int K, Cout;
+  int nrb, rpb;     // row blocks, rows per block
+  int nct;          // 256-column tiles
+  int ncb;          // streaming blocks
+  int hat_f32;
+};
+
+struct SNTable {
+  int n;
+  SNMat m[SN_MAX_MATS];
+};
+
+struct SNPlan {
+  int nrb, rpb, nct, ncb;
+  size_t ws_floats;
+};
+
+// block counts and workspace size of a [K, Cout] matrix; nrb = 0: shape out of range
+static inline SNPlan sn_plan(long K, long Cout) {
+  SNPlan p = {0, 0, 0, 0, 0};
+  if (K <= 0 || Cout <= 0 || Cout > 256L * SN_MAX_COL_TILES ||
+      K > (long)SN_MAX_ROW_BLOCKS * SN_MAX_ROWS_PER_BLOCK || K * Cout >= (1L << 31))
+    return p;
+  long nrb = (K + 7) / 8;
+  if (nrb > SN_MAX_ROW_BLOCKS) nrb = SN_MAX_ROW_BLOCKS;
+  p.rpb = (int)((K + nrb - 1) / nrb);
+  p.nrb = (int)((K + p.rpb - 1) / p.rpb);
+  p.nct = (int)((Cout + 255) / 256);
+  long ncb = (K * Cout + 4095) / 4096;  // 4 float4 per thread
+  p.ncb = (int)(ncb < 1 ? 1 : ncb > SN_MAX_STREAM_BLOCKS ? SN_MAX_STREAM_BLOCKS : ncb);
+  p.ws_floats = (size_t)SN_WS_CPART + (size_t)p.nrb * (size_t)Cout;
+  return p;
+}
+
 }  // namespace dcg
 
 extern "C" {

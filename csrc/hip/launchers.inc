@@ -55,6 +55,14 @@ int DCG_API(dcg_step_end)(float* pd, float* pg, float b1d, float b2d, float b1g,
                           unsigned long long* step, float* ls, int growth_interval, hipStream_t s);
 int DCG_API(dcg_ema)(float* s, elem_t* sbf, const float* w, size_t n, float decay, const unsigned long long* step,
                      int step_bias, const float* ls, hipStream_t st);
+// spectral normalisation (specnorm.hip): power step = wu, wtv, colsum, apply(from_state = 0);
+// apply(from_state = 1) rewrites the normalised copies from the stored sigma; projection = dot, project
+int DCG_API(dcg_sn_wu)(const dcg::SNTable* t, const float* ls, hipStream_t s);
+int DCG_API(dcg_sn_wtv)(const dcg::SNTable* t, const float* ls, hipStream_t s);
+int DCG_API(dcg_sn_colsum)(const dcg::SNTable* t, const float* ls, hipStream_t s);
+int DCG_API(dcg_sn_apply)(const dcg::SNTable* t, int from_state, const float* ls, hipStream_t s);
+int DCG_API(dcg_sn_dot)(const dcg::SNTable* t, hipStream_t s);
+int DCG_API(dcg_sn_project)(const dcg::SNTable* t, hipStream_t s);
 int DCG_API(dcg_nonfinite_check)(const float* g, size_t n, float* ls, hipStream_t s);
 int DCG_API(dcg_pack)(const float* src, int T, int A, int Bd, elem_t* nat, elem_t* tr, int st, int sb, int sa, hipStream_t s);
 int DCG_API(dcg_philox_uniform)(float* out, size_t n, uint64_t seed, const unsigned long long* step, uint64_t stream_id,

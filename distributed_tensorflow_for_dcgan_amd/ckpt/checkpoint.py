@@ -113,6 +113,10 @@ def collect_state(engine) -> "OrderedDict[str, np.ndarray]":
     if ema is not None:  # tf.train.ExponentialMovingAverage shadow names
         for k, v in ema.tensors.items():
             out[k + G_EMA_SUFFIX] = v.detach().cpu().numpy().astype(np.float32)
+    sn = getattr(m, "d_sn", None)
+    if sn is not None:  # D's spectral-norm state: <var>/sn_u, <var>/sn_v, <var>/sn_sigma
+        for k, v in sn.tf_names().items():
+            out[k] = v.detach().cpu().numpy().astype(np.float32)
     return out
 
 
@@ -152,6 +156,19 @@ def apply_state(engine, sd: Dict[str, np.ndarray], strict: bool = True) -> Dict[
             else:
                 ema.flat.copy_(m.g.flat)
                 info["g_ema"] = "initialised from the loaded weights (the checkpoint has no shadow variables)"
+    sn = getattr(m, "d_sn", None)
+    if sn is not None:
+        # D's spectral-norm state: the saved u, v, sigma when all are there (an exact resume, no
+        # iteration), else a fresh state on the loaded weights (a checkpoint written without it)
+        names = sn.tf_names()
+        with torch.no_grad():
+            if all(k in tsd for k in names):
+                for k, v in names.items():
+                    v.copy_(tsd[k].to(v.dtype).reshape(v.shape))
+                info["d_sn"] = "loaded"
+            else:
+                engine.reset_d_sn()
+                info["d_sn"] = "initialised from the loaded weights (the checkpoint has no sn_u / sn_v / sn_sigma)"
     if hasattr(engine, "after_state_load"):
         engine.after_state_load()
     return info

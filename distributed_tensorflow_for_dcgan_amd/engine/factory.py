@@ -14,6 +14,7 @@ import torch
 
 from ..models.config import DCGANConfig
 from ..models.dcgan import DCGAN
+from ..ops import reference as R
 from ..parallel import dist as D
 from .reference_step import ReferenceStep
 
@@ -27,15 +28,21 @@ class ReferenceEngine:
     def __init__(self, cfg: DCGANConfig, batch_size: int, device: torch.device, seed: int = 0,
                  lr: float = 2e-4, beta1: float = 0.5, zero_debias: bool = False, rank: int = 0,
                  world: int = 1, z_seed: Optional[int] = None, g_ema_decay: Optional[float] = None,
-                 gan_loss: Optional[str] = None, label_smooth: Optional[float] = None, **_):
+                 gan_loss: Optional[str] = None, label_smooth: Optional[float] = None,
+                 d_spectral_norm: Optional[bool] = None, **_):
         self.cfg = cfg
         self.batch_size = batch_size
         self.device = device
+        self.seed = int(seed)
         self.model = DCGAN(cfg, device=device, seed=seed, zero_debias=zero_debias)
         self.world = world
+        if d_spectral_norm is None:
+            d_spectral_norm = R.env_spectral_norm()
+        if R.check_spectral_norm(d_spectral_norm):
+            self.model.enable_d_spectral_norm(seed)
         if world > 1:
             D.broadcast_tensors([self.model.g.flat, self.model.d.flat, self.model.g_bn.flat,
-                                 self.model.d_bn.flat])
+                                 self.model.d_bn.flat] + ([self.model.d_sn.flat] if self.model.d_sn else []))
         if g_ema_decay is None:  # (the HIP engine's switch, so both engines follow one environment)
             g_ema_decay = float(os.environ.get("DCGAN_G_EMA_DECAY") or 0.0)
         if gan_loss is None:
@@ -43,7 +50,9 @@ class ReferenceEngine:
         if label_smooth is None:
             label_smooth = float(os.environ.get("DCGAN_LABEL_SMOOTH") or 0.0)
         self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None,
-                                       g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth)
+                                       g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth,
+                                       d_spectral_norm=bool(d_spectral_norm), seed=seed)
+        self.d_spectral_norm = self.step_impl.d_spectral_norm
         self.g_ema_decay = self.step_impl.g_ema_decay
         self.gan_loss, self.label_smooth = self.step_impl.gan_loss, self.step_impl.label_smooth
         self.opt_d, self.opt_g = self.step_impl.opt_d, self.step_impl.opt_g
@@ -121,6 +130,14 @@ class ReferenceEngine:
     def sync_state_for_checkpoint(self) -> None:
         pass
 
+    def sync_check_tensors(self):
+        """What the cross-rank divergence check compares."""
+        return [self.model.g.flat, self.model.d.flat] + ([self.model.d_sn.flat] if self.model.d_sn else [])
+
+    def reset_d_sn(self) -> None:
+        """Fresh spectral-norm state from the current weights (a checkpoint without one)."""
+        self.model.d_sn.reset(self.model.d.tensors, self.seed)
+
     def sync_bn_state(self) -> None:
         """Average the BN moving averages over ranks (collective; every rank must call it).
         Each rank tracks its own local-batch statistics; the reference's shared PS copy saw
@@ -133,17 +150,18 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                  dtype: str = "bf16", seed: int = 0, rank: int = 0, world: int = 1, graph: bool = True,
                  allreduce_dtype: str = "fp32", lr: float = 2e-4, beta1: float = 0.5,
                  zero_debias: bool = False, bucket_mb: float = 32.0, g_ema_decay: Optional[float] = None,
-                 gan_loss: Optional[str] = None, label_smooth: Optional[float] = None):
+                 gan_loss: Optional[str] = None, label_smooth: Optional[float] = None,
+                 d_spectral_norm: Optional[bool] = None):
     if engine == "auto":  # every dtype (bf16 / fp16 / fp32) runs on the HIP kernels on an MI355X
         engine = "hip" if device.type == "cuda" else "reference"
     if engine == "reference":
         return ReferenceEngine(cfg, batch_size, device, seed=seed, lr=lr, beta1=beta1,
                                zero_debias=zero_debias, rank=rank, world=world, g_ema_decay=g_ema_decay,
-                               gan_loss=gan_loss, label_smooth=label_smooth)
+                               gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm)
     if engine == "hip":
         from .hip_engine import HipEngine
         return HipEngine(cfg, batch_size, device, dtype=dtype, seed=seed, lr=lr, beta1=beta1,
                          zero_debias=zero_debias, rank=rank, world=world, graph=graph,
                          allreduce_dtype=allreduce_dtype, bucket_mb=bucket_mb, g_ema_decay=g_ema_decay,
-                         gan_loss=gan_loss, label_smooth=label_smooth)
+                         gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm)
     raise ValueError("unknown engine %r" % engine)

@@ -153,7 +153,8 @@ class HipDDPMixin:
         updates, where each rank's conv-kernel masters are current only on its shard -- the 16-bit
         mirrors plus the masters of the all-reduced slices."""
         if self._shards is None or not self._sharded():
-            return [self.model.g.flat, self.model.d.flat] + ([self.g_ema.flat] if self.g_ema is not None else [])
+            return ([self.model.g.flat, self.model.d.flat] + ([self.g_ema.flat] if self.g_ema is not None else [])
+                    + ([self.model.d_sn.flat] if self.model.d_sn is not None else []))
         out = [self.wbf_g.flat, self.wbf_d.flat]
         for name, m, a, b in self._small:
             out.append((self.model.d if m == "d" else self.model.g).flat[a:b])
@@ -182,6 +183,7 @@ class HipDDPMixin:
         wd, wg = (_p(self.wire_d.flat), _p(self.wire_g.flat)) if self._wire_direct() else (0, 0)
         prog.adam_bf("adam_d", _p(self.model.d.flat), md, _p(self.grad_d.flat), _p(od.m.flat), _p(od.v.flat),
                      _p(od.powers), self.model.d.flat.numel(), od.lr, od.beta1, od.beta2, od.eps, gs, 0, ls, wd)
+        self._sn_power(prog, ls)  # spectral norm: behind Adam(D) on its stream; step_end comes later
         self._c_split = prog.size()
         G = self.model.g
         es = 0 if self.f32 else self.wbf_g.flat.element_size()

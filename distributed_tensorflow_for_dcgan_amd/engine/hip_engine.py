@@ -12,7 +12,12 @@ every step from C++ (eager, the default) or as hipGraphs:
   progB          D's backward of d_loss, both halves (D grads final)            -- "D chain"
   progC          TF-Adam(G), TF-Adam(D), beta powers, global step (+ 16-bit weight mirrors);
                  with ``g_ema_decay`` > 0 also ``ema_g``, the moving average of G's weights, after
-                 the last Adam launch over G
+                 the last Adam launch over G; with ``d_spectral_norm`` also ``sn_power`` (4 launches)
+                 after the last Adam launch over D
+
+With ``d_spectral_norm`` D's conv GEMMs and head read W / sigma(W) (the mirror slices / an fp32
+copy of the head hold it) and progB projects each weight gradient back through sigma
+(``sn_project``, 2 launches) right behind the launch that finalises it.
 
 Schedules (``_schedule``), all proven free of cross-stream overlaps by ``schedule_check.py``:
   "fused"       one process: both chains on two streams, G weight gradients on a third, one
@@ -128,7 +133,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  world: int = 1, graph: bool = True, allreduce_dtype: str = "fp32", bucket_mb: float = 32.0,
                  rank_seeded_z: bool = True, schedule: Optional[str] = None, dry_run: bool = False,
                  ddp: Optional[bool] = None, g_ema_decay: Optional[float] = None, gan_loss: Optional[str] = None,
-                 label_smooth: Optional[float] = None, **_):
+                 label_smooth: Optional[float] = None, d_spectral_norm: Optional[bool] = None,
+                 z_seed: Optional[int] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -147,6 +153,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # forced one-rank process group (DCGAN_FORCE_DDP=1 / ddp=True: RCCL on a one-GPU box)
         self.ddp = world > 1 or (D.ddp_forced() if ddp is None else bool(ddp))
         self.seed = int(seed)
+        # seed of the in-kernel z stream (as ReferenceEngine's z_seed): None = the model seed
+        self.z_seed = self.seed if z_seed is None else int(z_seed)
         self.rank_seeded_z = bool(rank_seeded_z)  # False only in equivalence tests
         self.lr, self.beta1 = float(lr), float(beta1)
         # moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates = the
@@ -164,14 +172,25 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         if label_smooth is None:
             label_smooth = float(os.environ.get("DCGAN_LABEL_SMOOTH") or 0.0)
         self.gan_loss, self.label_smooth = R.check_gan_loss(gan_loss, label_smooth)
+        # spectral normalisation of D's conv kernels and head: D computes with W / sigma(W), one
+        # power-iteration step after each Adam(D). Off: no buffer, no launch. None: DCGAN_D_SPECTRAL_NORM
+        if d_spectral_norm is None:
+            d_spectral_norm = R.env_spectral_norm()
+        self.d_spectral_norm = R.check_spectral_norm(d_spectral_norm)
+        if self.d_spectral_norm and os.environ.get("DCGAN_DDP_SHARD", "0") == "1":
+            raise ValueError("d_spectral_norm is not supported with DCGAN_DDP_SHARD=1: sigma needs the whole "
+                             "matrix, and under the sharded update each rank holds only 1/W of D's fp32 masters")
         if schedule is None and os.environ.get("DCGAN_SERIAL_DBWD") == "1":
             schedule = "serial"
         if schedule is not None and schedule not in SCHEDULES:
             raise ValueError("schedule must be one of %s" % (SCHEDULES,))
         self._sched_req = schedule
         self.model = DCGAN(cfg, device=device, seed=seed, zero_debias=zero_debias)
+        if self.d_spectral_norm:
+            self.model.enable_d_spectral_norm(seed)  # fresh u (CPU generator) + one power step
         if self.ddp and not self.dry:
-            D.broadcast_tensors([self.model.g.flat, self.model.d.flat, self.model.g_bn.flat, self.model.d_bn.flat])
+            D.broadcast_tensors([self.model.g.flat, self.model.d.flat, self.model.g_bn.flat, self.model.d_bn.flat]
+                                + ([self.model.d_sn.flat] if self.d_spectral_norm else []))
         self.opt_d = TFAdam(self.model.d, lr, beta1, power_suffix="")
         self.opt_g = TFAdam(self.model.g, lr, beta1, power_suffix="_1")
         self.opt_d.use_hip = self.opt_g.use_hip = True
@@ -273,7 +292,10 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # fp32 masters (TF layouts: HWIO conv, [kh,kw,out,in] deconv), written by the Adam kernel;
         # fp32 runs read the masters themselves
         if self.f32:
-            self.wbf_d, self.wbf_g = self.model.d, self.model.g
+            # (with spectral norm the conv GEMMs read W / sigma: a separate fp32 copy of D, of
+            # which only the "/w" slices are written and read)
+            self.wbf_d = self.model.d.like() if self.d_spectral_norm else self.model.d
+            self.wbf_g = self.model.g
         else:
             self.wbf_d = self.model.d.like(self.edt)
             self.wbf_g = self.model.g.like(self.edt)
@@ -285,6 +307,20 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             self.g_ema.flat.copy_(self.model.g.flat)
             self.wbf_g_ema = self.g_ema if self.f32 else self.model.g.like(self.edt)
             self.model.g_ema = self.g_ema  # (what DCGAN.sampler(ema=True) and the checkpoints see)
+        # spectral norm: the head's normalised fp32 copy, one workspace per weight and the kernels'
+        # descriptor tuples (W, u, v, sigma, ws, copy, copy is fp32, gradient, K, Cout)
+        self.sn_head = None
+        self._sn_mats: Dict[str, tuple] = {}
+        if self.d_spectral_norm:
+            sn = self.model.d_sn
+            self.sn_head = t(cfg.d_lin_in, dtype=torch.float32, zero=True)
+            self._sn_ws = {}
+            for name, K, C in sn.shapes:
+                self._sn_ws[name] = t(self.ext.sn_plan(K, C)[4], dtype=torch.float32, zero=True)
+                head = name.endswith("/Matrix")
+                hat = self.sn_head if head else self.wbf_d[name]
+                self._sn_mats[name] = (_p(self.model.d[name]), _p(sn.u[name]), _p(sn.v[name]), _p(sn.sigma[name]),
+                                       _p(self._sn_ws[name]), _p(hat), int(head), _p(self.grad_d[name]), K, C)
         # fp16: dynamic loss scale state [scale, overflow flag, good steps] (device-resident, so
         # the whole step incl. skip / halve / grow stays inside the captured graphs)
         self.loss_scale = (torch.tensor([self.INIT_LOSS_SCALE, 0.0, 0.0], dtype=torch.float32, device=self.device)
@@ -335,6 +371,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                 pairs.append((self.g_ema, self.wbf_g_ema))
             for ps, pb in pairs:
                 self.progCast.cast_to_bf16("mirror", _p(ps.flat), 0, _p(pb.flat), ps.flat.numel(), 1.0, 0.0, 0)
+        if self.d_spectral_norm:  # the normalised copies from the stored sigma (no iteration)
+            self.progCast.sn_apply("sn_copy", list(self._sn_mats.values()), 0)
         self.progS = self.progS_ema = None  # sampler programs (weights / their moving average), built lazily
         self.progEval = None
         self.progSum = None
@@ -510,12 +548,30 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         L = self.dl[0]
         return not self.f32 and L.cin <= 4 and L.cout == 64
 
+    def _head_w(self) -> torch.Tensor:
+        """The head's weight as the step reads it: the fp32 master, or its normalised copy."""
+        return self.sn_head if self.d_spectral_norm else self.model.d[self.cfg.d_lin_name + "/Matrix"]
+
+    def _sn_project(self, prog, names) -> None:
+        """Spectral norm: project the finished gradients of `names` (dL/d(W / sigma), as the step's
+        kernels produce them) back to dL/dW, in place -- right behind the launch that finalises
+        them, so the wire casts, collectives, the nonfinite check and Adam see dL/dW."""
+        if self.d_spectral_norm:
+            prog.sn_project("sn_project." + names[0].split("/")[0], [self._sn_mats[n] for n in names], 0)
+
+    def _sn_power(self, prog, ls: int = 0) -> None:
+        """Spectral norm: one power step on the weights Adam(D) just wrote + the normalised copies
+        (over the mirror slices that Adam wrote), on Adam(D)'s stream, before step_end clears the
+        fp16 overflow flag (an overflowed step skips it, as it skips Adam)."""
+        if self.d_spectral_norm:
+            prog.sn_power("sn_power", list(self._sn_mats.values()), ls, 0)
+
     # ---- forward
     def _build_forward(self, prog, update_ema: bool, z, train_z: bool):
         cfg, B = self.cfg, self.B
         B2 = 2 * B
         Pg, Pd = self.model.g, self.model.d
-        zseed = self.seed * 1000003 + 17 + 7919 * self.rank * int(self.rank_seeded_z)
+        zseed = self.z_seed * 1000003 + 17 + 7919 * self.rank * int(self.rank_seeded_z)
         # G projection + g_bn0 + relu; train_z: z ~ U(-1,1) generated inside the projection kernel
         # (Philox keyed by the device step counter); g_bn0 partial statistics straight from it:
         # one partial row per (8-row block of z, spatial position) -- see linear_fwd_kernel
@@ -601,14 +657,14 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             # head GEMV with the top BN layer's apply + LeakyReLU fused (writes its activation) + the
             # fused 3 losses of the objective in its last-arriving block
             st = self.bn[last.bn]
-            prog.gemv_head_bn("d_head+bn_apply+loss", _p(self.d_x[last.name]), _p(Pd[lin + "/Matrix"]),
+            prog.gemv_head_bn("d_head+bn_apply+loss", _p(self.d_x[last.name]), _p(self._head_w()),
                               _p(Pd[lin + "/bias"]), _p(self.logits), B2, cfg.d_lin_in, 0, _p(self.losses),
                               _p(self.dl_d), _p(self.dl_g), _p(self.prob), _p(self.loss_scale), _p(st["scale"]),
                               _p(st["shift"]), last.cout, B, LRELU, cfg.lrelu_leak, _p(self.d_a[last.name]),
                               obj, self.label_smooth)
         else:
             # head GEMV + the fused 3 losses of the objective in its last-arriving block
-            prog.gemv_head("d_head+loss", _p(prev), _p(Pd[lin + "/Matrix"]), _p(Pd[lin + "/bias"]), _p(self.logits),
+            prog.gemv_head("d_head+loss", _p(prev), _p(self._head_w()), _p(Pd[lin + "/bias"]), _p(self.logits),
                            B2, cfg.d_lin_in, 0, _p(self.losses), _p(self.dl_d), _p(self.dl_g), _p(self.prob),
                            _p(self.loss_scale), obj, self.label_smooth)
 
@@ -654,6 +710,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                 else:
                     self._wgrad(prog, L.name, 0, src, L.in_hw, L.in_hw, L.cin, dx, B2, L.out_hw, L.out_hw, L.cout, pad,
                                 gD[L.name + "/w"], stream=ws)
+                # spectral norm: this kernel's gradient (and, with the top layer, the head's) is final
+                self._sn_project(prog, [L.name + "/w"] + ([lin + "/Matrix"] if i == len(self.dl) - 1 else []))
                 if i == len(self.dl) - 1:
                     # head + top layer gradients final: DDP splits the segment here so their
                     # all-reduce (76 % of D's bytes at 64x64) overlaps the rest of D's backward
@@ -715,7 +773,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         K = cfg.d_lin_in
         C = last.cout
         if not (bool(last.bn) and C % 64 == 0 and K % C == 0):
-            prog.head_bwd(name, _p(xa), _p(dl), _p(Pd[lin + "/Matrix"]), _p(dx), _p(dW), _p(db), R, K, 0)
+            prog.head_bwd(name, _p(xa), _p(dl), _p(self._head_w()), _p(dx), _p(dW), _p(db), R, K, 0)
             return None
         S = K // C
         # row splits: RS x the workgroups of one-per-64-columns (the head's R rows are few)
@@ -725,7 +783,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         part = self._stats_buf(name + ".bnstats", groups * RS * S, C)
         st = self.bn[last.bn]
         r0 = 0 if group_offset == 0 else self.B
-        prog.head_bwd_rs(name, _p(xa), _p(dl), _p(Pd[lin + "/Matrix"]), _p(dx), _p(dW), _p(db), R, K, 0,
+        prog.head_bwd_rs(name, _p(xa), _p(dl), _p(self._head_w()), _p(dx), _p(dW), _p(db), R, K, 0,
                          _p(self.d_x[last.name][r0:]), _p(self.d_a[last.name][r0:]), _p(st["mean"][group_offset:]),
                          _p(st["rstd"][group_offset:]), C, R // groups, LRELU, cfg.lrelu_leak, _p(part), RS)
         return part, RS * S
@@ -972,6 +1030,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             prog.adam_bf("adam_d", _p(self.model.d.flat), md, _p(self.grad_d.flat), _p(od.m.flat),
                          _p(od.v.flat), _p(od.powers), self.model.d.flat.numel(), od.lr, od.beta1, od.beta2, od.eps,
                          gs, 0, ls)
+            self._sn_power(prog, ls)
             prog.step_end("step_end", _p(od.powers), _p(og.powers), od.beta1, od.beta2, og.beta1, og.beta2,
                           _p(self.step_counter), 0, ls, self.LOSS_SCALE_GROWTH)
 
@@ -985,6 +1044,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                    _p(self.grad_d.flat), _p(od.m.flat), _p(od.v.flat), _p(od.powers), Dm.flat.numel(), od.lr,
                    od.beta1, od.beta2, od.eps, 1.0 / self.world, _p(self.step_counter), 0)
         self._ema_g(prog, 0)
+        self._sn_power(prog)
 
     def _repack_weights_now(self):
         if self.progCast.size():
@@ -1279,5 +1339,12 @@ class HipEngine(HipDDPMixin, HipEngineAux):
 
     def after_state_load(self) -> None:
         """Call after loading weights/slots from a checkpoint: refresh the 16-bit weight mirrors
-        (the moving average's too)."""
+        (the moving average's too) and, with spectral norm, the normalised copies from the loaded
+        state."""
         self._repack_weights_now()
+
+    def reset_d_sn(self) -> None:
+        """Fresh spectral-norm state from the current weights (a checkpoint without one)."""
+        if not self.dry:
+            torch.cuda.synchronize(self.device)
+        self.model.d_sn.reset(self.model.d.tensors, self.seed)

@@ -23,8 +23,13 @@ from ..optim.adam import TFAdam
 class ReferenceStep:
     def __init__(self, model: DCGAN, lr: float = 2e-4, beta1: float = 0.5,
                  grad_hook: Optional[Callable[[str, torch.Tensor], None]] = None, g_ema_decay: float = 0.0,
-                 gan_loss: str = "bce", label_smooth: float = 0.0):
+                 gan_loss: str = "bce", label_smooth: float = 0.0, d_spectral_norm: bool = False, seed: int = 0):
         self.model = model
+        # spectral normalisation of D's conv kernels and head (model.d_sn; ops.reference.sn_power /
+        # spectral_normalize): D computes with W / sigma(W), one power step after each Adam(D)
+        self.d_spectral_norm = R.check_spectral_norm(d_spectral_norm)
+        if self.d_spectral_norm and model.d_sn is None:
+            model.enable_d_spectral_norm(seed)
         # objective (ops.reference.gan_losses): bce | lsgan | hinge, D's real target = 1 - label_smooth
         self.gan_loss, self.label_smooth = R.check_gan_loss(gan_loss, label_smooth)
         # moving average of G's weights (model.g_ema; ops.reference.ema_update_), 0 = none kept
@@ -41,6 +46,8 @@ class ReferenceStep:
     def forward_losses(self, real: torch.Tensor, z: torch.Tensor, Pg=None, Pd=None, update_ema=True,
                        record=None):
         m = self.model
+        if self.d_spectral_norm:  # D computes with W / sigma(W); autograd projects the gradient
+            Pd = m.d_sn_weights(Pd)
         fake = m.generator(z, train=True, P=Pg, update_ema=update_ema, record=record)
         B = real.shape[0]
         both = torch.cat([real, fake], 0)
@@ -82,6 +89,8 @@ class ReferenceStep:
         self.opt_d.step(gd)
         self.opt_g.step(gg)
         self.global_step += 1
+        if self.d_spectral_norm:  # after Adam(D): one power step on the new weights
+            self.model.d_sn.power_step_(self.model.d.tensors)
         if self.g_ema_decay > 0:  # after Adam(G), with the step count after its increment
             with torch.no_grad():
                 R.ema_update_(self.model.g_ema.flat, self.model.g.flat, self.g_ema_decay, self.global_step)

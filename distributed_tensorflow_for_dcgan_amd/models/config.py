@@ -9,6 +9,7 @@ name and TF weight layout is derived in one place (SURVEY.md §2.6, Appendix A.2
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Tuple
 
@@ -54,6 +55,12 @@ class ConvSpec:
         return same_pads(self.in_hw if self.kind == "conv" else self.out_hw)
 
 
+def _env_d_bn() -> bool:
+    """Default of ``DCGANConfig.d_bn``: DCGAN_D_BATCH_NORM=0 drops D's batch norm wherever a config is
+    built without saying (the benchmark's A/B switch); unset / anything else keeps it."""
+    return (os.environ.get("DCGAN_D_BATCH_NORM") or "1").strip().lower() not in ("0", "false", "no", "off")
+
+
 @dataclass(frozen=True)
 class DCGANConfig:
     output_size: int = 64
@@ -67,6 +74,9 @@ class DCGANConfig:
     bn_momentum: float = 0.9
     lrelu_leak: float = 0.2
     init_stddev: float = 0.02
+    # batch norm in D (after every conv but the first). False: the BN-free discriminator that
+    # spectral normalisation is meant for -- no d_bn* variables, an empty d_bn state
+    d_bn: bool = field(default_factory=_env_d_bn)
 
     @property
     def n_stages(self) -> int:
@@ -121,7 +131,7 @@ class DCGANConfig:
             cout = self._ch(self.df_dim, 2 ** i)
             layers.append(ConvSpec(
                 name="d_h%d_conv" % i, kind="conv", in_hw=sizes[i], out_hw=sizes[i + 1],
-                cin=cin, cout=cout, bn=None if i == 0 else "d_bn%d" % i, act="lrelu"))
+                cin=cin, cout=cout, bn="d_bn%d" % i if (i > 0 and self.d_bn) else None, act="lrelu"))
             cin = cout
         return layers
 
@@ -169,6 +179,13 @@ class DCGANConfig:
     def d_bn_layers(self) -> List[Tuple[str, int]]:
         return [(L.bn, L.cout) for L in self.d_layers() if L.bn]
 
+    def d_sn_weights(self) -> List[Tuple[str, int, int]]:
+        """(TF name, K, Cout) of the weights D's spectral normalisation acts on, in d_variables()
+        order: every conv kernel viewed as TF's reshape(w, [-1, Cout]) and the head [K, 1]."""
+        out = [(L.name + "/w", 25 * L.cin, L.cout) for L in self.d_layers()]
+        out.append((self.d_lin_name + "/Matrix", self.d_lin_in, 1))
+        return out
+
     def param_counts(self) -> Dict[str, int]:
         g = sum(math.prod(s) for _, s, _ in self.g_variables())
         d = sum(math.prod(s) for _, s, _ in self.d_variables())
@@ -196,4 +213,5 @@ class DCGANConfig:
 def config_from_flags(flags) -> DCGANConfig:
     return DCGANConfig(output_size=int(flags.output_size), c_dim=int(flags.c_dim),
                        gf_dim=int(flags.gf_dim), df_dim=int(flags.df_dim), z_dim=int(flags.z_dim),
-                       depth=int(flags.depth), max_channels=int(flags.max_channels))
+                       depth=int(flags.depth), max_channels=int(flags.max_channels),
+                       d_bn=bool(getattr(flags, "d_batch_norm", True)))

@@ -203,6 +203,62 @@ class BNState:
         return out
 
 
+class SNState:
+    """Spectral-normalisation state of D's weights (``cfg.d_sn_weights()``): per weight the power
+    iteration's u [Cout] and v [K] and the norm estimate sigma [1], fp32 views of one flat buffer
+    (what DDP broadcasts and the divergence check compares). The forward of step t reads
+    W_t / sigma with the state computed from W_t at the end of step t-1."""
+
+    ALIGN = 64
+
+    def __init__(self, shapes: Sequence[Tuple[str, int, int]], device="cpu"):
+        self.shapes = list(shapes)
+        pad = lambda n: -(-n // self.ALIGN) * self.ALIGN  # noqa: E731
+        off, offs = 0, {}
+        for name, K, C in self.shapes:
+            offs[name] = (off, off + pad(C), off + pad(C) + pad(K))
+            off += pad(C) + pad(K) + self.ALIGN
+        self.flat = torch.zeros(off, device=device, dtype=torch.float32)
+        self.u: Dict[str, torch.Tensor] = {}
+        self.v: Dict[str, torch.Tensor] = {}
+        self.sigma: Dict[str, torch.Tensor] = {}
+        for name, K, C in self.shapes:
+            a, b, c = offs[name]
+            self.u[name] = self.flat[a:a + C]
+            self.v[name] = self.flat[b:b + K]
+            self.sigma[name] = self.flat[c:c + 1]
+
+    @torch.no_grad()
+    def reset(self, d_tensors: Dict[str, torch.Tensor], seed: int) -> None:
+        """Fresh state: u from ``ops.reference.sn_init_u(seed)``, then one power step on the
+        current weights (computed on the CPU, so every engine starts from the same bits)."""
+        us = R.sn_init_u(self.shapes, seed)
+        for name, K, C in self.shapes:
+            W = d_tensors[name].detach().to("cpu", torch.float32).reshape(K, C)
+            u, v, s = R.sn_power(W, us[name])
+            self.u[name].copy_(u)
+            self.v[name].copy_(v)
+            self.sigma[name].copy_(s.reshape(1))
+
+    @torch.no_grad()
+    def power_step_(self, d_tensors: Dict[str, torch.Tensor]) -> None:
+        """One power step per weight from the stored u (the reference engine's step 4)."""
+        for name, K, C in self.shapes:
+            u, v, s = R.sn_power(d_tensors[name].detach().reshape(K, C), self.u[name])
+            self.u[name].copy_(u)
+            self.v[name].copy_(v)
+            self.sigma[name].copy_(s.reshape(1))
+
+    def tf_names(self) -> "OrderedDict[str, torch.Tensor]":
+        """Checkpoint keys: <var>/sn_u, <var>/sn_v, <var>/sn_sigma."""
+        out = OrderedDict()
+        for name, _, _ in self.shapes:
+            out[name + "/sn_u"] = self.u[name]
+            out[name + "/sn_v"] = self.v[name]
+            out[name + "/sn_sigma"] = self.sigma[name]
+        return out
+
+
 # --------------------------------------------------------------------------- model
 class DCGAN:
     """Parameters + BN state of one DCGAN; reference forward functions."""
@@ -227,6 +283,26 @@ class DCGAN:
         # moving average of G's weights (tf.train.ExponentialMovingAverage shadows, same layout
         # as g); None unless an engine keeps one (g_ema_decay > 0)
         self.g_ema: Optional[ParamSet] = None
+        # spectral-normalisation state of D's weights; None unless an engine normalises them
+        # (d_spectral_norm)
+        self.d_sn: Optional[SNState] = None
+
+    def enable_d_spectral_norm(self, seed: int) -> SNState:
+        """Create D's spectral-norm state (fresh: ``SNState.reset``) and return it."""
+        self.d_sn = SNState(self.cfg.d_sn_weights(), device=self.device)
+        self.d_sn.reset(self.d.tensors, seed)
+        return self.d_sn
+
+    def d_sn_weights(self, P: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """D's parameters with every conv kernel and the head replaced by W / sigma(W)
+        (``ops.reference.spectral_normalize`` with the stored u, v), for ``discriminator(P=...)``;
+        differentiable in the entries of P."""
+        P = P if P is not None else self.d.tensors
+        out = dict(P)
+        for name, K, C in self.d_sn.shapes:
+            w = P[name]
+            out[name] = R.spectral_normalize(w.reshape(K, C), self.d_sn.u[name], self.d_sn.v[name]).reshape(w.shape)
+        return out
 
     # ---------------------------------------------------------------- reference G
     def generator(self, z: torch.Tensor, train: bool = True, P: Optional[Dict[str, torch.Tensor]] = None,

@@ -42,6 +42,7 @@ def collect(engine, losses: Dict[str, float], steps_per_sec: Optional[float] = N
             vals.append(S.histogram_from_stats(name, row))
             if name.endswith("/activations"):
                 vals.append(S.scalar(name[:-len("/activations")] + "/sparsity", float(row[5] / max(1.0, row[2]))))
+        vals += _sn_sigmas(engine)
         _tail(vals, steps_per_sec, loader_stats)
         return vals
     if "z" in acts:
@@ -62,8 +63,18 @@ def collect(engine, losses: Dict[str, float], steps_per_sec: Optional[float] = N
         vals.append(S.scalar(name + "/sparsity", float((a == 0).mean())))
     for name, t in engine.model.all_named_variables().items():
         vals.append(S.histogram(name, _np(t)))
+    vals += _sn_sigmas(engine)
     _tail(vals, steps_per_sec, loader_stats)
     return vals
+
+
+def _sn_sigmas(engine) -> List[bytes]:
+    """One scalar sn_sigma/<layer> per spectrally normalised D weight (d_spectral_norm)."""
+    sn = getattr(engine.model, "d_sn", None)
+    if sn is None:
+        return []
+    return [SummaryWriter.scalar("sn_sigma/" + name.split("/")[0], float(sn.sigma[name].item()))
+            for name, _, _ in sn.shapes]
 
 
 def _tail(vals: List[bytes], steps_per_sec: Optional[float], loader_stats: Optional[dict]) -> None:

@@ -680,3 +680,76 @@ def ema_(s: torch.Tensor, sbf: Optional[torch.Tensor], w: torch.Tensor, decay: f
     prog = ext().Program(dt)
     prog.ema("ema", _p(s), _p(sbf), _p(w), s.numel(), float(decay), _p(step), int(step_bias), _p(ls), 0)
     run(prog)
+
+
+# --------------------------------------------------------------------------- spectral norm (D)
+def sn_plan(K: int, Cout: int) -> Tuple[int, int, int, int, int]:
+    """(row blocks, rows per block, column tiles, streaming blocks, workspace floats) of the
+    spectral-norm kernels for a [K, Cout] matrix."""
+    return tuple(int(x) for x in ext().sn_plan(int(K), int(Cout)))
+
+
+def sn_workspace(K: int, Cout: int, device) -> torch.Tensor:
+    return torch.zeros(sn_plan(K, Cout)[4], dtype=torch.float32, device=device)
+
+
+_SN_BUILDS = {"bf16": 0, "fp16": 1, "fp32": 2}
+
+
+def _sn_tuples(what, mats, hats, grads, build):
+    """Program dtype + the descriptor tuples of ``Program.sn_*`` from (W, u, v, sigma, ws) rows."""
+    if build not in _SN_BUILDS:
+        raise ValueError("%s: build must be one of %s" % (what, sorted(_SN_BUILDS)))
+    dt = _SN_BUILDS[build]
+    edt = {0: torch.bfloat16, 1: torch.float16, 2: torch.float32}[dt]
+    out = []
+    for i, (W, u, v, sigma, ws) in enumerate(mats):
+        if W.dim() != 2:
+            raise ValueError("%s: W must be [K, Cout]" % what)
+        K, C = W.shape
+        if K == 0 or C == 0:
+            raise ValueError("%s: K and Cout must be positive" % what)
+        for t in (W, u, v, sigma, ws):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise TypeError("%s: W, u, v, sigma and ws must be contiguous float32" % what)
+        if u.numel() != C or v.numel() != K or sigma.numel() != 1 or ws.numel() < sn_plan(K, C)[4]:
+            raise ValueError("%s: u [Cout], v [K], sigma [1], ws [sn_plan(K, Cout)[4]]" % what)
+        hat = hats[i] if hats is not None else None
+        grad = grads[i] if grads is not None else None
+        hf = 0
+        if hat is not None:
+            if hat.dtype not in (torch.float32, edt) or hat.numel() != K * C or not hat.is_contiguous():
+                raise TypeError("%s: the normalised copy must be float32 or %s, K * Cout elements" % (what, edt))
+            hf = int(hat.dtype == torch.float32)
+        if grad is not None and (grad.dtype != torch.float32 or grad.numel() != K * C or not grad.is_contiguous()):
+            raise TypeError("%s: the gradient must be contiguous float32, K * Cout elements" % what)
+        out.append((_p(W), _p(u), _p(v), _p(sigma), _p(ws), _p(hat), hf, _p(grad), K, C))
+    return dt, out
+
+
+def sn_power_(mats, hats, ls: Optional[torch.Tensor] = None, build: str = "fp32") -> None:
+    """One power-iteration step per matrix, in place: mats = [(W [K, Cout], u, v, sigma, ws)], all
+    fp32; v = W u / max(|W u|, eps), sigma = max(|W^T v|, eps), u = W^T v / sigma, and hats[i]
+    (fp32, or the 16-bit dtype of ``build``) receives W * (1 / sigma). ls = fp16 loss-scale state: a
+    set overflow flag leaves everything untouched. 4 launches for all matrices (at most 8)."""
+    dt, tup = _sn_tuples("sn_power_", mats, hats, None, build)
+    prog = ext().Program(dt)
+    prog.sn_power("sn_power", tup, _p(ls), 0)
+    run(prog)
+
+
+def sn_apply_(mats, hats, build: str = "fp32") -> None:
+    """hats[i] = W * (1 / sigma) from the stored sigma (no iteration): 1 launch."""
+    dt, tup = _sn_tuples("sn_apply_", mats, hats, None, build)
+    prog = ext().Program(dt)
+    prog.sn_apply("sn_apply", tup, 0)
+    run(prog)
+
+
+def sn_project_(mats, grads, build: str = "fp32") -> None:
+    """In place grads[i] = (G - <G, W> / sigma * v u^T) / sigma with the stored u, v, sigma: the
+    gradient of W / sigma(W) projected back to W. 2 launches for all matrices."""
+    dt, tup = _sn_tuples("sn_project_", mats, None, grads, build)
+    prog = ext().Program(dt)
+    prog.sn_project("sn_project", tup, 0)
+    run(prog)

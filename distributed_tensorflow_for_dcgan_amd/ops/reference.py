@@ -13,7 +13,7 @@ is tested against. They reproduce, with explicit padding/cropping:
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -166,3 +166,65 @@ def check_ema_decay(decay) -> float:
     if not 0.0 <= d < 1.0:
         raise ValueError("g_ema_decay must satisfy 0 <= decay < 1, got %r" % (decay,))
     return d
+
+
+# --------------------------------------------------------------------------- spectral norm (D)
+SN_EPS = 1e-12
+
+
+def sn_power(W2d: torch.Tensor, u: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One power-iteration step on W2d [K, Cout] from u [Cout]: t = W u, v = t / max(|t|, eps),
+    s = W^T v, sigma = max(|s|, eps), u' = s / sigma. Returns (u', v, sigma); none of them
+    carries a gradient."""
+    with torch.no_grad():
+        t = W2d @ u
+        v = t / t.norm().clamp_min(SN_EPS)
+        s = W2d.t() @ v
+        sigma = s.norm().clamp_min(SN_EPS)
+        return s / sigma, v, sigma
+
+
+def spectral_normalize(W2d: torch.Tensor, u: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """W / sigma with sigma = v^T W u and u, v constants (differentiable in W: autograd of this
+    expression is the oracle of the projected gradient)."""
+    sigma = (v.detach() @ W2d @ u.detach()).clamp_min(SN_EPS)
+    return W2d / sigma
+
+
+def sn_project(G: torch.Tensor, W2d: torch.Tensor, u: torch.Tensor, v: torch.Tensor, sigma) -> torch.Tensor:
+    """dL/dW from G = dL/d(W / sigma): (G - <G, W / sigma> v u^T) / sigma, <G, W / sigma> taken as
+    <G, W> / sigma."""
+    sigma = torch.as_tensor(sigma, dtype=G.dtype).reshape(())
+    d = (G * W2d).sum() / sigma
+    return (G - d * torch.outer(v, u)) / sigma
+
+
+def sn_init_u(shapes: Sequence[Tuple[str, int, int]], seed: int) -> "Dict[str, torch.Tensor]":
+    """Fresh u vectors: randn from torch.Generator().manual_seed(seed) on the CPU, one draw per
+    weight in the order given ((name, K, Cout), d_variables() order), each normalised."""
+    gen = torch.Generator().manual_seed(int(seed))
+    out = {}
+    for name, _, cout in shapes:
+        u = torch.randn(cout, generator=gen)
+        out[name] = u / u.norm().clamp_min(SN_EPS)
+    return out
+
+
+def check_spectral_norm(flag) -> bool:
+    """Validated d_spectral_norm switch: a bool, 0 / 1, or one of their usual spellings."""
+    if isinstance(flag, str):
+        s = flag.strip().lower()
+        if s in ("1", "true", "yes", "on"):
+            return True
+        if s in ("", "0", "false", "no", "off"):
+            return False
+        raise ValueError("d_spectral_norm must be a boolean, got %r" % (flag,))
+    if isinstance(flag, bool) or (isinstance(flag, int) and flag in (0, 1)):
+        return bool(flag)
+    raise ValueError("d_spectral_norm must be a boolean, got %r" % (flag,))
+
+
+def env_spectral_norm() -> bool:
+    """The engines' default where none is given: DCGAN_D_SPECTRAL_NORM."""
+    import os
+    return check_spectral_norm(os.environ.get("DCGAN_D_SPECTRAL_NORM") or "0")

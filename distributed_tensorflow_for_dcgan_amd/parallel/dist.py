@@ -147,11 +147,12 @@ def broadcast_tensors(tensors: Sequence[torch.Tensor], src: int = 0) -> None:
     if not is_initialized():
         return
     for t in tensors:
-        dist.broadcast(t, src=src)
+        if t.numel():  # (a BN-free D has an empty d_bn state)
+            dist.broadcast(t, src=src)
 
 
 def all_reduce_mean_(t: torch.Tensor) -> None:
-    if not is_initialized():
+    if not is_initialized() or t.numel() == 0:
         return
     dist.all_reduce(t, op=dist.ReduceOp.SUM)
     t.mul_(1.0 / dist.get_world_size())

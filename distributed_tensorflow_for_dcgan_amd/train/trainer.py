@@ -158,10 +158,13 @@ def run(flags: Flags, out=None) -> int:
                           lr=float(flags.learning_rate), beta1=float(flags.beta1),
                           zero_debias=bool(flags.bn_zero_debias), bucket_mb=float(flags.bucket_mb),
                           g_ema_decay=float(flags.g_ema_decay), gan_loss=str(flags.gan_loss),
-                          label_smooth=float(flags.label_smooth))
+                          label_smooth=float(flags.label_smooth), d_spectral_norm=bool(flags.d_spectral_norm))
     if chief:
         print("GAN objective: %s, label_smooth %g (D's real target %g)" % (
             engine.gan_loss, engine.label_smooth, 1.0 - engine.label_smooth), file=out, flush=True)
+        print("discriminator: batch norm %s, spectral norm %s" % (
+            "on" if cfg.d_bn else "off", "on" if getattr(engine, "d_spectral_norm", False) else "off"),
+            file=out, flush=True)
     if flags.log_device_placement:
         for line in placement_report(engine, device, rank, world):
             print(line, file=out, flush=True)
@@ -176,6 +179,8 @@ def run(flags: Flags, out=None) -> int:
             print("note: checkpoint has no optimiser state (reference-style); Adam restarts at t=0", file=out)
         if info and "g_ema" in info:
             print("generator weight EMA: %s" % info["g_ema"], file=out)
+        if info and "d_sn" in info:
+            print("discriminator spectral norm state: %s" % info["d_sn"], file=out)
 
     if flags.explicitly_set("is_train") and not flags.is_train:
         try:

@@ -84,6 +84,13 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                                "(least squares) | hinge"),
     ("label_smooth", "float", 0.0, "one-sided label smoothing s, 0 <= s < 0.5: D's real target becomes 1 - s "
                                    "(bce and lsgan; the fake target and G's target do not move)"),
+    ("d_spectral_norm", "bool", False, "spectral normalisation of the discriminator's conv kernels and head: D "
+                                       "computes with W / sigma(W), sigma from one power-iteration step per "
+                                       "training step. In front of a batch norm it mostly acts on layer 0 and the "
+                                       "head (BN is scale-invariant); the SN-GAN recipe is --gan_loss=hinge "
+                                       "--d_spectral_norm --nod_batch_norm"),
+    ("d_batch_norm", "bool", True, "batch norm in the discriminator (--nod_batch_norm: a BN-free D, no d_bn* "
+                                   "variables); SN-GAN recipe: --gan_loss=hinge --d_spectral_norm --nod_batch_norm"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
