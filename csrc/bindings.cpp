@@ -819,6 +819,28 @@ class Program {
                            P<unsigned long long>(step), reinterpret_cast<unsigned*>(ctr), s);
     }, acc.v);
   }
+  // the D-only sub-step's one-launch update (adam1_kernel): TF-Adam over one set + its 16-bit
+  // mirror + its beta powers; no step counter, no other set
+  int adam1(std::string name, uintptr_t w, uintptr_t wbf, uintptr_t g, uintptr_t m, uintptr_t v, uintptr_t powers,
+            size_t n, float lr, float b1, float b2, float eps, float gscale, int stream) {
+    if (dt_ == 2) throw std::runtime_error("adam1: 16-bit builds only");
+    if (n % 4 || !w || !wbf || !g || !m || !v || !powers)
+      throw std::runtime_error("adam1: n % 4 == 0 and non-null w, mirror, g, m, v, powers");
+    void* ctr = dev_alloc(sizeof(unsigned), nullptr, true);
+    AccList acc;
+    acc.w(w, n * 4).w(wbf, n * es_).r(g, n * 4).w(m, n * 4).w(v, n * 4).w(powers, 8).w((uintptr_t)ctr, 4);
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_adam1)(P<float>(w), P<elem_t>(wbf), P<const float>(g), P<float>(m), P<float>(v), P<float>(powers), n,
+                           lr, b1, b2, eps, gscale, reinterpret_cast<unsigned*>(ctr), s);
+    }, acc.v);
+  }
+  // the sub-step's step_end (d_step_end_kernel): D's powers + the fp16 loss-scale rule only
+  int d_step_end(std::string name, uintptr_t pd, float b1d, float b2d, int stream, uintptr_t ls, int growth_interval) {
+    if (!pd) throw std::runtime_error("d_step_end: the powers must be non-null");
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_d_step_end)(P<float>(pd), b1d, b2d, P<float>(ls), growth_interval, s);
+    }, AccList().w(pd, 8).w(ls, 12).v);
+  }
   // narrow2.hip: TF-SAME stride-2 5x5 conv, 1..4 input -> 64 output channels, persistent `grid`
   // workgroups (<= tiles: nconv_tiles). bx != 0: fused BN-backward statistics of the layer below
   // (x = bx, y = by, one BN group), one partial row [2][64] per workgroup into part.
@@ -1130,6 +1152,7 @@ PYBIND11_MODULE(_dcgan_hip, m) {
   m.def("device_arch", &device_arch);
   m.attr("built_for") = "gfx950";
   m.attr("EMA_MAX_BLOCKS") = (unsigned)dcg::EMA_MAX_BLOCKS;
+  m.attr("ADAM1_MAX_BLOCKS") = (unsigned)dcg::ADAM1_MAX_BLOCKS;
   m.attr("SN_MAX_MATS") = (int)dcg::SN_MAX_MATS;
   // (row blocks, rows per block, column tiles, streaming blocks, workspace floats) of a [K, Cout] matrix
   m.def("sn_plan", [](long K, long Cout) {
@@ -1219,6 +1242,11 @@ PYBIND11_MODULE(_dcgan_hip, m) {
            py::arg("b2d"), py::arg("b1g"), py::arg("b2g"), py::arg("step"), py::arg("stream"), py::arg("ls") = 0,
            py::arg("growth_interval") = 2000)
       .def("adam2", &Program::adam2)
+      .def("adam1", &Program::adam1, py::arg("name"), py::arg("w"), py::arg("wbf"), py::arg("g"), py::arg("m"),
+           py::arg("v"), py::arg("powers"), py::arg("n"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
+           py::arg("gscale") = 1.f, py::arg("stream") = 0)
+      .def("d_step_end", &Program::d_step_end, py::arg("name"), py::arg("pd"), py::arg("b1d"), py::arg("b2d"),
+           py::arg("stream") = 0, py::arg("ls") = 0, py::arg("growth_interval") = 2000)
       .def("ema", &Program::ema, py::arg("name"), py::arg("s"), py::arg("sbf"), py::arg("w"), py::arg("n"),
            py::arg("decay"), py::arg("step"), py::arg("step_bias"), py::arg("ls"), py::arg("stream"))
       .def("sn_power", &Program::sn_power, py::arg("name"), py::arg("mats"), py::arg("ls"), py::arg("stream"))

@@ -92,6 +92,10 @@ struct WGrad3Args {                 // wgrad3.hip: 25-tap gather GEMM, in-kernel
 // workgroups; larger buffers grid-stride
 constexpr unsigned EMA_MAX_BLOCKS = 2048;
 
+// grid cap of the D sub-step's one-launch update (misc.hip adam1_kernel): as adam2_kernel's ~512
+// blocks, since every block bumps one arrival counter; larger buffers grid-stride
+constexpr unsigned ADAM1_MAX_BLOCKS = 512;
+
 // GAN objectives of the loss / head kernels (misc.hip gan_loss_block). The first three are the
 // ids of the launchers and bindings; GAN_BCE_T is the kernel instance of bce with a smoothed
 // real target, which the launchers pick themselves (real_target != 1).

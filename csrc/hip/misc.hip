@@ -892,6 +892,77 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* src, in
   }
 }
 
+// ---------------------------------------------------------------- D-only sub-step updates
+// The D-only sub-step's update (d_steps > 1, single-process 16-bit path): TF-Adam over ONE flat
+// buffer + its 16-bit mirror + ITS beta-power pair in one launch -- adam_kernel's arithmetic
+// (the results are bitwise those of adam_kernel followed by a powers update) with adam2_kernel's
+// last-arrival mechanism. Never touches the global step or the other model's powers.
+// n % 4 == 0 (64-aligned ParamSet padding); at most ADAM1_MAX_BLOCKS blocks, grid-stride.
+__global__ __launch_bounds__(256) void adam1_kernel(float* __restrict__ w, elem_t* __restrict__ wbf,
+                                                    const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, float* __restrict__ powers, size_t n,
+                                                    float lr, float b1, float b2, float eps, float gscale,
+                                                    unsigned* __restrict__ counter) {
+  __shared__ int flag;
+  const float lr_t = lr * sqrtf(1.f - powers[1]) / (1.f - powers[0]);
+  const size_t n4 = n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i] * gscale;
+    f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
+    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+    f32x4 wv = reinterpret_cast<f32x4*>(w)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      mv[k] = __builtin_fmaf(b1, mv[k], (1.f - b1) * gv[k]);
+      vv[k] = __builtin_fmaf(b2, vv[k], (1.f - b2) * gv[k] * gv[k]);
+      wv[k] -= lr_t * mv[k] / (sqrtf(vv[k]) + eps);
+    }
+    reinterpret_cast<f32x4*>(m)[i] = mv;
+    reinterpret_cast<f32x4*>(v)[i] = vv;
+    reinterpret_cast<f32x4*>(w)[i] = wv;
+    const elem4 o = {(elem_t)wv[0], (elem_t)wv[1], (elem_t)wv[2], (elem_t)wv[3]};
+    reinterpret_cast<elem4*>(wbf)[i] = o;
+  }
+  // last arrival: every block has read the powers above before it increments the counter
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    flag = old == gridDim.x - 1;
+    if (flag) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (flag && threadIdx.x == 0) {
+    powers[0] *= b1;
+    powers[1] *= b2;
+  }
+}
+
+// step_end_kernel's counterpart for a D-only sub-step (the paths that update D with adam_kernel:
+// fp32, fp16, DDP): D's beta powers only, and the same dynamic loss-scale rule -- a sub-step is
+// an optimiser step for it. Never touches the global step or G's powers.
+__global__ void d_step_end_kernel(float* __restrict__ pd, float b1d, float b2d, float* __restrict__ ls,
+                                  int growth_interval) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    bool skipped = false;
+    if (ls) {
+      skipped = ls[1] != 0.f;
+      if (skipped) {
+        ls[0] = fmaxf(ls[0] * 0.5f, 1.f);
+        ls[2] = 0.f;
+      } else if ((ls[2] += 1.f) >= (float)growth_interval) {
+        ls[0] = fminf(ls[0] * 2.f, 16777216.f);
+        ls[2] = 0.f;
+      }
+      ls[1] = 0.f;
+    }
+    if (!skipped) {  // a skipped sub-step does not advance D's beta powers
+      pd[0] *= b1d;
+      pd[1] *= b2d;
+    }
+  }
+}
+
 }  // namespace dcg
 
 using namespace dcg;
@@ -1018,6 +1089,26 @@ extern "C" int DCG_API(dcg_step_end)(float* pd, float* pg, float b1d, float b2d,
                                       unsigned long long* step, float* ls, int growth_interval, hipStream_t s) {
   hipLaunchKernelGGL(step_end_kernel, dim3(1), dim3(64), 0, s, pd, pg, b1d, b2d, b1g, b2g, step, ls,
                      growth_interval);
+  return (int)hipGetLastError();
+}
+
+// grid rule of adam1_kernel: one float4 per thread, capped at ADAM1_MAX_BLOCKS (every block bumps
+// ONE arrival counter, see dcg_adam2); larger buffers grid-stride
+extern "C" int DCG_API(dcg_adam1)(float* w, elem_t* wbf, const float* g, float* m, float* v, float* powers, size_t n,
+                                  float lr, float b1, float b2, float eps, float gscale, unsigned* counter,
+                                  hipStream_t s) {
+  if (n % 4 || !w || !wbf || !g || !m || !v || !powers || !counter) return -2;
+  size_t b = (n / 4 + 255) / 256;
+  if (b > ADAM1_MAX_BLOCKS) b = ADAM1_MAX_BLOCKS;
+  hipLaunchKernelGGL(adam1_kernel, dim3((unsigned)(b ? b : 1)), dim3(256), 0, s, w, wbf, g, m, v, powers, n, lr, b1, b2,
+                     eps, gscale, counter);
+  return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_d_step_end)(float* pd, float b1d, float b2d, float* ls, int growth_interval,
+                                       hipStream_t s) {
+  if (!pd) return -2;
+  hipLaunchKernelGGL(d_step_end_kernel, dim3(1), dim3(64), 0, s, pd, b1d, b2d, ls, growth_interval);
   return (int)hipGetLastError();
 }
 

@@ -29,7 +29,8 @@ class ReferenceEngine:
                  lr: float = 2e-4, beta1: float = 0.5, zero_debias: bool = False, rank: int = 0,
                  world: int = 1, z_seed: Optional[int] = None, g_ema_decay: Optional[float] = None,
                  gan_loss: Optional[str] = None, label_smooth: Optional[float] = None,
-                 d_spectral_norm: Optional[bool] = None, **_):
+                 d_spectral_norm: Optional[bool] = None, d_steps: Optional[int] = None,
+                 beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None, **_):
         self.cfg = cfg
         self.batch_size = batch_size
         self.device = device
@@ -49,16 +50,21 @@ class ReferenceEngine:
             gan_loss = os.environ.get("DCGAN_GAN_LOSS") or "bce"
         if label_smooth is None:
             label_smooth = float(os.environ.get("DCGAN_LABEL_SMOOTH") or 0.0)
+        # D updates per G update, Adam's beta2, per-network learning rates: None = DCGAN_D_STEPS /
+        # DCGAN_BETA2 / DCGAN_LR_D / DCGAN_LR_G, as the HIP engine
+        d_steps, beta2, lr_d, lr_g = R.resolve_d_steps(d_steps, beta2, lr_d, lr_g, lr)
         self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None,
                                        g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth,
-                                       d_spectral_norm=bool(d_spectral_norm), seed=seed)
+                                       d_spectral_norm=bool(d_spectral_norm), seed=seed, d_steps=d_steps,
+                                       beta2=beta2, lr_d=lr_d, lr_g=lr_g)
+        self.d_steps = self.step_impl.d_steps
         self.d_spectral_norm = self.step_impl.d_spectral_norm
         self.g_ema_decay = self.step_impl.g_ema_decay
         self.gan_loss, self.label_smooth = self.step_impl.gan_loss, self.step_impl.label_smooth
         self.opt_d, self.opt_g = self.step_impl.opt_d, self.step_impl.opt_g
         self.z_gen = torch.Generator(device=device if device.type == "cuda" else "cpu")
         self.z_gen.manual_seed((z_seed if z_seed is not None else seed) + 7919 * rank + 1)
-        self._real = None
+        self._reals = [None] * self.d_steps  # slot k < d_steps - 1: D sub-step k's batch; last: the full step's
         self._losses: Dict[str, float] = {}
 
     def _allreduce(self, which: str, flat: torch.Tensor) -> None:
@@ -72,16 +78,31 @@ class ReferenceEngine:
     def global_step(self, v: int) -> None:
         self.step_impl.global_step = int(v)
 
-    def set_synthetic_batch(self, real: torch.Tensor) -> None:
-        self._real = real.to(self.device, torch.float32)
+    @property
+    def _real(self):
+        return self._reals[-1]
 
-    def set_batch(self, real: torch.Tensor) -> None:
-        self._real = real.to(self.device, torch.float32, non_blocking=True)
+    def set_synthetic_batch(self, real: torch.Tensor) -> None:
+        self._reals = [real.to(self.device, torch.float32)] * self.d_steps
+
+    def set_batch(self, real: torch.Tensor, slot: int = 0) -> None:
+        """Slot k < d_steps - 1 is D sub-step k's batch, slot d_steps - 1 the full step's."""
+        if not 0 <= slot < self.d_steps:
+            raise ValueError("batch slot %d out of range for d_steps = %d" % (slot, self.d_steps))
+        self._reals[slot] = real.to(self.device, torch.float32, non_blocking=True)
 
     def sample_z(self, n: int) -> torch.Tensor:
         return torch.rand(n, self.cfg.z_dim, generator=self.z_gen, device=self.device) * 2 - 1
 
+    def train_d_step(self, k: int) -> None:
+        """D sub-step k alone (its losses: last_losses())."""
+        z = self.sample_z(self._reals[k].shape[0])
+        self._last_z = z
+        self._losses = self.step_impl.d_step(self._reals[k], z)
+
     def train_step(self) -> None:
+        for k in range(self.d_steps - 1):
+            self.train_d_step(k)
         z = self.sample_z(self._real.shape[0])
         self._last_z = z
         self._losses = self.step_impl.step(self._real, z)
@@ -151,17 +172,20 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                  allreduce_dtype: str = "fp32", lr: float = 2e-4, beta1: float = 0.5,
                  zero_debias: bool = False, bucket_mb: float = 32.0, g_ema_decay: Optional[float] = None,
                  gan_loss: Optional[str] = None, label_smooth: Optional[float] = None,
-                 d_spectral_norm: Optional[bool] = None):
+                 d_spectral_norm: Optional[bool] = None, d_steps: Optional[int] = None,
+                 beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None):
     if engine == "auto":  # every dtype (bf16 / fp16 / fp32) runs on the HIP kernels on an MI355X
         engine = "hip" if device.type == "cuda" else "reference"
     if engine == "reference":
         return ReferenceEngine(cfg, batch_size, device, seed=seed, lr=lr, beta1=beta1,
                                zero_debias=zero_debias, rank=rank, world=world, g_ema_decay=g_ema_decay,
-                               gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm)
+                               gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm,
+                               d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g)
     if engine == "hip":
         from .hip_engine import HipEngine
         return HipEngine(cfg, batch_size, device, dtype=dtype, seed=seed, lr=lr, beta1=beta1,
                          zero_debias=zero_debias, rank=rank, world=world, graph=graph,
                          allreduce_dtype=allreduce_dtype, bucket_mb=bucket_mb, g_ema_decay=g_ema_decay,
-                         gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm)
+                         gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm,
+                         d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g)
     raise ValueError("unknown engine %r" % engine)

@@ -151,7 +151,7 @@ class HipEngineAux:
             self.progEval = prog
         saved_real = self.d_in[:self.B].clone()
         saved_losses = self.losses.clone()
-        self.set_batch(real)
+        self.set_batch(real, self.d_steps - 1)  # (the full step's slot: d_in)
         self._ev_z.copy_(z.to(self.device, torch.float32))
         H.run(self.progEval)
         l = self.losses.tolist()
@@ -164,6 +164,10 @@ class HipEngineAux:
         device; which stream slots / graphs carry it."""
         progs = [("forward+G backward", self.progA), ("D backward", self.progB), ("G weight grads", self.progW),
                  ("optimisers", self.progC)]
+        for k, (pf, pb) in enumerate(self._sub):
+            progs += [("D sub-step %d forward" % k, pf), ("D sub-step %d D backward" % k, pb)]
+        if self._sub:
+            progs.append(("D sub-step update", self.progDU))
         out = ["HIP engine (%s): %d kernels per step, schedule %s, hipGraph %s%s" % (
             self.dtype_name, self.kernel_count(), self._schedule(), "captured" if self.graph_enabled else
             ("requested" if self.graph_requested else "off"),
@@ -176,8 +180,16 @@ class HipEngineAux:
         return out
 
     def _step_progs(self):
+        subs = [p for pair in self._sub for p in pair] + [self.progDU] * len(self._sub)
         return [p for p in (self.progA, self.progB, self.progW, self.progC, getattr(self, "progSh", None))
-                if p is not None]
+                if p is not None] + subs
+
+    def sub_op_names(self, k: int) -> List[str]:
+        """Names of the recorded ops of D sub-step k: forward, D chain, update."""
+        out = []
+        for p in self._sub[k] + (self.progDU,):
+            out += [p.name(i) for i in range(p.size())]
+        return out
 
     def op_names(self) -> List[str]:
         out = []

@@ -15,6 +15,13 @@ every step from C++ (eager, the default) or as hipGraphs:
                  the last Adam launch over G; with ``d_spectral_norm`` also ``sn_power`` (4 launches)
                  after the last Adam launch over D
 
+With ``d_steps`` = n > 1 a training step is n - 1 D-only sub-steps, then the step above. Sub-step k
+has Programs of its own (``_build_d_substeps``): the forward ops of progA[:a_fwd] on its own z seed
+(``_zseed``) and its own [real_k | fake] staging buffer, with G's BN moving averages left alone; the
+D chain; then ``progDU``: Adam(D) + mirror + D's beta powers (``adam1``: one launch on the
+single-process bf16 step; else ``adam_bf`` + ``d_step_end``) and ``sn_power``. No G chain, no progW,
+no Adam(G), no ``ema_g``, and the global step does not move.
+
 With ``d_spectral_norm`` D's conv GEMMs and head read W / sigma(W) (the mirror slices / an fp32
 copy of the head hold it) and progB projects each weight gradient back through sigma
 (``sn_project``, 2 launches) right behind the launch that finalises it.
@@ -134,7 +141,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  rank_seeded_z: bool = True, schedule: Optional[str] = None, dry_run: bool = False,
                  ddp: Optional[bool] = None, g_ema_decay: Optional[float] = None, gan_loss: Optional[str] = None,
                  label_smooth: Optional[float] = None, d_spectral_norm: Optional[bool] = None,
-                 z_seed: Optional[int] = None, **_):
+                 z_seed: Optional[int] = None, d_steps: Optional[int] = None, beta2: Optional[float] = None,
+                 lr_d: Optional[float] = None, lr_g: Optional[float] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -157,6 +165,11 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.z_seed = self.seed if z_seed is None else int(z_seed)
         self.rank_seeded_z = bool(rank_seeded_z)  # False only in equivalence tests
         self.lr, self.beta1 = float(lr), float(beta1)
+        # discriminator updates per generator update (d_steps - 1 recorded D-only sub-steps before
+        # each full step), Adam's beta2 and the per-network learning rates. None: DCGAN_D_STEPS /
+        # DCGAN_BETA2 / DCGAN_LR_D / DCGAN_LR_G, then 1 / TFAdam's beta2 / lr. All at their defaults:
+        # no buffer, launch or Program beyond the full step's
+        self.d_steps, self.beta2, self.lr_d, self.lr_g = R.resolve_d_steps(d_steps, beta2, lr_d, lr_g, lr)
         # moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates = the
         # global step); 0 = off: no buffers, no op. None: DCGAN_G_EMA_DECAY (A/B of its cost)
         if g_ema_decay is None:
@@ -185,14 +198,16 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         if schedule is not None and schedule not in SCHEDULES:
             raise ValueError("schedule must be one of %s" % (SCHEDULES,))
         self._sched_req = schedule
+        self._timing = False
+        R.check_d_steps_schedule(self.d_steps, self._schedule(), os.environ.get("DCGAN_DDP_SHARD", "0") == "1")
         self.model = DCGAN(cfg, device=device, seed=seed, zero_debias=zero_debias)
         if self.d_spectral_norm:
             self.model.enable_d_spectral_norm(seed)  # fresh u (CPU generator) + one power step
         if self.ddp and not self.dry:
             D.broadcast_tensors([self.model.g.flat, self.model.d.flat, self.model.g_bn.flat, self.model.d_bn.flat]
                                 + ([self.model.d_sn.flat] if self.d_spectral_norm else []))
-        self.opt_d = TFAdam(self.model.d, lr, beta1, power_suffix="")
-        self.opt_g = TFAdam(self.model.g, lr, beta1, power_suffix="_1")
+        self.opt_d = TFAdam(self.model.d, self.lr_d, beta1, self.beta2, power_suffix="")
+        self.opt_g = TFAdam(self.model.g, self.lr_g, beta1, self.beta2, power_suffix="_1")
         self.opt_d.use_hip = self.opt_g.use_hip = True
         self.grad_d = self.model.d.like()
         self.grad_g = self.model.g.like()
@@ -202,6 +217,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.graph_enabled = False
         self._timing = False
         self._graphs: List[Optional[torch.cuda.CUDAGraph]] = []
+        self._sub_graphs: List[List[Optional[torch.cuda.CUDAGraph]]] = []  # per D sub-step, per segment
         self.comm_stream = torch.cuda.Stream(device=device) if (self.ddp and not self.dry) else None
         self.allreduce_dtype = allreduce_dtype
         # bf16 wire of the segmented DDP step (bf16 engine): flat bf16 gradient images that cast
@@ -246,6 +262,9 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # ---------------- D input [real | fake]
         self.d_in = t(B2, s, s, cfg.c_dim, zero=True)
         self.fake = self.d_in[B:]
+        # staging area of d_steps real batches: D sub-step k reads (and G writes the fake half of)
+        # its own [real_k | fake] buffer; the last slot is the full step's d_in
+        self.d_ins = [t(B2, s, s, cfg.c_dim, zero=True) for _ in range(self.d_steps - 1)] + [self.d_in]
         self.d_x, self.d_a = {}, {}
         for i, L in enumerate(self.dl):
             if L.bn:
@@ -351,6 +370,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self._g_cuts = self._g_bucket_cuts()
         self._g_split = self._g_split_plan()
         self._build_shards()
+        self._build_d_substeps()
         self._build_updates()  # (after the G split: Adam(G) follows its collectives)
         self.progX, self._wire_ops = self._prog(), {}
         if self.wire_d is not None:  # fp32 gradient slice -> its bf16 wire image, one op per collective
@@ -377,6 +397,53 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.progEval = None
         self.progSum = None
 
+    def _build_d_substeps(self):
+        """d_steps > 1: the d_steps - 1 D-only sub-steps, each a forward program (the full step's
+        forward ops on sub-step k's z seed and [real_k | fake] buffer; G's BN moving averages are
+        left alone, D's update) and a D chain (``_build_d_backward_dloss``, cut at the same position
+        as progB for the DDP collectives). No G chain, no progW. The update (``progDU``) is shared."""
+        self._sub: List[Tuple[object, object]] = []
+        keep = (self._b_split, self._b_top_dgrad)
+        for k in range(self.d_steps - 1):
+            pf, pb = self._prog(), self._prog()
+            self._build_forward(pf, update_ema=True, z=self.z, train_z=True, update_ema_g=False, sub=k)
+            self._build_d_backward_dloss(pb, sub=k)
+            assert (self._b_split, self._b_top_dgrad) == keep and pb.size() == self.progB.size()
+            self._sub.append((pf, pb))
+        self._b_split, self._b_top_dgrad = keep
+
+    def _d_update_fused(self) -> bool:
+        """The sub-step's D update as ONE launch (adam1: Adam + mirror + D's powers) on the
+        single-process bf16 step, where the full step uses adam2; DCGAN_D_UPDATE=split: adam_bf +
+        d_step_end there too (A/B)."""
+        return (self._schedule() == "fused" and self.dt == 0
+                and (os.environ.get("DCGAN_D_UPDATE") or "fused") != "split")
+
+    def _build_d_update(self):
+        """progDU, the D sub-step's update after the D chain (and, under DDP, D's collectives):
+        Adam(D) + mirror + D's beta powers, then the power step. fp16: the overflow check over D's
+        gradient gates Adam, the powers and sn_power, and d_step_end applies the loss-scale rule."""
+        self.progDU = None
+        if self.d_steps <= 1:
+            return
+        prog = self.progDU = self._prog()
+        od, Dm = self.opt_d, self.model.d
+        n = Dm.flat.numel()
+        gs = 1.0 / self.world
+        if self._d_update_fused():
+            prog.adam1("adam_d1", _p(Dm.flat), _p(self.wbf_d.flat), _p(self.grad_d.flat), _p(od.m.flat), _p(od.v.flat),
+                       _p(od.powers), n, od.lr, od.beta1, od.beta2, od.eps, gs, 0)
+            self._sn_power(prog)
+            return
+        ls = _p(self.loss_scale)
+        if self.f16:
+            prog.nonfinite_check("ls.check_d", _p(self.grad_d.flat), n, ls, 0)
+        prog.adam_bf("adam_d", _p(Dm.flat), 0 if self.f32 else _p(self.wbf_d.flat), _p(self.grad_d.flat), _p(od.m.flat),
+                     _p(od.v.flat), _p(od.powers), n, od.lr, od.beta1, od.beta2, od.eps, gs, 0, ls,
+                     _p(self.wire_d.flat) if self._wire_direct() else 0)
+        self._sn_power(prog, ls)
+        prog.d_step_end("d_step_end", _p(od.powers), od.beta1, od.beta2, 0, ls, self.LOSS_SCALE_GROWTH)
+
     def _build_updates(self):
         """progC for the current schedule. The one-launch Adam over BOTH models is only used
         where nothing else can be touching D's gradients or weights any more ("fused": after
@@ -386,6 +453,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         step counter ("ddp" likewise). fp16: one overflow check gates both, everything in the
         second part."""
         self.progC = self._prog()
+        self._build_d_update()
         sch = self._schedule()
         if self._sharded():
             self._build_update_sharded(self.progC)
@@ -567,11 +635,29 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             prog.sn_power("sn_power", list(self._sn_mats.values()), ls, 0)
 
     # ---- forward
-    def _build_forward(self, prog, update_ema: bool, z, train_z: bool):
+    def _zseed(self, sub: Optional[int] = None) -> int:
+        """Seed of the in-kernel z stream (Philox keyed by it and the device step counter):
+        zseed = z_seed * 1000003 + 17 + 7919 * rank for the full step; D sub-step k, during which the
+        step counter does not move, draws from zseed_k = (zseed + (k + 1) * 0x9E3779B97F4A7C15) mod
+        2^64 (a fixed odd multiplier: the d_steps seeds of a step are pairwise different). No state:
+        a resumed run draws the same z sequence."""
+        zseed = self.z_seed * 1000003 + 17 + 7919 * self.rank * int(self.rank_seeded_z)
+        if sub is None:
+            return zseed
+        return (zseed + (sub + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+    def _build_forward(self, prog, update_ema: bool, z, train_z: bool, update_ema_g: Optional[bool] = None,
+                       sub: Optional[int] = None):
+        """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's). sub = k: the forward
+        of D sub-step k -- its z seed and its [real_k | fake] buffer, the same ops otherwise."""
         cfg, B = self.cfg, self.B
         B2 = 2 * B
         Pg, Pd = self.model.g, self.model.d
-        zseed = self.z_seed * 1000003 + 17 + 7919 * self.rank * int(self.rank_seeded_z)
+        zseed = self._zseed(sub)
+        if update_ema_g is None:
+            update_ema_g = update_ema
+        d_in = self.d_in if sub is None else self.d_ins[sub]
+        fake = d_in[B:]
         # G projection + g_bn0 + relu; train_z: z ~ U(-1,1) generated inside the projection kernel
         # (Philox keyed by the device step counter); g_bn0 partial statistics straight from it:
         # one partial row per (8-row block of z, spatial position) -- see linear_fwd_kernel
@@ -582,7 +668,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         prog.linear_fwd("g_h0_lin", _p(z), _p(Pg["g_h0_lin/Matrix"]), _p(Pg["g_h0_lin/bias"]), _p(self.g_h0_pre),
                         B, cfg.z_dim, cfg.g_lin_out, 0, _p(part0), C0,
                         _p(self.step_counter) if train_z else 0, zseed if train_z else 0)
-        self._bn_fwd(prog, "g_bn0", self.g_h0_pre, self.g_h0, rows0, C0, 1, RELU, part0, P0, update_ema)
+        self._bn_fwd(prog, "g_bn0", self.g_h0_pre, self.g_h0, rows0, C0, 1, RELU, part0, P0, update_ema_g)
         a_prev = self.g_h0
         Wg, Wd = self.wbf_g, self.wbf_d
         for L in self.gl:
@@ -596,7 +682,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                             L.out_hw, L.cout, pad, bias=Pg[L.name + "/biases"], stats=part)
                 out_applies = L is self.gl[-2] and self._gout_applies_bn()
                 self._bn_fwd(prog, L.bn, self.g_x[L.name], self.g_a[L.name], rows, L.cout, 1, RELU, part, P,
-                             update_ema, apply=not out_applies)
+                             update_ema_g, apply=not out_applies)
                 a_prev = self.g_a[L.name]
             elif self._gout_applies_bn():
                 # RGB layer: the lower layer's BN apply + ReLU in its halo staging (writes that
@@ -604,13 +690,13 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                 Lp = self.gl[-2]
                 st = self.bn[Lp.bn]
                 prog.narrow_deconv_bnin(L.name + "+bn_apply", _p(self.g_x[Lp.name]), _p(nat), _p(Pg[L.name + "/biases"]),
-                                        _p(self.fake), B, L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw, L.cout, pad,
+                                        _p(fake), B, L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw, L.cout, pad,
                                         TANH, cfg.lrelu_leak, _p(st["scale"]), _p(st["shift"]), RELU, cfg.lrelu_leak,
                                         _p(self.g_a[Lp.name]), 0)
             else:  # last: + bias, tanh, written into the fake half of D's input
-                self._deconv_out(prog, L.name, a_prev, nat, self.fake, B, L, pad, Pg[L.name + "/biases"], TANH)
+                self._deconv_out(prog, L.name, a_prev, nat, fake, B, L, pad, Pg[L.name + "/biases"], TANH)
         # D forward on [real | fake]
-        prev = self.d_in
+        prev = d_in
         for i, L in enumerate(self.dl):
             w = Wd[L.name + "/w"]  # HWIO [5,5,ci,co] = [tap][K][N]
             pad = same_pads(L.in_hw)[0]
@@ -669,8 +755,10 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                            _p(self.loss_scale), obj, self.label_smooth)
 
     # ---- D backward for d_loss (2B rows, both groups) -> all D gradients
-    def _build_d_backward_dloss(self, prog):
+    def _build_d_backward_dloss(self, prog, sub: Optional[int] = None):
+        """sub = k: the D chain of D sub-step k (layer 0's weight gradient reads its d_in)."""
         cfg, B = self.cfg, self.B
+        d_in = self.d_in if sub is None else self.d_ins[sub]
         B2 = 2 * B
         Pd, gD = self.model.d, self.grad_d
         lin = cfg.d_lin_name
@@ -694,16 +782,16 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                                     "d")
 
             def emit_wgrad(i=i, L=L, dx=dx):
-                src = self.d_in if i == 0 else self.d_a[self.dl[i - 1].name]
+                src = d_in if i == 0 else self.d_a[self.dl[i - 1].name]
                 pad = same_pads(L.in_hw)[0]
                 ws = 0
                 if i == 0 and self._d0_direct() and prog.nwgrad_ok(L.in_hw, L.in_hw, L.out_hw, L.out_hw):
                     # image window staged per workgroup, no column matrix (narrow2.hip nwgrad)
-                    prog.nwgrad(L.name + ".nwgrad", _p(self.d_in), B2, L.in_hw, L.in_hw, L.cin, _p(dx), L.out_hw,
+                    prog.nwgrad(L.name + ".nwgrad", _p(d_in), B2, L.in_hw, L.in_hw, L.cin, _p(dx), L.out_hw,
                                 L.out_hw, pad, _p(gD[L.name + "/w"]), ws)
                 elif i == 0 and L.cin % 8 != 0:
                     if self._d0_direct():  # the forward ran without a column matrix: build it here
-                        prog.im2col_s2("d0.im2col", _p(self.d_in), _p(self.d0_col), B2, L.in_hw, L.in_hw, L.cin,
+                        prog.im2col_s2("d0.im2col", _p(d_in), _p(self.d0_col), B2, L.in_hw, L.in_hw, L.cin,
                                        L.out_hw, L.out_hw, pad, pad, self.kp_d0, ws)
                     self._wgrad(prog, L.name, 2, self.d0_col, 1, 1, self.kp_d0, dx, B2 * L.out_hw ** 2, 1, 1, L.cout, 0,
                                 gD[L.name + "/w"], stream=ws)
@@ -1242,7 +1330,69 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         _, run, which = self._segments()[i]
         run(ex, stream, ex.side if which == self.MAIN else ex.alt[1])
 
+    # ---- D-only sub-steps (d_steps > 1)
+    def _sub_segments(self, k: int):
+        """D sub-step k as (name, runner, stream) segments, as ``_segments`` gives the full step.
+        "fused": one segment (forward on cs, the D chain on the alt streams, the join, the update).
+        "concurrent": forward | D chain top | D chain rest | update, with D's two collectives issued
+        between them (``_run_d_substep``), each gradient slice reduced where it becomes final."""
+        F, Bk = self._sub[k]
+        M, lin = self.MAIN, self._lin_segment
+        if self._schedule() == "fused":
+            run = lambda ex, cs, sec: self._run_fused_sub(ex, cs, k)  # noqa: E731
+            run.empty = False
+            return [("d_step", run, M)]
+        X = self.progX
+        wx = lambda name: ([(X, self._wire_ops[name], self._wire_ops[name] + 1)]  # noqa: E731
+                           if self._wire_direct() and name in self._wire_ops else [])
+        return [("d_fwd", lin([(F, 0, -1)]), M), ("d_bwd_top", lin([(Bk, 0, self._b_split)] + wx("dtop")), self.ALT),
+                ("d_bwd_rest", lin([(Bk, self._b_split, -1)] + wx("drest")), self.ALT),
+                ("d_update", lin([(self.progDU, 0, -1)]), M)]
+
+    def _run_fused_sub(self, ex, cs, k: int) -> None:
+        """D sub-step k of the "fused" schedule issued onto cs (+ the alt streams); also what gets
+        captured. The D chain runs on its own stream as in the full step; the update waits for it."""
+        F, Bk = self._sub[k]
+        ex.run(F, [cs, ex.side])
+        ex.wait(ex.alt[0], cs)
+        ex.run(Bk, ex.alt)
+        ex.wait(cs, ex.alt[0])
+        ex.run(self.progDU, [cs, ex.side])
+
+    def _sub_seg(self, ex, k: int, i: int, stream) -> None:
+        if self.graph_enabled:
+            g = self._sub_graphs[k][i]
+            if g is not None:
+                ex.replay(g, stream)
+            return
+        _, run, which = self._sub_segments(k)[i]
+        run(ex, stream, ex.side if which == self.MAIN else ex.alt[1])
+
+    def _run_d_substep(self, ex, k: int) -> None:
+        """Issue D sub-step k. It starts on the main stream behind everything the previous (sub-)step
+        queued there and ends with every stream it used joined back into the main stream."""
+        cs = ex.main()
+        if self._schedule() == "fused":
+            self._sub_seg(ex, k, 0, cs)
+            return
+        alt = ex.alt[0]
+        self._sub_seg(ex, k, 0, cs)            # z_k, G fwd, D fwd (real_k | fake), losses
+        ex.wait(alt, cs)
+        self._sub_seg(ex, k, 1, alt)           # D chain: head + top layer gradients
+        self._ar_launch(ex, "dtop", alt)
+        self._sub_seg(ex, k, 2, alt)           # D chain: the rest -> grad_d final
+        self._ar_launch(ex, "drest", alt)
+        self._ar_join(ex, cs)                  # Adam(D) after D's last collective
+        ex.wait(cs, alt)
+        self._sub_seg(ex, k, 3, cs)            # Adam(D), D's powers, sn_power
+
     def _run_step(self, ex):
+        """One training step: the d_steps - 1 D sub-steps in order, then the full step."""
+        for k in range(self.d_steps - 1):
+            self._run_d_substep(ex, k)
+        self._run_full_step(ex)
+
+    def _run_full_step(self, ex):
         cs = ex.main()
         sch = self._schedule()
         if sch in ("fused", "ddp"):
@@ -1280,14 +1430,22 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                         ex.wait(ex.comm, cs)  # the comm stream joins the capture from its start
                     run(ex, cs, ex.side if which == self.MAIN else ex.alt[1])
                 graphs.append(g)
-            self._graphs = graphs
+            sub_graphs = []
+            for k in range(self.d_steps - 1):  # one graph per sub-step (segmented: per segment)
+                sub_graphs.append([])
+                for name, run, which in self._sub_segments(k):
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        run(ex, torch.cuda.current_stream(self.device), ex.side if which == self.MAIN else ex.alt[1])
+                    sub_graphs[k].append(g)
+            self._graphs, self._sub_graphs = graphs, sub_graphs
             return True
         except Exception as e:  # pragma: no cover - depends on runtime
             print("[hip_engine] graph capture failed, running eagerly: %s" % e)
-            self._graphs = []
+            self._graphs, self._sub_graphs = [], []
             return False
 
-    def train_step(self) -> None:
+    def _prepare_run(self) -> None:
         if self.dry:
             raise RuntimeError("a dry-run engine only records the step (engine.schedule_check)")
         self._ensure_comm()
@@ -1295,12 +1453,33 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                 and not getattr(self, "_cap_tried", 0)):
             self._cap_tried = 1
             self.graph_enabled = self._capture()
-        self._run_step(self._get_exec())
+
+    def _count_d_bn(self) -> None:
+        for s in range(self.model.d_bn.slots):
+            self.model.d_bn.count_step(s)
+
+    def train_step(self) -> None:
+        """d_steps - 1 D sub-steps (each on its own staged batch and z), then the full step."""
+        for k in range(self.d_steps - 1):
+            self.train_d_step(k)
+        self.train_full_step()
+
+    def train_full_step(self) -> None:
+        """The full step alone: what train_step runs after the sub-steps (tests)."""
+        self._prepare_run()
+        self._run_full_step(self._get_exec())
         self._step_host += 1
         # one EMA update per BN slot per step (zero-debias bookkeeping, host-side counters)
         self.model.g_bn.count_step(0)
-        for s in range(self.model.d_bn.slots):
-            self.model.d_bn.count_step(s)
+        self._count_d_bn()
+
+    def train_d_step(self, k: int) -> None:
+        """D sub-step k alone (tests; its losses are readable through last_losses())."""
+        if not 0 <= k < self.d_steps - 1:
+            raise ValueError("sub-step %d out of range for d_steps = %d" % (k, self.d_steps))
+        self._prepare_run()
+        self._run_d_substep(self._get_exec(), k)
+        self._count_d_bn()  # D's BN moving averages update in every sub-step, G's do not
 
     @property
     def global_step(self) -> int:
@@ -1311,14 +1490,20 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.step_counter.fill_(int(v))
 
     def set_synthetic_batch(self, real: torch.Tensor) -> None:
-        self.set_batch(real)
+        """The same batch into every staging slot."""
+        for k in range(self.d_steps):
+            self.set_batch(real, k)
 
-    def set_batch(self, real: torch.Tensor) -> None:
-        """Copy a [B,H,W,C] batch (any float dtype, values already in [-1,1]) into the real half."""
+    def set_batch(self, real: torch.Tensor, slot: int = 0) -> None:
+        """Copy a [B,H,W,C] batch (any float dtype, values already in [-1,1]) into the real half of
+        staging slot `slot`: slot k < d_steps - 1 is D sub-step k's batch, slot d_steps - 1 the full
+        step's (d_steps = 1: the only one)."""
         B = self.B
         if real.shape[0] != B:
             raise ValueError("batch %d != engine batch %d" % (real.shape[0], B))
-        self.d_in[:B].copy_(real.to(self.device, non_blocking=True))
+        if not 0 <= slot < self.d_steps:
+            raise ValueError("batch slot %d out of range for d_steps = %d" % (slot, self.d_steps))
+        self.d_ins[slot][:B].copy_(real.to(self.device, non_blocking=True))
 
     def last_losses(self) -> Dict[str, float]:
         l = self.losses.tolist()

@@ -23,8 +23,13 @@ from ..optim.adam import TFAdam
 class ReferenceStep:
     def __init__(self, model: DCGAN, lr: float = 2e-4, beta1: float = 0.5,
                  grad_hook: Optional[Callable[[str, torch.Tensor], None]] = None, g_ema_decay: float = 0.0,
-                 gan_loss: str = "bce", label_smooth: float = 0.0, d_spectral_norm: bool = False, seed: int = 0):
+                 gan_loss: str = "bce", label_smooth: float = 0.0, d_spectral_norm: bool = False, seed: int = 0,
+                 d_steps: int = 1, beta2: float = R.ADAM_BETA2, lr_d: Optional[float] = None,
+                 lr_g: Optional[float] = None):
         self.model = model
+        # discriminator updates per generator update (d_steps - 1 D sub-steps, ``d_step``, before
+        # each full ``step``), Adam's beta2 and the per-network learning rates (TTUR)
+        self.d_steps, self.beta2, self.lr_d, self.lr_g = R.check_d_steps(d_steps, beta2, lr_d, lr_g, lr)
         # spectral normalisation of D's conv kernels and head (model.d_sn; ops.reference.sn_power /
         # spectral_normalize): D computes with W / sigma(W), one power step after each Adam(D)
         self.d_spectral_norm = R.check_spectral_norm(d_spectral_norm)
@@ -37,18 +42,20 @@ class ReferenceStep:
         if self.g_ema_decay > 0:
             model.g_ema = model.g.like()
             model.g_ema.flat.copy_(model.g.flat)
-        self.opt_d = TFAdam(model.d, lr, beta1, power_suffix="")
-        self.opt_g = TFAdam(model.g, lr, beta1, power_suffix="_1")
+        self.opt_d = TFAdam(model.d, self.lr_d, beta1, self.beta2, power_suffix="")
+        self.opt_g = TFAdam(model.g, self.lr_g, beta1, self.beta2, power_suffix="_1")
         self.global_step = 0
         self.grad_hook = grad_hook  # e.g. DDP all-reduce of the flat grad buffer
         self.last: Dict[str, torch.Tensor] = {}
 
     def forward_losses(self, real: torch.Tensor, z: torch.Tensor, Pg=None, Pd=None, update_ema=True,
-                       record=None):
+                       record=None, update_ema_g=None):
+        """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's)."""
         m = self.model
         if self.d_spectral_norm:  # D computes with W / sigma(W); autograd projects the gradient
             Pd = m.d_sn_weights(Pd)
-        fake = m.generator(z, train=True, P=Pg, update_ema=update_ema, record=record)
+        fake = m.generator(z, train=True, P=Pg, update_ema=update_ema if update_ema_g is None else update_ema_g,
+                           record=record)
         B = real.shape[0]
         both = torch.cat([real, fake], 0)
         _, logits = m.discriminator(both, groups=2, slots=(0, 1), train=True, P=Pd,
@@ -77,6 +84,36 @@ class ReferenceStep:
             if g is not None:
                 gg_flat[n].copy_(g)
         return out, gd_flat.flat, gg_flat.flat
+
+    def compute_d_grads(self, real: torch.Tensor, z: torch.Tensor):
+        """(losses dict, flat D grads) of a D sub-step: G's forward in training mode on batch
+        statistics with its BN moving averages left alone, only d_loss differentiated, through D."""
+        m = self.model
+        Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
+        out = self.forward_losses(real, z, None, Pd, update_ema=True, update_ema_g=False)
+        d_names = m.d.names()
+        dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], allow_unused=True)
+        gd_flat = m.d.like()
+        for n, g in zip(d_names, dg):
+            if g is not None:
+                gd_flat[n].copy_(g)
+        return out, gd_flat.flat
+
+    def d_step(self, real: torch.Tensor, z: torch.Tensor) -> Dict[str, float]:
+        """One D sub-step: a fresh z through G, D on [real | fake], the d_loss backward through D,
+        TF-Adam(D) (D's beta powers advance) and the power step. Nothing of G changes -- parameters,
+        Adam slots and powers, BN moving averages, weight EMA -- nor does the global step; D's BN
+        moving averages (both slots) update as in a full step."""
+        out, gd = self.compute_d_grads(real, z)
+        for s in range(2):
+            self.model.d_bn.count_step(s)
+        if self.grad_hook is not None:
+            self.grad_hook("d", gd)
+        self.opt_d.step(gd)
+        if self.d_spectral_norm:
+            self.model.d_sn.power_step_(self.model.d.tensors)
+        self.last = out
+        return {k: float(out[k].detach()) for k in ("d_loss_real", "d_loss_fake", "g_loss", "d_loss")}
 
     def step(self, real: torch.Tensor, z: torch.Tensor) -> Dict[str, float]:
         out, gd, gg = self.compute_grads(real, z)

@@ -10,7 +10,8 @@ order on a stream, ``record``/``wait`` events inside programs, ``wait_stream``-s
 marks issued by the schedule, and the collectives on the comm stream. Two ops are *ordered*
 when one's clock dominates the other's entry for its stream. Any unordered pair whose ranges
 overlap with at least one write is a race (RAW / WAR / WAW) and is reported. Two consecutive
-steps are recorded, so hazards across the step boundary are covered too.
+steps are recorded, so hazards across the step boundary are covered too; with ``d_steps`` > 1 a
+step is its D sub-steps followed by the full step, so the boundaries between them are covered as well.
 
 Race this catches (round-1 finding): the timed single-process "concurrent" schedule ran the
 one-launch two-model Adam in its "adam_G" segment, before the main stream had joined the D
@@ -167,7 +168,7 @@ def check_engine(eng, steps: int = 2) -> Tuple[List[Hazard], int]:
 
 def check(cfg=None, batch_size: int = 8, dtype: str = "bf16", world: int = 1, schedule: Optional[str] = None,
           timing: bool = False, steps: int = 2, allreduce_dtype: str = "fp32", g_ema_decay: float = 0.0,
-          gan_loss: str = "bce", label_smooth: float = 0.0, d_spectral_norm: bool = False):
+          gan_loss: str = "bce", label_smooth: float = 0.0, d_spectral_norm: bool = False, d_steps: int = 1):
     """Build a dry-run engine on the CPU and check one schedule. Returns (schedule, hazards, ops)."""
     import torch
 
@@ -176,7 +177,7 @@ def check(cfg=None, batch_size: int = 8, dtype: str = "bf16", world: int = 1, sc
     cfg = cfg or DCGANConfig()
     eng = HipEngine(cfg, batch_size, torch.device("cpu"), dtype=dtype, world=world, schedule=schedule, dry_run=True,
                     graph=False, allreduce_dtype=allreduce_dtype, g_ema_decay=g_ema_decay, gan_loss=gan_loss,
-                    label_smooth=label_smooth, d_spectral_norm=d_spectral_norm)
+                    label_smooth=label_smooth, d_spectral_norm=d_spectral_norm, d_steps=d_steps)
     if timing:  # (enable_timing without its CUDA events)
         eng._timing = True
         eng._build_updates()

@@ -635,6 +635,36 @@ def adam_(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, po
     run(prog)
 
 
+def adam1_max_blocks() -> int:
+    """Grid cap of the D sub-step's one-launch update (larger buffers grid-stride)."""
+    return int(ext().ADAM1_MAX_BLOCKS)
+
+
+def adam1_(w: torch.Tensor, wbf: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
+           powers: torch.Tensor, lr: float, beta1: float, beta2: float, eps: float, gscale: float = 1.0) -> None:
+    """The D sub-step's update in one launch: TF-Adam over w (fp32, numel % 4 == 0), its 16-bit mirror
+    wbf, and powers *= (beta1, beta2) once every block has read them."""
+    if wbf.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError("adam1_: the mirror must be bfloat16 or float16")
+    if any(t.dtype != torch.float32 for t in (w, g, m, v, powers)):
+        raise TypeError("adam1_: w, g, m, v and powers must be float32")
+    n = w.numel()
+    if n % 4 or any(t.numel() != n for t in (wbf, g, m, v)) or powers.numel() != 2:
+        raise ValueError("adam1_: equal sizes, numel % 4 == 0, two powers")
+    prog = ext().Program(int(wbf.dtype == torch.float16))
+    prog.adam1("adam1", _p(w), _p(wbf), _p(g), _p(m), _p(v), _p(powers), n, lr, beta1, beta2, eps, gscale, 0)
+    run(prog)
+
+
+def d_step_end_(powers: torch.Tensor, beta1: float, beta2: float, ls: Optional[torch.Tensor] = None,
+                growth_interval: int = 2000) -> None:
+    """The D sub-step's step end: powers *= (beta1, beta2) and the fp16 loss-scale rule on ls =
+    [scale, overflow flag, good steps] (overflow: halve, clear, leave the powers)."""
+    prog = ext().Program()
+    prog.d_step_end("d_step_end", _p(powers), beta1, beta2, 0, _p(ls), int(growth_interval))
+    run(prog)
+
+
 def gan_loss_id(kind: str, label_smooth: float = 0.0) -> int:
     """Objective id of the loss / head kernels for a validated (name, label_smooth) pair."""
     from .reference import check_gan_loss

@@ -139,6 +139,67 @@ def tf_adam_update(param: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: 
     param.sub_(lr_t * m / (v.sqrt() + eps))
 
 
+ADAM_BETA2 = 0.999   # TF-Adam's beta2 where none is given (optim.adam.TFAdam's default)
+MAX_D_STEPS = 16
+
+
+def check_d_steps(d_steps=1, beta2=ADAM_BETA2, lr_d=None, lr_g=None, lr=2e-4):
+    """Validated (d_steps, beta2, lr_d, lr_g): 1 <= d_steps <= 16 discriminator updates per generator
+    update, 0 <= beta2 < 1, and the per-network learning rates -- None or 0 = the common `lr`,
+    negative values are errors."""
+    if isinstance(d_steps, bool) or int(d_steps) != d_steps or not 1 <= int(d_steps) <= MAX_D_STEPS:
+        raise ValueError("d_steps must be an integer with 1 <= d_steps <= %d, got %r" % (MAX_D_STEPS, d_steps))
+    b2 = float(beta2)
+    if not 0.0 <= b2 < 1.0:
+        raise ValueError("beta2 must satisfy 0 <= beta2 < 1, got %r" % (beta2,))
+    if not float(lr) >= 0.0:
+        raise ValueError("learning_rate must not be negative, got %r" % (lr,))
+    out = []
+    for name, v in (("d_learning_rate", lr_d), ("g_learning_rate", lr_g)):
+        v = 0.0 if v is None else float(v)
+        if not v >= 0.0:
+            raise ValueError("%s must not be negative (0 = the common learning rate), got %r" % (name, v))
+        out.append(v if v > 0 else float(lr))
+    return int(d_steps), b2, out[0], out[1]
+
+
+def resolve_d_steps(d_steps=None, beta2=None, lr_d=None, lr_g=None, lr=2e-4):
+    """check_d_steps over the engines' arguments: None = the environment default (DCGAN_D_STEPS,
+    DCGAN_BETA2, DCGAN_LR_D, DCGAN_LR_G), then 1 / ADAM_BETA2 / `lr`. An explicit argument wins."""
+    import os
+
+    def env(name, conv):
+        v = os.environ.get(name)
+        if v is None or v.strip() == "":
+            return None
+        try:
+            return conv(v)
+        except ValueError:
+            raise ValueError("%s=%r is not a number" % (name, v)) from None
+    if d_steps is None:
+        d_steps = env("DCGAN_D_STEPS", int)
+    if beta2 is None:
+        beta2 = env("DCGAN_BETA2", float)
+    if lr_d is None:
+        lr_d = env("DCGAN_LR_D", float)
+    if lr_g is None:
+        lr_g = env("DCGAN_LR_G", float)
+    return check_d_steps(1 if d_steps is None else d_steps, ADAM_BETA2 if beta2 is None else beta2, lr_d, lr_g, lr)
+
+
+def check_d_steps_schedule(d_steps: int, schedule: str, sharded: bool) -> None:
+    """d_steps > 1 runs on the single-process step and the default (segmented, all-reduce) DDP step
+    only: the sharded update and the "ddp" / "serial" schedules have no D sub-step."""
+    if d_steps <= 1:
+        return
+    if sharded:
+        raise ValueError("d_steps > 1 is not supported with DCGAN_DDP_SHARD=1: the D sub-step updates D from "
+                         "all-reduced gradients, the sharded update has no sub-step schedule")
+    if schedule in ("ddp", "serial"):
+        raise ValueError("d_steps > 1 is not supported with the %r schedule: the D sub-step is recorded for the "
+                         "single-process (\"fused\") and the default DDP (\"concurrent\") schedules only" % schedule)
+
+
 def zero_fraction(x: torch.Tensor) -> torch.Tensor:
     """tf.nn.zero_fraction (sparsity summary, distriubted_model.py:80)."""
     return (x == 0).float().mean()

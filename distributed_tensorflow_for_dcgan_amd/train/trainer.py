@@ -8,7 +8,7 @@ checkpoint every ``--save_model_secs``; auto-resume from the newest checkpoint o
 
 Deliberate differences: synchronous data parallelism instead of the
 asynchronous parameter server (``--job_name=ps`` exits with a notice), every flag is honoured,
-epochs count W*B images per global step, the sample-time losses do not mutate the BN moving
+epochs count d_steps*W*B images per global step, the sample-time losses do not mutate the BN moving
 averages, samples go to ``--sample_dir``, optimiser state is checkpointed.
 """
 from __future__ import annotations
@@ -158,13 +158,21 @@ def run(flags: Flags, out=None) -> int:
                           lr=float(flags.learning_rate), beta1=float(flags.beta1),
                           zero_debias=bool(flags.bn_zero_debias), bucket_mb=float(flags.bucket_mb),
                           g_ema_decay=float(flags.g_ema_decay), gan_loss=str(flags.gan_loss),
-                          label_smooth=float(flags.label_smooth), d_spectral_norm=bool(flags.d_spectral_norm))
+                          label_smooth=float(flags.label_smooth), d_spectral_norm=bool(flags.d_spectral_norm),
+                          d_steps=int(flags.d_steps), beta2=float(flags.beta2),
+                          lr_d=float(flags.d_learning_rate), lr_g=float(flags.g_learning_rate))
+    n_d = int(getattr(engine, "d_steps", 1))  # real batches (and D updates) per training step
     if chief:
         print("GAN objective: %s, label_smooth %g (D's real target %g)" % (
             engine.gan_loss, engine.label_smooth, 1.0 - engine.label_smooth), file=out, flush=True)
         print("discriminator: batch norm %s, spectral norm %s" % (
             "on" if cfg.d_bn else "off", "on" if getattr(engine, "d_spectral_norm", False) else "off"),
             file=out, flush=True)
+        if n_d > 1 or engine.opt_d.lr != engine.opt_g.lr:
+            print("optimisers: %d discriminator update(s) per generator update (%d real batches per step), "
+                  "Adam lr D %g / G %g, beta1 %g, beta2 %g" % (n_d, n_d, engine.opt_d.lr, engine.opt_g.lr,
+                                                               engine.opt_d.beta1, engine.opt_d.beta2),
+                  file=out, flush=True)
     if flags.log_device_placement:
         for line in placement_report(engine, device, rank, world):
             print(line, file=out, flush=True)
@@ -204,7 +212,7 @@ def run(flags: Flags, out=None) -> int:
     n_ex = source.num_examples
     if flags.train_size != math.inf:
         n_ex = min(n_ex, int(flags.train_size))
-    step_per_epoch = max(1, -(-n_ex // (B * world)))
+    step_per_epoch = max(1, -(-n_ex // (n_d * B * world)))  # a step consumes d_steps x W x B images
     max_steps = int(flags.max_steps)
     if flags.epoch and int(flags.epoch) > 0:
         max_steps = min(max_steps, int(flags.epoch) * step_per_epoch)
@@ -235,7 +243,8 @@ def run(flags: Flags, out=None) -> int:
             if prof_range and step == prof_range[0] and prof is None:
                 prof = torch.profiler.profile(record_shapes=False, with_stack=False)
                 prof.__enter__()
-            engine.set_batch(source.next())
+            for k in range(n_d):  # slots 0 .. d_steps - 2: the D sub-steps' batches; the last: the full step's
+                engine.set_batch(source.next(), k)
             engine.train_step()
             step += 1
             if prof is not None and step >= prof_range[1]:
@@ -246,7 +255,7 @@ def run(flags: Flags, out=None) -> int:
             now = time.time()
             summary_due = chief and writer is not None and now >= next_summary
             if step % max(1, int(flags.log_every)) == 0 or summary_due or step == max_steps:
-                ips = B * world * (step - last_rate_step) / max(1e-9, now - last_rate_t) if step > last_rate_step else 0.0
+                ips = n_d * B * world * (step - last_rate_step) / max(1e-9, now - last_rate_t) if step > last_rate_step else 0.0
                 losslog.push((step, now - start_time, ips))
                 emit(losslog.ready(flush=summary_due or step == max_steps or bool(flags.timing)))
                 if flags.timing and hasattr(engine, "phase_times"):

@@ -91,6 +91,12 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                                        "--d_spectral_norm --nod_batch_norm"),
     ("d_batch_norm", "bool", True, "batch norm in the discriminator (--nod_batch_norm: a BN-free D, no d_bn* "
                                    "variables); SN-GAN recipe: --gan_loss=hinge --d_spectral_norm --nod_batch_norm"),
+    ("d_steps", "int", 1, "discriminator updates per generator update, 1..16: each training step runs d_steps - 1 "
+                          "D-only sub-steps (fresh z, own real batch, Adam over D alone) before the full step; "
+                          "SN-GAN / WGAN-style training uses 5. An epoch counts d_steps x W x B images per step"),
+    ("beta2", "float", 0.999, "Adam's second-moment decay, 0 <= beta2 < 1 (SN-GAN: --beta1=0 --beta2=0.9)"),
+    ("d_learning_rate", "float", 0.0, "learning rate of the discriminator's Adam (TTUR); 0 = --learning_rate"),
+    ("g_learning_rate", "float", 0.0, "learning rate of the generator's Adam (TTUR); 0 = --learning_rate"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -176,6 +182,11 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         check_gan_loss(ns.gan_loss, ns.label_smooth)
     except ValueError as e:
         parser.error("--gan_loss / --label_smooth: %s" % e)
+    from ..ops.reference import check_d_steps
+    try:
+        check_d_steps(ns.d_steps, ns.beta2, ns.d_learning_rate, ns.g_learning_rate, ns.learning_rate)
+    except (ValueError, TypeError, OverflowError) as e:
+        parser.error("--d_steps / --beta2 / --d_learning_rate / --g_learning_rate: %s" % e)
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
