@@ -785,54 +785,105 @@ class Program {
     return add(name + ".bias", stream, [=](hipStream_t s) { return KF(dcg_sum_vec)(P<const float>(dl), R, P<float>(db), s); },
                AccList().r(dl, (size_t)R * 4).w(db, 4).v);
   }
+  // Validated learning-rate schedule (kernels.h LrSched) of an Adam op: kind LR_NONE | LR_LINEAR |
+  // LR_COSINE | LR_EXPONENTIAL, decay over steps [start, start + steps] down to the factor `end`,
+  // linear warm-up over the first `warmup` steps. An active one needs the device step counter.
+  static LrSched lr_sched(const char* op, int kind, int64_t start, int64_t steps, double end, int64_t warmup,
+                          uintptr_t step) {
+    const std::string o(op);
+    if (kind < LR_NONE || kind > LR_EXPONENTIAL)
+      throw std::runtime_error(o + ": lr_kind must be 0 (none), 1 (linear), 2 (cosine) or 3 (exponential), got " +
+                               std::to_string(kind));
+    if (warmup < 0 || warmup > (int64_t)LR_MAX_STEPS)
+      throw std::runtime_error(o + ": lr_warmup must satisfy 0 <= warmup <= 2^24, got " + std::to_string(warmup));
+    LrSched S{kind, 1u, (unsigned)warmup, 0.f, 0ull};
+    if (kind != LR_NONE) {
+      if (start < 0) throw std::runtime_error(o + ": lr_start must not be negative, got " + std::to_string(start));
+      if (steps < 1 || steps > (int64_t)LR_MAX_STEPS)
+        throw std::runtime_error(o + ": lr_steps must satisfy 1 <= steps <= 2^24, got " + std::to_string(steps));
+      if (!(end >= 0.0 && end <= 1.0) || (kind == LR_EXPONENTIAL && !(end > 0.0)))
+        throw std::runtime_error(o + ": lr_end must satisfy 0 <= end <= 1 (> 0 for exponential), got " +
+                                 std::to_string(end));
+      S.steps = (unsigned)steps;
+      S.end = (float)end;
+      S.start = (unsigned long long)start;
+    }
+    if (lr_sched_on(S) && !step)
+      throw std::runtime_error(o + ": an active learning-rate schedule needs the step counter (lr_step != 0)");
+    return S;
+  }
   int adam(std::string name, uintptr_t w, uintptr_t g, uintptr_t m, uintptr_t v, uintptr_t powers, size_t n, float lr,
-           float b1, float b2, float eps, float gscale, int stream) {
-    return adam_bf(name, w, 0, g, m, v, powers, n, lr, b1, b2, eps, gscale, stream, 0, 0);
+           float b1, float b2, float eps, float gscale, int stream, int lr_kind, int64_t lr_start, int64_t lr_steps,
+           double lr_end, int64_t lr_warmup, uintptr_t lr_step) {
+    return adam_bf(name, w, 0, g, m, v, powers, n, lr, b1, b2, eps, gscale, stream, 0, 0, lr_kind, lr_start, lr_steps,
+                   lr_end, lr_warmup, lr_step);
   }
   // + elem_t mirror of the updated weights (same flat layout); gbf: read the gradient from this
   // bf16 buffer (the all-reduced bf16 wire of the DDP step) instead of g
   int adam_bf(std::string name, uintptr_t w, uintptr_t wbf, uintptr_t g, uintptr_t m, uintptr_t v, uintptr_t powers,
-              size_t n, float lr, float b1, float b2, float eps, float gscale, int stream, uintptr_t ls, uintptr_t gbf) {
+              size_t n, float lr, float b1, float b2, float eps, float gscale, int stream, uintptr_t ls, uintptr_t gbf,
+              int lr_kind, int64_t lr_start, int64_t lr_steps, double lr_end, int64_t lr_warmup, uintptr_t lr_step) {
+    const LrSched S = lr_sched("adam", lr_kind, lr_start, lr_steps, lr_end, lr_warmup, lr_step);
+    if (!lr_sched_on(S)) lr_step = 0;  // off: the kernel never reads the counter
     AccList acc;
-    acc.w(w, n * 4).w(wbf, n * es_).w(m, n * 4).w(v, n * 4).r(powers, 8).r(ls, 12);
+    acc.w(w, n * 4).w(wbf, n * es_).w(m, n * 4).w(v, n * 4).r(powers, 8).r(ls, 12).r(lr_step, 8);
     if (gbf) acc.r(gbf, n * 2);
     else acc.r(g, n * 4);
     return add(name, stream, [=](hipStream_t s) {
       return KF(dcg_adam)(P<float>(w), P<elem_t>(wbf), P<const float>(g), P<float>(m), P<float>(v), P<const float>(powers),
-                      n, lr, b1, b2, eps, gscale, P<const float>(ls), P<const void>(gbf), s);
+                      n, lr, b1, b2, eps, gscale, P<const float>(ls), P<const void>(gbf), &S,
+                      P<const unsigned long long>(lr_step), s);
     }, acc.v);
   }
   // both TF-Adams (A first) + beta powers / step counter in one launch (see adam2_kernel)
   int adam2(std::string name, uintptr_t wA, uintptr_t wbfA, uintptr_t gA, uintptr_t mA, uintptr_t vA, uintptr_t pA,
             size_t nA, float lrA, float b1A, float b2A, float epsA, uintptr_t wD, uintptr_t wbfD, uintptr_t gD,
             uintptr_t mD, uintptr_t vD, uintptr_t pD, size_t nD, float lrD, float b1D, float b2D, float epsD,
-            float gscale, uintptr_t step, int stream) {
+            float gscale, uintptr_t step, int stream, int lr_kind, int64_t lr_start, int64_t lr_steps, double lr_end,
+            int64_t lr_warmup) {
+    const LrSched S = lr_sched("adam2", lr_kind, lr_start, lr_steps, lr_end, lr_warmup, step);
     void* ctr = dev_alloc(sizeof(unsigned), nullptr, true);
     AccList acc;
     acc.w(wA, nA * 4).w(wbfA, nA * es_).r(gA, nA * 4).w(mA, nA * 4).w(vA, nA * 4).w(pA, 8)
         .w(wD, nD * 4).w(wbfD, nD * es_).r(gD, nD * 4).w(mD, nD * 4).w(vD, nD * 4).w(pD, 8).w(step, 8)
         .w((uintptr_t)ctr, 4);
+    if (lr_sched_on(S)) acc.r(step, 8);  // every block reads the counter the last arrival advances
     return add(name, stream, [=](hipStream_t s) {
       return KF(dcg_adam2)(P<float>(wA), P<elem_t>(wbfA), P<const float>(gA), P<float>(mA), P<float>(vA), P<float>(pA),
                            nA, lrA, b1A, b2A, epsA, P<float>(wD), P<elem_t>(wbfD), P<const float>(gD), P<float>(mD),
                            P<float>(vD), P<float>(pD), nD, lrD, b1D, b2D, epsD, gscale,
-                           P<unsigned long long>(step), reinterpret_cast<unsigned*>(ctr), s);
+                           P<unsigned long long>(step), reinterpret_cast<unsigned*>(ctr), &S, s);
     }, acc.v);
   }
   // the D-only sub-step's one-launch update (adam1_kernel): TF-Adam over one set + its 16-bit
   // mirror + its beta powers; no step counter, no other set
   int adam1(std::string name, uintptr_t w, uintptr_t wbf, uintptr_t g, uintptr_t m, uintptr_t v, uintptr_t powers,
-            size_t n, float lr, float b1, float b2, float eps, float gscale, int stream) {
+            size_t n, float lr, float b1, float b2, float eps, float gscale, int stream, int lr_kind, int64_t lr_start,
+            int64_t lr_steps, double lr_end, int64_t lr_warmup, uintptr_t lr_step) {
     if (dt_ == 2) throw std::runtime_error("adam1: 16-bit builds only");
+    const LrSched S = lr_sched("adam1", lr_kind, lr_start, lr_steps, lr_end, lr_warmup, lr_step);
+    if (!lr_sched_on(S)) lr_step = 0;
     if (n % 4 || !w || !wbf || !g || !m || !v || !powers)
       throw std::runtime_error("adam1: n % 4 == 0 and non-null w, mirror, g, m, v, powers");
     void* ctr = dev_alloc(sizeof(unsigned), nullptr, true);
     AccList acc;
-    acc.w(w, n * 4).w(wbf, n * es_).r(g, n * 4).w(m, n * 4).w(v, n * 4).w(powers, 8).w((uintptr_t)ctr, 4);
+    acc.w(w, n * 4).w(wbf, n * es_).r(g, n * 4).w(m, n * 4).w(v, n * 4).w(powers, 8).w((uintptr_t)ctr, 4)
+        .r(lr_step, 8);
     return add(name, stream, [=](hipStream_t s) {
       return KF(dcg_adam1)(P<float>(w), P<elem_t>(wbf), P<const float>(g), P<float>(m), P<float>(v), P<float>(powers), n,
-                           lr, b1, b2, eps, gscale, reinterpret_cast<unsigned*>(ctr), s);
+                           lr, b1, b2, eps, gscale, reinterpret_cast<unsigned*>(ctr), &S,
+                           P<const unsigned long long>(lr_step), s);
     }, acc.v);
+  }
+  // the schedule's factor at each of n int64 step values -> out float32[n] (dcg::lr_factor, the
+  // device function of the Adam kernels)
+  int lr_factor(std::string name, uintptr_t steps, uintptr_t out, size_t n, int lr_kind, int64_t lr_start,
+                int64_t lr_steps, double lr_end, int64_t lr_warmup, int stream) {
+    if (!steps || !out) throw std::runtime_error("lr_factor: steps and out must be non-null");
+    const LrSched S = lr_sched("lr_factor", lr_kind, lr_start, lr_steps, lr_end, lr_warmup, steps);
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_lr_factor)(P<const unsigned long long>(steps), P<float>(out), n, &S, s);
+    }, AccList().r(steps, n * 8).w(out, n * 4).v);
   }
   // the sub-step's step_end (d_step_end_kernel): D's powers + the fp16 loss-scale rule only
   int d_step_end(std::string name, uintptr_t pd, float b1d, float b2d, int stream, uintptr_t ls, int growth_interval) {
@@ -1234,17 +1285,30 @@ PYBIND11_MODULE(_dcgan_hip, m) {
            py::arg("label_smooth") = 0.0)
       .def("head_dgrad", &Program::head_dgrad)
       .def("head_wgrad", &Program::head_wgrad)
-      .def("adam", &Program::adam)
+      .def("adam", &Program::adam, py::arg("name"), py::arg("w"), py::arg("g"), py::arg("m"), py::arg("v"),
+           py::arg("powers"), py::arg("n"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
+           py::arg("gscale"), py::arg("stream"), py::arg("lr_kind") = 0, py::arg("lr_start") = 0, py::arg("lr_steps") = 1,
+           py::arg("lr_end") = 0.0, py::arg("lr_warmup") = 0, py::arg("lr_step") = 0)
       .def("adam_bf", &Program::adam_bf, py::arg("name"), py::arg("w"), py::arg("wbf"), py::arg("g"), py::arg("m"),
            py::arg("v"), py::arg("powers"), py::arg("n"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
-           py::arg("gscale"), py::arg("stream"), py::arg("ls") = 0, py::arg("gbf") = 0)
+           py::arg("gscale"), py::arg("stream"), py::arg("ls") = 0, py::arg("gbf") = 0, py::arg("lr_kind") = 0, py::arg("lr_start") = 0, py::arg("lr_steps") = 1,
+           py::arg("lr_end") = 0.0, py::arg("lr_warmup") = 0, py::arg("lr_step") = 0)
       .def("step_end", &Program::step_end, py::arg("name"), py::arg("pd"), py::arg("pg"), py::arg("b1d"),
            py::arg("b2d"), py::arg("b1g"), py::arg("b2g"), py::arg("step"), py::arg("stream"), py::arg("ls") = 0,
            py::arg("growth_interval") = 2000)
-      .def("adam2", &Program::adam2)
+      .def("adam2", &Program::adam2, py::arg("name"), py::arg("wA"), py::arg("wbfA"), py::arg("gA"), py::arg("mA"),
+           py::arg("vA"), py::arg("pA"), py::arg("nA"), py::arg("lrA"), py::arg("b1A"), py::arg("b2A"), py::arg("epsA"),
+           py::arg("wD"), py::arg("wbfD"), py::arg("gD"), py::arg("mD"), py::arg("vD"), py::arg("pD"), py::arg("nD"),
+           py::arg("lrD"), py::arg("b1D"), py::arg("b2D"), py::arg("epsD"), py::arg("gscale"), py::arg("step"),
+           py::arg("stream"), py::arg("lr_kind") = 0, py::arg("lr_start") = 0, py::arg("lr_steps") = 1,
+           py::arg("lr_end") = 0.0, py::arg("lr_warmup") = 0)
       .def("adam1", &Program::adam1, py::arg("name"), py::arg("w"), py::arg("wbf"), py::arg("g"), py::arg("m"),
            py::arg("v"), py::arg("powers"), py::arg("n"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
-           py::arg("gscale") = 1.f, py::arg("stream") = 0)
+           py::arg("gscale") = 1.f, py::arg("stream") = 0, py::arg("lr_kind") = 0, py::arg("lr_start") = 0, py::arg("lr_steps") = 1,
+           py::arg("lr_end") = 0.0, py::arg("lr_warmup") = 0, py::arg("lr_step") = 0)
+      .def("lr_factor", &Program::lr_factor, py::arg("name"), py::arg("steps"), py::arg("out"), py::arg("n"),
+           py::arg("lr_kind"), py::arg("lr_start"), py::arg("lr_steps"), py::arg("lr_end"), py::arg("lr_warmup"),
+           py::arg("stream") = 0)
       .def("d_step_end", &Program::d_step_end, py::arg("name"), py::arg("pd"), py::arg("b1d"), py::arg("b2d"),
            py::arg("stream") = 0, py::arg("ls") = 0, py::arg("growth_interval") = 2000)
       .def("ema", &Program::ema, py::arg("name"), py::arg("s"), py::arg("sbf"), py::arg("w"), py::arg("n"),

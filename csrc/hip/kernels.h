@@ -96,6 +96,25 @@ constexpr unsigned EMA_MAX_BLOCKS = 2048;
 // blocks, since every block bumps one arrival counter; larger buffers grid-stride
 constexpr unsigned ADAM1_MAX_BLOCKS = 512;
 
+// Learning-rate schedule of the Adam kernels (misc.hip dcg::lr_factor), by value in the kernel
+// arguments: the factor f(t) of the DEVICE step counter t that multiplies lr (one fp32 multiply)
+// ahead of the bias correction, so graph replays follow the live counter.
+//   k = t <= start ? 0 : min(t - start, steps),  p = float(k) / float(steps)
+//   linear 1 - (1 - end) p | cosine 1 - (1 - end) (1 - cos(pi p)) / 2 | exponential end^p
+//   k == 0 -> 1 and k == steps -> end by selection;  t < warmup: f *= float(t + 1) / float(warmup)
+// LR_NONE with warmup == 0 is "off": the counter is never read and lr is used as it is.
+enum LrKind : int { LR_NONE = 0, LR_LINEAR = 1, LR_COSINE = 2, LR_EXPONENTIAL = 3 };
+constexpr unsigned LR_MAX_STEPS = 1u << 24;  // steps and warmup: exact as fp32
+
+struct LrSched {
+  int kind;
+  unsigned steps, warmup;
+  float end;
+  unsigned long long start;
+};
+
+__host__ __device__ static inline bool lr_sched_on(const LrSched& s) { return s.kind != LR_NONE || s.warmup != 0; }
+
 // GAN objectives of the loss / head kernels (misc.hip gan_loss_block). The first three are the
 // ids of the launchers and bindings; GAN_BCE_T is the kernel instance of bce with a smoothed
 // real target, which the launchers pick themselves (real_target != 1).

@@ -50,12 +50,13 @@ int DCG_API(dcg_head_wgrad)(const elem_t* x, const float* dl, float* part, int R
 int DCG_API(dcg_sum_vec)(const float* v, int n, float* out, hipStream_t s);
 int DCG_API(dcg_adam)(float* w, elem_t* wbf, const float* g, float* m, float* v, const float* powers, size_t n,
                       float lr, float b1, float b2, float eps, float gscale, const float* ls,
-                     const void* g_bf16, hipStream_t s);
+                     const void* g_bf16, const dcg::LrSched* sched, const unsigned long long* step, hipStream_t s);
 int DCG_API(dcg_step_end)(float* pd, float* pg, float b1d, float b2d, float b1g, float b2g,
                           unsigned long long* step, float* ls, int growth_interval, hipStream_t s);
 // the D-only sub-step's updates: one-launch Adam + mirror + powers of one set; its step_end
 int DCG_API(dcg_adam1)(float* w, elem_t* wbf, const float* g, float* m, float* v, float* powers, size_t n, float lr,
-                       float b1, float b2, float eps, float gscale, unsigned* counter, hipStream_t s);
+                       float b1, float b2, float eps, float gscale, unsigned* counter, const dcg::LrSched* sched,
+                       const unsigned long long* step, hipStream_t s);
 int DCG_API(dcg_d_step_end)(float* pd, float b1d, float b2d, float* ls, int growth_interval, hipStream_t s);
 int DCG_API(dcg_ema)(float* s, elem_t* sbf, const float* w, size_t n, float decay, const unsigned long long* step,
                      int step_bias, const float* ls, hipStream_t st);
@@ -89,6 +90,10 @@ int DCG_API(dcg_sum_partials_split)(const float* part, int P, int stride, int C,
 int DCG_API(dcg_adam2)(float* wA, elem_t* wbfA, const float* gA, float* mA, float* vA, float* pA, size_t nA, float lrA,
                        float b1A, float b2A, float epsA, float* wD, elem_t* wbfD, const float* gD, float* mD,
                        float* vD, float* pD, size_t nD, float lrD, float b1D, float b2D, float epsD, float gscale,
-                       unsigned long long* step, unsigned* counter, hipStream_t s);
+                       unsigned long long* step, unsigned* counter, const dcg::LrSched* sched, hipStream_t s);
+// the schedule's factor at each of n step values (the device function the Adam kernels call);
+// sched == nullptr = off; -2: an active schedule with a null step pointer (all four launchers)
+int DCG_API(dcg_lr_factor)(const unsigned long long* steps, float* out, size_t n, const dcg::LrSched* sched,
+                           hipStream_t s);
 int DCG_API(dcg_tensor_summary)(const void* x, int x_dtype, size_t n, const double* edges, int nbins, double* out,
                                 double* part, unsigned* counter, int blocks, hipStream_t s);

@@ -544,16 +544,50 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const elem_t* __restrict_
   }
 }
 
+// ---------------------------------------------------------------- learning-rate schedule
+// The factor of kernels.h LrSched at the step counter *step (read live: graph replays follow it).
+// Block-uniform: `S` is a kernel argument and *step one scalar load, every branch below is taken
+// by the whole grid, so the caller's loop sees one extra float. The end points come from
+// selection, not arithmetic: k == 0 -> 1.0f, k == steps -> end, both exact.
+__device__ __forceinline__ float lr_factor(const LrSched& S, const unsigned long long* __restrict__ step) {
+  const unsigned long long t = step[0];
+  float f = 1.f;
+  if (S.kind != LR_NONE && t > S.start) {
+    const unsigned long long d = t - S.start;
+    if (d >= (unsigned long long)S.steps) {
+      f = S.end;
+    } else {
+      const float p = (float)(unsigned)d / (float)S.steps;  // both < 2^24: exact conversions
+      const float a = 1.f - S.end;
+      if (S.kind == LR_LINEAR) f = 1.f - a * p;
+      else if (S.kind == LR_COSINE) f = 1.f - a * (0.5f * (1.f - cospif(p)));
+      else f = exp2f(p * log2f(S.end));  // end > 0 (validated by the bindings)
+    }
+  }
+  if (t < (unsigned long long)S.warmup) f *= (float)((unsigned)t + 1u) / (float)S.warmup;
+  return f;
+}
+
+// lr_factor at each of n step values: the tests' probe and the trainer's log
+__global__ __launch_bounds__(256) void lr_factor_kernel(LrSched S, const unsigned long long* __restrict__ steps,
+                                                        float* __restrict__ out, size_t n) {
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = lr_factor(S, steps + i);
+}
+
 // ---------------------------------------------------------------- TF Adam
 // lr_t = lr*sqrt(1-b2^t)/(1-b1^t) from device powers (= b^t); w -= lr_t*m/(sqrt(v)+eps)
 // GW = bf16: the gradient is read from the all-reduced bf16 wire buffer (DDP with a bf16 wire:
 // no bf16 -> fp32 copy-back after the collective; the values are the same)
+// S / step: the learning-rate schedule, lr_eff = lr * lr_factor (one fp32 multiply). Every Adam
+// launch of a step runs ahead of the launch that advances the counter, so all see the same t.
+// An inactive schedule never reads the counter and leaves lr, and so every result bit, alone.
 template <typename GW>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, elem_t* __restrict__ wbf,
                                                    const GW* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, const float* __restrict__ powers, size_t n,
                                                    float lr, float b1, float b2, float eps, float gscale,
-                                                   const float* __restrict__ ls) {
+                                                   const float* __restrict__ ls, LrSched S,
+                                                   const unsigned long long* __restrict__ step) {
   // dynamic loss scaling (fp16): ls = [scale, overflow flag, good steps]; an overflowed step
   // is skipped entirely (weights, slots and the bf16/fp16 mirror untouched), else unscale
   if (ls) {
@@ -562,6 +596,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, elem_t
   }
   // wbf (optional): elem_t mirror of the updated weights in the SAME flat layout -- the only
   // weight copy the conv kernels read (they take either operand layout), so no repack pass
+  if (lr_sched_on(S)) lr *= lr_factor(S, step);
   const float lr_t = lr * sqrtf(1.f - powers[1]) / (1.f - powers[0]);
   const size_t n4 = n / 4;
   for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
@@ -603,6 +638,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, elem_t
 // step-end update in ONE launch (single-process bf16 path): the blocks walk the two flat
 // buffers' float4s as one index space; the last block to finish (agent counter) advances both
 // beta-power pairs and the global step -- after every block has read the powers (at its start).
+// With a learning-rate schedule every block also reads step[0] there, next to the powers and
+// ahead of its arrival on the agent counter: the ordering argument that covers `powers` (a block's
+// loads complete before its arrival, the last arrival alone writes) covers the step counter too.
 struct Adam2Set {
   float* w;
   elem_t* wbf;
@@ -616,7 +654,7 @@ struct Adam2Set {
 
 __global__ __launch_bounds__(256) void adam2_kernel(Adam2Set A, Adam2Set D, float gscale,
                                                     unsigned long long* __restrict__ step,
-                                                    unsigned* __restrict__ counter, unsigned blocksA) {
+                                                    unsigned* __restrict__ counter, unsigned blocksA, LrSched S) {
   __shared__ int flag;
   // block-uniform split of the grid between the two sets (per-lane selection of the kernarg
   // structs made the compiler spill them to scratch: 116 us instead of ~52)
@@ -629,7 +667,9 @@ __global__ __launch_bounds__(256) void adam2_kernel(Adam2Set A, Adam2Set D, floa
   f32x4* __restrict__ v = reinterpret_cast<f32x4*>(inA ? A.v : D.v);
   const float* pw = inA ? A.powers : D.powers;
   const float b1 = inA ? A.b1 : D.b1, b2 = inA ? A.b2 : D.b2, eps = inA ? A.eps : D.eps;
-  const float lr_t = (inA ? A.lr : D.lr) * sqrtf(1.f - pw[1]) / (1.f - pw[0]);
+  float lr = inA ? A.lr : D.lr;
+  if (lr_sched_on(S)) lr *= lr_factor(S, step);  // block-uniform; the same factor for both sets
+  const float lr_t = lr * sqrtf(1.f - pw[1]) / (1.f - pw[0]);
   const size_t n4 = (inA ? A.n : D.n) / 4;
   const unsigned b0 = inA ? blockIdx.x : blockIdx.x - gA, nb = inA ? gA : gridDim.x - gA;
   for (size_t i = (size_t)b0 * 256 + threadIdx.x; i < n4; i += (size_t)nb * 256) {
@@ -902,8 +942,10 @@ __global__ __launch_bounds__(256) void adam1_kernel(float* __restrict__ w, elem_
                                                     const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, float* __restrict__ powers, size_t n,
                                                     float lr, float b1, float b2, float eps, float gscale,
-                                                    unsigned* __restrict__ counter) {
+                                                    unsigned* __restrict__ counter, LrSched S,
+                                                    const unsigned long long* __restrict__ step) {
   __shared__ int flag;
+  if (lr_sched_on(S)) lr *= lr_factor(S, step);  // the global step: a sub-step never advances it
   const float lr_t = lr * sqrtf(1.f - powers[1]) / (1.f - powers[0]);
   const size_t n4 = n / 4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
@@ -1075,13 +1117,17 @@ extern "C" int DCG_API(dcg_sum_vec)(const float* v, int n, float* out, hipStream
 
 extern "C" int DCG_API(dcg_adam)(float* w, elem_t* wbf, const float* g, float* m, float* v, const float* powers,
                                   size_t n, float lr, float b1, float b2, float eps, float gscale, const float* ls,
-                                  const void* g_bf16, hipStream_t s) {
+                                  const void* g_bf16, const dcg::LrSched* sched, const unsigned long long* step,
+                                  hipStream_t s) {
+  const LrSched S = sched ? *sched : LrSched{};
+  if (lr_sched_on(S) && !step) return -2;
   if (g_bf16)
     hipLaunchKernelGGL(adam_kernel<__bf16>, dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, w, wbf,
-                       static_cast<const __bf16*>(g_bf16), m, v, powers, n, lr, b1, b2, eps, gscale, ls);
+                       static_cast<const __bf16*>(g_bf16), m, v, powers, n, lr, b1, b2, eps, gscale, ls, S,
+                       step);
   else
     hipLaunchKernelGGL(adam_kernel<float>, dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, w, wbf, g, m, v, powers, n, lr,
-                       b1, b2, eps, gscale, ls);
+                       b1, b2, eps, gscale, ls, S, step);
   return (int)hipGetLastError();
 }
 
@@ -1096,12 +1142,14 @@ extern "C" int DCG_API(dcg_step_end)(float* pd, float* pg, float b1d, float b2d,
 // ONE arrival counter, see dcg_adam2); larger buffers grid-stride
 extern "C" int DCG_API(dcg_adam1)(float* w, elem_t* wbf, const float* g, float* m, float* v, float* powers, size_t n,
                                   float lr, float b1, float b2, float eps, float gscale, unsigned* counter,
-                                  hipStream_t s) {
+                                  const dcg::LrSched* sched, const unsigned long long* step, hipStream_t s) {
   if (n % 4 || !w || !wbf || !g || !m || !v || !powers || !counter) return -2;
+  const LrSched S = sched ? *sched : LrSched{};
+  if (lr_sched_on(S) && !step) return -2;
   size_t b = (n / 4 + 255) / 256;
   if (b > ADAM1_MAX_BLOCKS) b = ADAM1_MAX_BLOCKS;
   hipLaunchKernelGGL(adam1_kernel, dim3((unsigned)(b ? b : 1)), dim3(256), 0, s, w, wbf, g, m, v, powers, n, lr, b1, b2,
-                     eps, gscale, counter);
+                     eps, gscale, counter, S, step);
   return (int)hipGetLastError();
 }
 
@@ -1212,8 +1260,10 @@ extern "C" int DCG_API(dcg_adam2)(float* wA, elem_t* wbfA, const float* gA, floa
                                   float lrA, float b1A, float b2A, float epsA, float* wD, elem_t* wbfD, const float* gD,
                                   float* mD, float* vD, float* pD, size_t nD, float lrD, float b1D, float b2D,
                                   float epsD, float gscale, unsigned long long* step, unsigned* counter,
-                                  hipStream_t s) {
+                                  const dcg::LrSched* sched, hipStream_t s) {
   if (nA % 4 || nD % 4 || !wbfA || !wbfD) return -2;
+  const LrSched S = sched ? *sched : LrSched{};
+  if (lr_sched_on(S) && !step) return -2;
   const dcg::Adam2Set A{wA, wbfA, gA, mA, vA, pA, nA, lrA, b1A, b2A, epsA};
   const dcg::Adam2Set D{wD, wbfD, gD, mD, vD, pD, nD, lrD, b1D, b2D, epsD};
   // ~512 blocks in total (grid-stride loops): every block bumps ONE arrival counter, and a
@@ -1222,7 +1272,14 @@ extern "C" int DCG_API(dcg_adam2)(float* wA, elem_t* wbfA, const float* gA, floa
   unsigned blocksA = (unsigned)std::max<size_t>(1, (512 * (nA / 4) + q - 1) / q);
   unsigned blocksD = (unsigned)std::max<size_t>(1, 512 - std::min<size_t>(511, blocksA));
   hipLaunchKernelGGL(dcg::adam2_kernel, dim3(blocksA + blocksD), dim3(256), 0, s, A, D, gscale, step, counter,
-                     blocksA);
+                     blocksA, S);
+  return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_lr_factor)(const unsigned long long* steps, float* out, size_t n, const dcg::LrSched* sched,
+                                      hipStream_t s) {
+  if (!steps || !out) return -2;
+  hipLaunchKernelGGL(lr_factor_kernel, dim3(grid_for(n)), dim3(256), 0, s, sched ? *sched : LrSched{}, steps, out, n);
   return (int)hipGetLastError();
 }
 

@@ -30,7 +30,10 @@ class ReferenceEngine:
                  world: int = 1, z_seed: Optional[int] = None, g_ema_decay: Optional[float] = None,
                  gan_loss: Optional[str] = None, label_smooth: Optional[float] = None,
                  d_spectral_norm: Optional[bool] = None, d_steps: Optional[int] = None,
-                 beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None, **_):
+                 beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None,
+                 lr_decay: Optional[str] = None,
+                 lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
+                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None, **_):
         self.cfg = cfg
         self.batch_size = batch_size
         self.device = device
@@ -53,10 +56,12 @@ class ReferenceEngine:
         # D updates per G update, Adam's beta2, per-network learning rates: None = DCGAN_D_STEPS /
         # DCGAN_BETA2 / DCGAN_LR_D / DCGAN_LR_G, as the HIP engine
         d_steps, beta2, lr_d, lr_g = R.resolve_d_steps(d_steps, beta2, lr_d, lr_g, lr)
+        # learning-rate schedule: None = DCGAN_LR_DECAY / _START / _STEPS / DCGAN_LR_END / DCGAN_LR_WARMUP
+        self.lr_sched = R.resolve_lr_schedule(lr_decay, lr_decay_start, lr_decay_steps, lr_end, lr_warmup)
         self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None,
                                        g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth,
                                        d_spectral_norm=bool(d_spectral_norm), seed=seed, d_steps=d_steps,
-                                       beta2=beta2, lr_d=lr_d, lr_g=lr_g)
+                                       beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=self.lr_sched)
         self.d_steps = self.step_impl.d_steps
         self.d_spectral_norm = self.step_impl.d_spectral_norm
         self.g_ema_decay = self.step_impl.g_ema_decay
@@ -173,19 +178,26 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                  zero_debias: bool = False, bucket_mb: float = 32.0, g_ema_decay: Optional[float] = None,
                  gan_loss: Optional[str] = None, label_smooth: Optional[float] = None,
                  d_spectral_norm: Optional[bool] = None, d_steps: Optional[int] = None,
-                 beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None):
+                 beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None,
+                 lr_decay: Optional[str] = None,
+                 lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
+                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None):
     if engine == "auto":  # every dtype (bf16 / fp16 / fp32) runs on the HIP kernels on an MI355X
         engine = "hip" if device.type == "cuda" else "reference"
     if engine == "reference":
         return ReferenceEngine(cfg, batch_size, device, seed=seed, lr=lr, beta1=beta1,
                                zero_debias=zero_debias, rank=rank, world=world, g_ema_decay=g_ema_decay,
                                gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm,
-                               d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g)
+                               d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=lr_decay,
+                               lr_decay_start=lr_decay_start, lr_decay_steps=lr_decay_steps, lr_end=lr_end,
+                               lr_warmup=lr_warmup)
     if engine == "hip":
         from .hip_engine import HipEngine
         return HipEngine(cfg, batch_size, device, dtype=dtype, seed=seed, lr=lr, beta1=beta1,
                          zero_debias=zero_debias, rank=rank, world=world, graph=graph,
                          allreduce_dtype=allreduce_dtype, bucket_mb=bucket_mb, g_ema_decay=g_ema_decay,
                          gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm,
-                         d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g)
+                         d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=lr_decay,
+                         lr_decay_start=lr_decay_start, lr_decay_steps=lr_decay_steps, lr_end=lr_end,
+                         lr_warmup=lr_warmup)
     raise ValueError("unknown engine %r" % engine)

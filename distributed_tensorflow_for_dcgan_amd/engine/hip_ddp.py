@@ -76,7 +76,7 @@ class HipDDPMixin:
             i0 = self.progSh.size()
             self.progSh.adam_bf("adam_shard." + name, _p(ps.flat) + 4 * k, _p(sr.agin), _p(sr.gs),
                                 _p(opt.m.flat) + 4 * k, _p(opt.v.flat) + 4 * k, _p(opt.powers), sr.n, opt.lr,
-                                opt.beta1, opt.beta2, opt.eps, 1.0 / self.world, 0, 0, 0)
+                                opt.beta1, opt.beta2, opt.eps, 1.0 / self.world, 0, 0, 0, **self._lr_kw())
             self._sh_ops[name] = (i0, self.progSh.size())
 
     def _build_update_sharded(self, prog):
@@ -89,7 +89,7 @@ class HipDDPMixin:
             es = mir.flat.element_size()
             prog.adam_bf("adam." + name, _p(ps.flat) + 4 * a, _p(mir.flat) + es * a, _p(grad.flat) + 4 * a,
                          _p(opt.m.flat) + 4 * a, _p(opt.v.flat) + 4 * a, _p(opt.powers), b - a, opt.lr, opt.beta1,
-                         opt.beta2, opt.eps, gs, 0, 0, 0)
+                         opt.beta2, opt.eps, gs, 0, 0, 0, **self._lr_kw())
         od, og = self.opt_d, self.opt_g
         prog.step_end("step_end", _p(od.powers), _p(og.powers), od.beta1, od.beta2, og.beta1, og.beta2,
                       _p(self.step_counter), 0, 0, self.LOSS_SCALE_GROWTH)
@@ -182,7 +182,8 @@ class HipDDPMixin:
         md = 0 if self.f32 else _p(self.wbf_d.flat)
         wd, wg = (_p(self.wire_d.flat), _p(self.wire_g.flat)) if self._wire_direct() else (0, 0)
         prog.adam_bf("adam_d", _p(self.model.d.flat), md, _p(self.grad_d.flat), _p(od.m.flat), _p(od.v.flat),
-                     _p(od.powers), self.model.d.flat.numel(), od.lr, od.beta1, od.beta2, od.eps, gs, 0, ls, wd)
+                     _p(od.powers), self.model.d.flat.numel(), od.lr, od.beta1, od.beta2, od.eps, gs, 0, ls, wd,
+                     **self._lr_kw())
         self._sn_power(prog, ls)  # spectral norm: behind Adam(D) on its stream; step_end comes later
         self._c_split = prog.size()
         G = self.model.g
@@ -192,7 +193,7 @@ class HipDDPMixin:
             if b > a:
                 prog.adam_bf(name, _p(G.flat) + 4 * a, mg + es * a if mg else 0, _p(self.grad_g.flat) + 4 * a,
                              _p(og.m.flat) + 4 * a, _p(og.v.flat) + 4 * a, _p(og.powers), b - a, og.lr, og.beta1,
-                             og.beta2, og.eps, gs, 0, ls, wg + 2 * a if wg else 0)
+                             og.beta2, og.eps, gs, 0, ls, wg + 2 * a if wg else 0, **self._lr_kw())
         n = G.flat.numel()
         if self._adam_g_split():
             lo, hi = self._g_split[3:]

@@ -142,7 +142,9 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  ddp: Optional[bool] = None, g_ema_decay: Optional[float] = None, gan_loss: Optional[str] = None,
                  label_smooth: Optional[float] = None, d_spectral_norm: Optional[bool] = None,
                  z_seed: Optional[int] = None, d_steps: Optional[int] = None, beta2: Optional[float] = None,
-                 lr_d: Optional[float] = None, lr_g: Optional[float] = None, **_):
+                 lr_d: Optional[float] = None, lr_g: Optional[float] = None, lr_decay: Optional[str] = None,
+                 lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
+                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -170,6 +172,11 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # DCGAN_BETA2 / DCGAN_LR_D / DCGAN_LR_G, then 1 / TFAdam's beta2 / lr. All at their defaults:
         # no buffer, launch or Program beyond the full step's
         self.d_steps, self.beta2, self.lr_d, self.lr_g = R.resolve_d_steps(d_steps, beta2, lr_d, lr_g, lr)
+        # learning-rate schedule (ops.reference.LrSchedule), evaluated by every recorded Adam launch
+        # from the device step counter: replays follow the live counter, a resume needs no new state.
+        # None: DCGAN_LR_DECAY / _START / _STEPS / DCGAN_LR_END / DCGAN_LR_WARMUP. Off: the Adam ops
+        # are recorded exactly as without it and never read the counter
+        self.lr_sched = R.resolve_lr_schedule(lr_decay, lr_decay_start, lr_decay_steps, lr_end, lr_warmup)
         # moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates = the
         # global step); 0 = off: no buffers, no op. None: DCGAN_G_EMA_DECAY (A/B of its cost)
         if g_ema_decay is None:
@@ -432,7 +439,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         gs = 1.0 / self.world
         if self._d_update_fused():
             prog.adam1("adam_d1", _p(Dm.flat), _p(self.wbf_d.flat), _p(self.grad_d.flat), _p(od.m.flat), _p(od.v.flat),
-                       _p(od.powers), n, od.lr, od.beta1, od.beta2, od.eps, gs, 0)
+                       _p(od.powers), n, od.lr, od.beta1, od.beta2, od.eps, gs, 0, **self._lr_kw())
             self._sn_power(prog)
             return
         ls = _p(self.loss_scale)
@@ -440,7 +447,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             prog.nonfinite_check("ls.check_d", _p(self.grad_d.flat), n, ls, 0)
         prog.adam_bf("adam_d", _p(Dm.flat), 0 if self.f32 else _p(self.wbf_d.flat), _p(self.grad_d.flat), _p(od.m.flat),
                      _p(od.v.flat), _p(od.powers), n, od.lr, od.beta1, od.beta2, od.eps, gs, 0, ls,
-                     _p(self.wire_d.flat) if self._wire_direct() else 0)
+                     _p(self.wire_d.flat) if self._wire_direct() else 0, **self._lr_kw())
         self._sn_power(prog, ls)
         prog.d_step_end("d_step_end", _p(od.powers), od.beta1, od.beta2, 0, ls, self.LOSS_SCALE_GROWTH)
 
@@ -1084,6 +1091,16 @@ class HipEngine(HipDDPMixin, HipEngineAux):
 
 
     # ---- optimiser (+ 16-bit weight mirrors)
+    def _lr_kw(self, with_step: bool = True) -> dict:
+        """The schedule's keyword arguments of an Adam op ({} when off: the op as it always was).
+        adam2 takes the counter as its own `step` argument (with_step=False)."""
+        if not self.lr_sched.active:
+            return {}
+        kw = dict(zip(("lr_kind", "lr_start", "lr_steps", "lr_end", "lr_warmup"), self.lr_sched.hip_args()))
+        if with_step:
+            kw["lr_step"] = _p(self.step_counter)
+        return kw
+
     def _ema_g(self, prog, step_bias: int, ls: int = 0) -> None:
         """The moving average of G's weights (+ its 16-bit mirror): one launch on the stream of,
         and after, the last Adam launch that writes G. step_bias = 1 where the step counter is
@@ -1112,12 +1129,12 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         if do_g:
             prog.adam_bf("adam_g", _p(self.model.g.flat), mg, _p(self.grad_g.flat), _p(og.m.flat),
                          _p(og.v.flat), _p(og.powers), self.model.g.flat.numel(), og.lr, og.beta1, og.beta2, og.eps,
-                         gs, 0, ls)
+                         gs, 0, ls, **self._lr_kw())
             self._ema_g(prog, 1, ls)
         if do_d:
             prog.adam_bf("adam_d", _p(self.model.d.flat), md, _p(self.grad_d.flat), _p(od.m.flat),
                          _p(od.v.flat), _p(od.powers), self.model.d.flat.numel(), od.lr, od.beta1, od.beta2, od.eps,
-                         gs, 0, ls)
+                         gs, 0, ls, **self._lr_kw())
             self._sn_power(prog, ls)
             prog.step_end("step_end", _p(od.powers), _p(og.powers), od.beta1, od.beta2, og.beta1, og.beta2,
                           _p(self.step_counter), 0, ls, self.LOSS_SCALE_GROWTH)
@@ -1130,7 +1147,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         prog.adam2("adam_gd", _p(G.flat), _p(self.wbf_g.flat), _p(self.grad_g.flat), _p(og.m.flat), _p(og.v.flat),
                    _p(og.powers), G.flat.numel(), og.lr, og.beta1, og.beta2, og.eps, _p(Dm.flat), _p(self.wbf_d.flat),
                    _p(self.grad_d.flat), _p(od.m.flat), _p(od.v.flat), _p(od.powers), Dm.flat.numel(), od.lr,
-                   od.beta1, od.beta2, od.eps, 1.0 / self.world, _p(self.step_counter), 0)
+                   od.beta1, od.beta2, od.eps, 1.0 / self.world, _p(self.step_counter), 0, **self._lr_kw(False))
         self._ema_g(prog, 0)
         self._sn_power(prog)
 

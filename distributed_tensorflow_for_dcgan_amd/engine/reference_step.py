@@ -25,8 +25,13 @@ class ReferenceStep:
                  grad_hook: Optional[Callable[[str, torch.Tensor], None]] = None, g_ema_decay: float = 0.0,
                  gan_loss: str = "bce", label_smooth: float = 0.0, d_spectral_norm: bool = False, seed: int = 0,
                  d_steps: int = 1, beta2: float = R.ADAM_BETA2, lr_d: Optional[float] = None,
-                 lr_g: Optional[float] = None):
+                 lr_g: Optional[float] = None, lr_decay="none", lr_decay_start: int = 0, lr_decay_steps: int = 0,
+                 lr_end: float = 0.0, lr_warmup: int = 0):
         self.model = model
+        # learning-rate schedule (ops.reference.LrSchedule): both Adam rates times lr_factor at the
+        # global step before its increment; the D sub-steps see the step of the full step after them
+        self.lr_sched = R.check_lr_schedule(*lr_decay) if isinstance(lr_decay, R.LrSchedule) else \
+            R.check_lr_schedule(lr_decay, lr_decay_start, lr_decay_steps, lr_end, lr_warmup)
         # discriminator updates per generator update (d_steps - 1 D sub-steps, ``d_step``, before
         # each full ``step``), Adam's beta2 and the per-network learning rates (TTUR)
         self.d_steps, self.beta2, self.lr_d, self.lr_g = R.check_d_steps(d_steps, beta2, lr_d, lr_g, lr)
@@ -47,6 +52,10 @@ class ReferenceStep:
         self.global_step = 0
         self.grad_hook = grad_hook  # e.g. DDP all-reduce of the flat grad buffer
         self.last: Dict[str, torch.Tensor] = {}
+
+    def lr_factor(self) -> float:
+        """The schedule's factor (fp32 oracle) at the current global step."""
+        return float(R.lr_factor(self.lr_sched, self.global_step)) if self.lr_sched.active else 1.0
 
     def forward_losses(self, real: torch.Tensor, z: torch.Tensor, Pg=None, Pd=None, update_ema=True,
                        record=None, update_ema_g=None):
@@ -109,7 +118,7 @@ class ReferenceStep:
             self.model.d_bn.count_step(s)
         if self.grad_hook is not None:
             self.grad_hook("d", gd)
-        self.opt_d.step(gd)
+        self.opt_d.step(gd, self.lr_factor())
         if self.d_spectral_norm:
             self.model.d_sn.power_step_(self.model.d.tensors)
         self.last = out
@@ -123,8 +132,9 @@ class ReferenceStep:
         if self.grad_hook is not None:
             self.grad_hook("d", gd)
             self.grad_hook("g", gg)
-        self.opt_d.step(gd)
-        self.opt_g.step(gg)
+        f = self.lr_factor()
+        self.opt_d.step(gd, f)
+        self.opt_g.step(gg, f)
         self.global_step += 1
         if self.d_spectral_norm:  # after Adam(D): one power step on the new weights
             self.model.d_sn.power_step_(self.model.d.tensors)

@@ -626,10 +626,46 @@ def im2col_s2(x: torch.Tensor, kpad: int) -> torch.Tensor:
     return out
 
 
+def _lr_kw(sched, step: Optional[torch.Tensor], op: str, with_step: bool = True) -> dict:
+    """Keyword arguments of an Adam op for a learning-rate schedule (ops.reference.LrSchedule)
+    evaluated on the device from `step` (int64[1], the global step); {} when there is none."""
+    if sched is None:
+        return {}
+    kw = dict(zip(("lr_kind", "lr_start", "lr_steps", "lr_end", "lr_warmup"), sched.hip_args()))
+    if step is not None:
+        if step.dtype != torch.int64 or step.numel() != 1:
+            raise TypeError("%s: step must be one int64" % op)
+        if with_step:
+            kw["lr_step"] = _p(step)
+    return kw
+
+
+def lr_factor(steps: torch.Tensor, sched) -> torch.Tensor:
+    """The schedule's factor at each step value, int64[N] -> float32[N], from the device function
+    the Adam kernels evaluate (dcg::lr_factor)."""
+    if steps.dtype != torch.int64:
+        raise TypeError("lr_factor: steps must be int64")
+    steps = steps.contiguous()
+    out = torch.empty(steps.shape, device=steps.device, dtype=torch.float32)
+    if steps.numel():
+        prog = ext().Program()
+        prog.lr_factor("lr_factor", _p(steps), _p(out), steps.numel(), *sched.hip_args())
+        run(prog)
+    return out
+
+
 def adam_(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, powers: torch.Tensor, lr: float,
-          beta1: float, beta2: float, eps: float, gscale: float = 1.0, advance_powers: bool = True) -> None:
+          beta1: float, beta2: float, eps: float, gscale: float = 1.0, advance_powers: bool = True,
+          lr_sched=None, step: Optional[torch.Tensor] = None) -> None:
+    """TF-Adam over w (fp32; g fp32, or bf16: the all-reduced wire image). lr_sched / step: lr times
+    the schedule's factor at step[0], evaluated in the kernel."""
     prog = ext().Program()
-    prog.adam("adam", _p(w), _p(g), _p(m), _p(v), _p(powers), w.numel(), lr, beta1, beta2, eps, gscale, 0)
+    kw = _lr_kw(lr_sched, step, "adam_")
+    if g.dtype == torch.bfloat16:
+        prog.adam_bf("adam", _p(w), 0, 0, _p(m), _p(v), _p(powers), w.numel(), lr, beta1, beta2, eps, gscale, 0, 0,
+                     _p(g), **kw)
+    else:
+        prog.adam("adam", _p(w), _p(g), _p(m), _p(v), _p(powers), w.numel(), lr, beta1, beta2, eps, gscale, 0, **kw)
     if advance_powers:
         prog.step_end("powers", _p(powers), 0, beta1, beta2, 0.0, 0.0, 0, 0)
     run(prog)
@@ -641,9 +677,10 @@ def adam1_max_blocks() -> int:
 
 
 def adam1_(w: torch.Tensor, wbf: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
-           powers: torch.Tensor, lr: float, beta1: float, beta2: float, eps: float, gscale: float = 1.0) -> None:
+           powers: torch.Tensor, lr: float, beta1: float, beta2: float, eps: float, gscale: float = 1.0,
+           lr_sched=None, step: Optional[torch.Tensor] = None) -> None:
     """The D sub-step's update in one launch: TF-Adam over w (fp32, numel % 4 == 0), its 16-bit mirror
-    wbf, and powers *= (beta1, beta2) once every block has read them."""
+    wbf, and powers *= (beta1, beta2) once every block has read them. lr_sched / step: as adam_."""
     if wbf.dtype not in (torch.bfloat16, torch.float16):
         raise TypeError("adam1_: the mirror must be bfloat16 or float16")
     if any(t.dtype != torch.float32 for t in (w, g, m, v, powers)):
@@ -652,7 +689,8 @@ def adam1_(w: torch.Tensor, wbf: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
     if n % 4 or any(t.numel() != n for t in (wbf, g, m, v)) or powers.numel() != 2:
         raise ValueError("adam1_: equal sizes, numel % 4 == 0, two powers")
     prog = ext().Program(int(wbf.dtype == torch.float16))
-    prog.adam1("adam1", _p(w), _p(wbf), _p(g), _p(m), _p(v), _p(powers), n, lr, beta1, beta2, eps, gscale, 0)
+    prog.adam1("adam1", _p(w), _p(wbf), _p(g), _p(m), _p(v), _p(powers), n, lr, beta1, beta2, eps, gscale, 0,
+               **_lr_kw(lr_sched, step, "adam1_"))
     run(prog)
 
 

@@ -13,7 +13,8 @@ is tested against. They reproduce, with explicit padding/cropping:
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Tuple
+import math
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -198,6 +199,135 @@ def check_d_steps_schedule(d_steps: int, schedule: str, sharded: bool) -> None:
     if schedule in ("ddp", "serial"):
         raise ValueError("d_steps > 1 is not supported with the %r schedule: the D sub-step is recorded for the "
                          "single-process (\"fused\") and the default DDP (\"concurrent\") schedules only" % schedule)
+
+
+# --------------------------------------------------------------------------- learning-rate schedule
+LR_KINDS = ("none", "linear", "cosine", "exponential")  # index = the kernels' id (kernels.h LrKind)
+LR_MAX_STEPS = 1 << 24  # decay and warm-up lengths: exact as fp32
+
+
+class LrSchedule(NamedTuple):
+    """Factor f(t) of the global step t (its value before the step's increment, TF's global_step)
+    that multiplies both networks' Adam rates:
+
+        k = 0 if t <= start else min(t - start, steps);  p = float(k) / float(steps)
+        none 1 | linear 1 - (1 - end) p | cosine 1 - (1 - end) (1 - cos(pi p)) / 2 | exponential end^p
+        k == 0 -> exactly 1, k == steps -> exactly end;  t < warmup: f *= float(t + 1) / float(warmup)
+
+    (tf polynomial_decay with power 1, cosine_decay with alpha = end, exponential_decay clamped at
+    `steps`). The schedule follows the global step: an fp16 step skipped on overflow advances it too."""
+    kind: str = "none"
+    start: int = 0
+    steps: int = 1
+    end: float = 1.0
+    warmup: int = 0
+
+    @property
+    def active(self) -> bool:
+        return self.kind != "none" or self.warmup > 0
+
+    def hip_args(self) -> tuple:
+        """(lr_kind, lr_start, lr_steps, lr_end, lr_warmup) of the Adam bindings."""
+        return (LR_KINDS.index(self.kind), self.start, self.steps, self.end, self.warmup)
+
+    def describe(self) -> str:
+        if not self.active:
+            return "constant"
+        s = "constant" if self.kind == "none" else "%s to %g x over steps %d..%d" % (
+            self.kind, self.end, self.start, self.start + self.steps)
+        return s + (", linear warm-up over %d steps" % self.warmup if self.warmup else "")
+
+
+def _lr_int(name, v, lo, hi):
+    if isinstance(v, bool) or isinstance(v, float) and not v.is_integer() or int(v) != v or not lo <= int(v) <= hi:
+        raise ValueError("%s must be an integer with %d <= %s <= %d, got %r" % (name, lo, name, hi, v))
+    return int(v)
+
+
+def check_lr_schedule(kind="none", start=0, steps=0, end=0.0, warmup=0, total_steps=None,
+                      open_ended=False) -> LrSchedule:
+    """Validated LrSchedule; errors name the flag. kind in LR_KINDS, start >= 0, 1 <= steps <= 2^24,
+    0 <= end <= 1 (> 0 for exponential), 0 <= warmup <= 2^24. steps = 0 with a decay kind means
+    "until the end of training": total_steps - start when `total_steps` is given (an error when
+    that is < 1), left at 0 for a later resolution when `open_ended`, else an error. With kind
+    "none" start / steps / end are not read."""
+    if not isinstance(kind, str) or kind.strip().lower() not in LR_KINDS:
+        raise ValueError("lr_decay must be one of %s, got %r" % (LR_KINDS, kind))
+    kind = kind.strip().lower()
+    warmup = _lr_int("lr_warmup_steps", warmup, 0, LR_MAX_STEPS)
+    if kind == "none":
+        return LrSchedule("none", 0, 1, 1.0, warmup)
+    start = _lr_int("lr_decay_start", start, 0, (1 << 62))
+    steps = _lr_int("lr_decay_steps", steps, 0, LR_MAX_STEPS)
+    if steps == 0:
+        if total_steps is not None:
+            steps = int(total_steps) - start
+            if not 1 <= steps <= LR_MAX_STEPS:
+                raise ValueError("lr_decay_steps=0 decays until the end of training, but %d steps of training minus "
+                                 "lr_decay_start=%d leaves %d (need 1 .. 2^24)" % (int(total_steps), start, steps))
+        elif not open_ended:
+            raise ValueError("lr_decay_steps must be an integer with 1 <= lr_decay_steps <= %d, got 0 (only the "
+                             "trainer resolves 0 = until the end of training)" % LR_MAX_STEPS)
+    end = float(end)
+    if not 0.0 <= end <= 1.0:
+        raise ValueError("lr_end must satisfy 0 <= lr_end <= 1, got %r" % (end,))
+    if kind == "exponential" and not end > 0.0:
+        raise ValueError("lr_end must be > 0 with lr_decay=exponential, got %r" % (end,))
+    return LrSchedule(kind, start, steps, end, warmup)
+
+
+def resolve_lr_schedule(kind=None, start=None, steps=None, end=None, warmup=None, total_steps=None) -> LrSchedule:
+    """check_lr_schedule over the engines' arguments: None = the environment default (DCGAN_LR_DECAY,
+    DCGAN_LR_DECAY_START, DCGAN_LR_DECAY_STEPS, DCGAN_LR_END, DCGAN_LR_WARMUP), then none / 0 / 0 /
+    0.0 / 0. An explicit argument wins. An LrSchedule as `kind` is validated as it is."""
+    import os
+    if isinstance(kind, LrSchedule):
+        return check_lr_schedule(*kind, total_steps=total_steps)
+
+    def env(name, conv):
+        v = os.environ.get(name)
+        if v is None or v.strip() == "":
+            return None
+        try:
+            return conv(v)
+        except ValueError:
+            raise ValueError("%s=%r is not a number" % (name, v)) from None
+    if kind is None:
+        kind = env("DCGAN_LR_DECAY", str)
+    if start is None:
+        start = env("DCGAN_LR_DECAY_START", int)
+    if steps is None:
+        steps = env("DCGAN_LR_DECAY_STEPS", int)
+    if end is None:
+        end = env("DCGAN_LR_END", float)
+    if warmup is None:
+        warmup = env("DCGAN_LR_WARMUP", int)
+    return check_lr_schedule("none" if kind is None else kind, 0 if start is None else start,
+                             0 if steps is None else steps, 0.0 if end is None else end,
+                             0 if warmup is None else warmup, total_steps=total_steps)
+
+
+def lr_factor(sched: LrSchedule, t, dtype=torch.float32) -> torch.Tensor:
+    """The schedule's factor at global step(s) t (int or int64 tensor), evaluated in `dtype`: fp32
+    is the device's arithmetic (`end` rounded to fp32 first), fp64 the closed form."""
+    t = torch.as_tensor(t, dtype=torch.int64)
+    one = torch.ones(t.shape, dtype=dtype)
+    f = one
+    if sched.kind != "none":
+        k = (t - sched.start).clamp(0, sched.steps)
+        p = k.to(dtype) / torch.tensor(float(sched.steps), dtype=dtype)
+        end = torch.tensor(sched.end, dtype=dtype)
+        if sched.kind == "linear":
+            g = 1 - (1 - end) * p
+        elif sched.kind == "cosine":
+            g = 1 - (1 - end) * (0.5 * (1 - torch.cos(torch.tensor(math.pi, dtype=dtype) * p)))
+        else:
+            g = torch.pow(end, p)
+        f = torch.where(k == 0, one, torch.where(k == sched.steps, end.expand(t.shape), g))
+    if sched.warmup > 0:
+        w = (t + 1).clamp(max=sched.warmup).to(dtype) / torch.tensor(float(sched.warmup), dtype=dtype)
+        f = torch.where(t < sched.warmup, f * w, f)
+    return f
 
 
 def zero_fraction(x: torch.Tensor) -> torch.Tensor:

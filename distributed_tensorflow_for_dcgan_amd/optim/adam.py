@@ -41,17 +41,22 @@ class TFAdam:
         b1p = float(self.powers[0])
         return int(round(math.log(b1p) / math.log(self.beta1))) - 1 if b1p > 0 else 0
 
-    def step(self, grads: torch.Tensor) -> None:
-        """Apply one update from a flat grad buffer (same layout as params.flat)."""
+    def step(self, grads: torch.Tensor, lr_factor: float = 1.0) -> None:
+        """Apply one update from a flat grad buffer (same layout as params.flat). lr_factor: the
+        learning-rate schedule's factor at this step (ops.reference.lr_factor), lr_eff = lr * f."""
+        f = float(lr_factor)
         if self.use_hip:
             from ..ops import hip
+            # one fp32 multiply, as the kernels form lr_eff from a device-evaluated factor
+            lr = self.lr if f == 1.0 else float(torch.tensor(self.lr, dtype=torch.float32)
+                                                * torch.tensor(f, dtype=torch.float32))
             hip.adam_(self.params.flat, grads, self.m.flat, self.v.flat, self.powers,
-                      self.lr, self.beta1, self.beta2, self.eps)
+                      lr, self.beta1, self.beta2, self.eps)
             return
         with torch.no_grad():
             b1p, b2p = float(self.powers[0]), float(self.powers[1])
             R.tf_adam_update(self.params.flat, grads, self.m.flat, self.v.flat, b1p, b2p,
-                             self.lr, self.beta1, self.beta2, self.eps)
+                             self.lr * f, self.beta1, self.beta2, self.eps)
             self.powers[0] = self.powers[0] * self.beta1
             self.powers[1] = self.powers[1] * self.beta2
 

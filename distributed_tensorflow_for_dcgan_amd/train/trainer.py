@@ -30,6 +30,7 @@ from ..models.config import config_from_flags
 from ..obs import images as IM
 from ..obs import summaries as SUM
 from ..obs.events import SummaryWriter
+from ..ops import reference as R
 from ..parallel import dist as D
 from ..utils.flags import Flags, apply_dataset_preset, cluster_from_flags
 
@@ -153,14 +154,32 @@ def run(flags: Flags, out=None) -> int:
         print("device %s rank %d/%d local_rank %d (%s) engine %s" % (device, rank, world, cl["local_rank"],
                                                                    cl["source"], flags.engine), file=out, flush=True)
 
-    engine = build_engine(cfg, B, device, engine=flags.engine, dtype=flags.dtype, seed=int(flags.seed), rank=rank,
-                          world=world, graph=bool(flags.graph), allreduce_dtype=flags.allreduce_dtype,
-                          lr=float(flags.learning_rate), beta1=float(flags.beta1),
-                          zero_debias=bool(flags.bn_zero_debias), bucket_mb=float(flags.bucket_mb),
-                          g_ema_decay=float(flags.g_ema_decay), gan_loss=str(flags.gan_loss),
-                          label_smooth=float(flags.label_smooth), d_spectral_norm=bool(flags.d_spectral_norm),
-                          d_steps=int(flags.d_steps), beta2=float(flags.beta2),
-                          lr_d=float(flags.d_learning_rate), lr_g=float(flags.g_learning_rate))
+    # --lr_decay_steps=0 with a decay: "until the end of training". The recorded Adam launches take
+    # the length as a constant, so the data source (whose size caps max_steps through --epoch) is
+    # opened ahead of the engine in that case alone
+    source = None
+    sample_only = flags.explicitly_set("is_train") and not flags.is_train
+    lr_steps = int(flags.lr_decay_steps)
+    if str(flags.lr_decay).strip().lower() != "none" and lr_steps == 0:
+        total = int(flags.lr_decay_start) + 1  # sample-only mode never steps: any valid length
+        if not sample_only:
+            hip_engine = flags.engine == "hip" or (flags.engine == "auto" and device.type == "cuda")
+            source = make_source(flags, B, shape, device, rank=rank, world=world,
+                                 engine_dtype=flags.dtype if hip_engine else "fp32")
+            total = _step_budget(flags, source.num_examples, int(flags.d_steps), B, world)[1]
+        try:
+            lr_steps = R.check_lr_schedule(flags.lr_decay, flags.lr_decay_start, 0, flags.lr_end,
+                                           flags.lr_warmup_steps, total_steps=total).steps
+        except ValueError as e:
+            if source is not None:
+                source.close()
+            raise SystemExit("--lr_decay_steps: %s" % e)
+    try:
+        engine = _build_engine(flags, cfg, B, device, rank, world, lr_steps)
+    except BaseException:
+        if source is not None:
+            source.close()
+        raise
     n_d = int(getattr(engine, "d_steps", 1))  # real batches (and D updates) per training step
     if chief:
         print("GAN objective: %s, label_smooth %g (D's real target %g)" % (
@@ -172,6 +191,10 @@ def run(flags: Flags, out=None) -> int:
             print("optimisers: %d discriminator update(s) per generator update (%d real batches per step), "
                   "Adam lr D %g / G %g, beta1 %g, beta2 %g" % (n_d, n_d, engine.opt_d.lr, engine.opt_g.lr,
                                                                engine.opt_d.beta1, engine.opt_d.beta2),
+                  file=out, flush=True)
+        sched = getattr(engine, "lr_sched", None)
+        if sched is not None and sched.active:
+            print("learning-rate schedule: %s (of the global step; both networks)" % sched.describe(),
                   file=out, flush=True)
     if flags.log_device_placement:
         for line in placement_report(engine, device, rank, world):
@@ -190,7 +213,7 @@ def run(flags: Flags, out=None) -> int:
         if info and "d_sn" in info:
             print("discriminator spectral norm state: %s" % info["d_sn"], file=out)
 
-    if flags.explicitly_set("is_train") and not flags.is_train:
+    if sample_only:
         try:
             return _test_mode(engine, flags, cfg, B, device, info, chief, out)
         finally:
@@ -200,7 +223,8 @@ def run(flags: Flags, out=None) -> int:
         engine.enable_timing()
 
     edt = getattr(engine, "dtype_name", None)
-    source = make_source(flags, B, shape, device, rank=rank, world=world, engine_dtype=edt)
+    if source is None:
+        source = make_source(flags, B, shape, device, rank=rank, world=world, engine_dtype=edt)
     sample_source = None
     if chief and not flags.synthetic and os.path.isdir(flags.sample_image_dir):
         sample_source = make_source(flags, B, shape, device, rank=0, world=1, data_dir=flags.sample_image_dir,
@@ -209,13 +233,7 @@ def run(flags: Flags, out=None) -> int:
     gen = torch.Generator().manual_seed(int(flags.seed) + 4242)
     sample_z = (torch.rand(B, cfg.z_dim, generator=gen) * 2 - 1).to(device)  # fixed (image_train.py:77)
 
-    n_ex = source.num_examples
-    if flags.train_size != math.inf:
-        n_ex = min(n_ex, int(flags.train_size))
-    step_per_epoch = max(1, -(-n_ex // (n_d * B * world)))  # a step consumes d_steps x W x B images
-    max_steps = int(flags.max_steps)
-    if flags.epoch and int(flags.epoch) > 0:
-        max_steps = min(max_steps, int(flags.epoch) * step_per_epoch)
+    step_per_epoch, max_steps = _step_budget(flags, source.num_examples, n_d, B, world)
 
     writer = SummaryWriter(flags.checkpoint_dir) if (chief and flags.summaries) else None
     prof_range = None
@@ -266,6 +284,11 @@ def run(flags: Flags, out=None) -> int:
                     print("Running Summary operation on the chief.", file=out)
                     rate = (step - last_rate_step) / max(1e-9, now - last_rate_t)
                     vals = SUM.collect(engine, L, steps_per_sec=rate, loader_stats=source.stats())
+                    # the rates of the step just taken (global step `step - 1` before its increment),
+                    # from the oracle on the host: no device read
+                    f = float(R.lr_factor(engine.lr_sched, step - 1)) if hasattr(engine, "lr_sched") else 1.0
+                    vals.append(SummaryWriter.scalar("learning_rate/d", engine.opt_d.lr * f))
+                    vals.append(SummaryWriter.scalar("learning_rate/g", engine.opt_g.lr * f))
                     writer.add_summary_values(vals, step)
                     writer.flush()
                     print("Finished running Summary operation.", file=out)
@@ -316,6 +339,31 @@ def run(flags: Flags, out=None) -> int:
         D.barrier()
         D.shutdown()
     return 0
+
+
+def _step_budget(flags, n_ex: int, n_d: int, B: int, world: int):
+    """(steps per epoch, max_steps after the --epoch cap): a step consumes d_steps x W x B images."""
+    if flags.train_size != math.inf:
+        n_ex = min(n_ex, int(flags.train_size))
+    step_per_epoch = max(1, -(-n_ex // (n_d * B * world)))
+    max_steps = int(flags.max_steps)
+    if flags.epoch and int(flags.epoch) > 0:
+        max_steps = min(max_steps, int(flags.epoch) * step_per_epoch)
+    return step_per_epoch, max_steps
+
+
+def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps):
+    return build_engine(cfg, B, device, engine=flags.engine, dtype=flags.dtype, seed=int(flags.seed), rank=rank,
+                        world=world, graph=bool(flags.graph), allreduce_dtype=flags.allreduce_dtype,
+                        lr=float(flags.learning_rate), beta1=float(flags.beta1),
+                        zero_debias=bool(flags.bn_zero_debias), bucket_mb=float(flags.bucket_mb),
+                        g_ema_decay=float(flags.g_ema_decay), gan_loss=str(flags.gan_loss),
+                        label_smooth=float(flags.label_smooth), d_spectral_norm=bool(flags.d_spectral_norm),
+                        d_steps=int(flags.d_steps), beta2=float(flags.beta2),
+                        lr_d=float(flags.d_learning_rate), lr_g=float(flags.g_learning_rate),
+                        lr_decay=str(flags.lr_decay), lr_decay_start=int(flags.lr_decay_start),
+                        lr_decay_steps=int(lr_decay_steps), lr_end=float(flags.lr_end),
+                        lr_warmup=int(flags.lr_warmup_steps))
 
 
 def _sample_ema(engine, flags) -> bool:

@@ -97,6 +97,15 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
     ("beta2", "float", 0.999, "Adam's second-moment decay, 0 <= beta2 < 1 (SN-GAN: --beta1=0 --beta2=0.9)"),
     ("d_learning_rate", "float", 0.0, "learning rate of the discriminator's Adam (TTUR); 0 = --learning_rate"),
     ("g_learning_rate", "float", 0.0, "learning rate of the generator's Adam (TTUR); 0 = --learning_rate"),
+    ("lr_decay", "str", "none", "learning-rate schedule, one of none, linear, cosine, exponential: both networks' "
+                                "rates times a factor of the global step that falls from 1 to --lr_end over "
+                                "--lr_decay_steps steps from --lr_decay_start on (SN-GAN: --lr_decay=linear; pix2pix: "
+                                "a constant first half with --lr_decay_start)"),
+    ("lr_decay_start", "int", 0, "first step of the decay: the factor is 1 up to and including this global step"),
+    ("lr_decay_steps", "int", 0, "length of the decay in steps, 1..2^24; 0 = until the end of training (max_steps after "
+                                 "the --epoch cap, minus --lr_decay_start)"),
+    ("lr_end", "float", 0.0, "final factor, 0 <= lr_end <= 1, reached exactly (> 0 with --lr_decay=exponential)"),
+    ("lr_warmup_steps", "int", 0, "linear warm-up: for the first n steps the factor is also times (step + 1) / n"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -187,6 +196,12 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         check_d_steps(ns.d_steps, ns.beta2, ns.d_learning_rate, ns.g_learning_rate, ns.learning_rate)
     except (ValueError, TypeError, OverflowError) as e:
         parser.error("--d_steps / --beta2 / --d_learning_rate / --g_learning_rate: %s" % e)
+    from ..ops.reference import check_lr_schedule
+    try:  # (--lr_decay_steps=0 with a decay stays open here: the trainer resolves it)
+        check_lr_schedule(ns.lr_decay, ns.lr_decay_start, ns.lr_decay_steps, ns.lr_end, ns.lr_warmup_steps,
+                          open_ended=True)
+    except (ValueError, TypeError, OverflowError) as e:
+        parser.error("--lr_decay / --lr_decay_start / --lr_decay_steps / --lr_end / --lr_warmup_steps: %s" % e)
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
