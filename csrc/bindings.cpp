@@ -1098,6 +1098,48 @@ class Program {
       return KF(dcg_philox_uniform)(P<float>(out), n, seed, P<const unsigned long long>(step), stream_id, lo, hi, s);
     }, AccList().w(out, n * 4).r(step, 8).v);
   }
+  // Validated instance-noise schedule (kernels.h NoiseSched): 0 <= sigma0, sigma1 <= 2, both finite;
+  // 1 <= steps <= 2^24 whenever they differ (not read when they are equal)
+  static NoiseSched noise_sched(const char* op, double sigma0, double sigma1, int64_t steps) {
+    const std::string o(op);
+    for (double v : {sigma0, sigma1})
+      if (!(v >= 0.0 && v <= (double)NOISE_MAX_SIGMA))  // (NaN fails both comparisons)
+        throw std::runtime_error(o + ": sigma0 and sigma1 must be finite with 0 <= sigma <= 2, got " +
+                                 std::to_string(sigma0) + ", " + std::to_string(sigma1));
+    if (sigma0 != sigma1 && (steps < 1 || steps > (int64_t)NOISE_MAX_STEPS))
+      throw std::runtime_error(o + ": steps must satisfy 1 <= steps <= 2^24 when sigma0 != sigma1, got " +
+                               std::to_string(steps));
+    return NoiseSched{(float)sigma0, (float)sigma1, sigma0 != sigma1 ? (unsigned)steps : 1u};
+  }
+  // instance noise on D's input: y = x + sigma(*step) * eps over n elements of the Program's element
+  // type (instance_noise_kernel); reads x and the 8-byte step counter, writes y
+  int instance_noise(std::string name, uintptr_t x, uintptr_t y, size_t n, uint64_t seed, uintptr_t step,
+                     uint64_t stream_id, double sigma0, double sigma1, int64_t steps, int stream) {
+    if (!x || !y || !step) throw std::runtime_error("instance_noise: x, y and step must be non-null");
+    if (x == y) throw std::runtime_error("instance_noise: y must be a buffer of its own");
+    const NoiseSched S = noise_sched("instance_noise", sigma0, sigma1, steps);
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_instance_noise)(P<const elem_t>(x), P<elem_t>(y), n, seed, P<const unsigned long long>(step),
+                                    stream_id, &S, s);
+    }, AccList().r(x, n * es_).r(step, 8).w(y, n * es_).v);
+  }
+  // fp32 standard normals of the Philox stream (seed, *step, stream_id) -> out float32[n]
+  int philox_normal(std::string name, uintptr_t out, size_t n, uint64_t seed, uintptr_t step, uint64_t stream_id,
+                    int stream) {
+    if (!out || !step) throw std::runtime_error("philox_normal: out and step must be non-null");
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_philox_normal)(P<float>(out), n, seed, P<const unsigned long long>(step), stream_id, s);
+    }, AccList().w(out, n * 4).r(step, 8).v);
+  }
+  // the noise schedule's sigma at each of n int64 step values -> out float32[n] (dcg::noise_sigma)
+  int noise_sigma(std::string name, uintptr_t steps_ptr, uintptr_t out, size_t n, double sigma0, double sigma1,
+                  int64_t steps, int stream) {
+    if (!steps_ptr || !out) throw std::runtime_error("noise_sigma: steps and out must be non-null");
+    const NoiseSched S = noise_sched("noise_sigma", sigma0, sigma1, steps);
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_noise_sigma)(P<const unsigned long long>(steps_ptr), P<float>(out), n, &S, s);
+    }, AccList().r(steps_ptr, n * 8).w(out, n * 4).v);
+  }
   int im2col_s2(std::string name, uintptr_t src, uintptr_t dst, int Bn, int H, int W, int C, int Ho, int Wo, int pl_y,
                 int pl_x, int Kpad, int stream) {
     return add(name, stream, [=](hipStream_t s) {
@@ -1334,6 +1376,13 @@ PYBIND11_MODULE(_dcgan_hip, m) {
            py::arg("chunks_per_wg") = 0)
       .def("pack", &Program::pack)
       .def("philox_uniform", &Program::philox_uniform)
+      .def("instance_noise", &Program::instance_noise, py::arg("name"), py::arg("x"), py::arg("y"), py::arg("n"),
+           py::arg("seed"), py::arg("step"), py::arg("stream_id"), py::arg("sigma0"), py::arg("sigma1"),
+           py::arg("steps"), py::arg("stream") = 0)
+      .def("philox_normal", &Program::philox_normal, py::arg("name"), py::arg("out"), py::arg("n"), py::arg("seed"),
+           py::arg("step"), py::arg("stream_id"), py::arg("stream") = 0)
+      .def("noise_sigma", &Program::noise_sigma, py::arg("name"), py::arg("steps_ptr"), py::arg("out"), py::arg("n"),
+           py::arg("sigma0"), py::arg("sigma1"), py::arg("steps"), py::arg("stream") = 0)
       .def("im2col_s2", &Program::im2col_s2)
       .def("cast_to_bf16", &Program::cast_to_bf16)
       .def("cast_bf16_f32", &Program::cast_bf16_f32)

@@ -115,6 +115,20 @@ struct LrSched {
 
 __host__ __device__ static inline bool lr_sched_on(const LrSched& s) { return s.kind != LR_NONE || s.warmup != 0; }
 
+// Instance noise on D's input (misc.hip instance_noise_kernel), by value in the kernel arguments:
+// sigma(t) of the DEVICE step counter t, so graph replays follow the live counter.
+//   sigma(t) = s1 if s0 == s1 or t >= steps, else fma(s1 - s0, float(t) / float(steps), s0)
+// The noise draws from Philox stream NOISE_STREAM of the step's z seed (z itself from stream 0).
+constexpr unsigned NOISE_MAX_STEPS = 1u << 24;  // exact as fp32
+constexpr float NOISE_MAX_SIGMA = 2.f;
+constexpr unsigned NOISE_MAX_BLOCKS = 2048;     // grid cap (256 CUs x 8 resident workgroups); grid-stride beyond
+constexpr unsigned long long NOISE_STREAM = 1;
+
+struct NoiseSched {
+  float s0, s1;
+  unsigned steps;
+};
+
 // GAN objectives of the loss / head kernels (misc.hip gan_loss_block). The first three are the
 // ids of the launchers and bindings; GAN_BCE_T is the kernel instance of bce with a smoothed
 // real target, which the launchers pick themselves (real_target != 1).

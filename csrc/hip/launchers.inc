@@ -72,6 +72,15 @@ int DCG_API(dcg_nonfinite_check)(const float* g, size_t n, float* ls, hipStream_
 int DCG_API(dcg_pack)(const float* src, int T, int A, int Bd, elem_t* nat, elem_t* tr, int st, int sb, int sa, hipStream_t s);
 int DCG_API(dcg_philox_uniform)(float* out, size_t n, uint64_t seed, const unsigned long long* step, uint64_t stream_id,
                        float lo, float hi, hipStream_t s);
+// instance noise: y = x + sigma(*step) * eps over n elements (eps: Box-Muller normals of the Philox
+// stream (seed, *step, stream_id)); its probes: the fp32 normals, sigma at each of n step values.
+// -2: a null pointer
+int DCG_API(dcg_instance_noise)(const elem_t* x, elem_t* y, size_t n, uint64_t seed, const unsigned long long* step,
+                                uint64_t stream_id, const dcg::NoiseSched* sched, hipStream_t s);
+int DCG_API(dcg_philox_normal)(float* out, size_t n, uint64_t seed, const unsigned long long* step, uint64_t stream_id,
+                               hipStream_t s);
+int DCG_API(dcg_noise_sigma)(const unsigned long long* steps, float* out, size_t n, const dcg::NoiseSched* sched,
+                             hipStream_t s);
 int DCG_API(dcg_im2col_s2)(const elem_t* src, elem_t* dst, int B, int H, int W, int C, int Ho, int Wo, int pl_y, int pl_x,
                   int Kpad, hipStream_t s);
 int DCG_API(dcg_cast_to_bf16)(const void* src, int src_dtype, elem_t* dst, size_t n, float scale, float shift, hipStream_t s);

@@ -7,6 +7,7 @@
 //   * TF-form Adam over a flat fp32 buffer + device-side beta powers (K17, graph-capturable)
 //   * elem_t weight packing (natural + per-tap transposed / im2col-ordered copies)
 //   * Philox-4x32-10 z ~ U(-1,1) keyed by a device step counter (K19, graph-capturable)
+//   * instance noise on D's input: Philox normals (Box-Muller), sigma annealed from the step counter
 //   * stride-2 TF-SAME im2col for 3-channel tensors, dtype casts
 #include <algorithm>
 #include <type_traits>
@@ -117,21 +118,62 @@ __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_
   c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
 }
 
-// 4 uniforms of counter i4 (Philox-4x32-10 keyed by seed, counter = (i4, step, stream)) in [lo, hi)
-__device__ __forceinline__ float philox_uniform_at(size_t idx, uint64_t seed, uint64_t st, uint64_t stream_id,
-                                                   float lo, float hi) {
-  const size_t i4 = idx >> 2;
-  uint32_t c0 = (uint32_t)i4, c1 = (uint32_t)(i4 >> 32), c2 = (uint32_t)st, c3 = (uint32_t)(st >> 32) ^ (uint32_t)stream_id;
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+// the ten rounds of Philox-4x32-10 (Random123) on counter (c0..c3) under key (k0, k1): the one
+// generator of z, the probes and the instance noise
+__device__ __forceinline__ void philox4x32_10(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
+                                              uint32_t k1) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
     philox_round(c0, c1, c2, c3, k0, k1);
     k0 += 0x9E3779B9u;
     k1 += 0xBB67AE85u;
   }
+}
+
+// the block of 4 words at counter (lo32(i4), hi32(i4), lo32(st), hi32(st) ^ stream_id), key = seed:
+// element e of a flat buffer draws lane e % 4 of block e / 4
+__device__ __forceinline__ void philox_block(size_t i4, uint64_t seed, uint64_t st, uint64_t stream_id,
+                                             uint32_t (&c)[4]) {
+  c[0] = (uint32_t)i4; c[1] = (uint32_t)((uint64_t)i4 >> 32); c[2] = (uint32_t)st;
+  c[3] = (uint32_t)(st >> 32) ^ (uint32_t)stream_id;
+  philox4x32_10(c[0], c[1], c[2], c[3], (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// 4 uniforms of counter i4 (Philox-4x32-10 keyed by seed, counter = (i4, step, stream)) in [lo, hi)
+__device__ __forceinline__ float philox_uniform_at(size_t idx, uint64_t seed, uint64_t st, uint64_t stream_id,
+                                                   float lo, float hi) {
+  uint32_t c[4];
+  philox_block(idx >> 2, seed, st, stream_id, c);
   const int j = (int)(idx & 3);
-  const uint32_t cj = j == 0 ? c0 : (j == 1 ? c1 : (j == 2 ? c2 : c3));
+  const uint32_t cj = j == 0 ? c[0] : (j == 1 ? c[1] : (j == 2 ? c[2] : c[3]));
   return lo + (hi - lo) * ((float)(cj >> 8) * (1.0f / 16777216.0f));
+}
+
+// 4 standard normals of block i4: Box-Muller per pair of words. (a, b) = (c0, c1) gives lanes 0, 1,
+// (c2, c3) lanes 2, 3: u0 = ((a >> 8) + 1) 2^-24 in (0, 1], u1 = (b >> 8) 2^-24 in [0, 1), r =
+// sqrt(-2 ln u0), even lane r cos(2 pi u1), odd lane r sin(2 pi u1). |e| <= sqrt(48 ln 2) ~ 5.77.
+__device__ __forceinline__ void philox_normal4(size_t i4, uint64_t seed, uint64_t st, uint64_t stream_id,
+                                               float (&e)[4]) {
+  uint32_t c[4];
+  philox_block(i4, seed, st, stream_id, c);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float u0 = (float)((c[2 * h] >> 8) + 1u) * (1.0f / 16777216.0f);
+    const float u1 = (float)(c[2 * h + 1] >> 8) * (1.0f / 16777216.0f);
+    const float r = sqrtf(-2.f * logf(u0));
+    float sn, cs;
+    sincospif(2.f * u1, &sn, &cs);
+    e[2 * h] = r * cs;
+    e[2 * h + 1] = r * sn;
+  }
+}
+
+// sigma(t) of kernels.h NoiseSched: block-uniform (S is a kernel argument, t one scalar load of the
+// step counter, read live so graph replays follow it). Both ends by selection: t = 0 -> s0 (the
+// fma adds an exact 0), t >= steps -> s1.
+__device__ __forceinline__ float noise_sigma(const NoiseSched& S, unsigned long long t) {
+  if (S.s0 == S.s1 || t >= (unsigned long long)S.steps) return S.s1;
+  return __builtin_fmaf(S.s1 - S.s0, (float)(unsigned)t / (float)S.steps, S.s0);  // t < 2^24: exact
 }
 
 // ---------------------------------------------------------------- linear: out = z @ W + b
@@ -803,15 +845,8 @@ __global__ __launch_bounds__(256) void philox_uniform_kernel(float* __restrict__
   const size_t i4 = blockIdx.x * 256 + threadIdx.x;
   if (i4 * 4 >= n) return;
   const uint64_t st = step ? step[0] : 0ull;
-  uint32_t c0 = (uint32_t)i4, c1 = (uint32_t)(i4 >> 32), c2 = (uint32_t)st, c3 = (uint32_t)(st >> 32) ^ (uint32_t)stream_id;
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c0, c1, c2, c3, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  const uint32_t c[4] = {c0, c1, c2, c3};
+  uint32_t c[4];
+  philox_block(i4, seed, st, stream_id, c);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const size_t idx = i4 * 4 + j;
@@ -819,6 +854,74 @@ __global__ __launch_bounds__(256) void philox_uniform_kernel(float* __restrict__
       const float u = (float)(c[j] >> 8) * (1.0f / 16777216.0f);  // [0, 1)
       out[idx] = lo + (hi - lo) * u;
     }
+  }
+}
+
+// fp32 standard normals of the stream (seed, *step, stream_id): the probe of philox_normal4
+__global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ out, size_t n, uint64_t seed,
+                                                            const unsigned long long* __restrict__ step,
+                                                            uint64_t stream_id) {
+  const uint64_t st = step[0];
+  const size_t nb = (n + 3) / 4;
+  for (size_t i4 = blockIdx.x * 256 + threadIdx.x; i4 < nb; i4 += (size_t)gridDim.x * 256) {
+    float e[4];
+    philox_normal4(i4, seed, st, stream_id, e);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i4 * 4 + j < n) out[i4 * 4 + j] = e[j];
+  }
+}
+
+// noise_sigma at each of n step values: the tests' probe
+__global__ __launch_bounds__(256) void noise_sigma_kernel(NoiseSched S, const unsigned long long* __restrict__ steps,
+                                                          float* __restrict__ out, size_t n) {
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = noise_sigma(S, steps[i]);
+}
+
+// ---------------------------------------------------------------- instance noise on D's input
+// y[e] = E(fma(sigma(t), eps[e], float(x[e]))), eps[e] = lane e % 4 of the normals of block e / 4 of
+// the stream (seed, t = *step, stream_id): D's stacked [real | fake] input x -> its noisy copy y
+// (separate buffers; x is only read). Streaming, grid-stride: 16 bytes per thread and iteration (8
+// sixteen-bit elements = two Philox blocks, or 4 floats = one), a scalar loop over the tail -- and
+// over everything when x or y is not 16-byte aligned; the element -> (block, lane) map is the same
+// either way. sigma == 0 copies the bits (fma(0, e, -0) would be +0).
+template <typename E>
+__global__ __launch_bounds__(256) void instance_noise_kernel(const E* __restrict__ x, E* __restrict__ y, size_t n,
+                                                             uint64_t seed,
+                                                             const unsigned long long* __restrict__ step,
+                                                             uint64_t stream_id, NoiseSched S) {
+  constexpr int V = 16 / (int)sizeof(E);  // elements per 16-byte access
+  constexpr int NB = V / 4;               // Philox blocks per access
+  const uint64_t st = step[0];
+  const float sg = noise_sigma(S, st);
+  const bool aligned = (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+  const size_t nv = aligned ? n / V : 0;
+  const size_t tid = blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  if (sg == 0.f) {
+    for (size_t v = tid; v < nv; v += stride)
+      reinterpret_cast<u32x4*>(y)[v] = reinterpret_cast<const u32x4*>(x)[v];
+    for (size_t e = nv * V + tid; e < n; e += stride) y[e] = x[e];
+    return;
+  }
+  for (size_t v = tid; v < nv; v += stride) {
+    typedef E EV __attribute__((ext_vector_type(V)));
+    const EV xv = __builtin_bit_cast(EV, reinterpret_cast<const u32x4*>(x)[v]);
+    EV yv;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      float e[4];
+      philox_normal4(v * NB + b, seed, st, stream_id, e);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) yv[4 * b + j] = (E)__builtin_fmaf(sg, e[j], (float)xv[4 * b + j]);
+    }
+    reinterpret_cast<u32x4*>(y)[v] = __builtin_bit_cast(u32x4, yv);
+  }
+  for (size_t i = nv * V + tid; i < n; i += stride) {
+    float e[4];
+    philox_normal4(i >> 2, seed, st, stream_id, e);
+    const int j = (int)(i & 3);
+    const float ej = j == 0 ? e[0] : (j == 1 ? e[1] : (j == 2 ? e[2] : e[3]));
+    y[i] = (E)__builtin_fmaf(sg, ej, (float)x[i]);
   }
 }
 
@@ -1186,6 +1289,32 @@ extern "C" int DCG_API(dcg_philox_uniform)(float* out, size_t n, uint64_t seed, 
                                   uint64_t stream_id, float lo, float hi, hipStream_t s) {
   hipLaunchKernelGGL(philox_uniform_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, out, n, seed, step,
                      stream_id, lo, hi);
+  return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_philox_normal)(float* out, size_t n, uint64_t seed, const unsigned long long* step,
+                                          uint64_t stream_id, hipStream_t s) {
+  if (!out || !step) return -2;
+  hipLaunchKernelGGL(philox_normal_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, out, n, seed, step,
+                     stream_id);
+  return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_noise_sigma)(const unsigned long long* steps, float* out, size_t n,
+                                        const dcg::NoiseSched* sched, hipStream_t s) {
+  if (!steps || !out || !sched) return -2;
+  hipLaunchKernelGGL(noise_sigma_kernel, dim3(grid_for(n)), dim3(256), 0, s, *sched, steps, out, n);
+  return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_instance_noise)(const elem_t* x, elem_t* y, size_t n, uint64_t seed,
+                                           const unsigned long long* step, uint64_t stream_id,
+                                           const dcg::NoiseSched* sched, hipStream_t s) {
+  if (!x || !y || !step || !sched) return -2;
+  size_t b = (n / (16 / sizeof(elem_t)) + 255) / 256;  // one 16-byte access per thread, capped; the rest grid-strides
+  if (b > NOISE_MAX_BLOCKS) b = NOISE_MAX_BLOCKS;
+  hipLaunchKernelGGL(instance_noise_kernel<elem_t>, dim3((unsigned)(b ? b : 1)), dim3(256), 0, s, x, y, n, seed, step,
+                     stream_id, *sched);
   return (int)hipGetLastError();
 }
 

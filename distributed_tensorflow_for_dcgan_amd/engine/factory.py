@@ -33,7 +33,9 @@ class ReferenceEngine:
                  beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None,
                  lr_decay: Optional[str] = None,
                  lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
-                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None, **_):
+                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
+                 instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
+                 instance_noise_steps: Optional[int] = None, **_):
         self.cfg = cfg
         self.batch_size = batch_size
         self.device = device
@@ -58,7 +60,12 @@ class ReferenceEngine:
         d_steps, beta2, lr_d, lr_g = R.resolve_d_steps(d_steps, beta2, lr_d, lr_g, lr)
         # learning-rate schedule: None = DCGAN_LR_DECAY / _START / _STEPS / DCGAN_LR_END / DCGAN_LR_WARMUP
         self.lr_sched = R.resolve_lr_schedule(lr_decay, lr_decay_start, lr_decay_steps, lr_end, lr_warmup)
+        # instance noise: None = DCGAN_INSTANCE_NOISE / _END / _STEPS; drawn from the HIP engine's seed
+        # formula (HipEngine._zseed), so both engines add the same noise for the same flags
+        self.noise = R.resolve_instance_noise(instance_noise, instance_noise_end, instance_noise_steps)
+        zs = self.seed if z_seed is None else int(z_seed)
         self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None,
+                                       instance_noise=self.noise, noise_seed=zs * 1000003 + 17 + 7919 * rank,
                                        g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth,
                                        d_spectral_norm=bool(d_spectral_norm), seed=seed, d_steps=d_steps,
                                        beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=self.lr_sched)
@@ -103,7 +110,7 @@ class ReferenceEngine:
         """D sub-step k alone (its losses: last_losses())."""
         z = self.sample_z(self._reals[k].shape[0])
         self._last_z = z
-        self._losses = self.step_impl.d_step(self._reals[k], z)
+        self._losses = self.step_impl.d_step(self._reals[k], z, sub=k)
 
     def train_step(self) -> None:
         for k in range(self.d_steps - 1):
@@ -119,7 +126,7 @@ class ReferenceEngine:
         rec: Dict[str, torch.Tensor] = {}
         B = self._real.shape[0]
         with torch.no_grad():
-            out = self.step_impl.forward_losses(self._real, self._last_z, update_ema=False, record=rec)
+            out = self.step_impl.forward_losses(self._real, self._last_z, update_ema=False, record=rec, noise=False)
         a = OrderedDict()
         a["z"] = self._last_z
         a["d"] = torch.sigmoid(out["logits_real"])
@@ -138,6 +145,10 @@ class ReferenceEngine:
     def last_losses(self) -> Dict[str, float]:
         return dict(self._losses)
 
+    def noise_sigma(self) -> float:
+        """sigma(t) of the instance noise at the current global step (0.0 when off)."""
+        return self.step_impl.noise_sigma()
+
     @property
     def g_ema(self):
         """Moving average of G's weights (a ParamSet laid out like model.g), None when off."""
@@ -150,7 +161,7 @@ class ReferenceEngine:
         """Sample-time d_loss/g_loss (image_train.py:181-184) without mutating BN EMAs."""
         with torch.no_grad():
             out = self.step_impl.forward_losses(real.to(self.device, torch.float32), z.to(self.device),
-                                                update_ema=False)
+                                                update_ema=False, noise=False)
         return {"d_loss": float(out["d_loss"]), "g_loss": float(out["g_loss"])}
 
     def sync_state_for_checkpoint(self) -> None:
@@ -181,7 +192,9 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                  beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None,
                  lr_decay: Optional[str] = None,
                  lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
-                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None):
+                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
+                 instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
+                 instance_noise_steps: Optional[int] = None):
     if engine == "auto":  # every dtype (bf16 / fp16 / fp32) runs on the HIP kernels on an MI355X
         engine = "hip" if device.type == "cuda" else "reference"
     if engine == "reference":
@@ -190,7 +203,8 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                                gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm,
                                d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=lr_decay,
                                lr_decay_start=lr_decay_start, lr_decay_steps=lr_decay_steps, lr_end=lr_end,
-                               lr_warmup=lr_warmup)
+                               lr_warmup=lr_warmup, instance_noise=instance_noise,
+                               instance_noise_end=instance_noise_end, instance_noise_steps=instance_noise_steps)
     if engine == "hip":
         from .hip_engine import HipEngine
         return HipEngine(cfg, batch_size, device, dtype=dtype, seed=seed, lr=lr, beta1=beta1,
@@ -199,5 +213,6 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                          gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm,
                          d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=lr_decay,
                          lr_decay_start=lr_decay_start, lr_decay_steps=lr_decay_steps, lr_end=lr_end,
-                         lr_warmup=lr_warmup)
+                         lr_warmup=lr_warmup, instance_noise=instance_noise,
+                         instance_noise_end=instance_noise_end, instance_noise_steps=instance_noise_steps)
     raise ValueError("unknown engine %r" % engine)

@@ -147,7 +147,7 @@ class HipEngineAux:
         if self.progEval is None:
             prog = self._prog()
             self._ev_z = self._t(self.B, self.cfg.z_dim, dtype=torch.float32)
-            self._build_forward(prog, update_ema=False, z=self._ev_z, train_z=False)
+            self._build_forward(prog, update_ema=False, z=self._ev_z, train_z=False, noise=False)  # D sees clean inputs
             self.progEval = prog
         saved_real = self.d_in[:self.B].clone()
         saved_losses = self.losses.clone()

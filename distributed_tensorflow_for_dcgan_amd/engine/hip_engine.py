@@ -6,7 +6,9 @@ every step from C++ (eager, the default) or as hipGraphs:
 
   progA[:a_fwd]  z ~ U(-1,1) (Philox, device step counter) -> G forward -> D forward on the 2B
                  batch [real | fake] with per-half BN statistics -> the 3 losses of the objective
-                 (``gan_loss``: bce | lsgan | hinge) + both seeds, fused into the head GEMV
+                 (``gan_loss``: bce | lsgan | hinge) + both seeds, fused into the head GEMV; with
+                 ``instance_noise`` one launch, ``d_noise``, between G and D writes the noisy copy
+                 of [real | fake] that D's layer 0 reads (forward here, weight gradient in progB)
   progA[a_fwd:]  the g_loss chain back through D(fake) and G's data gradients  -- "G chain"
   progW          G's weight gradients, each tied to the progA position that produces its operand
   progB          D's backward of d_loss, both halves (D grads final)            -- "D chain"
@@ -144,7 +146,9 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  z_seed: Optional[int] = None, d_steps: Optional[int] = None, beta2: Optional[float] = None,
                  lr_d: Optional[float] = None, lr_g: Optional[float] = None, lr_decay: Optional[str] = None,
                  lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
-                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None, **_):
+                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
+                 instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
+                 instance_noise_steps: Optional[int] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -177,6 +181,11 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # None: DCGAN_LR_DECAY / _START / _STEPS / DCGAN_LR_END / DCGAN_LR_WARMUP. Off: the Adam ops
         # are recorded exactly as without it and never read the counter
         self.lr_sched = R.resolve_lr_schedule(lr_decay, lr_decay_start, lr_decay_steps, lr_end, lr_warmup)
+        # instance noise (ops.reference.InstanceNoise): D's layer 0 reads x + sigma(t) * eps, a noisy copy
+        # of [real | fake] that one recorded launch (`d_noise`) writes from the device step counter; the
+        # g_loss chain and G keep reading the clean fake. None: DCGAN_INSTANCE_NOISE / _END / _STEPS.
+        # Off: no buffer, no op
+        self.noise = R.resolve_instance_noise(instance_noise, instance_noise_end, instance_noise_steps)
         # moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates = the
         # global step); 0 = off: no buffers, no op. None: DCGAN_G_EMA_DECAY (A/B of its cost)
         if g_ema_decay is None:
@@ -272,6 +281,10 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # staging area of d_steps real batches: D sub-step k reads (and G writes the fake half of)
         # its own [real_k | fake] buffer; the last slot is the full step's d_in
         self.d_ins = [t(B2, s, s, cfg.c_dim, zero=True) for _ in range(self.d_steps - 1)] + [self.d_in]
+        # instance noise: the noisy copy D's layer 0 reads. ONE buffer for the sub-steps and the full
+        # step: each ends with its D chain (the last reader) joined back into the main stream, where
+        # the next forward rewrites it (schedule_check proves it: tests/test_instance_noise.py)
+        self.d_noisy = torch.zeros_like(self.d_in) if self.noise.active else None
         self.d_x, self.d_a = {}, {}
         for i, L in enumerate(self.dl):
             if L.bn:
@@ -653,10 +666,24 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             return zseed
         return (zseed + (sub + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
 
+    def _d_input(self, sub: Optional[int] = None, noise: bool = True) -> torch.Tensor:
+        """What D's layer 0 reads (forward and weight gradient): [real | fake] of the full step or
+        of D sub-step `sub`, or its noisy copy under instance noise."""
+        if noise and self.noise.active:
+            return self.d_noisy
+        return self.d_in if sub is None else self.d_ins[sub]
+
+    def noise_sigma(self) -> float:
+        """sigma(t) of the instance noise at the current global step (0.0 when off)."""
+        n = self.noise
+        return float(R.noise_sigma(self.global_step, n.sigma0, n.sigma1, n.steps)) if n.active else 0.0
+
     def _build_forward(self, prog, update_ema: bool, z, train_z: bool, update_ema_g: Optional[bool] = None,
-                       sub: Optional[int] = None):
+                       sub: Optional[int] = None, noise: bool = True):
         """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's). sub = k: the forward
-        of D sub-step k -- its z seed and its [real_k | fake] buffer, the same ops otherwise."""
+        of D sub-step k -- its z seed and its [real_k | fake] buffer, the same ops otherwise. noise:
+        with instance noise on, record `d_noise` and let D's layer 0 read the noisy copy (False: the
+        sample-time losses, which stay clean)."""
         cfg, B = self.cfg, self.B
         B2 = 2 * B
         Pg, Pd = self.model.g, self.model.d
@@ -702,8 +729,12 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                                         _p(self.g_a[Lp.name]), 0)
             else:  # last: + bias, tanh, written into the fake half of D's input
                 self._deconv_out(prog, L.name, a_prev, nat, fake, B, L, pad, Pg[L.name + "/biases"], TANH)
-        # D forward on [real | fake]
-        prev = d_in
+        # D forward on [real | fake]; instance noise: on its noisy copy, written here -- behind the op
+        # that wrote the fake half, on the main stream -- from stream 1 of the step's z seed
+        prev = self._d_input(sub, noise)
+        if prev is not d_in:
+            prog.instance_noise("d_noise", _p(d_in), _p(prev), d_in.numel(), zseed, _p(self.step_counter),
+                                R.NOISE_STREAM, self.noise.sigma0, self.noise.sigma1, self.noise.steps, 0)
         for i, L in enumerate(self.dl):
             w = Wd[L.name + "/w"]  # HWIO [5,5,ci,co] = [tap][K][N]
             pad = same_pads(L.in_hw)[0]
@@ -763,9 +794,10 @@ class HipEngine(HipDDPMixin, HipEngineAux):
 
     # ---- D backward for d_loss (2B rows, both groups) -> all D gradients
     def _build_d_backward_dloss(self, prog, sub: Optional[int] = None):
-        """sub = k: the D chain of D sub-step k (layer 0's weight gradient reads its d_in)."""
+        """sub = k: the D chain of D sub-step k (layer 0's weight gradient reads its d_in, or the
+        noisy copy of it that the forward wrote)."""
         cfg, B = self.cfg, self.B
-        d_in = self.d_in if sub is None else self.d_ins[sub]
+        d_in = self._d_input(sub)
         B2 = 2 * B
         Pd, gD = self.model.d, self.grad_d
         lin = cfg.d_lin_name

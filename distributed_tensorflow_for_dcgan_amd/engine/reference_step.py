@@ -26,8 +26,16 @@ class ReferenceStep:
                  gan_loss: str = "bce", label_smooth: float = 0.0, d_spectral_norm: bool = False, seed: int = 0,
                  d_steps: int = 1, beta2: float = R.ADAM_BETA2, lr_d: Optional[float] = None,
                  lr_g: Optional[float] = None, lr_decay="none", lr_decay_start: int = 0, lr_decay_steps: int = 0,
-                 lr_end: float = 0.0, lr_warmup: int = 0):
+                 lr_end: float = 0.0, lr_warmup: int = 0, instance_noise=0.0, instance_noise_end: float = 0.0,
+                 instance_noise_steps: int = 0, noise_seed: int = 0):
         self.model = model
+        # instance noise (ops.reference.InstanceNoise): D sees [real | fake] + sigma(t) * eps, eps from
+        # Philox stream 1 of `noise_seed` (the HIP engine's z seed) at the global step; D sub-step k
+        # draws from ops.reference.substep_seed(noise_seed, k). G's gradient flows through it unchanged
+        self.noise = R.check_instance_noise(*instance_noise) if isinstance(instance_noise, R.InstanceNoise) else \
+            R.check_instance_noise(instance_noise, instance_noise_end, instance_noise_steps)
+        self.noise_seed = int(noise_seed)
+        self._sub_k = 0  # D sub-steps taken since the last full step
         # learning-rate schedule (ops.reference.LrSchedule): both Adam rates times lr_factor at the
         # global step before its increment; the D sub-steps see the step of the full step after them
         self.lr_sched = R.check_lr_schedule(*lr_decay) if isinstance(lr_decay, R.LrSchedule) else \
@@ -57,9 +65,23 @@ class ReferenceStep:
         """The schedule's factor (fp32 oracle) at the current global step."""
         return float(R.lr_factor(self.lr_sched, self.global_step)) if self.lr_sched.active else 1.0
 
+    def noise_sigma(self) -> float:
+        """sigma(t) of the instance noise (fp32 oracle) at the current global step; 0.0 when off."""
+        n = self.noise
+        return float(R.noise_sigma(self.global_step, n.sigma0, n.sigma1, n.steps)) if n.active else 0.0
+
+    def draw_noise(self, shape, sub: Optional[int] = None) -> Optional[torch.Tensor]:
+        """The additive sigma(t) * eps over a [2B, ...] input at the current global step: the full
+        step's (sub None) or D sub-step `sub`'s; None when the noise is off."""
+        if not self.noise.active:
+            return None
+        return R.instance_noise(shape, self.noise, R.substep_seed(self.noise_seed, sub), self.global_step)
+
     def forward_losses(self, real: torch.Tensor, z: torch.Tensor, Pg=None, Pd=None, update_ema=True,
-                       record=None, update_ema_g=None):
-        """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's)."""
+                       record=None, update_ema_g=None, noise=None, sub: Optional[int] = None):
+        """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's). noise: the additive
+        sigma * eps on D's input [2B, ...]; None = drawn (``draw_noise``, `sub` = the D sub-step) when
+        instance noise is on; False = none (sample-time losses stay clean)."""
         m = self.model
         if self.d_spectral_norm:  # D computes with W / sigma(W); autograd projects the gradient
             Pd = m.d_sn_weights(Pd)
@@ -67,6 +89,10 @@ class ReferenceStep:
                            record=record)
         B = real.shape[0]
         both = torch.cat([real, fake], 0)
+        if noise is None:
+            noise = self.draw_noise(both.shape, sub)
+        if noise is not None and noise is not False:
+            both = both + noise.to(both.device, both.dtype)
         _, logits = m.discriminator(both, groups=2, slots=(0, 1), train=True, P=Pd,
                                     update_ema=update_ema, record=record)
         lr_, lf = logits[:B], logits[B:]
@@ -74,12 +100,12 @@ class ReferenceStep:
         return {"fake": fake, "logits_real": lr_, "logits_fake": lf, "d_loss_real": d_real,
                 "d_loss_fake": d_fake, "g_loss": g_loss, "d_loss": d_loss}
 
-    def compute_grads(self, real: torch.Tensor, z: torch.Tensor, update_ema: bool = True):
+    def compute_grads(self, real: torch.Tensor, z: torch.Tensor, update_ema: bool = True, noise=None):
         """Returns (losses dict, flat D grads, flat G grads) without applying them."""
         m = self.model
         Pg = {k: v.detach().clone().requires_grad_(True) for k, v in m.g.tensors.items()}
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
-        out = self.forward_losses(real, z, Pg, Pd, update_ema=update_ema)
+        out = self.forward_losses(real, z, Pg, Pd, update_ema=update_ema, noise=noise)
         d_names, g_names = m.d.names(), m.g.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], retain_graph=True,
                                  allow_unused=True)
@@ -94,12 +120,13 @@ class ReferenceStep:
                 gg_flat[n].copy_(g)
         return out, gd_flat.flat, gg_flat.flat
 
-    def compute_d_grads(self, real: torch.Tensor, z: torch.Tensor):
+    def compute_d_grads(self, real: torch.Tensor, z: torch.Tensor, noise=None, sub: Optional[int] = None):
         """(losses dict, flat D grads) of a D sub-step: G's forward in training mode on batch
         statistics with its BN moving averages left alone, only d_loss differentiated, through D."""
         m = self.model
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
-        out = self.forward_losses(real, z, None, Pd, update_ema=True, update_ema_g=False)
+        out = self.forward_losses(real, z, None, Pd, update_ema=True, update_ema_g=False, noise=noise,
+                                  sub=self._sub_k if sub is None else sub)
         d_names = m.d.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], allow_unused=True)
         gd_flat = m.d.like()
@@ -108,12 +135,13 @@ class ReferenceStep:
                 gd_flat[n].copy_(g)
         return out, gd_flat.flat
 
-    def d_step(self, real: torch.Tensor, z: torch.Tensor) -> Dict[str, float]:
+    def d_step(self, real: torch.Tensor, z: torch.Tensor, noise=None, sub: Optional[int] = None) -> Dict[str, float]:
         """One D sub-step: a fresh z through G, D on [real | fake], the d_loss backward through D,
         TF-Adam(D) (D's beta powers advance) and the power step. Nothing of G changes -- parameters,
         Adam slots and powers, BN moving averages, weight EMA -- nor does the global step; D's BN
         moving averages (both slots) update as in a full step."""
-        out, gd = self.compute_d_grads(real, z)
+        out, gd = self.compute_d_grads(real, z, noise=noise, sub=sub)
+        self._sub_k += 1
         for s in range(2):
             self.model.d_bn.count_step(s)
         if self.grad_hook is not None:
@@ -124,8 +152,9 @@ class ReferenceStep:
         self.last = out
         return {k: float(out[k].detach()) for k in ("d_loss_real", "d_loss_fake", "g_loss", "d_loss")}
 
-    def step(self, real: torch.Tensor, z: torch.Tensor) -> Dict[str, float]:
-        out, gd, gg = self.compute_grads(real, z)
+    def step(self, real: torch.Tensor, z: torch.Tensor, noise=None) -> Dict[str, float]:
+        out, gd, gg = self.compute_grads(real, z, noise=noise)
+        self._sub_k = 0
         for s in range(2):  # one EMA update per BN slot per step (as the HIP engine counts)
             self.model.d_bn.count_step(s)
         self.model.g_bn.count_step(0)

@@ -654,6 +654,56 @@ def lr_factor(steps: torch.Tensor, sched) -> torch.Tensor:
     return out
 
 
+_ELEM_DT = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
+
+
+def _check_step(op: str, step: torch.Tensor) -> None:
+    if step.dtype != torch.int64 or step.numel() != 1:
+        raise TypeError("%s: step must be one int64" % op)
+
+
+def philox_normal(n: int, seed: int, step: torch.Tensor, stream_id: int = 1) -> torch.Tensor:
+    """float32[n] standard normals of the Philox stream (seed, step[0], stream_id), as the instance-noise
+    kernel draws them (Box-Muller per pair of lanes; oracle: ops.reference.philox_normal)."""
+    _check_step("philox_normal", step)
+    out = torch.empty(int(n), device=step.device, dtype=torch.float32)
+    if n:
+        prog = ext().Program()
+        prog.philox_normal("philox_normal", _p(out), int(n), int(seed), _p(step), int(stream_id))
+        run(prog)
+    return out
+
+
+def noise_sigma(steps: torch.Tensor, sigma0: float, sigma1: float, nsteps: int) -> torch.Tensor:
+    """sigma(t) of the instance-noise anneal at each step value, int64[N] -> float32[N], from the device
+    function the noise kernel evaluates (dcg::noise_sigma)."""
+    if steps.dtype != torch.int64:
+        raise TypeError("noise_sigma: steps must be int64")
+    steps = steps.contiguous()
+    out = torch.empty(steps.shape, device=steps.device, dtype=torch.float32)
+    prog = ext().Program()
+    prog.noise_sigma("noise_sigma", _p(steps) if steps.numel() else 0, _p(out), steps.numel(), float(sigma0),
+                     float(sigma1), int(nsteps))
+    run(prog)
+    return out
+
+
+def instance_noise(x: torch.Tensor, y: torch.Tensor, seed: int, step: torch.Tensor, sigma0: float, sigma1: float,
+                   nsteps: int, stream_id: int = 1) -> torch.Tensor:
+    """y = x + sigma(step[0]) * eps elementwise over the flat buffer (bf16, fp16 or fp32; y a buffer of
+    its own, same shape and dtype), eps the normals of the Philox stream (seed, step[0], stream_id)."""
+    if x.dtype not in _ELEM_DT or y.dtype != x.dtype or y.shape != x.shape:
+        raise TypeError("instance_noise: x and y must share a shape and a dtype of bf16, fp16 or fp32")
+    if not (x.is_contiguous() and y.is_contiguous()):
+        raise ValueError("instance_noise: x and y must be contiguous")
+    _check_step("instance_noise", step)
+    prog = ext().Program(_ELEM_DT[x.dtype])
+    prog.instance_noise("instance_noise", _p(x) if x.numel() else 0, _p(y) if y.numel() else 0, x.numel(), int(seed),
+                        _p(step), int(stream_id), float(sigma0), float(sigma1), int(nsteps))
+    run(prog)
+    return y
+
+
 def adam_(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, powers: torch.Tensor, lr: float,
           beta1: float, beta2: float, eps: float, gscale: float = 1.0, advance_powers: bool = True,
           lr_sched=None, step: Optional[torch.Tensor] = None) -> None:

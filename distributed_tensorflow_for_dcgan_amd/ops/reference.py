@@ -330,6 +330,185 @@ def lr_factor(sched: LrSchedule, t, dtype=torch.float32) -> torch.Tensor:
     return f
 
 
+# --------------------------------------------------------------------------- instance noise (D's input)
+NOISE_MAX_SIGMA = 2.0
+NOISE_MAX_STEPS = 1 << 24  # length of the anneal: exact as fp32
+NOISE_STREAM = 1           # Philox stream of the noise (z draws from stream 0)
+SUBSTEP_SEED_STRIDE = 0x9E3779B97F4A7C15  # seed of D sub-step k = seed + (k + 1) * this, mod 2^64
+
+
+class InstanceNoise(NamedTuple):
+    """D is trained on x + sigma(t) * eps, eps ~ N(0, I), over the stacked [real | fake] input, with
+    sigma annealed linearly over the global step t (its value before the step's increment):
+
+        sigma(t) = sigma1 if t >= steps else fma(sigma1 - sigma0, float(t) / float(steps), sigma0)
+
+    in fp32; sigma0 == sigma1 is a constant (steps is not read). Active when either end is > 0."""
+    sigma0: float = 0.0
+    sigma1: float = 0.0
+    steps: int = 1
+
+    @property
+    def active(self) -> bool:
+        return self.sigma0 > 0.0 or self.sigma1 > 0.0
+
+    def describe(self) -> str:
+        if not self.active:
+            return "off"
+        if self.sigma0 == self.sigma1:
+            return "sigma %g" % self.sigma0
+        return "sigma %g to %g over %d steps" % (self.sigma0, self.sigma1, self.steps)
+
+
+def check_instance_noise(sigma0=0.0, sigma1=0.0, steps=0, total_steps=None, open_ended=False) -> InstanceNoise:
+    """Validated InstanceNoise; errors name the flag. 0 <= sigma0, sigma1 <= 2, both finite; with
+    sigma0 != sigma1, 1 <= steps <= 2^24. steps = 0 then means "until the end of training":
+    `total_steps` when given (an error when that is < 1), left at 0 for a later resolution when
+    `open_ended`, else an error. With sigma0 == sigma1 steps is not read."""
+    out = []
+    for name, v in (("instance_noise", sigma0), ("instance_noise_end", sigma1)):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number, got %r" % (name, v)) from None
+        if not (math.isfinite(v) and 0.0 <= v <= NOISE_MAX_SIGMA):
+            raise ValueError("%s must be finite with 0 <= %s <= %g, got %r" % (name, name, NOISE_MAX_SIGMA, v))
+        out.append(v)
+    s0, s1 = out
+    if s0 == s1:
+        return InstanceNoise(s0, s1, 1)
+    steps = _lr_int("instance_noise_steps", steps, 0, NOISE_MAX_STEPS)
+    if steps == 0:
+        if total_steps is not None:
+            steps = int(total_steps)
+            if not 1 <= steps <= NOISE_MAX_STEPS:
+                raise ValueError("instance_noise_steps=0 anneals until the end of training, but that is %d steps "
+                                 "(need 1 .. 2^24)" % steps)
+        elif not open_ended:
+            raise ValueError("instance_noise_steps must be an integer with 1 <= instance_noise_steps <= %d, got 0 "
+                             "(only the trainer resolves 0 = until the end of training)" % NOISE_MAX_STEPS)
+    return InstanceNoise(s0, s1, steps)
+
+
+def resolve_instance_noise(sigma0=None, sigma1=None, steps=None, total_steps=None) -> InstanceNoise:
+    """check_instance_noise over the engines' arguments: None = the environment default
+    (DCGAN_INSTANCE_NOISE, DCGAN_INSTANCE_NOISE_END, DCGAN_INSTANCE_NOISE_STEPS), then 0 / 0 / 0. An
+    explicit argument wins. An InstanceNoise as `sigma0` is validated as it is."""
+    import os
+    if isinstance(sigma0, InstanceNoise):
+        return check_instance_noise(*sigma0, total_steps=total_steps)
+
+    def env(name, conv):
+        v = os.environ.get(name)
+        if v is None or v.strip() == "":
+            return None
+        try:
+            return conv(v)
+        except ValueError:
+            raise ValueError("%s=%r is not a number" % (name, v)) from None
+    if sigma0 is None:
+        sigma0 = env("DCGAN_INSTANCE_NOISE", float)
+    if sigma1 is None:
+        sigma1 = env("DCGAN_INSTANCE_NOISE_END", float)
+    if steps is None:
+        steps = env("DCGAN_INSTANCE_NOISE_STEPS", int)
+    return check_instance_noise(0.0 if sigma0 is None else sigma0, 0.0 if sigma1 is None else sigma1,
+                                0 if steps is None else steps, total_steps=total_steps)
+
+
+def noise_sigma(t, sigma0: float, sigma1: float, steps: int, dtype=torch.float32) -> torch.Tensor:
+    """sigma(t) of InstanceNoise at global step(s) t (int or int64 tensor): fp32 is the device's
+    arithmetic (both ends rounded to fp32, one fused multiply-add), fp64 the closed form."""
+    t = torch.as_tensor(t, dtype=torch.int64)
+    if dtype == torch.float64:
+        s0, s1 = torch.tensor(float(sigma0), dtype=dtype), torch.tensor(float(sigma1), dtype=dtype)
+        if float(sigma0) == float(sigma1):
+            return s0.expand(t.shape).clone()
+        p = t.clamp(0, int(steps)).to(dtype) / float(steps)
+        return torch.where(t >= int(steps), s1.expand(t.shape), s0 + (s1 - s0) * p)
+    f = torch.float32
+    s0, s1 = torch.tensor(float(sigma0), dtype=f), torch.tensor(float(sigma1), dtype=f)
+    if float(s0) == float(s1):
+        return s0.expand(t.shape).clone()
+    p = t.clamp(0, int(steps)).to(f) / torch.tensor(float(steps), dtype=f)
+    # fma in fp32: the product of two fp32 numbers is exact in fp64, the sum is rounded once there
+    g = ((s1 - s0).double() * p.double() + s0.double()).to(f)
+    return torch.where(t >= int(steps), s1.expand(t.shape), g)
+
+
+def substep_seed(seed: int, sub: Optional[int] = None) -> int:
+    """Seed of the Philox streams of D sub-step `sub` (None: the full step's, `seed` itself)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if sub is None:
+        return seed
+    return (seed + (int(sub) + 1) * SUBSTEP_SEED_STRIDE) & 0xFFFFFFFFFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox-4x32-10 (Random123) over numpy arrays: counter [..., 4] and key [..., 2] of 32-bit
+    words (broadcast against each other) -> uint32 [..., 4]."""
+    import numpy as np
+    c = np.asarray(counter).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    k = np.asarray(key).astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).copy() for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).copy() for i in range(2))
+    M0, M1, mask = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2  # 32 x 32 -> 64 bits, no overflow
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & mask, (p0 >> s32) ^ c3 ^ k1, p0 & mask
+        k0 = (k0 + np.uint64(0x9E3779B9)) & mask
+        k1 = (k1 + np.uint64(0xBB67AE85)) & mask
+    return np.stack([c0, c1, c2, c3], -1).astype(np.uint32)
+
+
+def philox_words(n: int, seed: int, step: int, stream: int = 0):
+    """The kernels' counter layout: element e of a flat buffer draws lane e % 4 of the block at counter
+    (lo32(e / 4), hi32(e / 4), lo32(step), hi32(step) ^ stream), key = the 64-bit seed. Returns the
+    uint32 [ceil(n / 4), 4] blocks."""
+    import numpy as np
+    m = (int(n) + 3) // 4
+    i4 = np.arange(m, dtype=np.uint64)
+    seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.empty((m, 4), dtype=np.uint64)
+    ctr[:, 0] = i4 & np.uint64(0xFFFFFFFF)
+    ctr[:, 1] = i4 >> np.uint64(32)
+    ctr[:, 2] = step & 0xFFFFFFFF
+    ctr[:, 3] = ((step >> 32) ^ int(stream)) & 0xFFFFFFFF
+    return philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+
+
+def philox_normal(n: int, seed: int, step: int, stream: int = NOISE_STREAM, dtype=torch.float64) -> torch.Tensor:
+    """n standard normals of the Philox stream (seed, step, stream): Box-Muller per pair of lanes.
+    Lanes 0, 1 of a block come from its words (c0, c1), lanes 2, 3 from (c2, c3): u0 = ((a >> 8) + 1)
+    2^-24 in (0, 1], u1 = (b >> 8) 2^-24 in [0, 1), r = sqrt(-2 ln u0), even lane r cos(2 pi u1), odd
+    lane r sin(2 pi u1). dtype float64: the closed form; float32: every operation in fp32, the angle
+    float32(2 pi) * u1."""
+    import numpy as np
+    if dtype not in (torch.float64, torch.float32):
+        raise ValueError("philox_normal: dtype must be torch.float64 or torch.float32")
+    ft = np.float64 if dtype == torch.float64 else np.float32
+    w = philox_words(n, seed, step, stream).reshape(-1, 2)  # [pairs, (a, b)]
+    u0 = ((w[:, 0] >> np.uint32(8)).astype(ft) + ft(1)) * ft(2.0 ** -24)
+    u1 = (w[:, 1] >> np.uint32(8)).astype(ft) * ft(2.0 ** -24)
+    r = np.sqrt(ft(-2) * np.log(u0))
+    ang = ft(2 * math.pi) * u1
+    out = np.stack([r * np.cos(ang), r * np.sin(ang)], -1).astype(ft).reshape(-1)[:int(n)]
+    return torch.from_numpy(np.ascontiguousarray(out))
+
+
+def instance_noise(shape, noise: InstanceNoise, seed: int, step: int, dtype=torch.float32) -> torch.Tensor:
+    """The additive sigma(step) * eps of InstanceNoise over a [2B, ...] input of `shape` (fp64 normals,
+    fp32 sigma), as the kernel lays it out: eps over the flat buffer, stream NOISE_STREAM."""
+    n = 1
+    for d in shape:
+        n *= int(d)
+    sig = float(noise_sigma(int(step), noise.sigma0, noise.sigma1, noise.steps))
+    eps = philox_normal(n, seed, int(step), NOISE_STREAM)
+    return (eps * sig).to(dtype).reshape(tuple(shape))
+
+
 def zero_fraction(x: torch.Tensor) -> torch.Tensor:
     """tf.nn.zero_fraction (sparsity summary, distriubted_model.py:80)."""
     return (x == 0).float().mean()

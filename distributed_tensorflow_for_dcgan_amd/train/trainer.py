@@ -160,22 +160,37 @@ def run(flags: Flags, out=None) -> int:
     source = None
     sample_only = flags.explicitly_set("is_train") and not flags.is_train
     lr_steps = int(flags.lr_decay_steps)
-    if str(flags.lr_decay).strip().lower() != "none" and lr_steps == 0:
-        total = int(flags.lr_decay_start) + 1  # sample-only mode never steps: any valid length
+    lr_open = str(flags.lr_decay).strip().lower() != "none" and lr_steps == 0
+    # --instance_noise_steps=0 with an anneal (--instance_noise != --instance_noise_end) likewise: the
+    # recorded noise launch takes the length as a constant
+    noise_steps = int(flags.instance_noise_steps)
+    noise_open = float(flags.instance_noise) != float(flags.instance_noise_end) and noise_steps == 0
+    if lr_open or noise_open:
+        total = None  # sample-only mode never steps: any valid length
         if not sample_only:
             hip_engine = flags.engine == "hip" or (flags.engine == "auto" and device.type == "cuda")
             source = make_source(flags, B, shape, device, rank=rank, world=world,
                                  engine_dtype=flags.dtype if hip_engine else "fp32")
             total = _step_budget(flags, source.num_examples, int(flags.d_steps), B, world)[1]
         try:
-            lr_steps = R.check_lr_schedule(flags.lr_decay, flags.lr_decay_start, 0, flags.lr_end,
-                                           flags.lr_warmup_steps, total_steps=total).steps
+            if lr_open:
+                lr_steps = R.check_lr_schedule(flags.lr_decay, flags.lr_decay_start, 0, flags.lr_end,
+                                               flags.lr_warmup_steps,
+                                               total_steps=int(flags.lr_decay_start) + 1 if total is None else total).steps
         except ValueError as e:
             if source is not None:
                 source.close()
             raise SystemExit("--lr_decay_steps: %s" % e)
+        try:
+            if noise_open:
+                noise_steps = R.check_instance_noise(flags.instance_noise, flags.instance_noise_end, 0,
+                                                     total_steps=1 if total is None else total).steps
+        except ValueError as e:
+            if source is not None:
+                source.close()
+            raise SystemExit("--instance_noise_steps: %s" % e)
     try:
-        engine = _build_engine(flags, cfg, B, device, rank, world, lr_steps)
+        engine = _build_engine(flags, cfg, B, device, rank, world, lr_steps, noise_steps)
     except BaseException:
         if source is not None:
             source.close()
@@ -196,6 +211,9 @@ def run(flags: Flags, out=None) -> int:
         if sched is not None and sched.active:
             print("learning-rate schedule: %s (of the global step; both networks)" % sched.describe(),
                   file=out, flush=True)
+        noise = getattr(engine, "noise", None)
+        if noise is not None and noise.active:
+            print("instance noise on D's inputs: %s (of the global step)" % noise.describe(), file=out, flush=True)
     if flags.log_device_placement:
         for line in placement_report(engine, device, rank, world):
             print(line, file=out, flush=True)
@@ -289,6 +307,10 @@ def run(flags: Flags, out=None) -> int:
                     f = float(R.lr_factor(engine.lr_sched, step - 1)) if hasattr(engine, "lr_sched") else 1.0
                     vals.append(SummaryWriter.scalar("learning_rate/d", engine.opt_d.lr * f))
                     vals.append(SummaryWriter.scalar("learning_rate/g", engine.opt_g.lr * f))
+                    noise = getattr(engine, "noise", None)
+                    if noise is not None and noise.active:  # sigma of the step just taken, from the oracle
+                        vals.append(SummaryWriter.scalar("instance_noise/sigma", float(R.noise_sigma(
+                            step - 1, noise.sigma0, noise.sigma1, noise.steps))))
                     writer.add_summary_values(vals, step)
                     writer.flush()
                     print("Finished running Summary operation.", file=out)
@@ -352,7 +374,7 @@ def _step_budget(flags, n_ex: int, n_d: int, B: int, world: int):
     return step_per_epoch, max_steps
 
 
-def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps):
+def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps, instance_noise_steps):
     return build_engine(cfg, B, device, engine=flags.engine, dtype=flags.dtype, seed=int(flags.seed), rank=rank,
                         world=world, graph=bool(flags.graph), allreduce_dtype=flags.allreduce_dtype,
                         lr=float(flags.learning_rate), beta1=float(flags.beta1),
@@ -363,7 +385,9 @@ def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps):
                         lr_d=float(flags.d_learning_rate), lr_g=float(flags.g_learning_rate),
                         lr_decay=str(flags.lr_decay), lr_decay_start=int(flags.lr_decay_start),
                         lr_decay_steps=int(lr_decay_steps), lr_end=float(flags.lr_end),
-                        lr_warmup=int(flags.lr_warmup_steps))
+                        lr_warmup=int(flags.lr_warmup_steps), instance_noise=float(flags.instance_noise),
+                        instance_noise_end=float(flags.instance_noise_end),
+                        instance_noise_steps=int(instance_noise_steps))
 
 
 def _sample_ema(engine, flags) -> bool:

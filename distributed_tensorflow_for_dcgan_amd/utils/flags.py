@@ -106,6 +106,14 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                                  "the --epoch cap, minus --lr_decay_start)"),
     ("lr_end", "float", 0.0, "final factor, 0 <= lr_end <= 1, reached exactly (> 0 with --lr_decay=exponential)"),
     ("lr_warmup_steps", "int", 0, "linear warm-up: for the first n steps the factor is also times (step + 1) / n"),
+    ("instance_noise", "float", 0.0, "instance noise on the discriminator's inputs: D is trained on x + sigma * eps, "
+                                     "eps ~ N(0, I), for the real and the fake half alike; sigma at step 0, "
+                                     "0 <= sigma <= 2, annealed linearly to --instance_noise_end. 0 (with "
+                                     "--instance_noise_end=0) turns it off"),
+    ("instance_noise_end", "float", 0.0, "sigma at the end of the anneal, 0 <= sigma <= 2 (equal to --instance_noise: "
+                                         "a constant sigma)"),
+    ("instance_noise_steps", "int", 0, "length of the anneal in steps, 1..2^24; 0 = until the end of training "
+                                       "(max_steps after the --epoch cap)"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -202,6 +210,11 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
                           open_ended=True)
     except (ValueError, TypeError, OverflowError) as e:
         parser.error("--lr_decay / --lr_decay_start / --lr_decay_steps / --lr_end / --lr_warmup_steps: %s" % e)
+    from ..ops.reference import check_instance_noise
+    try:  # (--instance_noise_steps=0 with an anneal stays open here: the trainer resolves it)
+        check_instance_noise(ns.instance_noise, ns.instance_noise_end, ns.instance_noise_steps, open_ended=True)
+    except (ValueError, TypeError, OverflowError) as e:
+        parser.error("--instance_noise / --instance_noise_end / --instance_noise_steps: %s" % e)
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
