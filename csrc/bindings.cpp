@@ -885,13 +885,6 @@ class Program {
       return KF(dcg_lr_factor)(P<const unsigned long long>(steps), P<float>(out), n, &S, s);
     }, AccList().r(steps, n * 8).w(out, n * 4).v);
   }
-  // the sub-step's step_end (d_step_end_kernel): D's powers + the fp16 loss-scale rule only
-  int d_step_end(std::string name, uintptr_t pd, float b1d, float b2d, int stream, uintptr_t ls, int growth_interval) {
-    if (!pd) throw std::runtime_error("d_step_end: the powers must be non-null");
-    return add(name, stream, [=](hipStream_t s) {
-      return KF(dcg_d_step_end)(P<float>(pd), b1d, b2d, P<float>(ls), growth_interval, s);
-    }, AccList().w(pd, 8).w(ls, 12).v);
-  }
   // narrow2.hip: TF-SAME stride-2 5x5 conv, 1..4 input -> 64 output channels, persistent `grid`
   // workgroups (<= tiles: nconv_tiles). bx != 0: fused BN-backward statistics of the layer below
   // (x = bx, y = by, one BN group), one partial row [2][64] per workgroup into part.
@@ -1078,6 +1071,7 @@ class Program {
     return add(name, stream, [=](hipStream_t s) { return KF(dcg_nonfinite_check)(P<const float>(g), n, P<float>(ls), s); },
                AccList().r(g, n * 4).w(ls, 12).v);
   }
+  // pd, pg, step: each optional (a D-only sub-step passes pd alone: D's powers + the loss-scale rule)
   int step_end(std::string name, uintptr_t pd, uintptr_t pg, float b1d, float b2d, float b1g, float b2g,
                uintptr_t step, int stream, uintptr_t ls, int growth_interval) {
     return add(name, stream, [=](hipStream_t s) {
@@ -1351,8 +1345,6 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("lr_factor", &Program::lr_factor, py::arg("name"), py::arg("steps"), py::arg("out"), py::arg("n"),
            py::arg("lr_kind"), py::arg("lr_start"), py::arg("lr_steps"), py::arg("lr_end"), py::arg("lr_warmup"),
            py::arg("stream") = 0)
-      .def("d_step_end", &Program::d_step_end, py::arg("name"), py::arg("pd"), py::arg("b1d"), py::arg("b2d"),
-           py::arg("stream") = 0, py::arg("ls") = 0, py::arg("growth_interval") = 2000)
       .def("ema", &Program::ema, py::arg("name"), py::arg("s"), py::arg("sbf"), py::arg("w"), py::arg("n"),
            py::arg("decay"), py::arg("step"), py::arg("step_bias"), py::arg("ls"), py::arg("stream"))
       .def("sn_power", &Program::sn_power, py::arg("name"), py::arg("mats"), py::arg("ls"), py::arg("stream"))

@@ -53,11 +53,10 @@ int DCG_API(dcg_adam)(float* w, elem_t* wbf, const float* g, float* m, float* v,
                      const void* g_bf16, const dcg::LrSched* sched, const unsigned long long* step, hipStream_t s);
 int DCG_API(dcg_step_end)(float* pd, float* pg, float b1d, float b2d, float b1g, float b2g,
                           unsigned long long* step, float* ls, int growth_interval, hipStream_t s);
-// the D-only sub-step's updates: one-launch Adam + mirror + powers of one set; its step_end
+// the D-only sub-step's update: one-launch Adam + mirror + powers of one set
 int DCG_API(dcg_adam1)(float* w, elem_t* wbf, const float* g, float* m, float* v, float* powers, size_t n, float lr,
                        float b1, float b2, float eps, float gscale, unsigned* counter, const dcg::LrSched* sched,
                        const unsigned long long* step, hipStream_t s);
-int DCG_API(dcg_d_step_end)(float* pd, float b1d, float b2d, float* ls, int growth_interval, hipStream_t s);
 int DCG_API(dcg_ema)(float* s, elem_t* sbf, const float* w, size_t n, float decay, const unsigned long long* step,
                      int step_bias, const float* ls, hipStream_t st);
 // spectral normalisation (specnorm.hip): power step = wu, wtv, colsum, apply(from_state = 0);

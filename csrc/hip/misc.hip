@@ -379,16 +379,8 @@ __global__ __launch_bounds__(256) void gemv_head_kernel(const elem_t* __restrict
   const __amdgpu_buffer_rsrc_t rl = make_rsrc(out, (uint32_t)(R * 4));
   if (threadIdx.x == 0)
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, logit), rl, (uint32_t)row * 4u, 0, 16);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
   __shared__ int last;
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(L.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = old == gridDim.x - 1;
-    if (last) __hip_atomic_store(L.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!last) return;
+  if (!last_arrival(L.counter, gridDim.x, &last)) return;
   gan_loss_block<OBJ>([&](int i) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, (uint32_t)i * 4u, 0, 16)); },
                       R / 2, L.t, L.out, L.dl_d, L.dl_g, L.prob, L.ls);
 }
@@ -623,6 +615,26 @@ __global__ __launch_bounds__(256) void lr_factor_kernel(LrSched S, const unsigne
 // S / step: the learning-rate schedule, lr_eff = lr * lr_factor (one fp32 multiply). Every Adam
 // launch of a step runs ahead of the launch that advances the counter, so all see the same t.
 // An inactive schedule never reads the counter and leaves lr, and so every result bit, alone.
+
+// The block-uniform prologue of every Adam kernel: the schedule's factor if on, then lr_t.
+__device__ __forceinline__ float adam_lr_t(float lr, const float* __restrict__ powers, const LrSched& S,
+                                           const unsigned long long* __restrict__ step) {
+  if (lr_sched_on(S)) lr *= lr_factor(S, step);
+  return lr * sqrtf(1.f - powers[1]) / (1.f - powers[0]);
+}
+
+// The update of one float4 (g already scaled), the one copy every Adam kernel runs. Explicit fma:
+// the same rounding on every TF-Adam path.
+__device__ __forceinline__ void adam_update4(f32x4& w, f32x4& m, f32x4& v, const f32x4 g, float lr_t, float b1,
+                                             float b2, float eps) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    m[k] = __builtin_fmaf(b1, m[k], (1.f - b1) * g[k]);
+    v[k] = __builtin_fmaf(b2, v[k], (1.f - b2) * g[k] * g[k]);
+    w[k] -= lr_t * m[k] / (sqrtf(v[k]) + eps);
+  }
+}
+
 template <typename GW>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, elem_t* __restrict__ wbf,
                                                    const GW* __restrict__ g, float* __restrict__ m,
@@ -638,8 +650,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, elem_t
   }
   // wbf (optional): elem_t mirror of the updated weights in the SAME flat layout -- the only
   // weight copy the conv kernels read (they take either operand layout), so no repack pass
-  if (lr_sched_on(S)) lr *= lr_factor(S, step);
-  const float lr_t = lr * sqrtf(1.f - powers[1]) / (1.f - powers[0]);
+  const float lr_t = adam_lr_t(lr, powers, S, step);
   const size_t n4 = n / 4;
   for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     f32x4 gv;
@@ -653,12 +664,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, elem_t
     f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
     f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
     f32x4 wv = reinterpret_cast<f32x4*>(w)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {  // explicit fma: the same rounding as every other TF-Adam path
-      mv[k] = __builtin_fmaf(b1, mv[k], (1.f - b1) * gv[k]);
-      vv[k] = __builtin_fmaf(b2, vv[k], (1.f - b2) * gv[k] * gv[k]);
-      wv[k] -= lr_t * mv[k] / (sqrtf(vv[k]) + eps);
-    }
+    adam_update4(wv, mv, vv, gv, lr_t, b1, b2, eps);
     reinterpret_cast<f32x4*>(m)[i] = mv;
     reinterpret_cast<f32x4*>(v)[i] = vv;
     reinterpret_cast<f32x4*>(w)[i] = wv;
@@ -709,9 +715,7 @@ __global__ __launch_bounds__(256) void adam2_kernel(Adam2Set A, Adam2Set D, floa
   f32x4* __restrict__ v = reinterpret_cast<f32x4*>(inA ? A.v : D.v);
   const float* pw = inA ? A.powers : D.powers;
   const float b1 = inA ? A.b1 : D.b1, b2 = inA ? A.b2 : D.b2, eps = inA ? A.eps : D.eps;
-  float lr = inA ? A.lr : D.lr;
-  if (lr_sched_on(S)) lr *= lr_factor(S, step);  // block-uniform; the same factor for both sets
-  const float lr_t = lr * sqrtf(1.f - pw[1]) / (1.f - pw[0]);
+  const float lr_t = adam_lr_t(inA ? A.lr : D.lr, pw, S, step);  // the same factor for both sets
   const size_t n4 = (inA ? A.n : D.n) / 4;
   const unsigned b0 = inA ? blockIdx.x : blockIdx.x - gA, nb = inA ? gA : gridDim.x - gA;
   for (size_t i = (size_t)b0 * 256 + threadIdx.x; i < n4; i += (size_t)nb * 256) {
@@ -719,12 +723,7 @@ __global__ __launch_bounds__(256) void adam2_kernel(Adam2Set A, Adam2Set D, floa
     f32x4 mv = m[i];
     f32x4 vv = v[i];
     f32x4 wv = w[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      mv[k] = __builtin_fmaf(b1, mv[k], (1.f - b1) * gv[k]);
-      vv[k] = __builtin_fmaf(b2, vv[k], (1.f - b2) * gv[k] * gv[k]);
-      wv[k] -= lr_t * mv[k] / (sqrtf(vv[k]) + eps);
-    }
+    adam_update4(wv, mv, vv, gv, lr_t, b1, b2, eps);
     m[i] = mv;
     v[i] = vv;
     w[i] = wv;
@@ -734,16 +733,9 @@ __global__ __launch_bounds__(256) void adam2_kernel(Adam2Set A, Adam2Set D, floa
   // counter == nullptr: a first part of the update (the beta powers and the step are advanced
   // by a later adam2 launch over the remaining ranges)
   if (!counter) return;
-  // last arrival: every block has read the powers above before it increments the counter
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    flag = old == gridDim.x - 1;
-    if (flag) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (flag && threadIdx.x == 0) {
+  // last arrival: every block has read the powers (and the step counter) above before it
+  // increments the counter
+  if (last_arrival(counter, gridDim.x, &flag) && threadIdx.x == 0) {
     A.powers[0] *= A.b1;
     A.powers[1] *= A.b2;
     D.powers[0] *= D.b1;
@@ -752,7 +744,10 @@ __global__ __launch_bounds__(256) void adam2_kernel(Adam2Set A, Adam2Set D, floa
   }
 }
 
-// after both Adams: beta powers *= beta (TF variable update) and the global step counter
+// after both Adams: beta powers *= beta (TF variable update) and the global step counter.
+// pd, pg and step are each optional: a D-only sub-step (the paths that update D with adam_kernel:
+// fp32, fp16, DDP) passes pd alone -- D's powers and the same loss-scale rule (a sub-step is an
+// optimiser step for it), never the global step or G's powers.
 __global__ void step_end_kernel(float* __restrict__ pd, float* __restrict__ pg, float b1d, float b2d, float b1g,
                                 float b2g, unsigned long long* __restrict__ step, float* __restrict__ ls,
                                 int growth_interval) {
@@ -1048,63 +1043,25 @@ __global__ __launch_bounds__(256) void adam1_kernel(float* __restrict__ w, elem_
                                                     unsigned* __restrict__ counter, LrSched S,
                                                     const unsigned long long* __restrict__ step) {
   __shared__ int flag;
-  if (lr_sched_on(S)) lr *= lr_factor(S, step);  // the global step: a sub-step never advances it
-  const float lr_t = lr * sqrtf(1.f - powers[1]) / (1.f - powers[0]);
+  const float lr_t = adam_lr_t(lr, powers, S, step);  // the global step: a sub-step never advances it
   const size_t n4 = n / 4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i] * gscale;
     f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
     f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
     f32x4 wv = reinterpret_cast<f32x4*>(w)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      mv[k] = __builtin_fmaf(b1, mv[k], (1.f - b1) * gv[k]);
-      vv[k] = __builtin_fmaf(b2, vv[k], (1.f - b2) * gv[k] * gv[k]);
-      wv[k] -= lr_t * mv[k] / (sqrtf(vv[k]) + eps);
-    }
+    adam_update4(wv, mv, vv, gv, lr_t, b1, b2, eps);
     reinterpret_cast<f32x4*>(m)[i] = mv;
     reinterpret_cast<f32x4*>(v)[i] = vv;
     reinterpret_cast<f32x4*>(w)[i] = wv;
     const elem4 o = {(elem_t)wv[0], (elem_t)wv[1], (elem_t)wv[2], (elem_t)wv[3]};
     reinterpret_cast<elem4*>(wbf)[i] = o;
   }
-  // last arrival: every block has read the powers above before it increments the counter
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    flag = old == gridDim.x - 1;
-    if (flag) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (flag && threadIdx.x == 0) {
+  // last arrival: every block has read the powers (and the step counter) above before it
+  // increments the counter
+  if (last_arrival(counter, gridDim.x, &flag) && threadIdx.x == 0) {
     powers[0] *= b1;
     powers[1] *= b2;
-  }
-}
-
-// step_end_kernel's counterpart for a D-only sub-step (the paths that update D with adam_kernel:
-// fp32, fp16, DDP): D's beta powers only, and the same dynamic loss-scale rule -- a sub-step is
-// an optimiser step for it. Never touches the global step or G's powers.
-__global__ void d_step_end_kernel(float* __restrict__ pd, float b1d, float b2d, float* __restrict__ ls,
-                                  int growth_interval) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    bool skipped = false;
-    if (ls) {
-      skipped = ls[1] != 0.f;
-      if (skipped) {
-        ls[0] = fmaxf(ls[0] * 0.5f, 1.f);
-        ls[2] = 0.f;
-      } else if ((ls[2] += 1.f) >= (float)growth_interval) {
-        ls[0] = fminf(ls[0] * 2.f, 16777216.f);
-        ls[2] = 0.f;
-      }
-      ls[1] = 0.f;
-    }
-    if (!skipped) {  // a skipped sub-step does not advance D's beta powers
-      pd[0] *= b1d;
-      pd[1] *= b2d;
-    }
   }
 }
 
@@ -1253,13 +1210,6 @@ extern "C" int DCG_API(dcg_adam1)(float* w, elem_t* wbf, const float* g, float* 
   if (b > ADAM1_MAX_BLOCKS) b = ADAM1_MAX_BLOCKS;
   hipLaunchKernelGGL(adam1_kernel, dim3((unsigned)(b ? b : 1)), dim3(256), 0, s, w, wbf, g, m, v, powers, n, lr, b1, b2,
                      eps, gscale, counter, S, step);
-  return (int)hipGetLastError();
-}
-
-extern "C" int DCG_API(dcg_d_step_end)(float* pd, float b1d, float b2d, float* ls, int growth_interval,
-                                       hipStream_t s) {
-  if (!pd) return -2;
-  hipLaunchKernelGGL(d_step_end_kernel, dim3(1), dim3(64), 0, s, pd, b1d, b2d, ls, growth_interval);
   return (int)hipGetLastError();
 }
 

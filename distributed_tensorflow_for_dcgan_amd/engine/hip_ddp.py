@@ -68,12 +68,13 @@ class HipDDPMixin:
         self._shards, self._small = {}, plan[1]
         self.progSh = self._prog()
         for name, m, a, b in plan[0]:
-            ps, grad, mir = ((self.model.d, self.grad_d, self.wbf_d) if m == "d" else (self.model.g, self.grad_g, self.wbf_g))
-            opt = self.opt_d if m == "d" else self.opt_g
+            ps, grad, mir, opt, _ = self._net(m)
             sr = D.ShardReducer(grad.flat[a:b], mir.flat[a:b], W, r)
             self._shards[name] = (sr, m, a, b)
             k = a + sr.lo
             i0 = self.progSh.size()
+            # spelled out, not _adam: the gradient and the mirror are the reducer's own shard
+            # buffers (offset 0), only the weights and the slots sit at the flat offset k
             self.progSh.adam_bf("adam_shard." + name, _p(ps.flat) + 4 * k, _p(sr.agin), _p(sr.gs),
                                 _p(opt.m.flat) + 4 * k, _p(opt.v.flat) + 4 * k, _p(opt.powers), sr.n, opt.lr,
                                 opt.beta1, opt.beta2, opt.eps, 1.0 / self.world, 0, 0, 0, **self._lr_kw())
@@ -82,17 +83,9 @@ class HipDDPMixin:
     def _build_update_sharded(self, prog):
         """Adam over the all-reduced fp32-read slices (full, every rank) + both beta powers + the
         step counter, after every shard's Adam has read the powers (the step's final join)."""
-        gs = 1.0 / self.world
         for name, m, a, b in self._small:
-            ps, grad, mir, opt = ((self.model.d, self.grad_d, self.wbf_d, self.opt_d) if m == "d" else
-                                  (self.model.g, self.grad_g, self.wbf_g, self.opt_g))
-            es = mir.flat.element_size()
-            prog.adam_bf("adam." + name, _p(ps.flat) + 4 * a, _p(mir.flat) + es * a, _p(grad.flat) + 4 * a,
-                         _p(opt.m.flat) + 4 * a, _p(opt.v.flat) + 4 * a, _p(opt.powers), b - a, opt.lr, opt.beta1,
-                         opt.beta2, opt.eps, gs, 0, 0, 0, **self._lr_kw())
-        od, og = self.opt_d, self.opt_g
-        prog.step_end("step_end", _p(od.powers), _p(og.powers), od.beta1, od.beta2, og.beta1, og.beta2,
-                      _p(self.step_counter), 0, 0, self.LOSS_SCALE_GROWTH)
+            self._adam(prog, "adam." + name, m, a, b)
+        self._step_end(prog)
 
     def _sh_rs(self, ex, name, src) -> None:
         if self.ddp:
@@ -175,26 +168,16 @@ class HipDDPMixin:
     def _build_update_d_first(self, prog):
         """Adam(D) (progC[:_c_split]), then Adam(G) + beta powers / global step: the step counter
         update must follow both Adams (each reads its model's beta powers)."""
-        gs = 1.0 / self.world
-        od, og = self.opt_d, self.opt_g
         ls = _p(self.loss_scale)
-        mg = 0 if self.f32 else _p(self.wbf_g.flat)
-        md = 0 if self.f32 else _p(self.wbf_d.flat)
-        wd, wg = (_p(self.wire_d.flat), _p(self.wire_g.flat)) if self._wire_direct() else (0, 0)
-        prog.adam_bf("adam_d", _p(self.model.d.flat), md, _p(self.grad_d.flat), _p(od.m.flat), _p(od.v.flat),
-                     _p(od.powers), self.model.d.flat.numel(), od.lr, od.beta1, od.beta2, od.eps, gs, 0, ls, wd,
-                     **self._lr_kw())
+        wire = self._wire_direct()
+        self._adam(prog, "adam_d", "d", ls=ls, wire=wire)
         self._sn_power(prog, ls)  # spectral norm: behind Adam(D) on its stream; step_end comes later
         self._c_split = prog.size()
-        G = self.model.g
-        es = 0 if self.f32 else self.wbf_g.flat.element_size()
 
         def adam_g(name, a, b):  # Adam(G) over G's flat range [a, b)
             if b > a:
-                prog.adam_bf(name, _p(G.flat) + 4 * a, mg + es * a if mg else 0, _p(self.grad_g.flat) + 4 * a,
-                             _p(og.m.flat) + 4 * a, _p(og.v.flat) + 4 * a, _p(og.powers), b - a, og.lr, og.beta1,
-                             og.beta2, og.eps, gs, 0, ls, wg + 2 * a if wg else 0, **self._lr_kw())
-        n = G.flat.numel()
+                self._adam(prog, name, "g", a, b, ls=ls, wire=wire)
+        n = self.model.g.flat.numel()
         if self._adam_g_split():
             lo, hi = self._g_split[3:]
             adam_g("adam_g_a", lo, hi)      # g_h1's slice: right after its own collective
@@ -212,8 +195,7 @@ class HipDDPMixin:
             self._c_split_a = self._c_split
             adam_g("adam_g", 0, n)
         self._ema_g(prog, 1, ls)  # after the last Adam launch over G, before the step counter moves
-        prog.step_end("step_end", _p(od.powers), _p(og.powers), od.beta1, od.beta2, og.beta1, og.beta2,
-                      _p(self.step_counter), 0, ls, self.LOSS_SCALE_GROWTH)
+        self._step_end(prog, ls)
 
     def _g_bucket_cuts(self) -> List[Tuple[int, int, int]]:
         """G's gradient buckets for the "ddp" schedule: (progW piece index, lo, hi) -- after G's

@@ -458,11 +458,10 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         ls = _p(self.loss_scale)
         if self.f16:
             prog.nonfinite_check("ls.check_d", _p(self.grad_d.flat), n, ls, 0)
-        prog.adam_bf("adam_d", _p(Dm.flat), 0 if self.f32 else _p(self.wbf_d.flat), _p(self.grad_d.flat), _p(od.m.flat),
-                     _p(od.v.flat), _p(od.powers), n, od.lr, od.beta1, od.beta2, od.eps, gs, 0, ls,
-                     _p(self.wire_d.flat) if self._wire_direct() else 0, **self._lr_kw())
+        self._adam(prog, "adam_d", "d", ls=ls, wire=self._wire_direct())
         self._sn_power(prog, ls)
-        prog.d_step_end("d_step_end", _p(od.powers), od.beta1, od.beta2, 0, ls, self.LOSS_SCALE_GROWTH)
+        # a sub-step's step_end: D's powers and the loss-scale rule, never G's powers or the global step
+        prog.step_end("d_step_end", _p(od.powers), 0, od.beta1, od.beta2, 0.0, 0.0, 0, 0, ls, self.LOSS_SCALE_GROWTH)
 
     def _build_updates(self):
         """progC for the current schedule. The one-launch Adam over BOTH models is only used
@@ -1133,6 +1132,31 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             kw["lr_step"] = _p(self.step_counter)
         return kw
 
+    def _net(self, net: str):
+        """(parameter set, gradient, 16-bit mirror -- None in fp32 --, optimiser, bf16 wire image or
+        None) of network "d" / "g"."""
+        if net == "d":
+            return self.model.d, self.grad_d, None if self.f32 else self.wbf_d, self.opt_d, self.wire_d
+        return self.model.g, self.grad_g, None if self.f32 else self.wbf_g, self.opt_g, self.wire_g
+
+    def _adam(self, prog, name: str, net: str, a: int = 0, b: Optional[int] = None, ls: int = 0,
+              wire: bool = False) -> None:
+        """One adam_bf op over the flat range [a, b) (default: all) of network `net`: weights, mirror,
+        gradient and both slots at the same element offset, the mean over the ranks as gscale.
+        wire: the gradient is read from the bf16 wire image instead."""
+        ps, grad, mir, opt, img = self._net(net)
+        b = ps.flat.numel() if b is None else b
+        at = lambda t: _p(t.flat) + t.flat.element_size() * a  # noqa: E731
+        prog.adam_bf(name, at(ps), 0 if mir is None else at(mir), at(grad), at(opt.m), at(opt.v), _p(opt.powers),
+                     b - a, opt.lr, opt.beta1, opt.beta2, opt.eps, 1.0 / self.world, 0, ls, at(img) if wire else 0,
+                     **self._lr_kw())
+
+    def _step_end(self, prog, ls: int = 0) -> None:
+        """Both beta-power pairs, the global step and (ls) the fp16 loss-scale rule, after both Adams."""
+        od, og = self.opt_d, self.opt_g
+        prog.step_end("step_end", _p(od.powers), _p(og.powers), od.beta1, od.beta2, og.beta1, og.beta2,
+                      _p(self.step_counter), 0, ls, self.LOSS_SCALE_GROWTH)
+
     def _ema_g(self, prog, step_bias: int, ls: int = 0) -> None:
         """The moving average of G's weights (+ its 16-bit mirror): one launch on the stream of,
         and after, the last Adam launch that writes G. step_bias = 1 where the step counter is
@@ -1148,28 +1172,19 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         Under DDP the G all-reduce completes first (it was issued before D's backward ends), so
         Adam(G) runs while D's last bucket is still on the wire. fp16: one overflow check over
         both (all-reduced) gradients gates both Adams, so everything runs in the last part."""
-        gs = 1.0 / self.world
-        od, og = self.opt_d, self.opt_g
         ls = _p(self.loss_scale)
         do_g = (first and not self.f16) or (not first and self.f16)
         do_d = not first
-        mg = 0 if self.f32 else _p(self.wbf_g.flat)
-        md = 0 if self.f32 else _p(self.wbf_d.flat)
         if self.f16 and do_d:
             prog.nonfinite_check("ls.check_d", _p(self.grad_d.flat), self.grad_d.flat.numel(), ls, 0)
             prog.nonfinite_check("ls.check_g", _p(self.grad_g.flat), self.grad_g.flat.numel(), ls, 0)
         if do_g:
-            prog.adam_bf("adam_g", _p(self.model.g.flat), mg, _p(self.grad_g.flat), _p(og.m.flat),
-                         _p(og.v.flat), _p(og.powers), self.model.g.flat.numel(), og.lr, og.beta1, og.beta2, og.eps,
-                         gs, 0, ls, **self._lr_kw())
+            self._adam(prog, "adam_g", "g", ls=ls)
             self._ema_g(prog, 1, ls)
         if do_d:
-            prog.adam_bf("adam_d", _p(self.model.d.flat), md, _p(self.grad_d.flat), _p(od.m.flat),
-                         _p(od.v.flat), _p(od.powers), self.model.d.flat.numel(), od.lr, od.beta1, od.beta2, od.eps,
-                         gs, 0, ls, **self._lr_kw())
+            self._adam(prog, "adam_d", "d", ls=ls)
             self._sn_power(prog, ls)
-            prog.step_end("step_end", _p(od.powers), _p(og.powers), od.beta1, od.beta2, og.beta1, og.beta2,
-                          _p(self.step_counter), 0, ls, self.LOSS_SCALE_GROWTH)
+            self._step_end(prog, ls)
 
     def _build_update_fused(self, prog):
         """Single-process bf16: both TF-Adams + the beta-power / global-step update in one launch

@@ -744,15 +744,6 @@ def adam1_(w: torch.Tensor, wbf: torch.Tensor, g: torch.Tensor, m: torch.Tensor,
     run(prog)
 
 
-def d_step_end_(powers: torch.Tensor, beta1: float, beta2: float, ls: Optional[torch.Tensor] = None,
-                growth_interval: int = 2000) -> None:
-    """The D sub-step's step end: powers *= (beta1, beta2) and the fp16 loss-scale rule on ls =
-    [scale, overflow flag, good steps] (overflow: halve, clear, leave the powers)."""
-    prog = ext().Program()
-    prog.d_step_end("d_step_end", _p(powers), beta1, beta2, 0, _p(ls), int(growth_interval))
-    run(prog)
-
-
 def gan_loss_id(kind: str, label_smooth: float = 0.0) -> int:
     """Objective id of the loss / head kernels for a validated (name, label_smooth) pair."""
     from .reference import check_gan_loss

@@ -1,7 +1,7 @@
 """GPU tests of the D-only sub-steps (``d_steps`` > 1), ``beta2`` and the per-network learning rates
 of the HIP engine: the sub-step's update kernels (adam1 = Adam + mirror + D's powers in one launch;
-d_step_end), a sub-step and whole cycles against ``ReferenceStep`` (bf16 / fp16 / fp32), the z of the
-sub-steps, hipGraph replay, the fp16 overflow sub-step, one-rank RCCL DDP, checkpoint resume through
+step_end as the sub-step records it, without G's powers and the step), a sub-step and whole cycles
+against ``ReferenceStep`` (bf16 / fp16 / fp32), the z of the sub-steps, hipGraph replay, the fp16 overflow sub-step, one-rank RCCL DDP, checkpoint resume through
 the trainer, and that the defaults change nothing.
 
 Comparisons with the reference are those of ``test_step_matches_reference`` in
@@ -119,19 +119,43 @@ def test_adam1_rejects_bad_arguments():
                                                  ([1024.0, 0.0, 1999.0], [2048.0, 0.0, 0.0], True),
                                                  (None, None, True)])
 def test_d_step_end_kernel(ls0, want_ls, advance):
-    """Overflow: halve, clear, D's powers stay; a good step: count; growth at the interval: double.
+    """The sub-step's op as the engine records it: step_end with null G powers and null step.
+    Overflow: halve, clear, D's powers stay; a good step: count; growth at the interval: double.
     G's powers (the neighbouring floats) and the step counter are bitwise untouched."""
+    _check_step_end(ls0, want_ls, advance, with_g_and_step=False)
+
+
+@pytest.mark.parametrize("ls0,want_ls,advance", [([1024.0, 0.0, 5.0], [1024.0, 0.0, 6.0], True),
+                                                 ([1024.0, 1.0, 5.0], [512.0, 0.0, 0.0], False)])
+def test_step_end_kernel_with_g_powers_and_step(ls0, want_ls, advance):
+    """The full step's op: a good step advances both power pairs and the counter; an overflowed one
+    advances the counter only, halves the scale and clears the flag."""
+    _check_step_end(ls0, want_ls, advance, with_g_and_step=True)
+
+
+def _check_step_end(ls0, want_ls, advance, with_g_and_step):
     h = H()
-    b1, b2 = 0.5, 0.9
+    b1, b2, b1g, b2g = 0.5, 0.9, 0.75, 0.999
     buf, view = _padded(torch.tensor([0.25, 0.81, 0.125, 0.729]))  # [D's powers | G's powers]
-    step = torch.tensor([7], dtype=torch.int64, device=dev)
+    sbuf = torch.full((2 * PAD + 1,), -3, dtype=torch.int64, device=dev)
+    step = sbuf[PAD:PAD + 1]
+    step.fill_(7)
     lsb, ls = (None, None) if ls0 is None else _padded(torch.tensor(ls0))
-    h.d_step_end_(view[:2], b1, b2, ls, 2000)
+    prog = h.ext().Program()
+    if with_g_and_step:
+        prog.step_end("step_end", view[:2].data_ptr(), view[2:].data_ptr(), b1, b2, b1g, b2g, step.data_ptr(), 0,
+                      0 if ls is None else ls.data_ptr(), 2000)
+    else:
+        prog.step_end("d_step_end", view[:2].data_ptr(), 0, b1, b2, 0.0, 0.0, 0, 0,
+                      0 if ls is None else ls.data_ptr(), 2000)
+    h.run(prog)
     torch.cuda.synchronize()
-    want_d = torch.tensor([0.25 * b1, 0.81 * b2] if advance else [0.25, 0.81])
+    f32 = lambda *x: torch.tensor(x, dtype=torch.float32)  # noqa: E731  (the products rounded as the kernel's)
+    want_d = f32(0.25, 0.81) * f32(b1, b2) if advance else f32(0.25, 0.81)
+    want_g = f32(0.125, 0.729) * f32(b1g, b2g) if advance and with_g_and_step else f32(0.125, 0.729)
     assert torch.equal(view[:2].cpu(), want_d)
-    assert torch.equal(view[2:].cpu(), torch.tensor([0.125, 0.729])) and int(step) == 7
-    assert _canaries_intact(buf)
+    assert torch.equal(view[2:].cpu(), want_g) and int(step) == (8 if with_g_and_step else 7)
+    assert _canaries_intact(buf) and _canaries_intact(sbuf, fill=-3)
     if ls is not None:
         assert ls.tolist() == want_ls and _canaries_intact(lsb)
 

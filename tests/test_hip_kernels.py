@@ -542,6 +542,61 @@ def test_adam_matches_tf_formula():
     assert torch.allclose(powers.cpu(), torch.tensor([b1p, b2p]), rtol=1e-6)
 
 
+@pytest.mark.parametrize("build", ["bf16", "fp16"])
+@pytest.mark.parametrize("nA,nD", [(4, 4), (2052, 1028), ((2 * 512 * 256 + 1) * 4, 1028)])
+def test_adam2_equals_two_adams_plus_step_end(nA, nD, build):
+    """Three updates of the one-launch adam2 against adam_bf(A) + adam_bf(D) + step_end on the same
+    inputs, bitwise: weights, mirrors, slots, both beta-power pairs and the step counter. The last
+    size gives set A's (at most 512) blocks a third grid-stride pass with one vector in it."""
+    from test_hip_d_spectral_norm import PAD, _canaries_intact, _padded
+    h = H()
+    edt, dt = (torch.float16, 1) if build == "fp16" else (torch.bfloat16, 0)
+    gen = torch.Generator().manual_seed(50)
+    hyp = {"A": (3e-4, 0.5, 0.9, 1e-8), "D": (1e-4, 0.6, 0.999, 1e-7)}  # lr, beta1, beta2, eps
+    gscale = 0.5
+    bufs, views, grads, w0s = {}, {}, {}, {}
+    for s, n in (("A", nA), ("D", nD)):
+        w0 = w0s[s] = torch.randn(n, generator=gen) * 0.02
+        grads[s] = [torch.randn(n, generator=gen) * 1e-2 for _ in range(3)]
+        for side in ("one", "two"):
+            for name, x, dtp in (("w", w0, None), ("wbf", torch.zeros(n), edt), ("g", torch.zeros(n), None),
+                                 ("m", torch.zeros(n), None), ("v", torch.zeros(n), None),
+                                 ("p", torch.tensor(hyp[s][1:3]), None)):
+                bufs[side, s, name], views[side, s, name] = _padded(x, dtype=dtp)
+    for side in ("one", "two"):
+        buf = torch.full((2 * PAD + 1,), 7, dtype=torch.int64, device=dev)
+        bufs[side, "step"], views[side, "step"] = buf, buf[PAD:PAD + 1]
+        views[side, "step"].fill_(11)
+    ptr = lambda side, s, k: views[side, s, k].data_ptr()  # noqa: E731
+    sets = lambda side, s, n: [ptr(side, s, k) for k in ("w", "wbf", "g", "m", "v", "p")] + [n, *hyp[s]]  # noqa: E731
+    one = h.ext().Program(dt)
+    one.adam2("adam_gd", *sets("one", "A", nA), *sets("one", "D", nD), gscale, views["one", "step"].data_ptr(), 0)
+    two = h.ext().Program(dt)
+    two.adam_bf("adam_a", *sets("two", "A", nA), gscale, 0)
+    two.adam_bf("adam_d", *sets("two", "D", nD), gscale, 0)
+    two.step_end("step_end", ptr("two", "D", "p"), ptr("two", "A", "p"), *hyp["D"][1:3], *hyp["A"][1:3],
+                 views["two", "step"].data_ptr(), 0)
+    assert one.size() == 1
+    for i in range(3):
+        for side in ("one", "two"):
+            for s in ("A", "D"):
+                views[side, s, "g"].copy_(grads[s][i])
+        h.run(one)
+        h.run(two)
+        torch.cuda.synchronize()
+        for s in ("A", "D"):
+            for k in ("w", "wbf", "m", "v", "p"):
+                assert torch.equal(views["one", s, k], views["two", s, k]), (i, s, k)
+        assert int(views["one", "step"]) == int(views["two", "step"]) == 12 + i
+    for key, buf in bufs.items():
+        assert _canaries_intact(buf), key
+    for s in ("A", "D"):  # and the update happened: weights moved, the mirror follows them, powers = beta^4
+        w = views["one", s, "w"]
+        assert not torch.equal(w.cpu(), w0s[s])
+        assert torch.equal(views["one", s, "wbf"], w.to(edt)) and float(views["one", s, "m"].abs().max()) > 0
+        assert torch.allclose(views["one", s, "p"].cpu(), torch.tensor(hyp[s][1:3]) ** 4, rtol=1e-6)
+
+
 def test_gan_loss_kernel():
     h = H()
     B = 37
