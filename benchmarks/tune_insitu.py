@@ -65,7 +65,7 @@ def used_keys(cfg, B, dtype="bf16", seed=False):
     orig_i, orig_w = H.igemm_cfg_for, H.wgrad3_cfg_for
 
     def log_i(mode, Bn, Hin, Win, Kc, Hout, Wout, N, *a, **k):
-        key = "%d,%d,%d,%d,%d,%d,%d,%d" % (mode, Bn, Hin, Win, Kc, Hout, Wout, N)
+        key = H.GemmShape(mode, Bn, Hin, Win, Kc, Hout, Wout, N).key
         r = orig_i(mode, Bn, Hin, Win, Kc, Hout, Wout, N, *a, **k)
         if key not in seen:
             seen.append(key)

@@ -129,8 +129,7 @@ class HipEngineAux:
             if L.bn:
                 xb, ab = t(B, L.out_hw, L.out_hw, L.cout), t(B, L.out_hw, L.out_hw, L.cout)
                 keep += [xb, ab]
-                self._igemm(prog, "s." + L.name, 1, prev, nat, xb, B, L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw,
-                            L.cout, pad, bias=Pg[L.name + "/biases"])
+                self._igemm(prog, "s." + L.name, H.GemmShape.fwd(L, B), prev, nat, xb, pad, bias=Pg[L.name + "/biases"])
                 coef(L.bn, L.cout)
                 rows = B * L.out_hw ** 2
                 prog.bn_apply_act("s." + L.bn, _p(xb), _p(ab), _p(sc[L.bn][0]), _p(sc[L.bn][1]), rows, L.cout, rows,

@@ -44,7 +44,7 @@ weight in the same flat layout, which the GEMMs read in either orientation.
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -129,6 +129,21 @@ class _TorchExec:
     def replay(graph, stream) -> None:
         with torch.cuda.stream(stream):
             graph.replay()
+
+
+class _DChain(NamedTuple):
+    """One pass back through D (``HipEngine._d_backward``): the rows it covers and where its
+    gradients go."""
+    prefix: str                   # of its op names
+    Bn: int                       # rows: 2B = [real | fake], B = the fake half
+    groups: int                   # BN statistics groups among those rows ...
+    group_offset: int             # ... from this one on (1: the fake half's statistics)
+    view: Callable                # the chain's rows of a [2B, ...] forward buffer (d_x / d_a)
+    da: Dict[str, torch.Tensor]   # its own buffers: per layer dL/d(activation),
+    dx: Dict[str, torch.Tensor]   # dL/d(pre-activation)
+    coef: Dict[str, torch.Tensor]  # and, per BN layer, the BN-backward coefficients
+    dl: torch.Tensor              # the seed dL/dlogit
+    grads: Optional[object]       # D's gradient set, or None: data gradients only
 
 
 class HipEngine(HipDDPMixin, HipEngineAux):
@@ -489,16 +504,15 @@ class HipEngine(HipDDPMixin, HipEngineAux):
 
 
     # ---- helpers
-    def _igemm(self, prog, name, mode, A, Bw, C, Bn, Hin, Win, Kc, Hout, Wout, N, pad, out_f32=False, ldc=None,
-               cofs=0, bias=None, act=NONE, stats=None, rows_per_group=None, bkn=False, kb_valid=-1, bnb=None,
-               stream=0):
-        """One conv-shaped GEMM. Bw is a weight view; bkn=True reads it as [tap][K][N] (D
-        forward, G dgrad, im2col'd layers), else as [tap][N][K]. bnb = (x, y, mean, rstd,
-        rows_per_group, act[, store_g]): the epilogue also emits the BN-backward partial sums of
-        the layer whose dL/da this GEMM produces (see _dgrad_bnb)."""
-        plan = H.igemm_cfg_for(mode, Bn, Hin, Win, Kc, Hout, Wout, N, rows_per_group, bkn, dtype=self.dt)
+    def _igemm(self, prog, name, shape, A, Bw, C, pad, out_f32=False, ldc=None, cofs=0, bias=None, act=NONE,
+               stats=None, rows_per_group=None, kb_valid=-1, bnb=None, stream=0):
+        """One conv-shaped GEMM (shape: ops.hip.GemmShape). Bw is a weight view; shape.bkn reads it as
+        [tap][K][N] (D forward, G dgrad, im2col'd layers), else as [tap][N][K]. bnb = (x, y, mean,
+        rstd, rows_per_group, act[, store_g]): the epilogue also emits the BN-backward partial sums
+        of the layer whose dL/da this GEMM produces (see _dgrad)."""
+        plan = shape.plan(rows_per_group, self.dt)
         if plan is None:
-            raise RuntimeError("no igemm tile for %s (mode %d, N %d, bkn %d)" % (name, mode, N, bkn))
+            raise RuntimeError("no igemm tile for %s (mode %d, N %d, bkn %d)" % (name, shape.mode, shape.N, shape.bkn))
         cfg, splits = plan
         bx = by = bm = br = 0
         brpg = bact = bstore = 0
@@ -506,70 +520,49 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             bx, by, bm, br = _p(bnb[0]), _p(bnb[1]), _p(bnb[2]), _p(bnb[3])
             brpg, bact = bnb[4], bnb[5]
             bstore = int(len(bnb) > 6 and bnb[6])
-        prog.igemm_ex(name, mode, _p(A), _p(Bw), _p(C), Bn, Hin, Win, Kc, Hout, Wout, N, pad, pad, cfg, int(out_f32),
-                      ldc or N, cofs, _p(bias), act, self.cfg.lrelu_leak, _p(stats), stream, int(bkn), kb_valid, splits,
-                      bx, by, bm, br, brpg, bact, self.cfg.lrelu_leak, bstore)
+        prog.igemm_ex(name, shape.mode, _p(A), _p(Bw), _p(C), *shape[1:8], pad, pad, cfg, int(out_f32),
+                      ldc or shape.N, cofs, _p(bias), act, self.cfg.lrelu_leak, _p(stats), stream, int(shape.bkn),
+                      kb_valid, splits, bx, by, bm, br, brpg, bact, self.cfg.lrelu_leak, bstore)
         return cfg
 
-    def _stats_tiles(self, mode, Bn, Hin, Win, Kc, Hout, Wout, N, rows_per_group=None, bkn=False):
-        """Number of partial-statistics rows a stats-emitting igemm writes (tiles x phases)."""
-        if mode == 1:
-            M, phases = Bn * (-(-Hout // 2)) * (-(-Wout // 2)), 4
-        else:
-            M, phases = Bn * Hout * Wout, 1
-        plan = H.igemm_cfg_for(mode, Bn, Hin, Win, Kc, Hout, Wout, N, rows_per_group, bkn, dtype=self.dt)
-        if plan is None:
-            return None
-        bm, _ = H.tile_of(plan[0], self.dt)
-        return -(-M // bm) * phases
+    def _dgrad(self, prog, name, shape, A, Bw, pad, act, y, da, bn=None, x=None, dx=None, actb=None, groups=1,
+               group_offset=0, kb_valid=-1):
+        """The data-gradient GEMM that produces dL/da of the layer below (activation output y, same
+        layout as the GEMM output), with that layer's backward fused into the store pass when a tile
+        allows. Returns (partials, partials per group) for the layer's backward, or None: the plain
+        GEMM wrote da and the layer runs its own statistics / activation pass (always in fp32).
 
-    def _dgrad_bnb(self, prog, mode, Bn, Hin, Win, Kc, Hout, Wout, N, bkn, bn_name, x, y, groups, act,
-                   group_offset=0):
-        """Fused BN-backward statistics for the data-gradient GEMM that writes dL/da of BN layer
-        ``bn_name`` (x = its pre-BN input, y = its activation output, same layout as the GEMM
-        output). Returns (igemm kwargs, partials, partials per group) or None when no tile keeps
-        the real/fake groups apart (odd sizes) or in fp32 -- the BN backward then runs its own
-        statistics pass. (The BN-backward finalize stays a separate kernel: fusing it into the GEMM
-        through a per-workgroup arrival measured slower, profiles/r2/ab_fused_finalize_r2.txt.)"""
-        if self.f32:
-            return None
-        if mode == 1:
-            if Hout % 2 or Wout % 2:
-                return None
-            M, phases = Bn * (Hout // 2) * (Wout // 2), 4
-        else:
-            M, phases = Bn * Hout * Wout, 1
-        rpg = M // groups
-        plan = H.igemm_cfg_for(mode, Bn, Hin, Win, Kc, Hout, Wout, N, rpg, bkn, dtype=self.dt)
-        if plan is None or N % 8 or not H.bnb_fits(plan[0]):
-            return None
-        bm, _ = H.tile_of(plan[0])
-        P = -(-M // bm) * phases
-        part = self._stats_buf(bn_name + ".bwd", P, N)
-        st = self.bn[bn_name]
-        mean, rstd = st["mean"][group_offset:], st["rstd"][group_offset:]
-        kw = dict(stats=part, rows_per_group=rpg, bnb=(x, y, mean, rstd, rpg, act))
-        return kw, part, P // groups
+        Layer below has BN `bn` (x = its pre-BN input): the epilogue emits the BN-backward statistics
+        into a fresh `<bn>.bwd` buffer, per group (`groups` row groups from `group_offset`), and dL/da
+        goes to da. The tile must divide a group, so the plan is asked with rows_per_group, and a
+        deconv with an odd output is never fused: its four phases have different row counts, and no
+        group size divides them all (igemm_ex checks it per phase). (The BN-backward finalize stays
+        a separate kernel: fusing it into the GEMM through a per-workgroup arrival measured slower,
+        profiles/r2/ab_fused_finalize_r2.txt.)
 
-    def _dgrad_actb(self, prog, mode, Bn, Hin, Win, Kc, Hout, Wout, N, bkn, name, y, act):
-        """Fused activation backward for the data-gradient GEMM that produces dL/da of a layer
-        WITHOUT BN: the GEMM stores dx = dL/da * act'(y) directly and emits per-tile partial
-        column sums of dx (the bias gradient). Returns (igemm kwargs, partials, #partials) or
-        None (fp32, or no vectorizable tile: the caller runs the separate act backward)."""
-        if self.f32:
+        No BN: the GEMM stores dx = dL/da * act'(y) itself and emits per-tile column sums of dx (the
+        bias gradient) into `<actb>.actb`. Nothing is grouped, so any tile serves (the plan is asked
+        without rows_per_group) and odd deconv sizes only round the partial rows up."""
+        rpg = None
+        fits = not self.f32
+        if bn is not None:
+            fits = fits and not (shape.mode == 1 and (shape.Hout % 2 or shape.Wout % 2))
+            rpg = shape.M // groups
+        plan = shape.plan(rpg, self.dt) if fits else None
+        if plan is None or shape.N % 8 or not H.bnb_fits(plan[0]):
+            self._igemm(prog, name, shape, A, Bw, da, pad, kb_valid=kb_valid)
             return None
-        plan = H.igemm_cfg_for(mode, Bn, Hin, Win, Kc, Hout, Wout, N, None, bkn, dtype=self.dt)
-        if plan is None or N % 8 or not H.bnb_fits(plan[0]):
-            return None
-        bm, _ = H.tile_of(plan[0])
-        if mode == 1:
-            M, phases = Bn * (-(-Hout // 2)) * (-(-Wout // 2)), 4
-        else:
-            M, phases = Bn * Hout * Wout, 1
-        P = -(-M // bm) * phases
-        part = self._stats_buf(name + ".actb", P, N)
-        kw = dict(stats=part, bnb=(y, y, None, None, 0, act, True))
-        return kw, part, P
+        P = shape.stat_rows(plan[0], self.dt)
+        if bn is not None:
+            part = self._stats_buf(bn + ".bwd", P, shape.N)
+            st = self.bn[bn]
+            bnb = (x, y, st["mean"][group_offset:], st["rstd"][group_offset:], rpg, act)
+            self._igemm(prog, name, shape, A, Bw, da, pad, stats=part, rows_per_group=rpg, kb_valid=kb_valid, bnb=bnb)
+            return part, P // groups
+        part = self._stats_buf(actb + ".actb", P, shape.N)
+        bnb = (y, y, None, None, 0, act, True)
+        self._igemm(prog, name, shape, A, Bw, dx, pad, stats=part, kb_valid=kb_valid, bnb=bnb)
+        return part, P
 
     def _deconv_out(self, prog, name, x, w, y, B, L, pad, bias, act):
         """G's output layer: the direct narrow kernel for RGB / gray outputs (16-bit), else the
@@ -578,8 +571,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             prog.narrow_deconv(name, _p(x), _p(w), _p(bias), _p(y), B, L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw,
                                L.cout, pad, act, self.cfg.lrelu_leak, 0)
         else:
-            self._igemm(prog, name, 1, x, w, y, B, L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw, L.cout, pad,
-                        bias=bias, act=act)
+            self._igemm(prog, name, H.GemmShape.fwd(L, B), x, w, y, pad, bias=bias, act=act)
 
     def _bn_fwd(self, prog, name, x, y, rows, C, groups, act, part, ppg, update_ema, apply=True):
         """BN finalize (+EMA) and apply+act over `groups` row groups (apply=False: the consumer
@@ -708,11 +700,12 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             nat = Wg[L.name + "/w"]  # [5,5,co,ci] = [tap][N][K]
             pad = same_pads(L.out_hw)[0]
             if L.bn:
-                P = self._stats_tiles(1, B, L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw, L.cout)
+                shape = H.GemmShape.fwd(L, B)
+                P = shape.stat_rows(shape.plan(None, self.dt)[0], self.dt)
                 part = self._stats_buf(L.bn, P, L.cout)
                 rows = B * L.out_hw ** 2
-                self._igemm(prog, L.name, 1, a_prev, nat, self.g_x[L.name], B, L.in_hw, L.in_hw, L.cin, L.out_hw,
-                            L.out_hw, L.cout, pad, bias=Pg[L.name + "/biases"], stats=part)
+                self._igemm(prog, L.name, shape, a_prev, nat, self.g_x[L.name], pad, bias=Pg[L.name + "/biases"],
+                            stats=part)
                 out_applies = L is self.gl[-2] and self._gout_applies_bn()
                 self._bn_fwd(prog, L.bn, self.g_x[L.name], self.g_a[L.name], rows, L.cout, 1, RELU, part, P,
                              update_ema_g, apply=not out_applies)
@@ -738,6 +731,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             w = Wd[L.name + "/w"]  # HWIO [5,5,ci,co] = [tap][K][N]
             pad = same_pads(L.in_hw)[0]
             rows = B2 * L.out_hw ** 2
+            shape = H.GemmShape.fwd(L, B2)
             if i == 0 and self._d0_direct():  # persistent direct MFMA conv, no column matrix (narrow2.hip)
                 prog.nconv("d0.nconv", _p(prev), _p(w), _p(Pd[L.name + "/biases"]), _p(self.d_a[L.name]), B2,
                            L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw, pad, pad, LRELU, cfg.lrelu_leak,
@@ -745,25 +739,23 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             elif i == 0 and L.cin % 8 != 0:
                 prog.im2col_s2("d0.im2col", _p(prev), _p(self.d0_col), B2, L.in_hw, L.in_hw, L.cin, L.out_hw,
                                L.out_hw, pad, pad, self.kp_d0, 0)
-                self._igemm(prog, L.name, 2, self.d0_col, w, self.d_a[L.name], B2, 1, 1, self.kp_d0, L.out_hw,
-                            L.out_hw, L.cout, 0, bias=Pd[L.name + "/biases"], act=LRELU, bkn=True,
+                self._igemm(prog, L.name, H.GemmShape(2, B2, 1, 1, self.kp_d0, L.out_hw, L.out_hw, L.cout, True),
+                            self.d0_col, w, self.d_a[L.name], 0, bias=Pd[L.name + "/biases"], act=LRELU,
                             kb_valid=25 * L.cin)
             elif not L.bn:
-                self._igemm(prog, L.name, 0, prev, w, self.d_a[L.name], B2, L.in_hw, L.in_hw, L.cin, L.out_hw,
-                            L.out_hw, L.cout, pad, bias=Pd[L.name + "/biases"], act=LRELU, bkn=True)
+                self._igemm(prog, L.name, shape, prev, w, self.d_a[L.name], pad, bias=Pd[L.name + "/biases"], act=LRELU)
             else:
                 rpg = B * L.out_hw ** 2
-                P = self._stats_tiles(0, B2, L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw, L.cout, rpg, True)
-                if P is not None:
+                plan = shape.plan(rpg, self.dt)
+                if plan is not None:
                     # BN partial statistics straight from the conv epilogue (tiles never straddle
                     # the real/fake boundary)
+                    P = shape.stat_rows(plan[0], self.dt)
                     part = self._stats_buf(L.bn, P, L.cout)
-                    self._igemm(prog, L.name, 0, prev, w, self.d_x[L.name], B2, L.in_hw, L.in_hw, L.cin, L.out_hw,
-                                L.out_hw, L.cout, pad, bias=Pd[L.name + "/biases"], stats=part, rows_per_group=rpg,
-                                bkn=True)
+                    self._igemm(prog, L.name, shape, prev, w, self.d_x[L.name], pad, bias=Pd[L.name + "/biases"],
+                                stats=part, rows_per_group=rpg)
                 else:  # odd sizes: no tile divides the group -> separate group-aligned stats pass
-                    self._igemm(prog, L.name, 0, prev, w, self.d_x[L.name], B2, L.in_hw, L.in_hw, L.cin, L.out_hw,
-                                L.out_hw, L.cout, pad, bias=Pd[L.name + "/biases"], bkn=True)
+                    self._igemm(prog, L.name, shape, prev, w, self.d_x[L.name], pad, bias=Pd[L.name + "/biases"])
                     rpb = self._rows_per_block(rpg, L.cout)
                     P = rows // rpb
                     part = self._stats_buf(L.bn, P, L.cout)
@@ -791,86 +783,87 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                            B2, cfg.d_lin_in, 0, _p(self.losses), _p(self.dl_d), _p(self.dl_g), _p(self.prob),
                            _p(self.loss_scale), obj, self.label_smooth)
 
-    # ---- D backward for d_loss (2B rows, both groups) -> all D gradients
-    def _build_d_backward_dloss(self, prog, sub: Optional[int] = None):
-        """sub = k: the D chain of D sub-step k (layer 0's weight gradient reads its d_in, or the
-        noisy copy of it that the forward wrote)."""
-        cfg, B = self.cfg, self.B
-        d_in = self._d_input(sub)
-        B2 = 2 * B
-        Pd, gD = self.model.d, self.grad_d
-        lin = cfg.d_lin_name
-        last = self.dl[-1]
-        fused_next = self._head_bwd(prog, "d_head.bwd", self.d_a[last.name], self.dl_d, self.d_da[last.name],
-                                    gD[lin + "/Matrix"], gD[lin + "/bias"], B2, last, 2, 0)
-        # fused_next: BN-backward partials emitted by the layer above (head / dgrad GEMM store pass)
-        for i in range(len(self.dl) - 1, -1, -1):
+    # ---- the pass back through D: the d_loss chain (2B rows, all D gradients) and the g_loss chain
+    def _d_backward(self, prog, ch: "_DChain", wgrad=None) -> int:
+        """One walk back through D over the rows of chain `ch`: the head backward with the top BN
+        layer's statistics fused in, then per layer its BN backward / bias sum from fused partials /
+        activation backward, wgrad(i, L, dx) when given (the chain's weight-gradient step), and the
+        data gradient into the layer below (_dgrad). ch.grads None: data gradients only. Ends with
+        ch.dx of layer 0; returns the position behind the top layer's data gradient (the chain's last
+        read of the top layer's kernel)."""
+        Pd, g, leak = self.model.d, ch.grads, self.cfg.lrelu_leak
+        lin, last, n = self.cfg.d_lin_name, self.dl[-1], len(self.dl)
+        # fused: BN-backward partials emitted by the layer above (head / dgrad GEMM store pass)
+        xa, dW, db = (None, None, None) if g is None else (self.d_a[last.name], g[lin + "/Matrix"], g[lin + "/bias"])
+        fused = self._head_bwd(prog, ch.prefix + ("d_head.dgrad" if g is None else "d_head.bwd"), xa, ch.dl,
+                               ch.da[last.name], dW, db, ch.Bn, last, ch.groups, ch.group_offset)
+        top_end = 0
+        for i in range(n - 1, -1, -1):
             L = self.dl[i]
-            rows = B2 * L.out_hw ** 2
-            da, a = self.d_da[L.name], self.d_a[L.name]
-            dx = self.d_dx[L.name]
+            rows = ch.Bn * L.out_hw ** 2
+            da, a, dx = ch.da[L.name], ch.view(self.d_a[L.name]), ch.dx[L.name]
             if L.bn:
-                self._bn_bwd(prog, L.bn, self.d_x[L.name], da, a, dx, rows, L.cout, 2, LRELU, Pd, gD,
-                             self.coef[L.bn], write_param_grads=True, fused=fused_next)
-            elif fused_next is not None:  # dx already stored by the upper dgrad GEMM; db from its partials
-                part, Pn = fused_next[0], fused_next[1]
-                prog.sum_partials(L.name + ".dbias", _p(part), Pn, 2 * L.cout, L.cout, _p(gD[L.name + "/biases"]), 0)
+                self._bn_bwd(prog, L.bn, ch.view(self.d_x[L.name]), da, a, dx, rows, L.cout, ch.groups, LRELU, Pd, g,
+                             ch.coef[L.bn], write_param_grads=g is not None, group_offset=ch.group_offset, fused=fused)
+            elif fused is not None:  # dx already stored by the upper dgrad GEMM; db from its partials
+                if g is not None:
+                    prog.sum_partials(ch.prefix + L.name + ".dbias", _p(fused[0]), fused[1], 2 * L.cout, L.cout,
+                                      _p(g[L.name + "/biases"]), 0)
+            elif g is None:
+                prog.act_bwd(ch.prefix + L.name + ".act_bwd", _p(da), _p(a), _p(dx), dx.numel(), LRELU, leak, 0)
             else:  # live bias (no BN after it): db = sum over rows of dx, fused with the act backward
-                self._act_bwd_dbias(prog, L.name + ".act_bwd", da, a, dx, rows, L.cout, LRELU, gD[L.name + "/biases"],
-                                    "d")
-
-            def emit_wgrad(i=i, L=L, dx=dx):
-                src = d_in if i == 0 else self.d_a[self.dl[i - 1].name]
-                pad = same_pads(L.in_hw)[0]
-                ws = 0
-                if i == 0 and self._d0_direct() and prog.nwgrad_ok(L.in_hw, L.in_hw, L.out_hw, L.out_hw):
-                    # image window staged per workgroup, no column matrix (narrow2.hip nwgrad)
-                    prog.nwgrad(L.name + ".nwgrad", _p(d_in), B2, L.in_hw, L.in_hw, L.cin, _p(dx), L.out_hw,
-                                L.out_hw, pad, _p(gD[L.name + "/w"]), ws)
-                elif i == 0 and L.cin % 8 != 0:
-                    if self._d0_direct():  # the forward ran without a column matrix: build it here
-                        prog.im2col_s2("d0.im2col", _p(d_in), _p(self.d0_col), B2, L.in_hw, L.in_hw, L.cin,
-                                       L.out_hw, L.out_hw, pad, pad, self.kp_d0, ws)
-                    self._wgrad(prog, L.name, 2, self.d0_col, 1, 1, self.kp_d0, dx, B2 * L.out_hw ** 2, 1, 1, L.cout, 0,
-                                gD[L.name + "/w"], stream=ws)
-                else:
-                    self._wgrad(prog, L.name, 0, src, L.in_hw, L.in_hw, L.cin, dx, B2, L.out_hw, L.out_hw, L.cout, pad,
-                                gD[L.name + "/w"], stream=ws)
-                # spectral norm: this kernel's gradient (and, with the top layer, the head's) is final
-                self._sn_project(prog, [L.name + "/w"] + ([lin + "/Matrix"] if i == len(self.dl) - 1 else []))
-                if i == len(self.dl) - 1:
-                    # head + top layer gradients final: DDP splits the segment here so their
-                    # all-reduce (76 % of D's bytes at 64x64) overlaps the rest of D's backward
-                    self._b_split = prog.size()
-
-            def emit_dgrad(i=i, L=L, dx=dx):
-                fused = None
-                pad = same_pads(L.in_hw)[0]
-                if i > 0:
-                    nat = self.wbf_d[L.name + "/w"]
-                    P_ = self.dl[i - 1]
-                    kw = {}
-                    out = self.d_da[P_.name]
-                    if P_.bn:
-                        r = self._dgrad_bnb(prog, 1, B2, L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, False,
-                                            P_.bn, self.d_x[P_.name], self.d_a[P_.name], 2, LRELU)
-                        if r is not None:
-                            kw, fused = r[0], (r[1], r[2])
-                    else:
-                        r = self._dgrad_actb(prog, 1, B2, L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, False,
-                                             P_.name, self.d_a[P_.name], LRELU)
-                        if r is not None:
-                            kw, fused, out = r[0], (r[1], r[2]), self.d_dx[P_.name]
-                    self._igemm(prog, L.name + ".dgrad", 1, dx, nat, out, B2, L.out_hw, L.out_hw, L.cout,
-                                L.in_hw, L.in_hw, L.cin, pad, **kw)
-                return fused
-
+                self._act_bwd_dbias(prog, ch.prefix + L.name + ".act_bwd", da, a, dx, rows, L.cout, LRELU,
+                                    g[L.name + "/biases"], "d")
             # weight gradient, then data gradient (dgrad-first measured neutral:
             # profiles/r2/ab_d_dgrad_first_r2.txt)
-            emit_wgrad()
-            fused_next = emit_dgrad()
-            if i == len(self.dl) - 1:
-                self._b_top_dgrad = prog.size()  # the D chain's last read of the top layer's kernel
+            if wgrad is not None:
+                wgrad(i, L, dx)
+            fused = None
+            if i > 0:
+                P_ = self.dl[i - 1]
+                fused = self._dgrad(prog, ch.prefix + L.name + ".dgrad", H.GemmShape.dgrad(L, ch.Bn), dx,
+                                    self.wbf_d[L.name + "/w"], same_pads(L.in_hw)[0], LRELU, ch.view(self.d_a[P_.name]),
+                                    ch.da[P_.name], bn=P_.bn, x=ch.view(self.d_x[P_.name]) if P_.bn else None,
+                                    dx=ch.dx[P_.name], actb=ch.prefix + P_.name, groups=ch.groups,
+                                    group_offset=ch.group_offset)
+            if i == n - 1:
+                top_end = prog.size()
+        return top_end
+
+    def _d_wgrad(self, prog, d_in, i, L, dx) -> None:
+        """The d_loss chain's weight-gradient step of D layer i (d_in: what layer 0 read)."""
+        B2, gD = 2 * self.B, self.grad_d
+        pad = same_pads(L.in_hw)[0]
+        ws = 0
+        if i == 0 and self._d0_direct() and prog.nwgrad_ok(L.in_hw, L.in_hw, L.out_hw, L.out_hw):
+            # image window staged per workgroup, no column matrix (narrow2.hip nwgrad)
+            prog.nwgrad(L.name + ".nwgrad", _p(d_in), B2, L.in_hw, L.in_hw, L.cin, _p(dx), L.out_hw,
+                        L.out_hw, pad, _p(gD[L.name + "/w"]), ws)
+        elif i == 0 and L.cin % 8 != 0:
+            if self._d0_direct():  # the forward ran without a column matrix: build it here
+                prog.im2col_s2("d0.im2col", _p(d_in), _p(self.d0_col), B2, L.in_hw, L.in_hw, L.cin,
+                               L.out_hw, L.out_hw, pad, pad, self.kp_d0, ws)
+            self._wgrad(prog, L.name, 2, self.d0_col, 1, 1, self.kp_d0, dx, B2 * L.out_hw ** 2, 1, 1, L.cout, 0,
+                        gD[L.name + "/w"], stream=ws)
+        else:
+            src = d_in if i == 0 else self.d_a[self.dl[i - 1].name]
+            self._wgrad(prog, L.name, 0, src, L.in_hw, L.in_hw, L.cin, dx, B2, L.out_hw, L.out_hw, L.cout, pad,
+                        gD[L.name + "/w"], stream=ws)
+        # spectral norm: this kernel's gradient (and, with the top layer, the head's) is final
+        top = i == len(self.dl) - 1
+        self._sn_project(prog, [L.name + "/w"] + ([self.cfg.d_lin_name + "/Matrix"] if top else []))
+        if top:
+            # head + top layer gradients final: DDP splits the segment here so their
+            # all-reduce (76 % of D's bytes at 64x64) overlaps the rest of D's backward
+            self._b_split = prog.size()
+
+    def _build_d_backward_dloss(self, prog, sub: Optional[int] = None):
+        """D's backward of d_loss: 2B rows, both statistics groups, all D gradients. sub = k: the D
+        chain of D sub-step k (layer 0's weight gradient reads its d_in, or the noisy copy of it that
+        the forward wrote). Sets _b_split and _b_top_dgrad."""
+        d_in = self._d_input(sub)
+        ch = _DChain("", 2 * self.B, 2, 0, lambda t: t, self.d_da, self.d_dx, self.coef, self.dl_d, self.grad_d)
+        self._b_top_dgrad = self._d_backward(prog, ch, lambda i, L, dx: self._d_wgrad(prog, d_in, i, L, dx))
 
     def _w_mark(self, prog, progw, begin: int, layer: str) -> None:
         """progW[begin:] (`layer`'s weight gradient) needs progA up to its current end."""
@@ -946,14 +939,12 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                    _p(dst), dst.numel(), 1.0, stream)
 
     def _bn_bwd(self, prog, name, x, dy, y, dx, rows, C, groups, act, P, grads, coef, write_param_grads,
-                row_offset_groups=None, fused=None):
-        """BN + activation backward. fused = (partials, partials per group) when the producing
-        data-gradient GEMM already emitted the statistics (else a column-stats pass here)."""
+                group_offset=0, fused=None):
+        """BN + activation backward over `groups` statistics groups from `group_offset` (1: the fake
+        half only). fused = (partials, partials per group) when the producing data-gradient GEMM
+        already emitted the statistics (else a column-stats pass here)."""
         st = self.bn[name]
-        mean, rstd = st["mean"], st["rstd"]
-        if row_offset_groups is not None:  # fake-half only (group 1)
-            mean = mean[row_offset_groups:row_offset_groups + 1]
-            rstd = rstd[row_offset_groups:row_offset_groups + 1]
+        mean, rstd = st["mean"][group_offset:], st["rstd"][group_offset:]
         rpg = rows // groups
         if fused is not None:
             part, ppg = fused[0], fused[1]
@@ -977,55 +968,23 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         gradients, each recorded with the progA position it needs (self._g_w). Under the fused
         schedule they run on the D chain's stream once that chain is done, beside the G
         data-gradient chain (which then has nothing else on its critical path)."""
-        cfg, B = self.cfg, self.B
-        Pd, Pg, gG = self.model.d, self.model.g, self.grad_g
-        last = self.dl[-1]
-        half = lambda t: t[B:]  # noqa: E731  fake half of a [2B, ...] buffer
-        fused_next = self._head_bwd(prog, "g.d_head.dgrad", None, self.dl_g, self.gc_da[last.name], None, None,
-                                    B, last, 1, 1)
-        for i in range(len(self.dl) - 1, -1, -1):
-            L = self.dl[i]
-            rows = B * L.out_hw ** 2
-            da, a, dx = self.gc_da[L.name], half(self.d_a[L.name]), self.gc_dx[L.name]
-            if L.bn:
-                self._bn_bwd(prog, L.bn, half(self.d_x[L.name]), da, a, dx, rows, L.cout, 1, LRELU, Pd, None,
-                             self.coef_g[L.bn], write_param_grads=False, row_offset_groups=1, fused=fused_next)
-            elif fused_next is None:  # (else dx was stored by the upper dgrad GEMM)
-                prog.act_bwd("g." + L.name + ".act_bwd", _p(da), _p(a), _p(dx), dx.numel(), LRELU, cfg.lrelu_leak, 0)
-            nat = self.wbf_d[L.name + "/w"]
-            pad = same_pads(L.in_hw)[0]
-            fused_next = None
-            if i > 0:
-                P_ = self.dl[i - 1]
-                kw = {}
-                out = self.gc_da[P_.name]
-                if P_.bn:
-                    r = self._dgrad_bnb(prog, 1, B, L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, False,
-                                        P_.bn, half(self.d_x[P_.name]), half(self.d_a[P_.name]), 1, LRELU,
-                                        group_offset=1)
-                    if r is not None:
-                        kw, fused_next = r[0], (r[1], r[2])
-                else:
-                    r = self._dgrad_actb(prog, 1, B, L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, False,
-                                         "g." + P_.name, half(self.d_a[P_.name]), LRELU)
-                    if r is not None:
-                        kw, fused_next, out = r[0], (r[1], r[2]), self.gc_dx[P_.name]
-                self._igemm(prog, "g." + L.name + ".dgrad", 1, dx, nat, out, B, L.out_hw,
-                            L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, pad, **kw)
-            else:
-                if self._img_dact():
-                    # image gradient with G's tanh backward fused (dL/d(G pre-activation) straight out)
-                    # + the G output bias gradient from its per-workgroup column sums
-                    Lg = self.gl[-1]
-                    prog.narrow_deconv_dact("g." + L.name + ".dgrad_img+tanh_bwd", _p(dx), _p(nat), _p(self.img_g),
-                                            _p(self.fake), B, L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin,
-                                            pad, TANH, 0.0, _p(self.grad_g[Lg.name + "/biases"]), 0)
-                elif not self.f32 and L.cin <= 4 and L.cout % 8 == 0 and L.cout <= 256:  # 3-channel image gradient
-                    prog.narrow_deconv("g." + L.name + ".dgrad_img", _p(dx), _p(nat), 0, _p(self.img_grad), B,
-                                       L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, pad, NONE, 0.0, 0)
-                else:
-                    self._igemm(prog, "g." + L.name + ".dgrad_img", 1, dx, nat, self.img_grad, B, L.out_hw,
-                                L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, pad)
+        B, L = self.B, self.dl[0]
+        # the fake half only: B rows, one statistics group (group 1), gradient buffers of its own
+        ch = _DChain("g.", B, 1, 1, lambda t: t[B:], self.gc_da, self.gc_dx, self.coef_g, self.dl_g, None)
+        self._d_backward(prog, ch)
+        dx, nat, pad = self.gc_dx[L.name], self.wbf_d[L.name + "/w"], same_pads(L.in_hw)[0]
+        if self._img_dact():
+            # image gradient with G's tanh backward fused (dL/d(G pre-activation) straight out)
+            # + the G output bias gradient from its per-workgroup column sums
+            Lg = self.gl[-1]
+            prog.narrow_deconv_dact("g." + L.name + ".dgrad_img+tanh_bwd", _p(dx), _p(nat), _p(self.img_g),
+                                    _p(self.fake), B, L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin,
+                                    pad, TANH, 0.0, _p(self.grad_g[Lg.name + "/biases"]), 0)
+        elif not self.f32 and L.cin <= 4 and L.cout % 8 == 0 and L.cout <= 256:  # 3-channel image gradient
+            prog.narrow_deconv("g." + L.name + ".dgrad_img", _p(dx), _p(nat), 0, _p(self.img_grad), B,
+                               L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, pad, NONE, 0.0, 0)
+        else:
+            self._igemm(prog, "g." + L.name + ".dgrad_img", H.GemmShape.dgrad(L, B), dx, nat, self.img_grad, pad)
         self._build_g_backward(prog, progw)
 
     def _build_g_backward(self, prog, progw):
@@ -1039,12 +998,17 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         if not self._img_dact():  # (else fused into the image-gradient kernel above)
             self._act_bwd_dbias(prog, "g_out.tanh_bwd", self.img_grad, self.fake, self.img_g, B * Lg.out_hw ** 2,
                                 Lg.cout, TANH, gG[Lg.name + "/biases"], "g")
-        a_prev = self.g_a[self.gl[-2].name] if n > 1 else self.g_h0
-        da_prev = self.g_da[self.gl[-2].name] if n > 1 else self.g_da0
-        x_prev = self.g_x[self.gl[-2].name] if n > 1 else self.g_h0_pre
-        bn_prev = self.gl[-2].bn if n > 1 else "g_bn0"
+
+        def below(j):  # what feeds G layer j: (activation, its gradient, pre-BN input, BN layer)
+            if j == 0:
+                return self.g_h0, self.g_da0, self.g_h0_pre, "g_bn0"
+            Lb = self.gl[j - 1]
+            return self.g_a[Lb.name], self.g_da[Lb.name], self.g_x[Lb.name], Lb.bn
+
+        a_prev, da_prev, x_prev, bn_prev = below(n - 1)
         padL = same_pads(Lg.out_hw)[0]
         wL = self.wbf_g[Lg.name + "/w"]  # [5,5,co,ci] read as [tap][K=co][N=ci]
+        w0 = progw.size()
         if self._g_out_direct():
             # narrow2.hip: the data gradient is the stride-2 conv of the image gradient with the
             # [5,5,co,ci] = HWIO[5,5,3,64] weight (nconv, BN-backward statistics of the layer below
@@ -1053,65 +1017,42 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             grid = H.nconv_grid(prog, B, Lg.in_hw, Lg.in_hw)
             part = self._stats_buf(bn_prev + ".bwd", grid, Lg.cin)
             st = self.bn[bn_prev]
-            w0 = progw.size()
             progw.nwgrad(Lg.name + ".nwgrad", _p(self.img_g), B, Lg.out_hw, Lg.out_hw, Lg.cout, _p(a_prev), Lg.in_hw,
                          Lg.in_hw, padL, _p(gG[Lg.name + "/w"]), 0)
             self._w_mark(prog, progw, w0, Lg.name)
             prog.nconv(Lg.name + ".dgrad", _p(self.img_g), _p(wL), 0, _p(da_prev), B, Lg.out_hw, Lg.out_hw, Lg.cout,
                        Lg.in_hw, Lg.in_hw, padL, padL, NONE, 0.0, grid, _p(x_prev), _p(a_prev), _p(st["mean"]),
                        _p(st["rstd"]), RELU, cfg.lrelu_leak, _p(part), 0)
-            fused_next = (part, grid, {})
+            fused_next = (part, grid)
         elif Lg.cout % 8 != 0:
             prog.im2col_s2("g_out.im2col", _p(self.img_g), _p(self.g_last_col), B, Lg.out_hw, Lg.out_hw, Lg.cout,
                            Lg.in_hw, Lg.in_hw, padL, padL, self.kp_g, 0)
-            w0 = progw.size()
             self._wgrad(progw, Lg.name, 2, self.g_last_col, 1, 1, self.kp_g, a_prev, B * Lg.in_hw ** 2, 1, 1, Lg.cin,
                         0, gG[Lg.name + "/w"])
             self._w_mark(prog, progw, w0, Lg.name)
-            r = self._dgrad_bnb(prog, 2, B, 1, 1, self.kp_g, Lg.in_hw, Lg.in_hw, Lg.cin, True, bn_prev, x_prev,
-                                a_prev, 1, RELU)
-            fused_next = None
-            kw = {}
-            if r is not None:
-                kw, fused_next = r[0], (r[1], r[2])
-            self._igemm(prog, Lg.name + ".dgrad", 2, self.g_last_col, wL, da_prev, B, 1, 1, self.kp_g, Lg.in_hw,
-                        Lg.in_hw, Lg.cin, 0, bkn=True, kb_valid=25 * Lg.cout, **kw)
+            shape = H.GemmShape(2, B, 1, 1, self.kp_g, Lg.in_hw, Lg.in_hw, Lg.cin, True)
+            fused_next = self._dgrad(prog, Lg.name + ".dgrad", shape, self.g_last_col, wL, 0, RELU, a_prev, da_prev,
+                                     bn=bn_prev, x=x_prev, kb_valid=25 * Lg.cout)
         else:
-            w0 = progw.size()
             self._wgrad(progw, Lg.name, 0, self.img_g, Lg.out_hw, Lg.out_hw, Lg.cout, a_prev, B, Lg.in_hw, Lg.in_hw,
                         Lg.cin, padL, gG[Lg.name + "/w"])
             self._w_mark(prog, progw, w0, Lg.name)
-            r = self._dgrad_bnb(prog, 0, B, Lg.out_hw, Lg.out_hw, Lg.cout, Lg.in_hw, Lg.in_hw, Lg.cin, True, bn_prev,
-                                x_prev, a_prev, 1, RELU)
-            fused_next = None
-            kw = {}
-            if r is not None:
-                kw, fused_next = r[0], (r[1], r[2])
-            self._igemm(prog, Lg.name + ".dgrad", 0, self.img_g, wL, da_prev, B, Lg.out_hw, Lg.out_hw, Lg.cout,
-                        Lg.in_hw, Lg.in_hw, Lg.cin, padL, bkn=True, **kw)
+            fused_next = self._dgrad(prog, Lg.name + ".dgrad", H.GemmShape.dgrad(Lg, B), self.img_g, wL, padL, RELU,
+                                     a_prev, da_prev, bn=bn_prev, x=x_prev)
         for j in range(n - 2, -1, -1):
             L = self.gl[j]
             rows = B * L.out_hw ** 2
             x, a, da, dx = self.g_x[L.name], self.g_a[L.name], self.g_da[L.name], self.g_dx[L.name]
             self._bn_bwd(prog, L.bn, x, da, a, dx, rows, L.cout, 1, RELU, Pg, gG, self.coef[L.bn],
                          write_param_grads=True, fused=fused_next)
-            src = self.g_a[self.gl[j - 1].name] if j > 0 else self.g_h0
-            dsrc = self.g_da[self.gl[j - 1].name] if j > 0 else self.g_da0
-            xsrc = self.g_x[self.gl[j - 1].name] if j > 0 else self.g_h0_pre
-            bsrc = self.gl[j - 1].bn if j > 0 else "g_bn0"
+            src, dsrc, xsrc, bsrc = below(j)
             pad = same_pads(L.out_hw)[0]
             w0 = progw.size()
             self._wgrad(progw, L.name, 0, dx, L.out_hw, L.out_hw, L.cout, src, B, L.in_hw, L.in_hw, L.cin, pad,
                         gG[L.name + "/w"])
             self._w_mark(prog, progw, w0, L.name)
-            r = self._dgrad_bnb(prog, 0, B, L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, True, bsrc, xsrc,
-                                src, 1, RELU)
-            fused_next = None
-            kw = {}
-            if r is not None:
-                kw, fused_next = r[0], (r[1], r[2])
-            self._igemm(prog, L.name + ".dgrad", 0, dx, self.wbf_g[L.name + "/w"], dsrc, B, L.out_hw, L.out_hw,
-                        L.cout, L.in_hw, L.in_hw, L.cin, pad, bkn=True, **kw)
+            fused_next = self._dgrad(prog, L.name + ".dgrad", H.GemmShape.dgrad(L, B), dx, self.wbf_g[L.name + "/w"],
+                                     pad, RELU, src, dsrc, bn=bsrc, x=xsrc)
         # g_bn0 backward + projection gradients
         C0 = cfg.g_base_ch
         rows0 = B * cfg.g_base_hw ** 2

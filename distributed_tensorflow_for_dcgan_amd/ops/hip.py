@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import importlib
 import os
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -253,6 +253,59 @@ def tuned_table() -> dict:
     return _TUNED
 
 
+class GemmShape(NamedTuple):
+    """One conv-shaped GEMM as ``Program.igemm_ex`` takes it: mode 0 = stride-2 conv (25 taps), 1 =
+    deconv (4 sub-pixel phases), 2 = plain GEMM; bkn: the weights are read as [tap][K][N]. A value
+    (no buffers): it owns the row / phase arithmetic that the tile policy, the tuned table and the
+    size of every fused-statistics buffer share with ``igemm_ex`` (mtiles * nphases)."""
+    mode: int
+    Bn: int
+    Hin: int
+    Win: int
+    Kc: int
+    Hout: int
+    Wout: int
+    N: int
+    bkn: bool = False
+
+    @classmethod
+    def fwd(cls, L, Bn: int) -> "GemmShape":
+        """The forward GEMM of layer L (a ConvSpec) at batch Bn: D's convs read [tap][K][N] weights."""
+        conv = L.kind == "conv"
+        return cls(0 if conv else 1, Bn, L.in_hw, L.in_hw, L.cin, L.out_hw, L.out_hw, L.cout, conv)
+
+    @classmethod
+    def dgrad(cls, L, Bn: int) -> "GemmShape":
+        """The data-gradient GEMM of layer L: the deconv of a conv layer, the conv of a deconv layer."""
+        conv = L.kind == "conv"
+        return cls(1 if conv else 0, Bn, L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, not conv)
+
+    @property
+    def phases(self) -> int:
+        return 4 if self.mode == 1 else 1
+
+    @property
+    def M(self) -> int:
+        """Rows per phase (a deconv's largest phase: odd sizes round up)."""
+        if self.mode == 1:
+            return self.Bn * (-(-self.Hout // 2)) * (-(-self.Wout // 2))
+        return self.Bn * self.Hout * self.Wout
+
+    @property
+    def key(self) -> str:
+        """Key of the tuned table."""
+        return "%d,%d,%d,%d,%d,%d,%d,%d" % self[:8]
+
+    def plan(self, rows_per_group: Optional[int] = None, dtype: int = 0) -> Optional[Tuple[int, int]]:
+        """(cfg, splits) of ``igemm_cfg_for``, looked up in the module at every call (the in-situ
+        tuner replaces it to see each lookup)."""
+        return igemm_cfg_for(*self[:8], rows_per_group, self.bkn, dtype=dtype)
+
+    def stat_rows(self, cfg: int, dtype: int = 0) -> int:
+        """Partial-statistics rows a stats-emitting launch with tile cfg writes (M tiles x phases)."""
+        return -(-self.M // tile_of(cfg, dtype)[0]) * self.phases
+
+
 def igemm_cfg_for(mode: int, Bn: int, Hin: int, Win: int, Kc: int, Hout: int, Wout: int, N: int,
                   rows_per_group: Optional[int] = None, bkn: bool = False,
                   dtype: int = 0) -> Optional[Tuple[int, int]]:
@@ -260,15 +313,13 @@ def igemm_cfg_for(mode: int, Bn: int, Hin: int, Win: int, Kc: int, Hout: int, Wo
     (weight layout, BN-statistics grouping), else the heuristics. None when no tile can
     produce group-aligned statistics (caller computes them in a separate pass). dtype 2 =
     the fp32 build (its own tile family, no tuned table)."""
-    if mode == 1:
-        M, phases, taps = Bn * (-(-Hout // 2)) * (-(-Wout // 2)), 4, 9
-    else:
-        M, phases, taps = Bn * Hout * Wout, 1, (25 if mode == 0 else 1)
+    shape = GemmShape(mode, Bn, Hin, Win, Kc, Hout, Wout, N, bkn)
+    M, phases, taps = shape.M, shape.phases, {0: 25, 1: 9}.get(mode, 1)
     if dtype == 2:
         if mode == 1 and rows_per_group is not None:
             return None
         return pick_igemm_f32(M, N, phases, rows_per_group)
-    ent = tuned_table().get("%d,%d,%d,%d,%d,%d,%d,%d" % (mode, Bn, Hin, Win, Kc, Hout, Wout, N))
+    ent = tuned_table().get(shape.key)
     if ent is not None:
         cfg, sp = ent
         ok = (cfg >= 200 and igemm3_pp_ok(cfg, mode, Kc)) or (not bkn and sp == 1 and cfg % 100 in IGEMM_CFGS)

@@ -345,3 +345,32 @@ def test_checker_finds_the_top_kernel_gather_before_its_last_reader(monkeypatch)
     eng._run_step = early
     hz, _ = SC.check_engine(eng)
     assert any("all_gather" in h.a or "all_gather" in h.b for h in hz), "\n".join(map(str, hz[:10]))
+
+
+def test_gemm_shape_statistics_rows_match_the_recorded_launch():
+    """ops.hip.GemmShape.stat_rows sizes every fused-statistics buffer; Program.igemm_ex writes
+    mtiles * nphases partial rows. For every igemm the dry default, BN-free and 28x28x1 engines record
+    (16-bit and fp32, B = 4) the two agree -- all three modes, both weight layouts, an odd deconv
+    size and grouped plans among them."""
+    from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
+    from distributed_tensorflow_for_dcgan_amd.ops import hip as H
+    seen = []
+
+    class Rec(HipEngine):
+        def _igemm(self, prog, name, shape, *a, **kw):
+            cfg = super()._igemm(prog, name, shape, *a, **kw)
+            assert isinstance(shape, H.GemmShape) and min(shape.Hout, shape.Wout) >= 2, (name, shape)
+            assert prog.last_mtiles() * prog.last_nphases() == shape.stat_rows(cfg, self.dt), (name, shape, cfg)
+            assert prog.last_nphases() == shape.phases, (name, shape)
+            seen.append((shape, kw.get("rows_per_group")))
+            return cfg
+
+    for cfg in (DCGANConfig(), DCGANConfig(d_bn=False), DCGANConfig(output_size=28, c_dim=1)):
+        for dtype in ("bf16", "fp32"):
+            Rec(cfg, 4, torch.device("cpu"), dtype=dtype, dry_run=True, graph=False)
+    assert {s.mode for s, _ in seen} == {0, 1, 2}
+    assert {s.bkn for s, _ in seen} == {False, True}
+    assert any(s.mode == 1 and s.Hin == 7 and s.Hout == 14 for s, _ in seen)  # 7 -> 14 ...
+    assert any(s.mode == 1 and s.Hout % 2 for s, _ in seen)                   # ... and an odd output
+    for mode in (0, 1):  # grouped plans: D's forward statistics, the fused BN-backward statistics
+        assert any(rpg is not None for s, rpg in seen if s.mode == mode)

@@ -48,3 +48,23 @@ def test_tuner_offers_fitting_wgrad5_configs():
     assert not any(c in (402, 403, 404, 405, 406, 407) for c, _ in nb)
     nb = T.neighbours("w3,128,256,256,8,8,16", (310, 4))
     assert {(402, 4), (404, 4), (406, 4), (412, 4)} <= set(nb) and not any(c in (400, 401, 405) for c, _ in nb)
+
+
+@pytest.mark.parametrize("hook,dtype", [("igemm_cfg_for", "bf16"), ("igemm_cfg_for", "fp32"),
+                                        ("wgrad3_cfg_for", "bf16"), ("wgrad3_cfg_for", "fp16")])
+def test_engine_build_looks_the_tile_policy_up_in_the_module(monkeypatch, hook, dtype):
+    """The in-situ tuner (``tune_insitu.used_keys``) replaces ``H.igemm_cfg_for`` / ``H.wgrad3_cfg_for``
+    to see every lookup of a build: the engine must reach both through the module, at call time."""
+    import torch
+    from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
+    from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
+
+    class Seen(Exception):
+        pass
+
+    def raiser(*a, **k):
+        raise Seen(hook)
+
+    monkeypatch.setattr(H, hook, raiser)
+    with pytest.raises(Seen):
+        HipEngine(DCGANConfig(), 4, torch.device("cpu"), dtype=dtype, dry_run=True, graph=False)
