@@ -129,6 +129,13 @@ struct NoiseSched {
   unsigned steps;
 };
 
+// DiffAugment on D's input (misc.hip d_augment_kernel): a policy bitmask over the two geometric
+// transforms. Sample n draws the 4 words of ONE Philox block, counter (n, step, AUG_STREAM), of the
+// step's z seed: (ty, tx, oy, ox), always all four; the mask selects which of them apply.
+enum AugPolicy : int { AUG_TRANSLATION = 1, AUG_CUTOUT = 2, AUG_ALL = 3 };
+constexpr unsigned long long AUG_STREAM = 2;
+constexpr int AUG_MAX_SIZE = 1 << 14;  // S: keeps every index of one image inside 32 bits
+
 // GAN objectives of the loss / head kernels (misc.hip gan_loss_block). The first three are the
 // ids of the launchers and bindings; GAN_BCE_T is the kernel instance of bce with a smoothed
 // real target, which the launchers pick themselves (real_target != 1).

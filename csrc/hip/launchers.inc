@@ -80,6 +80,12 @@ int DCG_API(dcg_philox_normal)(float* out, size_t n, uint64_t seed, const unsign
                                hipStream_t s);
 int DCG_API(dcg_noise_sigma)(const unsigned long long* steps, float* out, size_t n, const dcg::NoiseSched* sched,
                              hipStream_t s);
+// DiffAugment (translation / cutout, kernels.h AugPolicy) of x [N][S][S][C] into y, params int32 [N][4]
+// = (ty, tx, oy, ox). mode 0: drawn from the Philox stream (seed, *step, AUG_STREAM) and written to
+// params; 1: read from params; 2: the transposed gather (backward) of the rows in params.
+// -2: a null pointer, x == y, N < 1, S outside 1..2^14, C outside 1..4, an empty or unknown policy / mode
+int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy, int mode,
+                           uint64_t seed, const unsigned long long* step, hipStream_t s);
 int DCG_API(dcg_im2col_s2)(const elem_t* src, elem_t* dst, int B, int H, int W, int C, int Ho, int Wo, int pl_y, int pl_x,
                   int Kpad, hipStream_t s);
 int DCG_API(dcg_cast_to_bf16)(const void* src, int src_dtype, elem_t* dst, size_t n, float scale, float shift, hipStream_t s);

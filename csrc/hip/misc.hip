@@ -8,6 +8,7 @@
 //   * elem_t weight packing (natural + per-tap transposed / im2col-ordered copies)
 //   * Philox-4x32-10 z ~ U(-1,1) keyed by a device step counter (K19, graph-capturable)
 //   * instance noise on D's input: Philox normals (Box-Muller), sigma annealed from the step counter
+//   * DiffAugment on D's input: translation + cutout gathers (forward and transpose) from one Philox block per image
 //   * stride-2 TF-SAME im2col for 3-channel tensors, dtype casts
 #include <algorithm>
 #include <type_traits>
@@ -920,6 +921,97 @@ __global__ __launch_bounds__(256) void instance_noise_kernel(const E* __restrict
   }
 }
 
+// ---------------------------------------------------------------- DiffAugment on D's input
+// Translation + cutout of x [N][S][S][C] into y (a buffer of its own), per sample n from the 4 words
+// w0..w3 of the Philox block at counter (n, t = *step, AUG_STREAM) of the step's z seed:
+//   s = (S + 4) / 8, k = (S + 1) / 2, r = S + (1 - k % 2), mulhi(w, m) = (w * m) >> 32
+//   ty = mulhi(w0, 2s + 1) - s, tx = mulhi(w1, 2s + 1) - s, oy = mulhi(w2, r), ox = mulhi(w3, r)
+//   box(i, j) = oy - k/2 <= i < oy - k/2 + k and ox - k/2 <= j < ox - k/2 + k
+//   y[n,i,j,c] = +0 if box(i, j), else x[n,i+ty,j+tx,c] if that is inside the image, else +0
+// and its transpose (MODE 2): gx[n,p,q,c] = gy[n,p-ty,q-tx,c] if inside and not in the box, else +0.
+// Pure data movement on the element's bits (U = an unsigned integer of the element's size): a gather
+// either way, no arithmetic on values, so -0 and NaN payloads pass through.
+// A workgroup stays inside one image (bpi workgroups of 256 * V elements each per image), so the
+// draw is block-uniform. MODE 0 draws and the thread of an image's first element records (ty, tx,
+// oy, ox) in params[n]; MODE 1 (the probe) and MODE 2 read params[n] instead -- the backward cannot
+// drift from the forward and needs no ordering against the step counter's increment.
+// vec: one 16-byte store per thread over the row-flattened image (rows a multiple of 16 bytes and y
+// 16-byte aligned: a thread's V elements then share a row); else V element stores per thread,
+// strided by 256. Source loads are element loads (they sit tx * C elements off the output).
+template <typename U, int MODE>
+__global__ __launch_bounds__(256) void d_augment_kernel(const U* __restrict__ x, U* __restrict__ y,
+                                                        int* __restrict__ params, int S, int C, int policy,
+                                                        unsigned bpi, uint64_t seed,
+                                                        const unsigned long long* __restrict__ step, int vec) {
+  constexpr int V = 16 / (int)sizeof(U);
+  const unsigned n = blockIdx.x / bpi, chunk = blockIdx.x - n * bpi;
+  const int k = (S + 1) / 2;
+  int ty, tx, oy, ox;
+  if (MODE == 0) {
+    uint32_t w[4];
+    philox_block((size_t)n, seed, step[0], AUG_STREAM, w);
+    const int s = (S + 4) / 8;
+    const uint32_t r = (uint32_t)(S + (1 - k % 2));
+    ty = (int)__umulhi(w[0], 2u * s + 1u) - s;
+    tx = (int)__umulhi(w[1], 2u * s + 1u) - s;
+    oy = (int)__umulhi(w[2], r);
+    ox = (int)__umulhi(w[3], r);
+    if (chunk == 0 && threadIdx.x == 0) {
+      int* p = params + 4 * (size_t)n;
+      p[0] = ty; p[1] = tx; p[2] = oy; p[3] = ox;
+    }
+  } else {
+    // given rows: clamped to where they stop mattering (|shift| >= S empties the image, a box
+    // origin outside [-S, 2S] misses it), so the index arithmetic below cannot overflow
+    const int* p = params + 4 * (size_t)n;
+    ty = min(max(p[0], -S), S);
+    tx = min(max(p[1], -S), S);
+    oy = min(max(p[2], -S), 2 * S);
+    ox = min(max(p[3], -S), 2 * S);
+  }
+  if (!(policy & AUG_TRANSLATION)) ty = tx = 0;
+  const bool cut = (policy & AUG_CUTOUT) != 0;
+  const int by0 = oy - k / 2, bx0 = ox - k / 2;
+  const int sy = MODE == 2 ? -ty : ty, sx = MODE == 2 ? -tx : tx;
+  const unsigned RC = (unsigned)(S * C), HWC = (unsigned)S * RC;
+  const U* xi = x + (size_t)n * HWC;
+  U* yi = y + (size_t)n * HWC;
+  // output element (i, j, c): its source pixel, the box tested at the forward's output pixel
+  auto gather = [&](int i, int j, int c) -> U {
+    const int si = i + sy, sj = j + sx;
+    const int bi = MODE == 2 ? si : i, bj = MODE == 2 ? sj : j;
+    bool ok = (unsigned)si < (unsigned)S && (unsigned)sj < (unsigned)S;
+    if (cut && bi >= by0 && bi < by0 + k && bj >= bx0 && bj < bx0 + k) ok = false;
+    return ok ? xi[((unsigned)si * (unsigned)S + (unsigned)sj) * (unsigned)C + (unsigned)c] : (U)0;
+  };
+  if (vec) {
+    const unsigned e0 = (chunk * 256u + threadIdx.x) * V;
+    if (e0 >= HWC) return;
+    const int i = (int)(e0 / RC);
+    const unsigned re = e0 - (unsigned)i * RC;
+    int j = (int)(re / (unsigned)C), c = (int)(re - (unsigned)j * (unsigned)C);
+    typedef U UV __attribute__((ext_vector_type(V)));
+    UV v;
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      v[u] = gather(i, j, c);
+      if (++c == C) { c = 0; ++j; }
+    }
+    *reinterpret_cast<u32x4*>(yi + e0) = __builtin_bit_cast(u32x4, v);
+  } else {
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      const unsigned e = chunk * (256u * V) + (unsigned)u * 256u + threadIdx.x;
+      if (e < HWC) {
+        const int i = (int)(e / RC);
+        const unsigned re = e - (unsigned)i * RC;
+        const int j = (int)(re / (unsigned)C);
+        yi[e] = gather(i, j, (int)(re - (unsigned)j * (unsigned)C));
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- im2col (stride 2, TF SAME)
 // src elem_t [B][H][W][C] -> dst elem_t [B*Ho*Wo][Kpad], k = tap*C + c (tap = ky*5 + kx), zero pad.
 // One workgroup per IM_ROWS output rows of one image: the 2*IM_ROWS+3 input rows they read
@@ -1265,6 +1357,32 @@ extern "C" int DCG_API(dcg_instance_noise)(const elem_t* x, elem_t* y, size_t n,
   if (b > NOISE_MAX_BLOCKS) b = NOISE_MAX_BLOCKS;
   hipLaunchKernelGGL(instance_noise_kernel<elem_t>, dim3((unsigned)(b ? b : 1)), dim3(256), 0, s, x, y, n, seed, step,
                      stream_id, *sched);
+  return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy,
+                                      int mode, uint64_t seed, const unsigned long long* step, hipStream_t s) {
+  if (!x || !y || !params || x == y || (mode == 0 && !step)) return -2;
+  if (N < 1 || S < 1 || S > AUG_MAX_SIZE || C < 1 || C > 4 || policy < 1 || policy > AUG_ALL || mode < 0 || mode > 2)
+    return -2;
+  typedef std::conditional<sizeof(elem_t) == 2, uint16_t, uint32_t>::type U;
+  constexpr size_t V = 16 / sizeof(U);
+  const size_t hwc = (size_t)S * S * C;
+  const size_t bpi = (hwc + 256 * V - 1) / (256 * V);
+  if (bpi * (size_t)N > 0x7FFFFFFFull) return -2;
+  const int vec = ((size_t)S * C * sizeof(U)) % 16 == 0 && ((uintptr_t)y & 15) == 0;
+  const dim3 grid((unsigned)(bpi * (size_t)N)), block(256);
+  const U* xu = reinterpret_cast<const U*>(x);
+  U* yu = reinterpret_cast<U*>(y);
+  if (mode == 0)
+    hipLaunchKernelGGL((d_augment_kernel<U, 0>), grid, block, 0, s, xu, yu, params, S, C, policy, (unsigned)bpi, seed,
+                       step, vec);
+  else if (mode == 1)
+    hipLaunchKernelGGL((d_augment_kernel<U, 1>), grid, block, 0, s, xu, yu, params, S, C, policy, (unsigned)bpi, seed,
+                       step, vec);
+  else
+    hipLaunchKernelGGL((d_augment_kernel<U, 2>), grid, block, 0, s, xu, yu, params, S, C, policy, (unsigned)bpi, seed,
+                       step, vec);
   return (int)hipGetLastError();
 }
 

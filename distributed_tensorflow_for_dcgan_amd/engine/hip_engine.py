@@ -8,7 +8,9 @@ every step from C++ (eager, the default) or as hipGraphs:
                  batch [real | fake] with per-half BN statistics -> the 3 losses of the objective
                  (``gan_loss``: bce | lsgan | hinge) + both seeds, fused into the head GEMV; with
                  ``instance_noise`` one launch, ``d_noise``, between G and D writes the noisy copy
-                 of [real | fake] that D's layer 0 reads (forward here, weight gradient in progB)
+                 of [real | fake] that D's layer 0 reads (forward here, weight gradient in progB);
+                 with ``d_augment`` one launch before it, ``d_aug``, writes the translated / cut-out
+                 copy and its draws, and ``d_aug_bwd`` in the G chain takes the image gradient back
   progA[a_fwd:]  the g_loss chain back through D(fake) and G's data gradients  -- "G chain"
   progW          G's weight gradients, each tied to the progA position that produces its operand
   progB          D's backward of d_loss, both halves (D grads final)            -- "D chain"
@@ -163,7 +165,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
                  lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
                  instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
-                 instance_noise_steps: Optional[int] = None, **_):
+                 instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -201,6 +203,13 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # g_loss chain and G keep reading the clean fake. None: DCGAN_INSTANCE_NOISE / _END / _STEPS.
         # Off: no buffer, no op
         self.noise = R.resolve_instance_noise(instance_noise, instance_noise_end, instance_noise_steps)
+        # DiffAugment (ops.reference.DAugment): D sees augment([real | fake]), translation and / or cutout
+        # per sample, which one recorded launch (`d_aug`) draws from stream 2 of the step's z seed and the
+        # device step counter and writes, with its draws, behind G's RGB layer -- before the noise when
+        # both are on. Its Jacobian is not the identity: the g_loss chain's image gradient passes through
+        # the transposed gather (`d_aug_bwd`, from the recorded draws) before G's tanh backward, which
+        # therefore runs unfused. None: DCGAN_D_AUGMENT. Off: no buffer, no op
+        self.aug = R.resolve_d_augment(d_augment)
         # moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates = the
         # global step); 0 = off: no buffers, no op. None: DCGAN_G_EMA_DECAY (A/B of its cost)
         if g_ema_decay is None:
@@ -300,6 +309,10 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # step: each ends with its D chain (the last reader) joined back into the main stream, where
         # the next forward rewrites it (schedule_check proves it: tests/test_instance_noise.py)
         self.d_noisy = torch.zeros_like(self.d_in) if self.noise.active else None
+        # DiffAugment: the augmented copy (shared the same way), the draws int32 [2B][4] = (ty, tx, oy,
+        # ox) that `d_aug` records, and the image gradient taken back through the fake half's rows
+        self.d_auged = torch.zeros_like(self.d_in) if self.aug.active else None
+        self.aug_params = t(B2, 4, dtype=torch.int32, zero=True) if self.aug.active else None
         self.d_x, self.d_a = {}, {}
         for i, L in enumerate(self.dl):
             if L.bn:
@@ -327,6 +340,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.gc_dx = {L.name: t(B, L.out_hw, L.out_hw, L.cout) for L in self.dl}
         self.img_grad = t(B, s, s, cfg.c_dim)
         self.img_g = t(B, s, s, cfg.c_dim)
+        self.img_grad_t = t(B, s, s, cfg.c_dim) if self.aug.active else None
         Lg = self.gl[-1]
         self.kp_g = _kpad(cfg.c_dim)
         self.g_last_col = t(B * Lg.in_hw ** 2, self.kp_g)
@@ -611,9 +625,10 @@ class HipEngine(HipDDPMixin, HipEngineAux):
 
     def _img_dact(self) -> bool:
         """D layer 0's image gradient (g_loss chain) with G's tanh backward + bias gradient fused
-        (narrow.hip DACT): 16-bit, 64-channel D layer 0, <= 4 image channels."""
+        (narrow.hip DACT): 16-bit, 64-channel D layer 0, <= 4 image channels. Not under DiffAugment:
+        the image gradient is then taken at the augmented pixels, tanh' at the clean ones."""
         L = self.dl[0]
-        return not self.f32 and L.cin <= 4 and L.cout == 64 and self.gl[-1].cout == L.cin
+        return not self.aug.active and not self.f32 and L.cin <= 4 and L.cout == 64 and self.gl[-1].cout == L.cin
 
     def _g_out_direct(self) -> bool:
         """G's 1..4-channel output layer backward on narrow2.hip (nconv data gradient + nwgrad)."""
@@ -659,9 +674,13 @@ class HipEngine(HipDDPMixin, HipEngineAux):
 
     def _d_input(self, sub: Optional[int] = None, noise: bool = True) -> torch.Tensor:
         """What D's layer 0 reads (forward and weight gradient): [real | fake] of the full step or
-        of D sub-step `sub`, or its noisy copy under instance noise."""
+        of D sub-step `sub`, or its perturbed copy: the noisy one under instance noise (the noise of
+        the augmented copy when both are on), else the augmented one under DiffAugment. noise=False:
+        the clean input whatever is switched on."""
         if noise and self.noise.active:
             return self.d_noisy
+        if noise and self.aug.active:
+            return self.d_auged
         return self.d_in if sub is None else self.d_ins[sub]
 
     def noise_sigma(self) -> float:
@@ -673,8 +692,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                        sub: Optional[int] = None, noise: bool = True):
         """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's). sub = k: the forward
         of D sub-step k -- its z seed and its [real_k | fake] buffer, the same ops otherwise. noise:
-        with instance noise on, record `d_noise` and let D's layer 0 read the noisy copy (False: the
-        sample-time losses, which stay clean)."""
+        with DiffAugment / instance noise on, record `d_aug` / `d_noise` and let D's layer 0 read the
+        perturbed copy (False: the sample-time losses, which stay clean of both)."""
         cfg, B = self.cfg, self.B
         B2 = 2 * B
         Pg, Pd = self.model.g, self.model.d
@@ -721,11 +740,17 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                                         _p(self.g_a[Lp.name]), 0)
             else:  # last: + bias, tanh, written into the fake half of D's input
                 self._deconv_out(prog, L.name, a_prev, nat, fake, B, L, pad, Pg[L.name + "/biases"], TANH)
-        # D forward on [real | fake]; instance noise: on its noisy copy, written here -- behind the op
-        # that wrote the fake half, on the main stream -- from stream 1 of the step's z seed
+        # D forward on [real | fake]; DiffAugment / instance noise: on its augmented / noisy copy,
+        # written here -- behind the op that wrote the fake half, on the main stream -- from streams
+        # 2 / 1 of the step's z seed; the noise lands on the augmented copy when both are on
         prev = self._d_input(sub, noise)
-        if prev is not d_in:
-            prog.instance_noise("d_noise", _p(d_in), _p(prev), d_in.numel(), zseed, _p(self.step_counter),
+        clean = d_in
+        if noise and self.aug.active:
+            prog.d_augment("d_aug", _p(d_in), _p(self.d_auged), _p(self.aug_params), B2, cfg.output_size, cfg.c_dim,
+                           self.aug.mask, zseed, _p(self.step_counter), 0)
+            clean = self.d_auged
+        if prev is not clean:
+            prog.instance_noise("d_noise", _p(clean), _p(prev), d_in.numel(), zseed, _p(self.step_counter),
                                 R.NOISE_STREAM, self.noise.sigma0, self.noise.sigma1, self.noise.steps, 0)
         for i, L in enumerate(self.dl):
             w = Wd[L.name + "/w"]  # HWIO [5,5,ci,co] = [tap][K][N]
@@ -985,6 +1010,11 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                                L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, pad, NONE, 0.0, 0)
         else:
             self._igemm(prog, "g." + L.name + ".dgrad_img", H.GemmShape.dgrad(L, B), dx, nat, self.img_grad, pad)
+        if self.aug.active:
+            # DiffAugment: dL/d(augmented fake) -> dL/d(fake), the transposed gather over the draws the
+            # forward recorded for the fake half (rows B..2B-1 of aug_params)
+            prog.d_augment_bwd("d_aug_bwd", _p(self.img_grad), _p(self.img_grad_t), _p(self.aug_params[B:]), B,
+                               L.in_hw, L.cin, self.aug.mask, 0)
         self._build_g_backward(prog, progw)
 
     def _build_g_backward(self, prog, progw):
@@ -996,7 +1026,9 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         n = len(self.gl)
         Lg = self.gl[-1]
         if not self._img_dact():  # (else fused into the image-gradient kernel above)
-            self._act_bwd_dbias(prog, "g_out.tanh_bwd", self.img_grad, self.fake, self.img_g, B * Lg.out_hw ** 2,
+            # (DiffAugment: the gradient at the clean pixels, where tanh' is taken)
+            img_grad = self.img_grad_t if self.aug.active else self.img_grad
+            self._act_bwd_dbias(prog, "g_out.tanh_bwd", img_grad, self.fake, self.img_g, B * Lg.out_hw ** 2,
                                 Lg.cout, TANH, gG[Lg.name + "/biases"], "g")
 
         def below(j):  # what feeds G layer j: (activation, its gradient, pre-BN input, BN layer)

@@ -173,7 +173,8 @@ def check(cfg=None, batch_size: int = 8, dtype: str = "bf16", world: int = 1, sc
     """Build a dry-run engine on the CPU and check one schedule. Returns (schedule, hazards, ops).
     engine_kw: further HipEngine arguments (the learning-rate schedule's lr_decay, lr_decay_steps, ...:
     with one on, every Adam op reads the step counter that step_end / adam2 writes; instance_noise,
-    ...: the d_noise op reads that counter too and writes the buffer D's layer 0 reads on two streams)."""
+    ...: the d_noise op reads that counter too and writes the buffer D's layer 0 reads on two streams;
+    d_augment: so does d_aug, whose recorded draws d_aug_bwd reads on the g_loss chain)."""
     import torch
 
     from ..models.config import DCGANConfig

@@ -755,6 +755,75 @@ def instance_noise(x: torch.Tensor, y: torch.Tensor, seed: int, step: torch.Tens
     return y
 
 
+def _aug_mask(policy) -> int:
+    from . import reference as R
+    return policy if isinstance(policy, int) and not isinstance(policy, bool) else R.check_d_augment(policy).mask
+
+
+def _aug_images(op: str, x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    if x.dtype not in _ELEM_DT or x.dim() != 4 or x.shape[1] != x.shape[2]:
+        raise TypeError("%s: x must be [N, S, S, C] in bf16, fp16 or fp32" % op)
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    if out.dtype != x.dtype or out.shape != x.shape:
+        raise TypeError("%s: out must have x's shape and dtype" % op)
+    if not (x.is_contiguous() and out.is_contiguous()):
+        raise ValueError("%s: x and out must be contiguous" % op)
+    return out
+
+
+def augment_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.Tensor] = None,
+                 params_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """DiffAugment of x [N, S, S, C] as the training step runs it (d_augment_kernel): sample n draws
+    (ty, tx, oy, ox) from the Philox stream (seed, step, 2). Returns (y, params int32 [N, 4]); policy: a
+    DAugment, a policy list ("translation,cutout") or the kernels' bitmask. Oracle: ops.reference.augment
+    over ops.reference.augment_params."""
+    out = _aug_images("augment_draw", x, out)
+    if not torch.is_tensor(step):
+        v = int(step) & 0xFFFFFFFFFFFFFFFF  # (the counter's 64 bits as the int64 that holds them)
+        step = torch.tensor([v - (1 << 64) if v >> 63 else v], dtype=torch.int64, device=x.device)
+    _check_step("augment_draw", step)
+    N, S, C = x.shape[0], x.shape[1], x.shape[3]
+    if params_out is None:
+        params_out = torch.empty(N, 4, device=x.device, dtype=torch.int32)
+    if params_out.dtype != torch.int32 or tuple(params_out.shape) != (N, 4) or not params_out.is_contiguous():
+        raise TypeError("augment_draw: params_out must be a contiguous int32 [N, 4]")
+    prog = ext().Program(_ELEM_DT[x.dtype])
+    prog.d_augment("d_augment", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0, _p(params_out) if N else 0,
+                   N, S, C, _aug_mask(policy), int(seed), _p(step))
+    run(prog)
+    return out, params_out
+
+
+def augment_params(n: int, S: int, seed: int, step, device="cuda") -> torch.Tensor:
+    """int32 [n, 4] = (ty, tx, oy, ox) as d_augment_kernel draws them for n samples of an S x S image
+    from the Philox stream (seed, step, 2): the rows the kernel itself records, over a one-channel
+    dummy image (oracle: ops.reference.augment_params)."""
+    x = torch.zeros(int(n), int(S), int(S), 1, device=device, dtype=torch.bfloat16)
+    return augment_draw(x, seed, step, 3)[1]
+
+
+def augment_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool = False,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """DiffAugment of x [N, S, S, C] under given params [N, 4] = (ty, tx, oy, ox) (the kernel's probe
+    entry), or with transpose=True its transposed gather, the backward (d_augment_bwd). Oracles:
+    ops.reference.augment / augment_transpose."""
+    op = "augment_apply"
+    out = _aug_images(op, x, out)
+    N, S, C = x.shape[0], x.shape[1], x.shape[3]
+    if tuple(params.shape) != (N, 4) or params.dtype not in (torch.int32, torch.int64):
+        raise TypeError("%s: params must be an integer [N, 4]" % op)
+    p = params.to(device=x.device, dtype=torch.int32).contiguous()
+    prog = ext().Program(_ELEM_DT[x.dtype])
+    px, po, pp = (_p(x), _p(out), _p(p)) if x.numel() else (0, 0, 0)
+    if transpose:
+        prog.d_augment_bwd("d_augment_bwd", px, po, pp, N, S, C, _aug_mask(policy))
+    else:
+        prog.d_augment("d_augment", px, po, pp, N, S, C, _aug_mask(policy), 0, 0)
+    run(prog)
+    return out
+
+
 def adam_(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, powers: torch.Tensor, lr: float,
           beta1: float, beta2: float, eps: float, gscale: float = 1.0, advance_powers: bool = True,
           lr_sched=None, step: Optional[torch.Tensor] = None) -> None:

@@ -509,6 +509,121 @@ def instance_noise(shape, noise: InstanceNoise, seed: int, step: int, dtype=torc
     return (eps * sig).to(dtype).reshape(tuple(shape))
 
 
+# --------------------------------------------------------------------------- DiffAugment (D's input)
+AUG_STREAM = 2  # Philox stream of the augmentation draws (z: 0, instance noise: 1)
+AUG_POLICIES = ("translation", "cutout")  # bit i of the kernels' policy mask (kernels.h AugPolicy)
+
+
+class DAugment(NamedTuple):
+    """Differentiable augmentation of what D sees (Zhao et al. 2020), reals and fakes alike, G's
+    gradient passing through its transpose. Two geometric policies, as published for CIFAR-10:
+    translation by up to 1/8 of the image (zero fill) and a cutout of half the image's side."""
+    translation: bool = False
+    cutout: bool = False
+
+    @property
+    def active(self) -> bool:
+        return self.translation or self.cutout
+
+    @property
+    def mask(self) -> int:
+        """The kernels' policy bitmask."""
+        return int(self.translation) | int(self.cutout) << 1
+
+    def describe(self) -> str:
+        return ",".join(n for n, on in zip(AUG_POLICIES, self) if on) or "off"
+
+
+def check_d_augment(spec="") -> DAugment:
+    """Validated DAugment from a comma-separated policy list: "", "none", "translation", "cutout" or
+    both in any order. Anything else is a ValueError naming the offending token."""
+    if isinstance(spec, DAugment):
+        return DAugment(bool(spec.translation), bool(spec.cutout))
+    if spec is None:
+        spec = ""
+    if not isinstance(spec, str):
+        raise ValueError("d_augment must be a comma-separated list of %s, got %r" % (AUG_POLICIES, spec))
+    toks = [t.strip().lower() for t in spec.split(",")]
+    toks = [t for t in toks if t]
+    if toks == ["none"]:
+        toks = []
+    for t in toks:
+        if t not in AUG_POLICIES:
+            raise ValueError("d_augment: unknown policy %r (known: %s, or none)" % (t, ", ".join(AUG_POLICIES)))
+    return DAugment("translation" in toks, "cutout" in toks)
+
+
+def resolve_d_augment(spec=None) -> DAugment:
+    """check_d_augment over the engines' argument: None = the environment default DCGAN_D_AUGMENT,
+    then off. An explicit argument wins."""
+    import os
+    if spec is None:
+        spec = os.environ.get("DCGAN_D_AUGMENT") or ""
+    return check_d_augment(spec)
+
+
+def augment_params(n: int, S: int, seed: int, step: int) -> torch.Tensor:
+    """int64 [n, 4] = (ty, tx, oy, ox) of samples 0..n-1 of an S x S image: sample i takes the words
+    w0..w3 of the Philox block at counter (i, step, AUG_STREAM) under `seed`. With s = (S + 4) // 8,
+    k = (S + 1) // 2, r = S + (1 - k % 2) and mulhi(w, m) = (w * m) >> 32: ty, tx = mulhi(w0 | w1,
+    2s + 1) - s in [-s, s]; oy, ox = mulhi(w2 | w3, r) in [0, r). All four are always drawn."""
+    import numpy as np
+    S = int(S)
+    w = philox_words(4 * int(n), seed, step, AUG_STREAM).astype(np.uint64)[:int(n)]
+    s, k = (S + 4) // 8, (S + 1) // 2
+    r = S + (1 - k % 2)
+    out = np.empty((int(n), 4), dtype=np.int64)
+    sh = np.uint64(32)
+    out[:, 0] = ((w[:, 0] * np.uint64(2 * s + 1)) >> sh).astype(np.int64) - s
+    out[:, 1] = ((w[:, 1] * np.uint64(2 * s + 1)) >> sh).astype(np.int64) - s
+    out[:, 2] = ((w[:, 2] * np.uint64(r)) >> sh).astype(np.int64)
+    out[:, 3] = ((w[:, 3] * np.uint64(r)) >> sh).astype(np.int64)
+    return torch.from_numpy(out)
+
+
+def _augment_gather(x: torch.Tensor, params: torch.Tensor, aug: DAugment, transpose: bool) -> torch.Tensor:
+    if x.dim() != 4 or x.shape[1] != x.shape[2]:
+        raise ValueError("augment: x must be [N, S, S, C], got %s" % (tuple(x.shape),))
+    N, S = x.shape[0], x.shape[1]
+    p = torch.as_tensor(params, dtype=torch.int64).to(x.device)
+    if tuple(p.shape) != (N, 4):
+        raise ValueError("augment: params must be [N, 4] = (ty, tx, oy, ox), got %s" % (tuple(p.shape),))
+    zero = torch.zeros((), dtype=torch.int64, device=x.device)
+    ty, tx = (p[:, 0], p[:, 1]) if aug.translation else (zero.expand(N), zero.expand(N))
+    if transpose:
+        ty, tx = -ty, -tx
+    a = torch.arange(S, device=x.device)
+    si, sj = a[None, :] + ty[:, None], a[None, :] + tx[:, None]  # source row / column of each output one
+    keep = ((si >= 0) & (si < S))[:, :, None] & ((sj >= 0) & (sj < S))[:, None, :]
+    if aug.cutout:
+        k = (S + 1) // 2
+        by, bx = (si, sj) if transpose else (a[None, :].expand(N, S), a[None, :].expand(N, S))
+        y0, x0 = (p[:, 2] - k // 2)[:, None], (p[:, 3] - k // 2)[:, None]
+        box = ((by >= y0) & (by < y0 + k))[:, :, None] & ((bx >= x0) & (bx < x0 + k))[:, None, :]
+        keep = keep & ~box
+    g = x[torch.arange(N, device=x.device)[:, None, None], si.clamp(0, S - 1)[:, :, None],
+          sj.clamp(0, S - 1)[:, None, :]]
+    return torch.where(keep[..., None], g, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+def augment(x: torch.Tensor, params: torch.Tensor, aug: DAugment) -> torch.Tensor:
+    """The augmentation of x [N, S, S, C] (NHWC) under params [N, 4] = (ty, tx, oy, ox), k = (S + 1) // 2:
+
+        y[n,i,j,c] = +0                     if cutout and oy - k//2 <= i < oy - k//2 + k (and j, ox alike)
+                   = x[n, i+ty, j+tx, c]    if that pixel is inside the image (translation off: ty = tx = 0)
+                   = +0                     otherwise
+
+    the published rand_translation followed by rand_cutout for those draws. A gather and a
+    torch.where: values pass through bit for bit, every zero is +0, and autograd gives the backward."""
+    return _augment_gather(x, params, aug, False)
+
+
+def augment_transpose(g: torch.Tensor, params: torch.Tensor, aug: DAugment) -> torch.Tensor:
+    """The transpose of ``augment`` as a gather of its own: gx[n,p,q,c] = g[n, p-ty, q-tx, c] if that
+    index is inside the image and outside the box, else +0."""
+    return _augment_gather(g, params, aug, True)
+
+
 def zero_fraction(x: torch.Tensor) -> torch.Tensor:
     """tf.nn.zero_fraction (sparsity summary, distriubted_model.py:80)."""
     return (x == 0).float().mean()

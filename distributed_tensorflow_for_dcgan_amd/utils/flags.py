@@ -114,6 +114,10 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                                          "a constant sigma)"),
     ("instance_noise_steps", "int", 0, "length of the anneal in steps, 1..2^24; 0 = until the end of training "
                                        "(max_steps after the --epoch cap)"),
+    ("d_augment", "str", "", "differentiable augmentation (DiffAugment) of the discriminator's inputs, reals and "
+                                "fakes alike, G's gradient passing through it: a comma-separated list of "
+                                "translation (up to 1/8 of the image, zero fill) and cutout (half the image's "
+                                "side); empty or none turns it off"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -215,6 +219,11 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         check_instance_noise(ns.instance_noise, ns.instance_noise_end, ns.instance_noise_steps, open_ended=True)
     except (ValueError, TypeError, OverflowError) as e:
         parser.error("--instance_noise / --instance_noise_end / --instance_noise_steps: %s" % e)
+    from ..ops.reference import check_d_augment
+    try:
+        check_d_augment(ns.d_augment)
+    except ValueError as e:
+        parser.error("--d_augment: %s" % e)
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
