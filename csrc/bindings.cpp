@@ -1155,6 +1155,44 @@ class Program {
                                (const unsigned long long*)nullptr, s);
     }, AccList().r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes).v);
   }
+  // the checks the color ops share, in the style of aug_check: a rejected call throws before anything is recorded
+  void color_check(const char* op, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy) const {
+    const std::string o(op);
+    if (!x || !y || !params) throw std::runtime_error(o + ": the image buffers and params must be non-null");
+    if (x == y) throw std::runtime_error(o + ": the output must be a buffer of its own");
+    if (policy < 1 || policy > (int)COLOR_ALL)
+      throw std::runtime_error(o + ": policy must be a non-empty mask of brightness (1) | saturation (2) | contrast (4), got " +
+                               std::to_string(policy));
+    if (N < 1) throw std::runtime_error(o + ": N must be >= 1, got " + std::to_string(N));
+    if (S < 1 || S > AUG_MAX_SIZE) throw std::runtime_error(o + ": S must satisfy 1 <= S <= 2^14, got " + std::to_string(S));
+    if (C < 1 || C > 4) throw std::runtime_error(o + ": C must satisfy 1 <= C <= 4, got " + std::to_string(C));
+  }
+  // DiffAugment's color policy on D's input x [N][S][S][C] -> y (d_color_kernel), params float [N][4] = (b, s,
+  // c, Mx). step != 0: (b, s, c) come from the Philox stream (seed, *step, COLOR_STREAM): reads x and the
+  // 8-byte counter, writes y and params. step == 0 (the probe): reads x, reads (b, s, c) of and writes Mx to params
+  int d_color(std::string name, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy,
+              uint64_t seed, uintptr_t step, int stream) {
+    color_check("d_color", x, y, params, N, S, C, policy);
+    const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * 16;
+    const int mode = step ? 0 : 1;
+    AccList acc;
+    acc.r(x, bytes).w(y, bytes);
+    if (mode == 0) acc.r(step, 8).w(params, pbytes); else acc.r(params, pbytes).w(params, pbytes);
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_d_color)(P<const elem_t>(x), P<elem_t>(y), P<float>(params), N, S, C, policy, mode, seed,
+                             P<const unsigned long long>(step), s);
+    }, acc.v);
+  }
+  // its transpose: gy [N][S][S][C] -> gx under (s, c) of the recorded params rows; reads gy and params, writes gx
+  int d_color_bwd(std::string name, uintptr_t gy, uintptr_t gx, uintptr_t params, int N, int S, int C, int policy,
+                  int stream) {
+    color_check("d_color_bwd", gy, gx, params, N, S, C, policy);
+    const size_t bytes = (size_t)N * S * S * C * es_;
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_d_color)(P<const elem_t>(gy), P<elem_t>(gx), P<float>(params), N, S, C, policy, 2, 0,
+                             (const unsigned long long*)nullptr, s);
+    }, AccList().r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes).v);
+  }
   // fp32 standard normals of the Philox stream (seed, *step, stream_id) -> out float32[n]
   int philox_normal(std::string name, uintptr_t out, size_t n, uint64_t seed, uintptr_t step, uint64_t stream_id,
                     int stream) {
@@ -1413,6 +1451,11 @@ PYBIND11_MODULE(_dcgan_hip, m) {
            py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("seed"), py::arg("step"),
            py::arg("stream") = 0)
       .def("d_augment_bwd", &Program::d_augment_bwd, py::arg("name"), py::arg("gy"), py::arg("gx"), py::arg("params"),
+           py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("stream") = 0)
+      .def("d_color", &Program::d_color, py::arg("name"), py::arg("x"), py::arg("y"), py::arg("params"),
+           py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("seed"), py::arg("step"),
+           py::arg("stream") = 0)
+      .def("d_color_bwd", &Program::d_color_bwd, py::arg("name"), py::arg("gy"), py::arg("gx"), py::arg("params"),
            py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("stream") = 0)
       .def("philox_normal", &Program::philox_normal, py::arg("name"), py::arg("out"), py::arg("n"), py::arg("seed"),
            py::arg("step"), py::arg("stream_id"), py::arg("stream") = 0)

@@ -136,6 +136,12 @@ enum AugPolicy : int { AUG_TRANSLATION = 1, AUG_CUTOUT = 2, AUG_ALL = 3 };
 constexpr unsigned long long AUG_STREAM = 2;
 constexpr int AUG_MAX_SIZE = 1 << 14;  // S: keeps every index of one image inside 32 bits
 
+// DiffAugment's color policy on D's input (misc.hip d_color_kernel): a bitmask of its own over the three
+// pointwise transforms, applied in this order ahead of AugPolicy's. Sample n draws words w0..w2 of
+// ONE Philox block, counter (n, step, COLOR_STREAM), of the step's z seed: (b, s, c), always all three.
+enum ColorPolicy : int { COLOR_BRIGHTNESS = 1, COLOR_SATURATION = 2, COLOR_CONTRAST = 4, COLOR_ALL = 7 };
+constexpr unsigned long long COLOR_STREAM = 3;
+
 // GAN objectives of the loss / head kernels (misc.hip gan_loss_block). The first three are the
 // ids of the launchers and bindings; GAN_BCE_T is the kernel instance of bce with a smoothed
 // real target, which the launchers pick themselves (real_target != 1).

@@ -86,6 +86,13 @@ int DCG_API(dcg_noise_sigma)(const unsigned long long* steps, float* out, size_t
 // -2: a null pointer, x == y, N < 1, S outside 1..2^14, C outside 1..4, an empty or unknown policy / mode
 int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy, int mode,
                            uint64_t seed, const unsigned long long* step, hipStream_t s);
+// DiffAugment's color policy (brightness / saturation / contrast, kernels.h ColorPolicy) of x [N][S][S][C]
+// into y, params float [N][4] = (b, s, c, Mx). mode 0: (b, s, c) drawn from the Philox stream (seed, *step,
+// COLOR_STREAM), all four written; 1: (b, s, c) read from params, Mx written; 2: the transpose (backward)
+// under (s, c) of params, which it only reads.
+// -2: a null pointer, x == y, N < 1, S outside 1..2^14, C outside 1..4, an empty or unknown policy / mode
+int DCG_API(dcg_d_color)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy, int mode,
+                         uint64_t seed, const unsigned long long* step, hipStream_t s);
 int DCG_API(dcg_im2col_s2)(const elem_t* src, elem_t* dst, int B, int H, int W, int C, int Ho, int Wo, int pl_y, int pl_x,
                   int Kpad, hipStream_t s);
 int DCG_API(dcg_cast_to_bf16)(const void* src, int src_dtype, elem_t* dst, size_t n, float scale, float shift, hipStream_t s);

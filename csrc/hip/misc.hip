@@ -9,6 +9,7 @@
 //   * Philox-4x32-10 z ~ U(-1,1) keyed by a device step counter (K19, graph-capturable)
 //   * instance noise on D's input: Philox normals (Box-Muller), sigma annealed from the step counter
 //   * DiffAugment on D's input: translation + cutout gathers (forward and transpose) from one Philox block per image
+//   * DiffAugment's color policy: brightness, saturation, contrast about a per-image mean (forward and transpose)
 //   * stride-2 TF-SAME im2col for 3-channel tensors, dtype casts
 #include <algorithm>
 #include <type_traits>
@@ -1012,6 +1013,181 @@ __global__ __launch_bounds__(256) void d_augment_kernel(const U* __restrict__ x,
   }
 }
 
+// ---------------------------------------------------------------- DiffAugment's color policy on D's input
+// Brightness, saturation and contrast (kernels.h ColorPolicy) of x [N][S][S][C] into y, per sample n
+// from the words w0..w2 of the Philox block at counter (n, t = *step, COLOR_STREAM) of the step's z
+// seed: u_i = float(w_i >> 8) 2^-24, b = u0 - 0.5, s = 2 u1, c = u2 + 0.5. Per element, each operation
+// rounded on its own (contraction is off in these functions: numpy in fp32 is the bitwise oracle):
+//   brightness  v = v + b
+//   saturation  m = (v_0 + .. + v_{C-1}) / C over the pixel's channels;  v = s (v - m) + m
+//   contrast    M = Mx + b (Mx alone without brightness), Mx = sum(x[n]) / (S S C);  v = c (v - M) + M
+// Saturation keeps a pixel's channel mean, so M is the mean of the image after the first two stages
+// in exact arithmetic and one reduction over the input serves. MODE 0 draws and records params[n] =
+// (b, s, c, Mx); MODE 1 (the probe) reads (b, s, c) from params[n] and writes Mx back; MODE 2 is the
+// transpose over g = dL/dy: each stage is a symmetric map, so contrast about the gradient's own mean,
+// then saturation, with (s, c) of params[n]; it writes nothing to params.
+// One workgroup of 1024 threads per image: the draw and the mean are workgroup-uniform. A thread owns
+// whole pixels -- groups of V = 16 / sizeof(E) consecutive ones, C aligned 16-byte vectors, group g of
+// thread g % 1024 -- so the channel mean never leaves the thread. Pass 1 (contrast only): per-thread
+// fp32 partials in element order, summed across the wave by xor shuffles and across the 16 waves in
+// wave order through LDS: the order is a function of (S, C, E) alone, no atomics. Pass 2 applies the
+// map, to a thread's first group from registers and to further ones (S S > 1024 V) re-read. vec: S S
+// a multiple of V and both buffers 16-byte aligned; else the same groups by element accesses, the
+// same values in the same order. No index depends on params.
+constexpr int COLOR_THREADS = 1024;
+
+template <int C>
+__device__ __forceinline__ void color_saturate(float* v, float s) {
+#pragma clang fp contract(off)
+  float m = v[0];
+#pragma unroll
+  for (int ch = 1; ch < C; ++ch) m = m + v[ch];
+  m = m / (float)C;
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) {
+    const float d = v[ch] - m;
+    const float q = s * d;
+    v[ch] = q + m;
+  }
+}
+
+__device__ __forceinline__ float color_contrast(float v, float c, float M) {
+#pragma clang fp contract(off)
+  const float d = v - M;
+  const float q = c * d;
+  return q + M;
+}
+
+// the sum of one value per thread over the workgroup, the same in every thread
+__device__ __forceinline__ float color_block_sum(float acc, float* wsum) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc = acc + __shfl_xor(acc, off);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  float t = wsum[0];
+#pragma unroll
+  for (int w = 1; w < COLOR_THREADS / 64; ++w) t = t + wsum[w];
+  return t;
+}
+
+template <typename E, int MODE, int C>
+__global__ __launch_bounds__(COLOR_THREADS) void d_color_kernel(const E* __restrict__ x, E* __restrict__ y,
+                                                                float* __restrict__ params, int S, int policy,
+                                                                uint64_t seed,
+                                                                const unsigned long long* __restrict__ step, int vec) {
+#pragma clang fp contract(off)
+  constexpr int V = 16 / (int)sizeof(E);
+  constexpr int GE = V * C;  // elements of a group
+  typedef E EV __attribute__((ext_vector_type(V)));
+  __shared__ float wsum[COLOR_THREADS / 64];
+  const unsigned n = blockIdx.x, tid = threadIdx.x;
+  const unsigned HW = (unsigned)S * (unsigned)S, HWC = HW * (unsigned)C;  // S <= 2^14, C <= 4: < 2^31
+  const unsigned G = (HW + V - 1) / V;
+  const E* xi = x + (size_t)n * HWC;
+  E* yi = y + (size_t)n * HWC;
+  float* p = params + 4 * (size_t)n;
+  float b, s, c;
+  if (MODE == 0) {
+    uint32_t w[4];
+    philox_block((size_t)n, seed, step[0], COLOR_STREAM, w);
+    const float u0 = (float)(w[0] >> 8) * (1.0f / 16777216.0f);
+    const float u1 = (float)(w[1] >> 8) * (1.0f / 16777216.0f);
+    const float u2 = (float)(w[2] >> 8) * (1.0f / 16777216.0f);
+    b = u0 - 0.5f;
+    s = 2.f * u1;
+    c = u2 + 0.5f;
+  } else {
+    b = p[0]; s = p[1]; c = p[2];
+  }
+  const bool bri = MODE != 2 && (policy & COLOR_BRIGHTNESS) != 0;
+  const bool sat = (policy & COLOR_SATURATION) != 0, con = (policy & COLOR_CONTRAST) != 0;
+
+  auto load = [&](unsigned g, float (&v)[GE]) {
+    const unsigned e0 = g * GE;
+    if (vec) {
+#pragma unroll
+      for (int k = 0; k < C; ++k) {
+        const EV ev = __builtin_bit_cast(EV, *reinterpret_cast<const u32x4*>(xi + e0 + k * V));
+#pragma unroll
+        for (int u = 0; u < V; ++u) v[k * V + u] = (float)ev[u];
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < GE; ++u) v[u] = e0 + u < HWC ? (float)xi[e0 + u] : 0.f;
+    }
+  };
+
+  float keep[GE];  // the thread's first group: read once
+#pragma unroll
+  for (int u = 0; u < GE; ++u) keep[u] = 0.f;
+  if (tid < G) load(tid, keep);
+
+  float Mx = 0.f;
+  if (con) {  // pass 1 (workgroup-uniform branch)
+    float acc = 0.f;
+#pragma unroll
+    for (int u = 0; u < GE; ++u) acc = acc + keep[u];
+    for (unsigned g = tid + COLOR_THREADS; g < G; g += COLOR_THREADS) {
+      float v[GE];
+      load(g, v);
+#pragma unroll
+      for (int u = 0; u < GE; ++u) acc = acc + v[u];
+    }
+    Mx = color_block_sum(acc, wsum) / (float)HWC;
+  }
+  if (MODE != 2 && tid == 0) {
+    if (MODE == 0) { p[0] = b; p[1] = s; p[2] = c; }
+    p[3] = Mx;
+  }
+  const float M = bri ? Mx + b : Mx;
+
+  auto apply_store = [&](unsigned g, float (&v)[GE]) {
+#pragma unroll
+    for (int px = 0; px < V; ++px) {
+      float* pv = v + px * C;
+      if (MODE == 2) {
+        if (con) {
+#pragma unroll
+          for (int ch = 0; ch < C; ++ch) pv[ch] = color_contrast(pv[ch], c, M);
+        }
+        if (sat) color_saturate<C>(pv, s);
+      } else {
+        if (bri) {
+#pragma unroll
+          for (int ch = 0; ch < C; ++ch) pv[ch] = pv[ch] + b;
+        }
+        if (sat) color_saturate<C>(pv, s);
+        if (con) {
+#pragma unroll
+          for (int ch = 0; ch < C; ++ch) pv[ch] = color_contrast(pv[ch], c, M);
+        }
+      }
+    }
+    const unsigned e0 = g * GE;
+    if (vec) {
+#pragma unroll
+      for (int k = 0; k < C; ++k) {
+        EV ev;
+#pragma unroll
+        for (int u = 0; u < V; ++u) ev[u] = (E)v[k * V + u];
+        *reinterpret_cast<u32x4*>(yi + e0 + k * V) = __builtin_bit_cast(u32x4, ev);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < GE; ++u)
+        if (e0 + u < HWC) yi[e0 + u] = (E)v[u];
+    }
+  };
+
+  if (tid < G) apply_store(tid, keep);
+  for (unsigned g = tid + COLOR_THREADS; g < G; g += COLOR_THREADS) {  // pass 2 beyond the registers
+    float v[GE];
+    load(g, v);
+    apply_store(g, v);
+  }
+}
+
 // ---------------------------------------------------------------- im2col (stride 2, TF SAME)
 // src elem_t [B][H][W][C] -> dst elem_t [B*Ho*Wo][Kpad], k = tap*C + c (tap = ky*5 + kx), zero pad.
 // One workgroup per IM_ROWS output rows of one image: the 2*IM_ROWS+3 input rows they read
@@ -1383,6 +1559,37 @@ extern "C" int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, i
   else
     hipLaunchKernelGGL((d_augment_kernel<U, 2>), grid, block, 0, s, xu, yu, params, S, C, policy, (unsigned)bpi, seed,
                        step, vec);
+  return (int)hipGetLastError();
+}
+
+template <int MODE, int C>
+static void d_color_launch(const elem_t* x, elem_t* y, float* params, int N, int S, int policy, uint64_t seed,
+                           const unsigned long long* step, int vec, hipStream_t s) {
+  hipLaunchKernelGGL((d_color_kernel<elem_t, MODE, C>), dim3((unsigned)N), dim3(COLOR_THREADS), 0, s, x, y, params, S,
+                     policy, seed, step, vec);
+}
+
+template <int MODE>
+static void d_color_launch_c(int C, const elem_t* x, elem_t* y, float* params, int N, int S, int policy, uint64_t seed,
+                             const unsigned long long* step, int vec, hipStream_t s) {
+  switch (C) {
+    case 1: d_color_launch<MODE, 1>(x, y, params, N, S, policy, seed, step, vec, s); break;
+    case 2: d_color_launch<MODE, 2>(x, y, params, N, S, policy, seed, step, vec, s); break;
+    case 3: d_color_launch<MODE, 3>(x, y, params, N, S, policy, seed, step, vec, s); break;
+    default: d_color_launch<MODE, 4>(x, y, params, N, S, policy, seed, step, vec, s); break;
+  }
+}
+
+extern "C" int DCG_API(dcg_d_color)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy,
+                                    int mode, uint64_t seed, const unsigned long long* step, hipStream_t s) {
+  if (!x || !y || !params || x == y || (mode == 0 && !step)) return -2;
+  if (N < 1 || S < 1 || S > AUG_MAX_SIZE || C < 1 || C > 4 || policy < 1 || policy > COLOR_ALL || mode < 0 || mode > 2)
+    return -2;
+  constexpr size_t V = 16 / sizeof(elem_t);
+  const int vec = ((size_t)S * S) % V == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+  if (mode == 0) d_color_launch_c<0>(C, x, y, params, N, S, policy, seed, step, vec, s);
+  else if (mode == 1) d_color_launch_c<1>(C, x, y, params, N, S, policy, seed, step, vec, s);
+  else d_color_launch_c<2>(C, x, y, params, N, S, policy, seed, step, vec, s);
   return (int)hipGetLastError();
 }
 

@@ -10,7 +10,9 @@ every step from C++ (eager, the default) or as hipGraphs:
                  ``instance_noise`` one launch, ``d_noise``, between G and D writes the noisy copy
                  of [real | fake] that D's layer 0 reads (forward here, weight gradient in progB);
                  with ``d_augment`` one launch before it, ``d_aug``, writes the translated / cut-out
-                 copy and its draws, and ``d_aug_bwd`` in the G chain takes the image gradient back
+                 copy and its draws, and ``d_aug_bwd`` in the G chain takes the image gradient back;
+                 with ``d_color_augment`` one launch before that, ``d_color``, writes the brightness /
+                 saturation / contrast copy, and ``d_color_bwd`` follows ``d_aug_bwd`` in the G chain
   progA[a_fwd:]  the g_loss chain back through D(fake) and G's data gradients  -- "G chain"
   progW          G's weight gradients, each tied to the progA position that produces its operand
   progB          D's backward of d_loss, both halves (D grads final)            -- "D chain"
@@ -165,7 +167,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
                  lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
                  instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
-                 instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None, **_):
+                 instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
+                 d_color_augment: Optional[str] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -210,6 +213,13 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # the transposed gather (`d_aug_bwd`, from the recorded draws) before G's tanh backward, which
         # therefore runs unfused. None: DCGAN_D_AUGMENT. Off: no buffer, no op
         self.aug = R.resolve_d_augment(d_augment)
+        # DiffAugment's color policy (ops.reference.DColor), a switch of its own: D sees noise(geometric(
+        # color([real | fake]))), the published order. One recorded launch (`d_color`) ahead of `d_aug`
+        # draws (b, s, c) per sample from stream 3 of the step's z seed and the device step counter and
+        # writes the colored copy with (b, s, c, Mx); its Jacobian is a dense linear map per image, which
+        # `d_color_bwd` applies transposed to the g_loss chain's image gradient, behind `d_aug_bwd` and
+        # ahead of G's tanh backward. None: DCGAN_D_COLOR_AUGMENT. Off: no buffer, no op
+        self.color = R.resolve_d_color(d_color_augment)
         # moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates = the
         # global step); 0 = off: no buffers, no op. None: DCGAN_G_EMA_DECAY (A/B of its cost)
         if g_ema_decay is None:
@@ -313,6 +323,9 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # ox) that `d_aug` records, and the image gradient taken back through the fake half's rows
         self.d_auged = torch.zeros_like(self.d_in) if self.aug.active else None
         self.aug_params = t(B2, 4, dtype=torch.int32, zero=True) if self.aug.active else None
+        # the color policy: the colored copy (shared the same way) and float32 [2B][4] = (b, s, c, Mx)
+        self.d_colored = torch.zeros_like(self.d_in) if self.color.active else None
+        self.color_params = t(B2, 4, dtype=torch.float32, zero=True) if self.color.active else None
         self.d_x, self.d_a = {}, {}
         for i, L in enumerate(self.dl):
             if L.bn:
@@ -341,6 +354,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.img_grad = t(B, s, s, cfg.c_dim)
         self.img_g = t(B, s, s, cfg.c_dim)
         self.img_grad_t = t(B, s, s, cfg.c_dim) if self.aug.active else None
+        self.img_grad_c = t(B, s, s, cfg.c_dim) if self.color.active else None  # ... and back through the color map
         Lg = self.gl[-1]
         self.kp_g = _kpad(cfg.c_dim)
         self.g_last_col = t(B * Lg.in_hw ** 2, self.kp_g)
@@ -625,10 +639,10 @@ class HipEngine(HipDDPMixin, HipEngineAux):
 
     def _img_dact(self) -> bool:
         """D layer 0's image gradient (g_loss chain) with G's tanh backward + bias gradient fused
-        (narrow.hip DACT): 16-bit, 64-channel D layer 0, <= 4 image channels. Not under DiffAugment:
-        the image gradient is then taken at the augmented pixels, tanh' at the clean ones."""
+        (narrow.hip DACT): 16-bit, 64-channel D layer 0, <= 4 image channels. Not under DiffAugment
+        (either switch): the image gradient is then taken at the augmented pixels, tanh' at the clean ones."""
         L = self.dl[0]
-        return not self.aug.active and not self.f32 and L.cin <= 4 and L.cout == 64 and self.gl[-1].cout == L.cin
+        return not self.aug.active and not self.color.active and not self.f32 and L.cin <= 4 and L.cout == 64 and self.gl[-1].cout == L.cin
 
     def _g_out_direct(self) -> bool:
         """G's 1..4-channel output layer backward on narrow2.hip (nconv data gradient + nwgrad)."""
@@ -675,12 +689,15 @@ class HipEngine(HipDDPMixin, HipEngineAux):
     def _d_input(self, sub: Optional[int] = None, noise: bool = True) -> torch.Tensor:
         """What D's layer 0 reads (forward and weight gradient): [real | fake] of the full step or
         of D sub-step `sub`, or its perturbed copy: the noisy one under instance noise (the noise of
-        the augmented copy when both are on), else the augmented one under DiffAugment. noise=False:
-        the clean input whatever is switched on."""
+        the augmented copy when both are on), else the augmented one under DiffAugment, else the colored
+        one under its color policy (each stage reads the one before it). noise=False: the clean input
+        whatever is switched on."""
         if noise and self.noise.active:
             return self.d_noisy
         if noise and self.aug.active:
             return self.d_auged
+        if noise and self.color.active:
+            return self.d_colored
         return self.d_in if sub is None else self.d_ins[sub]
 
     def noise_sigma(self) -> float:
@@ -742,11 +759,16 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                 self._deconv_out(prog, L.name, a_prev, nat, fake, B, L, pad, Pg[L.name + "/biases"], TANH)
         # D forward on [real | fake]; DiffAugment / instance noise: on its augmented / noisy copy,
         # written here -- behind the op that wrote the fake half, on the main stream -- from streams
-        # 2 / 1 of the step's z seed; the noise lands on the augmented copy when both are on
+        # 2 / 1 of the step's z seed; the noise lands on the augmented copy when both are on. The color
+        # policy (stream 3) comes first: color, then translation / cutout, then noise
         prev = self._d_input(sub, noise)
         clean = d_in
+        if noise and self.color.active:
+            prog.d_color("d_color", _p(d_in), _p(self.d_colored), _p(self.color_params), B2, cfg.output_size,
+                         cfg.c_dim, self.color.mask, zseed, _p(self.step_counter), 0)
+            clean = self.d_colored
         if noise and self.aug.active:
-            prog.d_augment("d_aug", _p(d_in), _p(self.d_auged), _p(self.aug_params), B2, cfg.output_size, cfg.c_dim,
+            prog.d_augment("d_aug", _p(clean), _p(self.d_auged), _p(self.aug_params), B2, cfg.output_size, cfg.c_dim,
                            self.aug.mask, zseed, _p(self.step_counter), 0)
             clean = self.d_auged
         if prev is not clean:
@@ -1015,6 +1037,11 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             # forward recorded for the fake half (rows B..2B-1 of aug_params)
             prog.d_augment_bwd("d_aug_bwd", _p(self.img_grad), _p(self.img_grad_t), _p(self.aug_params[B:]), B,
                                L.in_hw, L.cin, self.aug.mask, 0)
+        if self.color.active:
+            # the color policy: dL/d(colored fake) -> dL/d(fake), its transposed map under (s, c) of the rows
+            # the forward recorded for the fake half
+            prog.d_color_bwd("d_color_bwd", _p(self.img_grad_t if self.aug.active else self.img_grad),
+                             _p(self.img_grad_c), _p(self.color_params[B:]), B, L.in_hw, L.cin, self.color.mask, 0)
         self._build_g_backward(prog, progw)
 
     def _build_g_backward(self, prog, progw):
@@ -1027,7 +1054,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         Lg = self.gl[-1]
         if not self._img_dact():  # (else fused into the image-gradient kernel above)
             # (DiffAugment: the gradient at the clean pixels, where tanh' is taken)
-            img_grad = self.img_grad_t if self.aug.active else self.img_grad
+            img_grad = self.img_grad_c if self.color.active else self.img_grad_t if self.aug.active else self.img_grad
             self._act_bwd_dbias(prog, "g_out.tanh_bwd", img_grad, self.fake, self.img_g, B * Lg.out_hw ** 2,
                                 Lg.cout, TANH, gG[Lg.name + "/biases"], "g")
 

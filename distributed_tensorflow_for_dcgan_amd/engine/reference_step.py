@@ -27,12 +27,15 @@ class ReferenceStep:
                  d_steps: int = 1, beta2: float = R.ADAM_BETA2, lr_d: Optional[float] = None,
                  lr_g: Optional[float] = None, lr_decay="none", lr_decay_start: int = 0, lr_decay_steps: int = 0,
                  lr_end: float = 0.0, lr_warmup: int = 0, instance_noise=0.0, instance_noise_end: float = 0.0,
-                 instance_noise_steps: int = 0, noise_seed: int = 0, d_augment=""):
+                 instance_noise_steps: int = 0, noise_seed: int = 0, d_augment="", d_color_augment=""):
         self.model = model
         # DiffAugment (ops.reference.DAugment): D sees augment([real | fake]) -- translation and / or
         # cutout, drawn per sample from Philox stream 2 of `noise_seed` at the global step (D sub-step
         # k: substep_seed(noise_seed, k)) -- before the additive noise; G's gradient flows through it
         self.aug = R.check_d_augment(d_augment)
+        # its color policy (ops.reference.DColor), ahead of translation / cutout: brightness, saturation,
+        # contrast per sample, (b, s, c) from Philox stream 3 of the same seed at the global step
+        self.color = R.check_d_color(d_color_augment)
         # instance noise (ops.reference.InstanceNoise): D sees [real | fake] + sigma(t) * eps, eps from
         # Philox stream 1 of `noise_seed` (the HIP engine's z seed) at the global step; D sub-step k
         # draws from ops.reference.substep_seed(noise_seed, k). G's gradient flows through it unchanged
@@ -88,13 +91,22 @@ class ReferenceStep:
             return None
         return R.augment_params(shape[0], shape[1], R.substep_seed(self.noise_seed, sub), self.global_step)
 
+    def draw_color(self, shape, sub: Optional[int] = None) -> Optional[torch.Tensor]:
+        """The color policy's params float32 [2B, 3] = (b, s, c) over a [2B, S, S, C] input at the current
+        global step: the full step's (sub None) or D sub-step `sub`'s; None when it is off."""
+        if not self.color.active:
+            return None
+        return R.color_params(shape[0], R.substep_seed(self.noise_seed, sub), self.global_step)
+
     def forward_losses(self, real: torch.Tensor, z: torch.Tensor, Pg=None, Pd=None, update_ema=True,
-                       record=None, update_ema_g=None, noise=None, sub: Optional[int] = None, augment=None):
+                       record=None, update_ema_g=None, noise=None, sub: Optional[int] = None, augment=None,
+                       color=None):
         """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's). noise: the additive
         sigma * eps on D's input [2B, ...]; None = drawn (``draw_noise``, `sub` = the D sub-step) when
         instance noise is on; False = none (sample-time losses stay clean). augment: the params [2B, 4]
         of DiffAugment, applied before the noise; None = drawn (``draw_augment``) when it is on; False =
-        none."""
+        none. color: the params [2B, 3 or 4] of the color policy, applied before `augment`; None = drawn
+        (``draw_color``) when it is on; False = none."""
         m = self.model
         if self.d_spectral_norm:  # D computes with W / sigma(W); autograd projects the gradient
             Pd = m.d_sn_weights(Pd)
@@ -102,6 +114,10 @@ class ReferenceStep:
                            record=record)
         B = real.shape[0]
         both = torch.cat([real, fake], 0)
+        if color is None:
+            color = self.draw_color(both.shape, sub)
+        if color is not None and color is not False:
+            both = R.color_augment(both, color, self.color)
         if augment is None:
             augment = self.draw_augment(both.shape, sub)
         if augment is not None and augment is not False:
@@ -117,12 +133,13 @@ class ReferenceStep:
         return {"fake": fake, "logits_real": lr_, "logits_fake": lf, "d_loss_real": d_real,
                 "d_loss_fake": d_fake, "g_loss": g_loss, "d_loss": d_loss}
 
-    def compute_grads(self, real: torch.Tensor, z: torch.Tensor, update_ema: bool = True, noise=None, augment=None):
+    def compute_grads(self, real: torch.Tensor, z: torch.Tensor, update_ema: bool = True, noise=None, augment=None,
+                      color=None):
         """Returns (losses dict, flat D grads, flat G grads) without applying them."""
         m = self.model
         Pg = {k: v.detach().clone().requires_grad_(True) for k, v in m.g.tensors.items()}
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
-        out = self.forward_losses(real, z, Pg, Pd, update_ema=update_ema, noise=noise, augment=augment)
+        out = self.forward_losses(real, z, Pg, Pd, update_ema=update_ema, noise=noise, augment=augment, color=color)
         d_names, g_names = m.d.names(), m.g.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], retain_graph=True,
                                  allow_unused=True)
@@ -138,13 +155,13 @@ class ReferenceStep:
         return out, gd_flat.flat, gg_flat.flat
 
     def compute_d_grads(self, real: torch.Tensor, z: torch.Tensor, noise=None, sub: Optional[int] = None,
-                        augment=None):
+                        augment=None, color=None):
         """(losses dict, flat D grads) of a D sub-step: G's forward in training mode on batch
         statistics with its BN moving averages left alone, only d_loss differentiated, through D."""
         m = self.model
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
         out = self.forward_losses(real, z, None, Pd, update_ema=True, update_ema_g=False, noise=noise,
-                                  sub=self._sub_k if sub is None else sub, augment=augment)
+                                  sub=self._sub_k if sub is None else sub, augment=augment, color=color)
         d_names = m.d.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], allow_unused=True)
         gd_flat = m.d.like()
@@ -154,12 +171,12 @@ class ReferenceStep:
         return out, gd_flat.flat
 
     def d_step(self, real: torch.Tensor, z: torch.Tensor, noise=None, sub: Optional[int] = None,
-               augment=None) -> Dict[str, float]:
+               augment=None, color=None) -> Dict[str, float]:
         """One D sub-step: a fresh z through G, D on [real | fake], the d_loss backward through D,
         TF-Adam(D) (D's beta powers advance) and the power step. Nothing of G changes -- parameters,
         Adam slots and powers, BN moving averages, weight EMA -- nor does the global step; D's BN
         moving averages (both slots) update as in a full step."""
-        out, gd = self.compute_d_grads(real, z, noise=noise, sub=sub, augment=augment)
+        out, gd = self.compute_d_grads(real, z, noise=noise, sub=sub, augment=augment, color=color)
         self._sub_k += 1
         for s in range(2):
             self.model.d_bn.count_step(s)
@@ -171,8 +188,8 @@ class ReferenceStep:
         self.last = out
         return {k: float(out[k].detach()) for k in ("d_loss_real", "d_loss_fake", "g_loss", "d_loss")}
 
-    def step(self, real: torch.Tensor, z: torch.Tensor, noise=None, augment=None) -> Dict[str, float]:
-        out, gd, gg = self.compute_grads(real, z, noise=noise, augment=augment)
+    def step(self, real: torch.Tensor, z: torch.Tensor, noise=None, augment=None, color=None) -> Dict[str, float]:
+        out, gd, gg = self.compute_grads(real, z, noise=noise, augment=augment, color=color)
         self._sub_k = 0
         for s in range(2):  # one EMA update per BN slot per step (as the HIP engine counts)
             self.model.d_bn.count_step(s)

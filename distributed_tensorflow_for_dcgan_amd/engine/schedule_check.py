@@ -174,7 +174,8 @@ def check(cfg=None, batch_size: int = 8, dtype: str = "bf16", world: int = 1, sc
     engine_kw: further HipEngine arguments (the learning-rate schedule's lr_decay, lr_decay_steps, ...:
     with one on, every Adam op reads the step counter that step_end / adam2 writes; instance_noise,
     ...: the d_noise op reads that counter too and writes the buffer D's layer 0 reads on two streams;
-    d_augment: so does d_aug, whose recorded draws d_aug_bwd reads on the g_loss chain)."""
+    d_augment: so does d_aug, whose recorded draws d_aug_bwd reads on the g_loss chain;
+    d_color_augment: and d_color ahead of it, whose recorded (s, c) d_color_bwd reads behind d_aug_bwd)."""
     import torch
 
     from ..models.config import DCGANConfig

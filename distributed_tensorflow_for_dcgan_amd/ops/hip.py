@@ -824,6 +824,69 @@ def augment_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool
     return out
 
 
+def _color_mask(policy) -> int:
+    from . import reference as R
+    return policy if isinstance(policy, int) and not isinstance(policy, bool) else R.check_d_color(policy).mask
+
+
+def color_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.Tensor] = None,
+               params_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """DiffAugment's color policy over x [N, S, S, C] as the training step runs it (d_color_kernel): sample
+    n draws (b, s, c) from the Philox stream (seed, step, 3). Returns (y, params float32 [N, 4] = (b, s, c,
+    Mx)); policy: a DColor, a policy list ("brightness,saturation,contrast") or the kernels' bitmask.
+    Oracle: ops.reference.color_augment over ops.reference.color_params."""
+    out = _aug_images("color_draw", x, out)
+    if not torch.is_tensor(step):
+        v = int(step) & 0xFFFFFFFFFFFFFFFF  # (the counter's 64 bits as the int64 that holds them)
+        step = torch.tensor([v - (1 << 64) if v >> 63 else v], dtype=torch.int64, device=x.device)
+    _check_step("color_draw", step)
+    N, S, C = x.shape[0], x.shape[1], x.shape[3]
+    if params_out is None:
+        params_out = torch.empty(N, 4, device=x.device, dtype=torch.float32)
+    if params_out.dtype != torch.float32 or tuple(params_out.shape) != (N, 4) or not params_out.is_contiguous():
+        raise TypeError("color_draw: params_out must be a contiguous float32 [N, 4]")
+    prog = ext().Program(_ELEM_DT[x.dtype])
+    prog.d_color("d_color", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0, _p(params_out) if N else 0,
+                 N, S, C, _color_mask(policy), int(seed), _p(step))
+    run(prog)
+    return out, params_out
+
+
+def color_params(n: int, seed: int, step, device="cuda") -> torch.Tensor:
+    """float32 [n, 4] = (b, s, c, Mx) as d_color_kernel draws them for n samples from the Philox stream
+    (seed, step, 3): the rows the kernel itself records, over a one-pixel dummy image of zeros (Mx = 0;
+    oracle of the first three columns: ops.reference.color_params)."""
+    x = torch.zeros(int(n), 1, 1, 1, device=device, dtype=torch.bfloat16)
+    return color_draw(x, seed, step, 7)[1]
+
+
+def color_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool = False,
+                out: Optional[torch.Tensor] = None, params_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The color policy over x [N, S, S, C] under given params [N, 3 or 4] = (b, s, c[, Mx]) (the kernel's
+    probe entry: it computes Mx itself and leaves it in column 3 of params_out, a float32 [N, 4], when
+    one is given), or with transpose=True its transpose, the backward (d_color_bwd). Oracles:
+    ops.reference.color_augment / color_augment_transpose."""
+    op = "color_apply"
+    out = _aug_images(op, x, out)
+    N, S, C = x.shape[0], x.shape[1], x.shape[3]
+    if params.dim() != 2 or params.shape[0] != N or params.shape[1] not in (3, 4) or not params.is_floating_point():
+        raise TypeError("%s: params must be a floating-point [N, 3] or [N, 4]" % op)
+    p = params_out
+    if p is None:
+        p = torch.zeros(N, 4, device=x.device, dtype=torch.float32)
+    if p.dtype != torch.float32 or tuple(p.shape) != (N, 4) or not p.is_contiguous() or p.device != x.device:
+        raise TypeError("%s: params_out must be a contiguous float32 [N, 4] on x's device" % op)
+    p[:, :3] = params[:, :3].to(device=x.device, dtype=torch.float32)
+    prog = ext().Program(_ELEM_DT[x.dtype])
+    px, po, pp = (_p(x), _p(out), _p(p)) if x.numel() else (0, 0, 0)
+    if transpose:
+        prog.d_color_bwd("d_color_bwd", px, po, pp, N, S, C, _color_mask(policy))
+    else:
+        prog.d_color("d_color", px, po, pp, N, S, C, _color_mask(policy), 0, 0)
+    run(prog)
+    return out
+
+
 def adam_(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, powers: torch.Tensor, lr: float,
           beta1: float, beta2: float, eps: float, gscale: float = 1.0, advance_powers: bool = True,
           lr_sched=None, step: Optional[torch.Tensor] = None) -> None:

@@ -624,6 +624,155 @@ def augment_transpose(g: torch.Tensor, params: torch.Tensor, aug: DAugment) -> t
     return _augment_gather(g, params, aug, True)
 
 
+# --------------------------------------------------------------------------- DiffAugment's color policy
+COLOR_STREAM = 3  # Philox stream of the color draws (z: 0, instance noise: 1, translation / cutout: 2)
+COLOR_POLICIES = ("brightness", "saturation", "contrast")  # bit i of the kernels' mask (kernels.h ColorPolicy)
+
+
+class DColor(NamedTuple):
+    """The color policy of DiffAugment (Zhao et al. 2020) on what D sees, reals and fakes alike, ahead
+    of translation / cutout: per sample a brightness shift b in [-0.5, 0.5), a saturation scale s in
+    [0, 2) about the pixel's channel mean and a contrast scale c in [0.5, 1.5] about the image's
+    mean. Each is switched on its own (the paper's `color` is all three)."""
+    brightness: bool = False
+    saturation: bool = False
+    contrast: bool = False
+
+    @property
+    def active(self) -> bool:
+        return self.brightness or self.saturation or self.contrast
+
+    @property
+    def mask(self) -> int:
+        """The kernels' policy bitmask."""
+        return int(self.brightness) | int(self.saturation) << 1 | int(self.contrast) << 2
+
+    def describe(self) -> str:
+        return ",".join(n for n, on in zip(COLOR_POLICIES, self) if on) or "off"
+
+
+def check_d_color(spec="") -> DColor:
+    """Validated DColor from a comma-separated list of brightness, saturation, contrast (any subset, any
+    order); "" and "none" mean off. Anything else is a ValueError naming the offending token."""
+    if isinstance(spec, DColor):
+        return DColor(*(bool(v) for v in spec))
+    if spec is None:
+        spec = ""
+    if not isinstance(spec, str):
+        raise ValueError("d_color_augment must be a comma-separated list of %s, got %r" % (COLOR_POLICIES, spec))
+    toks = [t.strip().lower() for t in spec.split(",")]
+    toks = [t for t in toks if t]
+    if toks == ["none"]:
+        toks = []
+    for t in toks:
+        if t not in COLOR_POLICIES:
+            raise ValueError("d_color_augment: unknown policy %r (known: %s, or none)" % (t, ", ".join(COLOR_POLICIES)))
+    return DColor(*(n in toks for n in COLOR_POLICIES))
+
+
+def resolve_d_color(spec=None) -> DColor:
+    """check_d_color over the engines' argument: None = the environment default
+    DCGAN_D_COLOR_AUGMENT, then off. An explicit argument wins."""
+    import os
+    if spec is None:
+        spec = os.environ.get("DCGAN_D_COLOR_AUGMENT") or ""
+    return check_d_color(spec)
+
+
+def color_params(n: int, seed: int, step: int) -> torch.Tensor:
+    """float32 [n, 3] = (b, s, c) of samples 0..n-1: sample i takes the words w0..w2 of the Philox block
+    at counter (i, step, COLOR_STREAM) under `seed`; u_k = float(w_k >> 8) * 2^-24 and, in fp32,
+    b = u0 - 0.5, s = 2 * u1, c = u2 + 0.5. All three are always drawn."""
+    import numpy as np
+    w = philox_words(4 * int(n), seed, step, COLOR_STREAM)[:int(n)]
+    u = (w[:, :3] >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    out = np.stack([u[:, 0] - np.float32(0.5), np.float32(2) * u[:, 1], u[:, 2] + np.float32(0.5)], -1)
+    return torch.from_numpy(np.ascontiguousarray(out.astype(np.float32)))
+
+
+def _color_setup(x: torch.Tensor, params) -> Tuple[torch.Tensor, torch.Tensor, torch.dtype]:
+    if x.dim() != 4:
+        raise ValueError("color_augment: x must be [N, S, S, C], got %s" % (tuple(x.shape),))
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    p = torch.as_tensor(params).to(device=x.device, dtype=ct)
+    if p.dim() != 2 or p.shape[0] != x.shape[0] or p.shape[1] not in (3, 4):
+        raise ValueError("color_augment: params must be [N, 3] = (b, s, c) or [N, 4] = (b, s, c, Mx), got %s"
+                         % (tuple(p.shape),))
+    return x.to(ct), p, ct
+
+
+def _count(v: torch.Tensor, n: int) -> torch.Tensor:
+    # a tensor divisor: a correctly rounded division on every device (a Python number may turn into a
+    # multiplication by its reciprocal)
+    return torch.full((), float(n), dtype=v.dtype, device=v.device)
+
+
+def _channel_mean(v: torch.Tensor) -> torch.Tensor:
+    m = v[..., 0]
+    for ch in range(1, v.shape[-1]):  # in channel order
+        m = m + v[..., ch]
+    return (m / _count(v, v.shape[-1]))[..., None]
+
+
+def _image_mean(v: torch.Tensor) -> torch.Tensor:
+    n = v.shape[1] * v.shape[2] * v.shape[3]
+    return v.reshape(v.shape[0], -1).sum(1) / _count(v, n)
+
+
+def color_mean(x: torch.Tensor) -> torch.Tensor:
+    """Mx [N] of the definition below: the sum of an image's elements in the compute type, divided by
+    their count (the kernel records its own in column 3 of its params; the two differ by the order of
+    the sum)."""
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    return _image_mean(x.to(ct))
+
+
+def color_augment(x: torch.Tensor, params: torch.Tensor, color: DColor) -> torch.Tensor:
+    """The color policy over x [N, S, S, C] (NHWC) under params [N, 3] = (b, s, c), every operation a
+    separately rounded fp32 one (fp64 for an fp64 x), the stages that `color` switches off skipped:
+
+        brightness : v = v + b
+        saturation : m = (v_0 + .. + v_{C-1}) / C per pixel, in channel order;  v = s * (v - m) + m
+        contrast   : M = Mx + b if brightness else Mx, Mx = sum(x[n]) / (S*S*C);  v = c * (v - M) + M
+
+    M is the published mean of the image after brightness and saturation, in exact arithmetic
+    (saturation keeps a pixel's channel mean): one reduction over the input serves. A fourth column of
+    params gives Mx (what the kernel recorded); else it is ``color_mean(x)``. Differentiable."""
+    v, p, ct = _color_setup(x, params)
+    col = lambda i: p[:, i].reshape(-1, 1, 1, 1)  # noqa: E731
+    if color.brightness:
+        v = v + col(0)
+    if color.saturation:
+        m = _channel_mean(v)
+        v = col(1) * (v - m) + m
+    if color.contrast:
+        M = (p[:, 3] if p.shape[1] == 4 else _image_mean(x.to(ct))).reshape(-1, 1, 1, 1)
+        if color.brightness:
+            M = M + col(0)
+        v = col(2) * (v - M) + M
+    return v.to(x.dtype)
+
+
+def color_augment_transpose(g: torch.Tensor, params: torch.Tensor, color: DColor, mean=None) -> torch.Tensor:
+    """The transpose of ``color_augment``'s linear part over g = dL/dy: each stage is a symmetric map,
+    so it is the same stage functions in reverse order on the gradient's own mean (brightness is the
+    identity):
+
+        contrast   : Gm = sum(g[n]) / (S*S*C);  v = c * (v - Gm) + Gm
+        saturation : m over the channels of those values;  v = s * (v - m) + m
+
+    mean: Gm [N] given instead of summed here."""
+    v, p, ct = _color_setup(g, params)
+    col = lambda i: p[:, i].reshape(-1, 1, 1, 1)  # noqa: E731
+    if color.contrast:
+        Gm = (_image_mean(v) if mean is None else torch.as_tensor(mean).to(device=v.device, dtype=ct)).reshape(-1, 1, 1, 1)
+        v = col(2) * (v - Gm) + Gm
+    if color.saturation:
+        m = _channel_mean(v)
+        v = col(1) * (v - m) + m
+    return v.to(g.dtype)
+
+
 def zero_fraction(x: torch.Tensor) -> torch.Tensor:
     """tf.nn.zero_fraction (sparsity summary, distriubted_model.py:80)."""
     return (x == 0).float().mean()

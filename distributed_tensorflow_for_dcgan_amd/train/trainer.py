@@ -218,6 +218,10 @@ def run(flags: Flags, out=None) -> int:
         if aug is not None and aug.active:
             print("differentiable augmentation of D's inputs: %s (reals and fakes, a fresh draw per sample and "
                   "step)" % aug.describe(), file=out, flush=True)
+        color = getattr(engine, "color", None)
+        if color is not None and color.active:
+            print("color augmentation of D's inputs: %s (reals and fakes, ahead of translation / cutout, a fresh "
+                  "draw per sample and step)" % color.describe(), file=out, flush=True)
     if flags.log_device_placement:
         for line in placement_report(engine, device, rank, world):
             print(line, file=out, flush=True)
@@ -391,7 +395,8 @@ def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps, instance_n
                         lr_decay_steps=int(lr_decay_steps), lr_end=float(flags.lr_end),
                         lr_warmup=int(flags.lr_warmup_steps), instance_noise=float(flags.instance_noise),
                         instance_noise_end=float(flags.instance_noise_end),
-                        instance_noise_steps=int(instance_noise_steps), d_augment=str(flags.d_augment))
+                        instance_noise_steps=int(instance_noise_steps), d_augment=str(flags.d_augment),
+                        d_color_augment=str(flags.d_color_augment))
 
 
 def _sample_ema(engine, flags) -> bool:

@@ -118,6 +118,9 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                                 "fakes alike, G's gradient passing through it: a comma-separated list of "
                                 "translation (up to 1/8 of the image, zero fill) and cutout (half the image's "
                                 "side); empty or none turns it off"),
+    ("d_color_augment", "str", "", "DiffAugment's color policy on the discriminator's inputs, ahead of --d_augment: "
+                                      "a comma-separated list of brightness, saturation and contrast, each drawn per "
+                                      "sample and step; empty or none turns it off"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -224,6 +227,11 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         check_d_augment(ns.d_augment)
     except ValueError as e:
         parser.error("--d_augment: %s" % e)
+    from ..ops.reference import check_d_color
+    try:
+        check_d_color(ns.d_color_augment)
+    except ValueError as e:
+        parser.error("--d_color_augment: %s" % e)
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
