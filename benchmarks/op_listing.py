@@ -35,7 +35,8 @@ from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig  # no
 
 POSITIONS = ("_a_fwd", "_a_gd_end", "_b_split", "_b_top_dgrad", "_g_w", "_g_w_layer", "_c_split", "_c_split_a")
 ANONYMOUS = ("_keep", "_s_keep")  # engine attributes whose entries have no stable path
-ENV = ("DCGAN_D_BATCH_NORM", "DCGAN_DDP_SHARD", "DCGAN_D_AUGMENT", "DCGAN_D_COLOR_AUGMENT")
+ENV = ("DCGAN_D_BATCH_NORM", "DCGAN_DDP_SHARD", "DCGAN_D_AUGMENT", "DCGAN_D_COLOR_AUGMENT", "DCGAN_G_TOPK",
+       "DCGAN_G_TOPK_STEPS")
 MIN_PTR = 1 << 16  # smaller integers are sizes, counts and flags
 
 
@@ -167,27 +168,29 @@ def listing(cfg, B, env, **kw):
 def grid(quick=False):
     """(label, cfg kwargs, env, engine kwargs) of every configuration."""
     models = {"28x28x1": dict(output_size=28, c_dim=1), "64x64x3": {}, "128x128x3": dict(output_size=128)}
-    for (mname, mkw), dtype, d_bn, sn, d_steps, noise, aug, color, world, sched in itertools.product(
+    for (mname, mkw), dtype, d_bn, sn, d_steps, noise, aug, color, topk, world, sched in itertools.product(
             models.items(), ("bf16", "fp16", "fp32"), (True, False), (False, True), (1, 3), (None, 0.1),
-            ("", "translation,cutout"), ("", "brightness,saturation,contrast"), (1, 2), (None, "serial")):
-        if quick and (mname == "128x128x3" or d_steps == 3 and (noise or aug or color)):
+            ("", "translation,cutout"), ("", "brightness,saturation,contrast"), (None, 0.5), (1, 2), (None, "serial")):
+        if quick and (mname == "128x128x3" or d_steps == 3 and (noise or aug or color or topk)):
             continue
         variants = [("", {}, {})]
         if mname == "64x64x3":
             variants.append((" force_ddp", {}, dict(ddp=True)) if world == 1
                             else (" shard", {"DCGAN_DDP_SHARD": "1"}, {}))
         for vname, env, vkw in variants:
-            # (DiffAugment / its color policy off keeps the label it had before the switch existed: those lines compare
-            # one to one with a listing from an older tree)
-            label = "%s %s d_bn=%d sn=%d d_steps=%d noise=%d world=%d sched=%s%s%s%s" % (
+            # (DiffAugment / its color policy / top-k off keeps the label it had before the switch existed: those lines
+            # compare one to one with a listing from an older tree)
+            label = "%s %s d_bn=%d sn=%d d_steps=%d noise=%d world=%d sched=%s%s%s%s%s" % (
                 mname, dtype, d_bn, sn, d_steps, noise is not None, world, sched or "default", vname,
-                " aug=1" if aug else "", " color=1" if color else "")
+                " aug=1" if aug else "", " color=1" if color else "", " topk=1" if topk else "")
             kw = dict(dtype=dtype, d_spectral_norm=sn, d_steps=d_steps, instance_noise=noise or 0.0,
                       instance_noise_steps=1000, world=world, schedule=sched, **vkw)
             if aug:
                 kw["d_augment"] = aug
             if color:
                 kw["d_color_augment"] = color
+            if topk:
+                kw.update(g_topk=topk, g_topk_steps=1000)
             yield label, dict(mkw, d_bn=d_bn), env, kw
 
 

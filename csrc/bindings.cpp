@@ -703,6 +703,55 @@ class Program {
     }, AccList().r(logits, (size_t)B * 8).w(out, 16).w(dl_d, (size_t)B * 8).w(dl_g, (size_t)B * 4)
            .w(prob, (size_t)B * 8).r(ls, 12).v);
   }
+  // Validated top-k schedule (kernels.h TopkSched): 1 <= B <= 4096, 1 <= kmin <= B, 1 <= steps <= 2^24
+  static TopkSched topk_sched(const char* op, int64_t B, int64_t kmin, int64_t steps) {
+    const std::string o(op);
+    if (B < 1 || B > (int64_t)TOPK_MAX_B)
+      throw std::runtime_error(o + ": B must satisfy 1 <= B <= 4096, got " + std::to_string(B));
+    if (kmin < 1 || kmin > B)
+      throw std::runtime_error(o + ": kmin must satisfy 1 <= kmin <= B, got " + std::to_string(kmin));
+    if (steps < 1 || steps > (int64_t)TOPK_MAX_STEPS)
+      throw std::runtime_error(o + ": steps must satisfy 1 <= steps <= 2^24, got " + std::to_string(steps));
+    return TopkSched{(unsigned)kmin, (unsigned)steps};
+  }
+  // top-k generator updates (g_topk_kernel): of the B fake logits the k(*step) highest keep their seed,
+  // dl_g_k = dl_g * B / k, the others get +0; sel int32[B], info float[4] = (g_loss_topk, threshold,
+  // B / k, k). Reads logits_fake, dl_g and the 8-byte step counter, writes the three outputs
+  int g_topk(std::string name, uintptr_t logits_fake, uintptr_t dl_g, uintptr_t dl_g_k, uintptr_t sel, uintptr_t info,
+             int64_t B, int64_t kmin, int64_t steps, uintptr_t step, int objective, int stream) {
+    if (!logits_fake || !dl_g || !dl_g_k || !sel || !info || !step)
+      throw std::runtime_error("g_topk: logits_fake, dl_g, dl_g_k, sel, info and step must be non-null");
+    const TopkSched S = topk_sched("g_topk", B, kmin, steps);
+    if (objective != GAN_BCE && objective != GAN_LSGAN && objective != GAN_HINGE)
+      throw std::runtime_error("g_topk: objective must be 0 (bce), 1 (lsgan) or 2 (hinge), got " +
+                               std::to_string(objective));
+    const size_t nb = (size_t)B * 4;
+    const std::pair<uintptr_t, size_t> outs[3] = {{dl_g_k, nb}, {sel, nb}, {info, 16}};
+    const std::pair<uintptr_t, size_t> ins[3] = {{logits_fake, nb}, {dl_g, nb}, {step, 8}};
+    auto overlap = [](const std::pair<uintptr_t, size_t>& a, const std::pair<uintptr_t, size_t>& b) {
+      return a.first < b.first + b.second && b.first < a.first + a.second;
+    };
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j)
+        if (overlap(outs[i], ins[j]) || (j > i && overlap(outs[i], outs[j])))
+          throw std::runtime_error("g_topk: dl_g_k, sel and info must be buffers of their own");
+    }
+    const int Bi = (int)B;
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_g_topk)(P<const float>(logits_fake), P<const float>(dl_g), P<float>(dl_g_k), P<int>(sel),
+                            P<float>(info), Bi, &S, P<const unsigned long long>(step), objective, s);
+    }, AccList().r(logits_fake, nb).r(dl_g, nb).r(step, 8).w(dl_g_k, nb).w(sel, nb).w(info, 16).v);
+  }
+  // the top-k schedule's k at each of n int64 step values -> out int32[n] (dcg::topk_k)
+  int topk_k(std::string name, uintptr_t steps_ptr, uintptr_t out, size_t n, int64_t B, int64_t kmin, int64_t steps,
+             int stream) {
+    if (!steps_ptr || !out) throw std::runtime_error("topk_k: steps and out must be non-null");
+    const TopkSched S = topk_sched("topk_k", B, kmin, steps);
+    const int Bi = (int)B;
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_topk_k)(P<const unsigned long long>(steps_ptr), P<int>(out), n, Bi, &S, s);
+    }, AccList().r(steps_ptr, n * 8).w(out, n * 4).v);
+  }
   // stats (optional): BN partial statistics of the output, channel = column % C ->
   // [(B / 8) * (N / C)][2][C] partial rows (the row block of the kernel is 8)
   // gen_step != 0: z ~ U(-1,1) generated in-kernel (Philox keyed by gen_seed and the device
@@ -1387,6 +1436,11 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("gan_loss", &Program::gan_loss, py::arg("name"), py::arg("logits"), py::arg("B"), py::arg("out"),
            py::arg("dl_d"), py::arg("dl_g"), py::arg("prob"), py::arg("stream"), py::arg("ls") = 0,
            py::arg("objective") = 0, py::arg("label_smooth") = 0.0)
+      .def("g_topk", &Program::g_topk, py::arg("name"), py::arg("logits_fake"), py::arg("dl_g"), py::arg("dl_g_k"),
+           py::arg("sel"), py::arg("info"), py::arg("B"), py::arg("kmin"), py::arg("steps"), py::arg("step"),
+           py::arg("obj") = 0, py::arg("stream") = 0)
+      .def("topk_k", &Program::topk_k, py::arg("name"), py::arg("steps_ptr"), py::arg("out"), py::arg("n"),
+           py::arg("B"), py::arg("kmin"), py::arg("steps"), py::arg("stream") = 0)
       .def("linear_fwd", &Program::linear_fwd, py::arg("name"), py::arg("z"), py::arg("W"), py::arg("b"),
            py::arg("out"), py::arg("B"), py::arg("K"), py::arg("N"), py::arg("stream"), py::arg("stats") = 0,
            py::arg("C") = 0, py::arg("gen_step") = 0, py::arg("gen_seed") = 0)

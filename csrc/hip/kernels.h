@@ -147,6 +147,17 @@ constexpr unsigned long long COLOR_STREAM = 3;
 // real target, which the launchers pick themselves (real_target != 1).
 enum GanObjective : int { GAN_BCE = 0, GAN_LSGAN = 1, GAN_HINGE = 2, GAN_BCE_T = 3 };
 
+// Top-k generator updates (misc.hip g_topk_kernel), by value in the kernel arguments: G's seed keeps
+// the k(t) highest-scored of the B fakes, k annealed from B to kmin over the DEVICE step counter t, so
+// graph replays follow the live counter.
+//   k(t) = B - ((B - kmin) * min(t, steps)) / steps      (integer arithmetic: exact, stateless)
+constexpr int TOPK_MAX_B = 4096;               // the keys of one batch in LDS: 16 KB
+constexpr unsigned TOPK_MAX_STEPS = 1u << 24;
+
+struct TopkSched {
+  unsigned kmin, steps;
+};
+
 // ---- spectral normalisation of D's weights (specnorm.hip). One descriptor per normalised
 // weight, viewed as W [K, Cout] row-major (TF's reshape(w, [-1, Cout]); the head is [K, 1]); a table
 // of up to SN_MAX_MATS of them rides in the kernel arguments so one grid covers them all.

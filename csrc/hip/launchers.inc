@@ -39,6 +39,14 @@ int DCG_API(dcg_colsum_small)(const elem_t* x, int R, int C, float* part, int bl
 // objective = GAN_BCE | GAN_LSGAN | GAN_HINGE, real_target = 1 - label_smooth (1 for hinge); -2 otherwise
 int DCG_API(dcg_gan_loss)(const float* logits, int B, float* out, float* dl_d, float* dl_g, float* prob,
                           const float* ls, int objective, float real_target, hipStream_t s);
+// top-k generator updates over the fake half of the logits x[B] and the all-sample seed dl_g[B]: dl_g_k[B],
+// sel int32[B], info float[4] = (g_loss_topk, threshold, B / k, k), k = k(*step) of `sched`; its probe: k at
+// each of n step values. -2: a null pointer, B outside 1..TOPK_MAX_B, kmin outside 1..B, steps outside
+// 1..2^24, an objective other than GAN_BCE | GAN_LSGAN | GAN_HINGE
+int DCG_API(dcg_g_topk)(const float* x, const float* dl_g, float* dl_g_k, int* sel, float* info, int B,
+                        const dcg::TopkSched* sched, const unsigned long long* step, int objective, hipStream_t s);
+int DCG_API(dcg_topk_k)(const unsigned long long* steps, int* out, size_t n, int B, const dcg::TopkSched* sched,
+                        hipStream_t s);
 int DCG_API(dcg_linear_fwd)(float* z, const float* W, const float* b, elem_t* out, int B, int K, int N, float* stats,
                             int C, const unsigned long long* gen_step, uint64_t gen_seed, hipStream_t s);
 int DCG_API(dcg_linear_wgrad)(const float* z, const elem_t* dh, float* dW, float* db, int B, int K, int N, hipStream_t s);

@@ -110,6 +110,93 @@ __global__ __launch_bounds__(256) void gan_loss_kernel(const float* __restrict__
   gan_loss_block<OBJ>([&](int i) { return logits[i]; }, B, t, out, dl_d, dl_g, prob, ls);
 }
 
+// ---------------------------------------------------------------- top-k generator updates
+// G learns from the k(t) fakes D scores highest (kernels.h TopkSched). x = the fake half of the
+// logits, dl_g = the all-sample seed the loss block wrote (it carries 1 / B and the fp16 loss scale):
+//   key(x)  = bits ^ (sign ? 0xFFFFFFFF : 0x80000000): uint32, monotone in x, -0 < +0, NaNs by their bits
+//   rank(i) = #{j : key_j > key_i} + #{j < i : key_j == key_i}: a permutation of 0..B-1, so exactly k
+//             samples have rank < k whatever the input
+//   dl_g_k[i] = rank(i) < k ? dl_g[i] * (float(B) / float(k)) : +0;  sel[i] = rank(i) < k
+//   info = (mean of g_term over the selected, logit of rank k - 1, float(B) / float(k), float(k))
+__device__ __forceinline__ uint32_t topk_key(float x) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, x);
+  return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+// k(t): block-uniform (S is a kernel argument, t one scalar load of the step counter); (B - kmin) *
+// min(t, steps) < 2^12 * 2^24
+__device__ __forceinline__ int topk_k(int B, const TopkSched& S, unsigned long long t) {
+  const unsigned long long tt = t < (unsigned long long)S.steps ? t : (unsigned long long)S.steps;
+  return B - (int)(((unsigned long long)((unsigned)B - S.kmin) * tt) / (unsigned long long)S.steps);
+}
+
+// G's per-sample loss of objective GOBJ (GAN_BCE | GAN_LSGAN | GAN_HINGE), the lg terms of gan_loss_block
+template <int GOBJ>
+__device__ __forceinline__ float g_term(float x) {
+  if constexpr (GOBJ == GAN_BCE) {
+    return fmaxf(x, 0.f) - x + log1pf(expf(-fabsf(x)));
+  } else if constexpr (GOBJ == GAN_LSGAN) {
+    return 0.5f * (x - 1.f) * (x - 1.f);
+  } else {
+    static_assert(GOBJ == GAN_HINGE, "unknown objective");
+    return -x;
+  }
+}
+
+// ONE workgroup of 256 threads, B <= TOPK_MAX_B. The keys are staged in LDS once, padded to a
+// multiple of 4 with key 0 at j >= B (never > a key, never an earlier tie); thread tid owns samples
+// tid, tid + 256, ... and ranks each against the LDS copy, four keys per (broadcast) 16-byte read.
+// The loss: per-thread partials in ascending i, then gan_loss_block's LDS tree -- its order
+// depends on B alone.
+template <int GOBJ>
+__global__ __launch_bounds__(256) void g_topk_kernel(const float* __restrict__ x, const float* __restrict__ dl_g,
+                                                     float* __restrict__ dl_g_k, int* __restrict__ sel,
+                                                     float* __restrict__ info, int B, TopkSched S,
+                                                     const unsigned long long* __restrict__ step) {
+  __shared__ u32x4 keys4[TOPK_MAX_B / 4];
+  __shared__ float red[256];
+  uint32_t* keys = reinterpret_cast<uint32_t*>(keys4);
+  const int tid = threadIdx.x;
+  const int B4 = (B + 3) & ~3;
+  for (int i = tid; i < B4; i += 256) keys[i] = i < B ? topk_key(x[i]) : 0u;
+  const int k = topk_k(B, S, step[0]);
+  const float scale = (float)B / (float)k;
+  __syncthreads();
+  float lg = 0.f;
+  for (int i = tid; i < B; i += 256) {
+    const uint32_t ki = keys[i];
+    int rank = 0;
+    for (int j = 0; j < B4; j += 4) {
+      const u32x4 kj = keys4[j >> 2];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) rank += (int)(kj[c] > ki) + (int)((kj[c] == ki) & (j + c < i));
+    }
+    const bool s = rank < k;
+    const float xi = x[i];
+    sel[i] = s ? 1 : 0;
+    dl_g_k[i] = s ? dl_g[i] * scale : 0.f;
+    if (s) lg += g_term<GOBJ>(xi);
+    if (rank == k - 1) info[1] = xi;
+  }
+  red[tid] = lg;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    info[0] = red[0] * (1.f / (float)k);
+    info[2] = scale;
+    info[3] = (float)k;
+  }
+}
+
+// topk_k at each of n step values: the tests' probe
+__global__ __launch_bounds__(256) void topk_k_kernel(TopkSched S, int B, const unsigned long long* __restrict__ steps,
+                                                     int* __restrict__ out, size_t n) {
+  for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = topk_k(B, S, steps[i]);
+}
+
 // ---------------------------------------------------------------- Philox z ~ U(-1, 1)
 __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
                                              uint32_t k1) {
@@ -1372,6 +1459,35 @@ extern "C" int DCG_API(dcg_gan_loss)(const float* logits, int B, float* out, flo
     hipLaunchKernelGGL(gan_loss_kernel<decltype(obj)::value>, dim3(1), dim3(256), 0, s, logits, B, real_target, out,
                        dl_d, dl_g, prob, ls);
   });
+}
+
+static inline bool topk_sched_ok(int B, const dcg::TopkSched* S) {
+  return S && B >= 1 && B <= TOPK_MAX_B && S->kmin >= 1 && S->kmin <= (unsigned)B && S->steps >= 1 &&
+         S->steps <= TOPK_MAX_STEPS;
+}
+
+extern "C" int DCG_API(dcg_g_topk)(const float* x, const float* dl_g, float* dl_g_k, int* sel, float* info, int B,
+                                   const dcg::TopkSched* sched, const unsigned long long* step, int objective,
+                                   hipStream_t s) {
+  if (!x || !dl_g || !dl_g_k || !sel || !info || !step || !topk_sched_ok(B, sched)) return -2;
+  auto launch = [&](auto obj) {  // G's target is never smoothed: label-smoothed bce is GAN_BCE here
+    hipLaunchKernelGGL(g_topk_kernel<decltype(obj)::value>, dim3(1), dim3(256), 0, s, x, dl_g, dl_g_k, sel, info, B,
+                       *sched, step);
+  };
+  switch (objective) {
+    case GAN_BCE: launch(std::integral_constant<int, GAN_BCE>{}); break;
+    case GAN_LSGAN: launch(std::integral_constant<int, GAN_LSGAN>{}); break;
+    case GAN_HINGE: launch(std::integral_constant<int, GAN_HINGE>{}); break;
+    default: return -2;
+  }
+  return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_topk_k)(const unsigned long long* steps, int* out, size_t n, int B,
+                                   const dcg::TopkSched* sched, hipStream_t s) {
+  if (!steps || !out || !topk_sched_ok(B, sched)) return -2;
+  hipLaunchKernelGGL(topk_k_kernel, dim3(grid_for(n)), dim3(256), 0, s, *sched, B, steps, out, n);
+  return (int)hipGetLastError();
 }
 
 extern "C" int DCG_API(dcg_linear_fwd)(float* z, const float* W, const float* b, elem_t* out, int B, int K, int N,

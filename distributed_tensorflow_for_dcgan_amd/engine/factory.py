@@ -36,7 +36,8 @@ class ReferenceEngine:
                  lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
                  instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
                  instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
-                 d_color_augment: Optional[str] = None, **_):
+                 d_color_augment: Optional[str] = None, g_topk: Optional[float] = None,
+                 g_topk_steps: Optional[int] = None, **_):
         self.cfg = cfg
         self.batch_size = batch_size
         self.device = device
@@ -67,10 +68,12 @@ class ReferenceEngine:
         # DiffAugment of D's inputs: None = DCGAN_D_AUGMENT; drawn from the same seed as the noise
         self.aug = R.resolve_d_augment(d_augment)
         self.color = R.resolve_d_color(d_color_augment)  # its color policy; None = DCGAN_D_COLOR_AUGMENT
+        # top-k generator updates: None = DCGAN_G_TOPK / DCGAN_G_TOPK_STEPS
+        self.topk = R.resolve_g_topk(g_topk, g_topk_steps)
         zs = self.seed if z_seed is None else int(z_seed)
         self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None,
                                        instance_noise=self.noise, noise_seed=zs * 1000003 + 17 + 7919 * rank,
-                                       d_augment=self.aug, d_color_augment=self.color,
+                                       d_augment=self.aug, d_color_augment=self.color, g_topk=self.topk,
                                        g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth,
                                        d_spectral_norm=bool(d_spectral_norm), seed=seed, d_steps=d_steps,
                                        beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=self.lr_sched)
@@ -132,7 +135,7 @@ class ReferenceEngine:
         B = self._real.shape[0]
         with torch.no_grad():
             out = self.step_impl.forward_losses(self._real, self._last_z, update_ema=False, record=rec, noise=False,
-                                                augment=False, color=False)
+                                                augment=False, color=False, topk=False)
         a = OrderedDict()
         a["z"] = self._last_z
         a["d"] = torch.sigmoid(out["logits_real"])
@@ -155,6 +158,20 @@ class ReferenceEngine:
         """sigma(t) of the instance noise at the current global step (0.0 when off)."""
         return self.step_impl.noise_sigma()
 
+    def topk_selection(self) -> Optional[torch.Tensor]:
+        """The bool mask [B] of the fakes G learned from in the last full step (None: top-k off)."""
+        sel = self.step_impl.last.get("topk_sel") if self.topk.active else None
+        return None if sel is None else sel.clone()
+
+    def last_topk(self):
+        """(k, g_loss_topk, threshold logit) of the last full step; None when top-k is off."""
+        sel = self.topk_selection()
+        if sel is None:
+            return None
+        last = self.step_impl.last
+        k = int(sel.sum())
+        return k, float(last["g_loss_topk"].detach()), float(R.topk_threshold(last["logits_fake"].detach(), k))
+
     @property
     def g_ema(self):
         """Moving average of G's weights (a ParamSet laid out like model.g), None when off."""
@@ -167,7 +184,8 @@ class ReferenceEngine:
         """Sample-time d_loss/g_loss (image_train.py:181-184) without mutating BN EMAs."""
         with torch.no_grad():
             out = self.step_impl.forward_losses(real.to(self.device, torch.float32), z.to(self.device),
-                                                update_ema=False, noise=False, augment=False, color=False)
+                                                update_ema=False, noise=False, augment=False, color=False,
+                                                topk=False)
         return {"d_loss": float(out["d_loss"]), "g_loss": float(out["g_loss"])}
 
     def sync_state_for_checkpoint(self) -> None:
@@ -201,7 +219,8 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                  lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
                  instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
                  instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
-                 d_color_augment: Optional[str] = None):
+                 d_color_augment: Optional[str] = None, g_topk: Optional[float] = None,
+                 g_topk_steps: Optional[int] = None):
     if engine == "auto":  # every dtype (bf16 / fp16 / fp32) runs on the HIP kernels on an MI355X
         engine = "hip" if device.type == "cuda" else "reference"
     if engine == "reference":
@@ -212,7 +231,8 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                                lr_decay_start=lr_decay_start, lr_decay_steps=lr_decay_steps, lr_end=lr_end,
                                lr_warmup=lr_warmup, instance_noise=instance_noise,
                                instance_noise_end=instance_noise_end, instance_noise_steps=instance_noise_steps,
-                               d_augment=d_augment, d_color_augment=d_color_augment)
+                               d_augment=d_augment, d_color_augment=d_color_augment, g_topk=g_topk,
+                               g_topk_steps=g_topk_steps)
     if engine == "hip":
         from .hip_engine import HipEngine
         return HipEngine(cfg, batch_size, device, dtype=dtype, seed=seed, lr=lr, beta1=beta1,
@@ -223,5 +243,6 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                          lr_decay_start=lr_decay_start, lr_decay_steps=lr_decay_steps, lr_end=lr_end,
                          lr_warmup=lr_warmup, instance_noise=instance_noise,
                          instance_noise_end=instance_noise_end, instance_noise_steps=instance_noise_steps,
-                         d_augment=d_augment, d_color_augment=d_color_augment)
+                         d_augment=d_augment, d_color_augment=d_color_augment, g_topk=g_topk,
+                         g_topk_steps=g_topk_steps)
     raise ValueError("unknown engine %r" % engine)

@@ -13,7 +13,8 @@ every step from C++ (eager, the default) or as hipGraphs:
                  copy and its draws, and ``d_aug_bwd`` in the G chain takes the image gradient back;
                  with ``d_color_augment`` one launch before that, ``d_color``, writes the brightness /
                  saturation / contrast copy, and ``d_color_bwd`` follows ``d_aug_bwd`` in the G chain
-  progA[a_fwd:]  the g_loss chain back through D(fake) and G's data gradients  -- "G chain"
+  progA[a_fwd:]  the g_loss chain back through D(fake) and G's data gradients  -- "G chain"; with
+                 ``g_topk`` < 1 its first op, ``g_topk``, keeps the seeds of the k(t) best-scored fakes
   progW          G's weight gradients, each tied to the progA position that produces its operand
   progB          D's backward of d_loss, both halves (D grads final)            -- "D chain"
   progC          TF-Adam(G), TF-Adam(D), beta powers, global step (+ 16-bit weight mirrors);
@@ -168,7 +169,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
                  instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
                  instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
-                 d_color_augment: Optional[str] = None, **_):
+                 d_color_augment: Optional[str] = None, g_topk: Optional[float] = None,
+                 g_topk_steps: Optional[int] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -220,6 +222,15 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # `d_color_bwd` applies transposed to the g_loss chain's image gradient, behind `d_aug_bwd` and
         # ahead of G's tanh backward. None: DCGAN_D_COLOR_AUGMENT. Off: no buffer, no op
         self.color = R.resolve_d_color(d_color_augment)
+        # top-k generator updates (ops.reference.GTopK): the g_loss chain's seed keeps the k(t) fakes D
+        # scores highest, times B / k, and is +0 on the others; one recorded launch (`g_topk`), the first
+        # op behind the forward on the G chain's stream, selects them from the logits and the device step
+        # counter into buffers of its own. D's losses, seeds and chain are untouched, D sub-steps record
+        # no such op. None: DCGAN_G_TOPK / DCGAN_G_TOPK_STEPS. Off (nu = 1): no buffer, no op
+        self.topk = R.resolve_g_topk(g_topk, g_topk_steps)
+        if self.topk.active and batch_size > R.TOPK_MAX_B:
+            raise ValueError("g_topk needs batch_size <= %d (the selection ranks one batch in one workgroup), "
+                             "got %d" % (R.TOPK_MAX_B, batch_size))
         # moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates = the
         # global step); 0 = off: no buffers, no op. None: DCGAN_G_EMA_DECAY (A/B of its cost)
         if g_ema_decay is None:
@@ -338,6 +349,11 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.losses = t(4, dtype=torch.float32, zero=True)
         self.dl_d = t(B2, dtype=torch.float32)
         self.dl_g = t(B, dtype=torch.float32)
+        # top-k generator updates: the g_loss chain's seed, the 0 / 1 selection and (g_loss_topk,
+        # threshold, B / k, k), all written by `g_topk` alone
+        self.dl_g_k = t(B, dtype=torch.float32, zero=True) if self.topk.active else None
+        self.topk_sel = t(B, dtype=torch.int32, zero=True) if self.topk.active else None
+        self.topk_info = t(4, dtype=torch.float32, zero=True) if self.topk.active else None
         # ---------------- BN state (fwd): mean/rstd/scale/shift per layer [groups][C]
         self.bn = {}
         for name, C in cfg.g_bn_layers():
@@ -1017,7 +1033,14 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         data-gradient chain (which then has nothing else on its critical path)."""
         B, L = self.B, self.dl[0]
         # the fake half only: B rows, one statistics group (group 1), gradient buffers of its own
-        ch = _DChain("g.", B, 1, 1, lambda t: t[B:], self.gc_da, self.gc_dx, self.coef_g, self.dl_g, None)
+        seed = self.dl_g
+        if self.topk.active:
+            # top-k: G learns from the k(t) best-scored fakes; the chain's kernels only see another seed
+            seed = self.dl_g_k
+            prog.g_topk("g_topk", _p(self.logits[B:]), _p(self.dl_g), _p(seed), _p(self.topk_sel),
+                        _p(self.topk_info), B, R.topk_kmin(B, self.topk.nu), self.topk.steps,
+                        _p(self.step_counter), H.gan_loss_id(self.gan_loss, self.label_smooth), 0)
+        ch = _DChain("g.", B, 1, 1, lambda t: t[B:], self.gc_da, self.gc_dx, self.coef_g, seed, None)
         self._d_backward(prog, ch)
         dx, nat, pad = self.gc_dx[L.name], self.wbf_d[L.name + "/w"], same_pads(L.in_hw)[0]
         if self._img_dact():
@@ -1575,6 +1598,17 @@ class HipEngine(HipDDPMixin, HipEngineAux):
 
     def losses_tensor(self) -> torch.Tensor:
         return self.losses
+
+    def last_topk(self):
+        """(k, g_loss_topk, threshold logit) of the last full step's top-k selection; None when off."""
+        if not self.topk.active:
+            return None
+        g, thr, _, k = self.topk_info.tolist()
+        return int(k), g, thr
+
+    def topk_selection(self) -> Optional[torch.Tensor]:
+        """The bool mask [B] of the fakes G learned from in the last full step (None: top-k off)."""
+        return self.topk_sel.ne(0) if self.topk.active else None
 
     def sync_state_for_checkpoint(self) -> None:
         torch.cuda.synchronize(self.device)

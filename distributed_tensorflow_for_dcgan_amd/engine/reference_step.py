@@ -27,8 +27,13 @@ class ReferenceStep:
                  d_steps: int = 1, beta2: float = R.ADAM_BETA2, lr_d: Optional[float] = None,
                  lr_g: Optional[float] = None, lr_decay="none", lr_decay_start: int = 0, lr_decay_steps: int = 0,
                  lr_end: float = 0.0, lr_warmup: int = 0, instance_noise=0.0, instance_noise_end: float = 0.0,
-                 instance_noise_steps: int = 0, noise_seed: int = 0, d_augment="", d_color_augment=""):
+                 instance_noise_steps: int = 0, noise_seed: int = 0, d_augment="", d_color_augment="",
+                 g_topk=1.0, g_topk_steps: int = 0):
         self.model = model
+        # top-k generator updates (ops.reference.GTopK): g_loss is differentiated over the k(t) fakes D
+        # scores highest only, k annealed from B to ceil(nu B) over the global step; D's losses and
+        # gradients and the reported g_loss stay those of all B samples
+        self.topk = R.check_g_topk(*g_topk) if isinstance(g_topk, R.GTopK) else R.check_g_topk(g_topk, g_topk_steps)
         # DiffAugment (ops.reference.DAugment): D sees augment([real | fake]) -- translation and / or
         # cutout, drawn per sample from Philox stream 2 of `noise_seed` at the global step (D sub-step
         # k: substep_seed(noise_seed, k)) -- before the additive noise; G's gradient flows through it
@@ -77,6 +82,12 @@ class ReferenceStep:
         n = self.noise
         return float(R.noise_sigma(self.global_step, n.sigma0, n.sigma1, n.steps)) if n.active else 0.0
 
+    def topk_k(self, B: int) -> int:
+        """k(t) of the top-k selection among B fakes at the current global step; B when it is off."""
+        if not self.topk.active:
+            return int(B)
+        return R.topk_k(self.global_step, B, R.topk_kmin(B, self.topk.nu), self.topk.steps)
+
     def draw_noise(self, shape, sub: Optional[int] = None) -> Optional[torch.Tensor]:
         """The additive sigma(t) * eps over a [2B, ...] input at the current global step: the full
         step's (sub None) or D sub-step `sub`'s; None when the noise is off."""
@@ -100,13 +111,16 @@ class ReferenceStep:
 
     def forward_losses(self, real: torch.Tensor, z: torch.Tensor, Pg=None, Pd=None, update_ema=True,
                        record=None, update_ema_g=None, noise=None, sub: Optional[int] = None, augment=None,
-                       color=None):
+                       color=None, topk=None):
         """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's). noise: the additive
         sigma * eps on D's input [2B, ...]; None = drawn (``draw_noise``, `sub` = the D sub-step) when
         instance noise is on; False = none (sample-time losses stay clean). augment: the params [2B, 4]
         of DiffAugment, applied before the noise; None = drawn (``draw_augment``) when it is on; False =
         none. color: the params [2B, 3 or 4] of the color policy, applied before `augment`; None = drawn
-        (``draw_color``) when it is on; False = none."""
+        (``draw_color``) when it is on; False = none. topk: the bool mask [B] of the fakes G learns from;
+        None = the selection on this forward's own fake logits (``topk_k`` of them) when top-k is on; False
+        = none. The result carries it as ``topk_sel`` (None when unused) beside ``g_loss_topk``, the mean
+        of G's loss over the selected (``g_loss`` itself when unused)."""
         m = self.model
         if self.d_spectral_norm:  # D computes with W / sigma(W); autograd projects the gradient
             Pd = m.d_sn_weights(Pd)
@@ -130,20 +144,29 @@ class ReferenceStep:
                                     update_ema=update_ema, record=record)
         lr_, lf = logits[:B], logits[B:]
         d_real, d_fake, g_loss, d_loss = R.gan_losses(lr_, lf, self.gan_loss, self.label_smooth)
+        if topk is None:
+            topk = R.topk_select(lf, self.topk_k(B)) if self.topk.active else False
+        if topk is False:
+            topk, g_topk = None, g_loss
+        else:
+            topk = torch.as_tensor(topk).to(lf.device, torch.bool).reshape(-1)
+            g_topk = R.topk_g_loss(lf, topk, self.gan_loss)
         return {"fake": fake, "logits_real": lr_, "logits_fake": lf, "d_loss_real": d_real,
-                "d_loss_fake": d_fake, "g_loss": g_loss, "d_loss": d_loss}
+                "d_loss_fake": d_fake, "g_loss": g_loss, "d_loss": d_loss, "g_loss_topk": g_topk, "topk_sel": topk}
 
     def compute_grads(self, real: torch.Tensor, z: torch.Tensor, update_ema: bool = True, noise=None, augment=None,
-                      color=None):
-        """Returns (losses dict, flat D grads, flat G grads) without applying them."""
+                      color=None, topk=None):
+        """Returns (losses dict, flat D grads, flat G grads) without applying them. G's gradients are
+        those of ``g_loss_topk`` (which is ``g_loss`` without a top-k selection)."""
         m = self.model
         Pg = {k: v.detach().clone().requires_grad_(True) for k, v in m.g.tensors.items()}
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
-        out = self.forward_losses(real, z, Pg, Pd, update_ema=update_ema, noise=noise, augment=augment, color=color)
+        out = self.forward_losses(real, z, Pg, Pd, update_ema=update_ema, noise=noise, augment=augment, color=color,
+                                  topk=topk)
         d_names, g_names = m.d.names(), m.g.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], retain_graph=True,
                                  allow_unused=True)
-        gg = torch.autograd.grad(out["g_loss"], [Pg[n] for n in g_names], allow_unused=True)
+        gg = torch.autograd.grad(out["g_loss_topk"], [Pg[n] for n in g_names], allow_unused=True)
         gd_flat = m.d.like()
         gg_flat = m.g.like()
         for n, g in zip(d_names, dg):
@@ -161,7 +184,7 @@ class ReferenceStep:
         m = self.model
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
         out = self.forward_losses(real, z, None, Pd, update_ema=True, update_ema_g=False, noise=noise,
-                                  sub=self._sub_k if sub is None else sub, augment=augment, color=color)
+                                  sub=self._sub_k if sub is None else sub, augment=augment, color=color, topk=False)
         d_names = m.d.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], allow_unused=True)
         gd_flat = m.d.like()
@@ -188,8 +211,11 @@ class ReferenceStep:
         self.last = out
         return {k: float(out[k].detach()) for k in ("d_loss_real", "d_loss_fake", "g_loss", "d_loss")}
 
-    def step(self, real: torch.Tensor, z: torch.Tensor, noise=None, augment=None, color=None) -> Dict[str, float]:
-        out, gd, gg = self.compute_grads(real, z, noise=noise, augment=augment, color=color)
+    def step(self, real: torch.Tensor, z: torch.Tensor, noise=None, augment=None, color=None,
+             topk=None) -> Dict[str, float]:
+        """topk: the mask of the fakes G learns from (an engine's recorded one); None = the reference's
+        own selection when top-k is on; False = none."""
+        out, gd, gg = self.compute_grads(real, z, noise=noise, augment=augment, color=color, topk=topk)
         self._sub_k = 0
         for s in range(2):  # one EMA update per BN slot per step (as the HIP engine counts)
             self.model.d_bn.count_step(s)

@@ -175,7 +175,9 @@ def check(cfg=None, batch_size: int = 8, dtype: str = "bf16", world: int = 1, sc
     with one on, every Adam op reads the step counter that step_end / adam2 writes; instance_noise,
     ...: the d_noise op reads that counter too and writes the buffer D's layer 0 reads on two streams;
     d_augment: so does d_aug, whose recorded draws d_aug_bwd reads on the g_loss chain;
-    d_color_augment: and d_color ahead of it, whose recorded (s, c) d_color_bwd reads behind d_aug_bwd)."""
+    d_color_augment: and d_color ahead of it, whose recorded (s, c) d_color_bwd reads behind d_aug_bwd;
+    g_topk, g_topk_steps: the g_topk op at the head of the G chain reads the logits, dl_g and that
+    counter and writes the seed the g_loss chain starts from)."""
     import torch
 
     from ..models.config import DCGANConfig

@@ -950,6 +950,56 @@ def gan_loss(logits: torch.Tensor, kind: str = "bce", label_smooth: float = 0.0,
     return out, dl_d, dl_g, prob
 
 
+def g_topk(logits: torch.Tensor, dl_g: torch.Tensor, k_or_sched, kind: str = "bce",
+           step: Optional[torch.Tensor] = None, out=None):
+    """The top-k kernel on the fp32 fake logits [B] and the all-sample seed dl_g [B] (as gan_loss wrote it,
+    loss scale included): (dl_g_k float32[B], sel int32[B], info float32[4] = g_loss_topk, threshold, B / k,
+    k). k_or_sched: an int k, or (kmin, nsteps) evaluated at the device counter step[0] (int64). out: the
+    three output buffers, when the caller brings its own. Oracle: ops.reference.topk_*."""
+    if logits.dtype != torch.float32 or logits.dim() != 1 or dl_g.dtype != torch.float32 or dl_g.shape != logits.shape:
+        raise TypeError("g_topk: logits and dl_g must be float32 vectors of B elements")
+    if not (logits.is_contiguous() and dl_g.is_contiguous()):
+        raise ValueError("g_topk: logits and dl_g must be contiguous")
+    from .reference import check_gan_loss
+    obj = GAN_LOSS_IDS[check_gan_loss(kind)[0]]
+    B = logits.numel()
+    if isinstance(k_or_sched, int):  # a fixed k: the end of a one-step anneal
+        kmin, nsteps = k_or_sched, 1
+        if step is None:
+            step = torch.ones(1, device=logits.device, dtype=torch.int64)
+    else:
+        kmin, nsteps = k_or_sched
+        if step is None:
+            raise TypeError("g_topk: a (kmin, nsteps) schedule needs the step counter")
+    _check_step("g_topk", step)
+    if out is None:
+        out = (torch.empty(B, device=logits.device, dtype=torch.float32),
+               torch.empty(B, device=logits.device, dtype=torch.int32),
+               torch.empty(4, device=logits.device, dtype=torch.float32))
+    dl_g_k, sel, info = out
+    if dl_g_k.dtype != torch.float32 or sel.dtype != torch.int32 or info.dtype != torch.float32 or \
+            dl_g_k.numel() != B or sel.numel() != B or info.numel() != 4:
+        raise TypeError("g_topk: out must be (float32[B], int32[B], float32[4])")
+    prog = ext().Program()
+    prog.g_topk("g_topk", _p(logits) if B else 0, _p(dl_g) if B else 0, _p(dl_g_k) if B else 0, _p(sel) if B else 0,
+                _p(info), B, int(kmin), int(nsteps), _p(step), obj)
+    run(prog)
+    return dl_g_k, sel, info
+
+
+def topk_k(steps: torch.Tensor, B: int, kmin: int, nsteps: int) -> torch.Tensor:
+    """k(t) of the top-k anneal at each step value, int64[N] -> int32[N], from the device function the
+    top-k kernel evaluates (dcg::topk_k)."""
+    if steps.dtype != torch.int64:
+        raise TypeError("topk_k: steps must be int64")
+    steps = steps.contiguous()
+    out = torch.empty(steps.shape, device=steps.device, dtype=torch.int32)
+    prog = ext().Program()
+    prog.topk_k("topk_k", _p(steps) if steps.numel() else 0, _p(out), steps.numel(), int(B), int(kmin), int(nsteps))
+    run(prog)
+    return out
+
+
 def ema_max_blocks() -> int:
     """Grid cap of the streaming EMA kernel (larger buffers grid-stride)."""
     return int(ext().EMA_MAX_BLOCKS)

@@ -773,6 +773,154 @@ def color_augment_transpose(g: torch.Tensor, params: torch.Tensor, color: DColor
     return v.to(g.dtype)
 
 
+# --------------------------------------------------------------------------- top-k generator updates
+TOPK_MAX_B = 4096          # the kernel stages one batch of keys in LDS
+TOPK_MAX_STEPS = 1 << 24   # length of the anneal of k
+
+
+class GTopK(NamedTuple):
+    """Top-k training of G (Sinha et al., NeurIPS 2020): in G's update only, the B - k fakes D scores
+    lowest are dropped. k is annealed linearly, in integers, over the global step t (its value before
+    the step's increment) from B down to kmin = ceil(B * nu):
+
+        k(t) = B - ((B - kmin) * min(t, steps)) // steps
+
+    nu = 1 is off. D's losses, its gradients and the logged g_loss are those of all B samples."""
+    nu: float = 1.0
+    steps: int = 1
+
+    @property
+    def active(self) -> bool:
+        return self.nu < 1.0
+
+    def describe(self) -> str:
+        if not self.active:
+            return "off"
+        return "k from B to ceil(%g B) over %d steps" % (self.nu, self.steps)
+
+
+def check_g_topk(nu=1.0, steps=0, total_steps=None, open_ended=False) -> GTopK:
+    """Validated GTopK; errors name the flag. 0 < nu <= 1 and finite; when active (nu < 1), 1 <= steps
+    <= 2^24. steps = 0 then means "until the end of training": `total_steps` when given (an error when
+    that is < 1), left at 0 for a later resolution when `open_ended`, else an error. With nu = 1 steps
+    is not read."""
+    try:
+        nu = float(nu)
+    except (TypeError, ValueError):
+        raise ValueError("g_topk must be a number, got %r" % (nu,)) from None
+    if not (math.isfinite(nu) and 0.0 < nu <= 1.0):
+        raise ValueError("g_topk must be finite with 0 < g_topk <= 1, got %r" % (nu,))
+    if nu == 1.0:
+        return GTopK(1.0, 1)
+    steps = _lr_int("g_topk_steps", steps, 0, TOPK_MAX_STEPS)
+    if steps == 0:
+        if total_steps is not None:
+            steps = int(total_steps)
+            if not 1 <= steps <= TOPK_MAX_STEPS:
+                raise ValueError("g_topk_steps=0 anneals until the end of training, but that is %d steps "
+                                 "(need 1 .. 2^24)" % steps)
+        elif not open_ended:
+            raise ValueError("g_topk_steps must be an integer with 1 <= g_topk_steps <= %d, got 0 "
+                             "(only the trainer resolves 0 = until the end of training)" % TOPK_MAX_STEPS)
+    return GTopK(nu, steps)
+
+
+def resolve_g_topk(nu=None, steps=None, total_steps=None) -> GTopK:
+    """check_g_topk over the engines' arguments: None = the environment default (DCGAN_G_TOPK,
+    DCGAN_G_TOPK_STEPS), then 1 / 0. An explicit argument wins. A GTopK as `nu` is validated as it is."""
+    import os
+    if isinstance(nu, GTopK):
+        return check_g_topk(*nu, total_steps=total_steps)
+
+    def env(name, conv):
+        v = os.environ.get(name)
+        if v is None or v.strip() == "":
+            return None
+        try:
+            return conv(v)
+        except ValueError:
+            raise ValueError("%s=%r is not a number" % (name, v)) from None
+    if nu is None:
+        nu = env("DCGAN_G_TOPK", float)
+    if steps is None:
+        steps = env("DCGAN_G_TOPK_STEPS", int)
+    return check_g_topk(1.0 if nu is None else nu, 0 if steps is None else steps, total_steps=total_steps)
+
+
+def topk_kmin(B: int, nu: float) -> int:
+    """The final k: max(1, min(B, ceil(B * nu - 1e-9))) in Python floats (the kernel takes it as a
+    launch constant; the 1e-9 keeps B * nu = an integer + rounding noise at that integer)."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("topk_kmin: B must be >= 1, got %r" % (B,))
+    return max(1, min(B, int(math.ceil(B * float(nu) - 1e-9))))
+
+
+def topk_k(t, B: int, kmin: int, steps: int) -> int:
+    """k(t) = B - ((B - kmin) * min(t, steps)) // steps: B at t = 0, kmin from t = steps on."""
+    B, kmin, steps = int(B), int(kmin), int(steps)
+    if not (1 <= kmin <= B and steps >= 1):
+        raise ValueError("topk_k: need 1 <= kmin <= B and steps >= 1, got B=%d kmin=%d steps=%d" % (B, kmin, steps))
+    t = min(max(int(t), 0), steps)
+    return B - ((B - kmin) * t) // steps
+
+
+def topk_keys(x_fake: torch.Tensor) -> torch.Tensor:
+    """The kernel's sort key of each fp32 logit as int64 in [0, 2^32): monotone in x, -0 below +0,
+    NaNs ordered by their bits (positive ones above +inf, negative ones below -inf)."""
+    bits = x_fake.detach().to(torch.float32).contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    return torch.where(bits >> 31 != 0, bits ^ 0xFFFFFFFF, bits ^ 0x80000000)
+
+
+def topk_rank(x_fake: torch.Tensor) -> torch.Tensor:
+    """rank(i) = #{j : key_j > key_i} + #{j < i : key_j == key_i}: a permutation of 0..B-1 (int64)."""
+    key = topk_keys(x_fake.reshape(-1))
+    order = torch.sort(-key, stable=True).indices  # descending keys, the lower index first among ties
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(order.numel(), dtype=order.dtype, device=order.device)
+    return rank
+
+
+def topk_select(x_fake: torch.Tensor, k: int) -> torch.Tensor:
+    """bool [B]: the samples with rank < k -- exactly k of them, whatever the input."""
+    B = x_fake.numel()
+    if not 1 <= int(k) <= B:
+        raise ValueError("topk_select: need 1 <= k <= B, got k=%r, B=%d" % (k, B))
+    return topk_rank(x_fake) < int(k)
+
+
+def topk_threshold(x_fake: torch.Tensor, k: int) -> torch.Tensor:
+    """The logit of the sample with rank k - 1 (the lowest one selected), bits untouched."""
+    return x_fake.reshape(-1)[topk_rank(x_fake) == int(k) - 1][0]
+
+
+def topk_seed(dl_g: torch.Tensor, sel: torch.Tensor, B: int, k: int) -> torch.Tensor:
+    """G's seed under top-k: dl_g[i] * (float32(B) / float32(k)) on the selected rows (one fp32 divide,
+    one fp32 multiply), +0 elsewhere. dl_g = d g_loss / d logit_fake of the all-sample mean, so the
+    result is the gradient of the mean over the selected k."""
+    scale = torch.tensor(float(B), dtype=torch.float32) / torch.tensor(float(k), dtype=torch.float32)
+    g = dl_g.detach().to(torch.float32)
+    return torch.where(sel.to(torch.bool), g * scale.to(g.device), torch.zeros_like(g))
+
+
+def topk_g_term(x_fake: torch.Tensor, kind: str = "bce") -> torch.Tensor:
+    """G's per-sample loss: bce (target 1, never smoothed), lsgan 0.5 (x - 1)^2, hinge -x."""
+    if kind not in GAN_LOSSES:
+        raise ValueError("gan_loss must be one of %s, got %r" % ("|".join(GAN_LOSSES), kind))
+    if kind == "bce":
+        return sigmoid_cross_entropy_with_logits(x_fake, torch.ones_like(x_fake))
+    if kind == "lsgan":
+        return 0.5 * (x_fake - 1.0).pow(2)
+    return -x_fake
+
+
+def topk_g_loss(x_fake: torch.Tensor, sel: torch.Tensor, kind: str = "bce") -> torch.Tensor:
+    """g_loss_topk = (1 / k) * the sum of G's per-sample loss over the selected (x's dtype: fp32 or
+    fp64); differentiable in x."""
+    sel = sel.to(torch.bool)
+    return topk_g_term(x_fake[sel], kind).sum() / int(sel.sum())
+
+
 def zero_fraction(x: torch.Tensor) -> torch.Tensor:
     """tf.nn.zero_fraction (sparsity summary, distriubted_model.py:80)."""
     return (x == 0).float().mean()

@@ -165,7 +165,10 @@ def run(flags: Flags, out=None) -> int:
     # recorded noise launch takes the length as a constant
     noise_steps = int(flags.instance_noise_steps)
     noise_open = float(flags.instance_noise) != float(flags.instance_noise_end) and noise_steps == 0
-    if lr_open or noise_open:
+    # --g_topk_steps=0 with --g_topk < 1 likewise: the recorded top-k launch takes the length as a constant
+    topk_steps = int(flags.g_topk_steps)
+    topk_open = float(flags.g_topk) < 1.0 and topk_steps == 0
+    if lr_open or noise_open or topk_open:
         total = None  # sample-only mode never steps: any valid length
         if not sample_only:
             hip_engine = flags.engine == "hip" or (flags.engine == "auto" and device.type == "cuda")
@@ -189,8 +192,15 @@ def run(flags: Flags, out=None) -> int:
             if source is not None:
                 source.close()
             raise SystemExit("--instance_noise_steps: %s" % e)
+        try:
+            if topk_open:
+                topk_steps = R.check_g_topk(flags.g_topk, 0, total_steps=1 if total is None else total).steps
+        except ValueError as e:
+            if source is not None:
+                source.close()
+            raise SystemExit("--g_topk_steps: %s" % e)
     try:
-        engine = _build_engine(flags, cfg, B, device, rank, world, lr_steps, noise_steps)
+        engine = _build_engine(flags, cfg, B, device, rank, world, lr_steps, noise_steps, topk_steps)
     except BaseException:
         if source is not None:
             source.close()
@@ -222,6 +232,10 @@ def run(flags: Flags, out=None) -> int:
         if color is not None and color.active:
             print("color augmentation of D's inputs: %s (reals and fakes, ahead of translation / cutout, a fresh "
                   "draw per sample and step)" % color.describe(), file=out, flush=True)
+        topk = getattr(engine, "topk", None)
+        if topk is not None and topk.active:
+            print("top-k generator updates: %s (of the global step; G learns from the k best-scored of its B "
+                  "fakes)" % topk.describe(), file=out, flush=True)
     if flags.log_device_placement:
         for line in placement_report(engine, device, rank, world):
             print(line, file=out, flush=True)
@@ -319,6 +333,12 @@ def run(flags: Flags, out=None) -> int:
                     if noise is not None and noise.active:  # sigma of the step just taken, from the oracle
                         vals.append(SummaryWriter.scalar("instance_noise/sigma", float(R.noise_sigma(
                             step - 1, noise.sigma0, noise.sigma1, noise.steps))))
+                    topk = getattr(engine, "topk", None)
+                    if topk is not None and topk.active:  # the selection of the step just taken
+                        k, g_topk_loss, thr = engine.last_topk()
+                        vals.append(SummaryWriter.scalar("g_topk/k", float(k)))
+                        vals.append(SummaryWriter.scalar("g_topk/threshold", thr))
+                        vals.append(SummaryWriter.scalar("g_loss_topk", g_topk_loss))
                     writer.add_summary_values(vals, step)
                     writer.flush()
                     print("Finished running Summary operation.", file=out)
@@ -382,7 +402,7 @@ def _step_budget(flags, n_ex: int, n_d: int, B: int, world: int):
     return step_per_epoch, max_steps
 
 
-def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps, instance_noise_steps):
+def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps, instance_noise_steps, g_topk_steps):
     return build_engine(cfg, B, device, engine=flags.engine, dtype=flags.dtype, seed=int(flags.seed), rank=rank,
                         world=world, graph=bool(flags.graph), allreduce_dtype=flags.allreduce_dtype,
                         lr=float(flags.learning_rate), beta1=float(flags.beta1),
@@ -396,7 +416,8 @@ def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps, instance_n
                         lr_warmup=int(flags.lr_warmup_steps), instance_noise=float(flags.instance_noise),
                         instance_noise_end=float(flags.instance_noise_end),
                         instance_noise_steps=int(instance_noise_steps), d_augment=str(flags.d_augment),
-                        d_color_augment=str(flags.d_color_augment))
+                        d_color_augment=str(flags.d_color_augment), g_topk=float(flags.g_topk),
+                        g_topk_steps=int(g_topk_steps))
 
 
 def _sample_ema(engine, flags) -> bool:

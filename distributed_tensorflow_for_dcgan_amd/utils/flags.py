@@ -121,6 +121,11 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
     ("d_color_augment", "str", "", "DiffAugment's color policy on the discriminator's inputs, ahead of --d_augment: "
                                       "a comma-separated list of brightness, saturation and contrast, each drawn per "
                                       "sample and step; empty or none turns it off"),
+    ("g_topk", "float", 1.0, "top-k generator updates: G learns only from the k fakes the discriminator scores "
+                             "highest, k annealed linearly from the batch size down to ceil(g_topk * batch_size); "
+                             "the final fraction, 0 < g_topk <= 1. 1 turns it off"),
+    ("g_topk_steps", "int", 0, "length of the anneal of k in steps, 1..2^24; 0 = until the end of training "
+                               "(max_steps after the --epoch cap)"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -232,6 +237,11 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         check_d_color(ns.d_color_augment)
     except ValueError as e:
         parser.error("--d_color_augment: %s" % e)
+    from ..ops.reference import check_g_topk
+    try:  # (--g_topk_steps=0 with --g_topk < 1 stays open here: the trainer resolves it)
+        check_g_topk(ns.g_topk, ns.g_topk_steps, open_ended=True)
+    except (ValueError, TypeError, OverflowError) as e:
+        parser.error("--g_topk / --g_topk_steps: %s" % e)
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
