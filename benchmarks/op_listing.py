@@ -36,7 +36,7 @@ from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig  # no
 POSITIONS = ("_a_fwd", "_a_gd_end", "_b_split", "_b_top_dgrad", "_g_w", "_g_w_layer", "_c_split", "_c_split_a")
 ANONYMOUS = ("_keep", "_s_keep")  # engine attributes whose entries have no stable path
 ENV = ("DCGAN_D_BATCH_NORM", "DCGAN_DDP_SHARD", "DCGAN_D_AUGMENT", "DCGAN_D_COLOR_AUGMENT", "DCGAN_G_TOPK",
-       "DCGAN_G_TOPK_STEPS")
+       "DCGAN_G_TOPK_STEPS", "DCGAN_D_AUGMENT_P", "DCGAN_ADA_TARGET", "DCGAN_ADA_INTERVAL", "DCGAN_ADA_KIMG")
 MIN_PTR = 1 << 16  # smaller integers are sizes, counts and flags
 
 
@@ -177,14 +177,19 @@ def grid(quick=False):
         if mname == "64x64x3":
             variants.append((" force_ddp", {}, dict(ddp=True)) if world == 1
                             else (" shard", {"DCGAN_DDP_SHARD": "1"}, {}))
-        for vname, env, vkw in variants:
+        # adaptive augmentation probability: a fixed p and the controller, beside the ungated listing, where
+        # both augmentation switches are on and nothing else is
+        adas = [("", {})]
+        if aug and color and noise is None and not topk:
+            adas += [(" ada=fixed", dict(d_augment_p=0.5)), (" ada=adaptive", dict(ada_target=0.6, ada_interval=2))]
+        for (vname, env, vkw), (aname, akw) in itertools.product(variants, adas):
             # (DiffAugment / its color policy / top-k off keeps the label it had before the switch existed: those lines
             # compare one to one with a listing from an older tree)
             label = "%s %s d_bn=%d sn=%d d_steps=%d noise=%d world=%d sched=%s%s%s%s%s" % (
                 mname, dtype, d_bn, sn, d_steps, noise is not None, world, sched or "default", vname,
-                " aug=1" if aug else "", " color=1" if color else "", " topk=1" if topk else "")
+                " aug=1" if aug else "", " color=1" if color else "", " topk=1" if topk else "") + aname
             kw = dict(dtype=dtype, d_spectral_norm=sn, d_steps=d_steps, instance_noise=noise or 0.0,
-                      instance_noise_steps=1000, world=world, schedule=sched, **vkw)
+                      instance_noise_steps=1000, world=world, schedule=sched, **vkw, **akw)
             if aug:
                 kw["d_augment"] = aug
             if color:

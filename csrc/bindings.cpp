@@ -23,6 +23,7 @@
 #include <pybind11/stl.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <functional>
 #include <memory>
@@ -1166,6 +1167,23 @@ class Program {
                                     stream_id, &S, s);
     }, AccList().r(x, n * es_).r(step, 8).w(y, n * es_).v);
   }
+  // the checks the gated DiffAugment ops add: the drawing launch needs the state with the gate buffer, and
+  // the gate buffer (and the word of the state it reads) is no part of the images or params
+  void gate_check(const char* op, uintptr_t gates, uintptr_t ada_state, bool draws, uintptr_t x, uintptr_t y,
+                  size_t bytes, uintptr_t params, size_t pbytes, size_t gbytes) const {
+    const std::string o(op);
+    if (!gates) {
+      if (ada_state) throw std::runtime_error(o + ": ada_state given without a gates buffer");
+      return;
+    }
+    if (draws && !ada_state) throw std::runtime_error(o + ": gates with a step counter need ada_state (p24)");
+    auto overlap = [](uintptr_t a, size_t an, uintptr_t b, size_t bn) { return a < b + bn && b < a + an; };
+    if (overlap(gates, gbytes, x, bytes) || overlap(gates, gbytes, y, bytes) || overlap(gates, gbytes, params, pbytes))
+      throw std::runtime_error(o + ": gates must be a buffer of its own");
+    if (ada_state && (overlap(ada_state, 4, y, bytes) || overlap(ada_state, 4, params, pbytes) ||
+                      overlap(ada_state, 4, gates, gbytes)))
+      throw std::runtime_error(o + ": ada_state must be a buffer of its own");
+  }
   // the checks the DiffAugment ops share: a rejected call throws before anything is recorded
   void aug_check(const char* op, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy) const {
     const std::string o(op);
@@ -1181,28 +1199,39 @@ class Program {
   // DiffAugment of D's input x [N][S][S][C] -> y (d_augment_kernel). step != 0: the draws come from
   // the Philox stream (seed, *step, AUG_STREAM) and land in params int32 [N][4]: reads x and the
   // 8-byte counter, writes y and params. step == 0 (the probe): reads x and params, writes y
+  // gates != 0 (adaptive augmentation): the gated kernel. step != 0 also reads the 4 bytes of p24 at
+  // ada_state and writes gates int32 [N]; the probe reads gates
   int d_augment(std::string name, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy,
-                uint64_t seed, uintptr_t step, int stream) {
+                uint64_t seed, uintptr_t step, int stream, uintptr_t gates, uintptr_t ada_state) {
     aug_check("d_augment", x, y, params, N, S, C, policy);
-    const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * 16;
+    const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * 16, gbytes = (size_t)N * 4;
     const int mode = step ? 0 : 1;
+    gate_check("d_augment", gates, mode == 0 ? ada_state : 0, mode == 0, x, y, bytes, params, pbytes, gbytes);
     AccList acc;
     acc.r(x, bytes).w(y, bytes);
     if (mode == 0) acc.r(step, 8).w(params, pbytes); else acc.r(params, pbytes);
+    if (gates && mode == 0) acc.r(ada_state, 4).w(gates, gbytes);
+    else if (gates) acc.r(gates, gbytes);
     return add(name, stream, [=](hipStream_t s) {
-      return KF(dcg_d_augment)(P<const elem_t>(x), P<elem_t>(y), P<int>(params), N, S, C, policy, mode, seed,
-                               P<const unsigned long long>(step), s);
+      return KF(dcg_d_augment_gated)(P<const elem_t>(x), P<elem_t>(y), P<int>(params), N, S, C, policy, mode, seed,
+                                     P<const unsigned long long>(step), P<int>(gates),
+                                     mode == 0 ? P<const int>(ada_state) : nullptr, s);
     }, acc.v);
   }
   // its transpose: gy [N][S][S][C] -> gx through the recorded params rows; reads gy and params, writes gx
+  // gates != 0: under the recorded gate rows int32 [N], which it reads too
   int d_augment_bwd(std::string name, uintptr_t gy, uintptr_t gx, uintptr_t params, int N, int S, int C, int policy,
-                    int stream) {
+                    int stream, uintptr_t gates) {
     aug_check("d_augment_bwd", gy, gx, params, N, S, C, policy);
-    const size_t bytes = (size_t)N * S * S * C * es_;
+    const size_t bytes = (size_t)N * S * S * C * es_, gbytes = (size_t)N * 4;
+    gate_check("d_augment_bwd", gates, 0, false, gy, gx, bytes, params, (size_t)N * 16, gbytes);
+    AccList acc;
+    acc.r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes);
+    if (gates) acc.r(gates, gbytes);
     return add(name, stream, [=](hipStream_t s) {
-      return KF(dcg_d_augment)(P<const elem_t>(gy), P<elem_t>(gx), P<int>(params), N, S, C, policy, 2, 0,
-                               (const unsigned long long*)nullptr, s);
-    }, AccList().r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes).v);
+      return KF(dcg_d_augment_gated)(P<const elem_t>(gy), P<elem_t>(gx), P<int>(params), N, S, C, policy, 2, 0,
+                                     (const unsigned long long*)nullptr, P<int>(gates), (const int*)nullptr, s);
+    }, acc.v);
   }
   // the checks the color ops share, in the style of aug_check: a rejected call throws before anything is recorded
   void color_check(const char* op, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy) const {
@@ -1219,28 +1248,63 @@ class Program {
   // DiffAugment's color policy on D's input x [N][S][S][C] -> y (d_color_kernel), params float [N][4] = (b, s,
   // c, Mx). step != 0: (b, s, c) come from the Philox stream (seed, *step, COLOR_STREAM): reads x and the
   // 8-byte counter, writes y and params. step == 0 (the probe): reads x, reads (b, s, c) of and writes Mx to params
+  // gates != 0 (adaptive augmentation): the gated kernel, as d_augment's
   int d_color(std::string name, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy,
-              uint64_t seed, uintptr_t step, int stream) {
+              uint64_t seed, uintptr_t step, int stream, uintptr_t gates, uintptr_t ada_state) {
     color_check("d_color", x, y, params, N, S, C, policy);
-    const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * 16;
+    const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * 16, gbytes = (size_t)N * 4;
     const int mode = step ? 0 : 1;
+    gate_check("d_color", gates, mode == 0 ? ada_state : 0, mode == 0, x, y, bytes, params, pbytes, gbytes);
     AccList acc;
     acc.r(x, bytes).w(y, bytes);
     if (mode == 0) acc.r(step, 8).w(params, pbytes); else acc.r(params, pbytes).w(params, pbytes);
+    if (gates && mode == 0) acc.r(ada_state, 4).w(gates, gbytes);
+    else if (gates) acc.r(gates, gbytes);
     return add(name, stream, [=](hipStream_t s) {
-      return KF(dcg_d_color)(P<const elem_t>(x), P<elem_t>(y), P<float>(params), N, S, C, policy, mode, seed,
-                             P<const unsigned long long>(step), s);
+      return KF(dcg_d_color_gated)(P<const elem_t>(x), P<elem_t>(y), P<float>(params), N, S, C, policy, mode, seed,
+                                   P<const unsigned long long>(step), P<int>(gates),
+                                   mode == 0 ? P<const int>(ada_state) : nullptr, s);
     }, acc.v);
   }
   // its transpose: gy [N][S][S][C] -> gx under (s, c) of the recorded params rows; reads gy and params, writes gx
+  // gates != 0: under the recorded gate rows int32 [N], which it reads too
   int d_color_bwd(std::string name, uintptr_t gy, uintptr_t gx, uintptr_t params, int N, int S, int C, int policy,
-                  int stream) {
+                  int stream, uintptr_t gates) {
     color_check("d_color_bwd", gy, gx, params, N, S, C, policy);
-    const size_t bytes = (size_t)N * S * S * C * es_;
+    const size_t bytes = (size_t)N * S * S * C * es_, gbytes = (size_t)N * 4;
+    gate_check("d_color_bwd", gates, 0, false, gy, gx, bytes, params, (size_t)N * 16, gbytes);
+    AccList acc;
+    acc.r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes);
+    if (gates) acc.r(gates, gbytes);
     return add(name, stream, [=](hipStream_t s) {
-      return KF(dcg_d_color)(P<const elem_t>(gy), P<elem_t>(gx), P<float>(params), N, S, C, policy, 2, 0,
-                             (const unsigned long long*)nullptr, s);
-    }, AccList().r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes).v);
+      return KF(dcg_d_color_gated)(P<const elem_t>(gy), P<elem_t>(gx), P<float>(params), N, S, C, policy, 2, 0,
+                                   (const unsigned long long*)nullptr, P<int>(gates), (const int*)nullptr, s);
+    }, acc.v);
+  }
+  // one step of the adaptive-augmentation controller (ada_update_kernel): reads the B fp32 real logits,
+  // reads and writes the 32 bytes of state int32 [8] = (p24, acc, cnt, r_acc, windows, 0, 0, 0)
+  int ada_update(std::string name, uintptr_t logits, int64_t B, uintptr_t state, double thr, int64_t target_n,
+                 int64_t delta24, int64_t interval, int stream) {
+    if (!logits || !state) throw std::runtime_error("ada_update: logits and state must be non-null");
+    if (B < 1 || B >= (1ll << 31)) throw std::runtime_error("ada_update: B must be >= 1, got " + std::to_string(B));
+    if (interval < 1 || interval > (int64_t)ADA_MAX_INTERVAL)
+      throw std::runtime_error("ada_update: interval must satisfy 1 <= interval <= 2^16, got " + std::to_string(interval));
+    const int64_t span = B * interval;
+    if (span >= (1ll << 31))
+      throw std::runtime_error("ada_update: B * interval must stay below 2^31, got " + std::to_string(span));
+    if (delta24 < 1 || delta24 > (int64_t)ADA_ONE)
+      throw std::runtime_error("ada_update: delta24 must satisfy 1 <= delta24 <= 2^24, got " + std::to_string(delta24));
+    if (target_n < -span || target_n > span)
+      throw std::runtime_error("ada_update: |target_n| must not exceed B * interval, got " + std::to_string(target_n));
+    if (!(thr == thr) || std::isinf(thr)) throw std::runtime_error("ada_update: thr must be finite");
+    const size_t nb = (size_t)B * 4, sb = (size_t)ADA_STATE_WORDS * 4;
+    if (logits < state + sb && state < logits + nb)
+      throw std::runtime_error("ada_update: state must be a buffer of its own");
+    const int Bi = (int)B, Tn = (int)target_n, d24 = (int)delta24, iv = (int)interval;
+    const float thrf = (float)thr;
+    return add(name, stream, [=](hipStream_t s) {
+      return KF(dcg_ada_update)(P<const float>(logits), Bi, P<int>(state), thrf, Tn, d24, iv, s);
+    }, AccList().r(logits, nb).r(state, sb).w(state, sb).v);
   }
   // fp32 standard normals of the Philox stream (seed, *step, stream_id) -> out float32[n]
   int philox_normal(std::string name, uintptr_t out, size_t n, uint64_t seed, uintptr_t step, uint64_t stream_id,
@@ -1503,14 +1567,16 @@ PYBIND11_MODULE(_dcgan_hip, m) {
            py::arg("steps"), py::arg("stream") = 0)
       .def("d_augment", &Program::d_augment, py::arg("name"), py::arg("x"), py::arg("y"), py::arg("params"),
            py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("seed"), py::arg("step"),
-           py::arg("stream") = 0)
+           py::arg("stream") = 0, py::arg("gates") = 0, py::arg("ada_state") = 0)
       .def("d_augment_bwd", &Program::d_augment_bwd, py::arg("name"), py::arg("gy"), py::arg("gx"), py::arg("params"),
-           py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("stream") = 0)
+           py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("stream") = 0, py::arg("gates") = 0)
       .def("d_color", &Program::d_color, py::arg("name"), py::arg("x"), py::arg("y"), py::arg("params"),
            py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("seed"), py::arg("step"),
-           py::arg("stream") = 0)
+           py::arg("stream") = 0, py::arg("gates") = 0, py::arg("ada_state") = 0)
       .def("d_color_bwd", &Program::d_color_bwd, py::arg("name"), py::arg("gy"), py::arg("gx"), py::arg("params"),
-           py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("stream") = 0)
+           py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("stream") = 0, py::arg("gates") = 0)
+      .def("ada_update", &Program::ada_update, py::arg("name"), py::arg("logits"), py::arg("B"), py::arg("state"),
+           py::arg("thr"), py::arg("target_n"), py::arg("delta24"), py::arg("interval"), py::arg("stream") = 0)
       .def("philox_normal", &Program::philox_normal, py::arg("name"), py::arg("out"), py::arg("n"), py::arg("seed"),
            py::arg("step"), py::arg("stream_id"), py::arg("stream") = 0)
       .def("noise_sigma", &Program::noise_sigma, py::arg("name"), py::arg("steps_ptr"), py::arg("out"), py::arg("n"),

@@ -142,6 +142,22 @@ constexpr int AUG_MAX_SIZE = 1 << 14;  // S: keeps every index of one image insi
 enum ColorPolicy : int { COLOR_BRIGHTNESS = 1, COLOR_SATURATION = 2, COLOR_CONTRAST = 4, COLOR_ALL = 7 };
 constexpr unsigned long long COLOR_STREAM = 3;
 
+// Adaptive augmentation probability (ADA, Karras et al. 2020) for the two policies above: each selected
+// transform applies to a sample with probability p = p24 * 2^-24, p24 an integer in [0, 2^24] that lives
+// in word 0 of a device state int32 [8] = (p24, acc, cnt, r_acc, windows, 0, 0, 0). The gated kernel
+// instances draw one more Philox block per sample -- AUG_GATE_STREAM: w0 translation, w1 cutout;
+// COLOR_GATE_STREAM: w0 brightness, w1 saturation, w2 contrast -- and policy bit i is on iff (w_i >> 8)
+// < p24; they record the effective policy per sample for the transposes. misc.hip ada_update_kernel
+// steers p24 once per step from the real logits x_0..x_{B-1}:
+//   acc += sum_i ((x_i > thr) - (x_i < thr));  cnt += 1
+//   cnt == interval:  p24 = clamp(p24 + ((acc > Tn) - (acc < Tn)) * delta24, 0, 2^24);
+//                     r_acc = acc; windows += 1; acc = cnt = 0
+constexpr unsigned long long AUG_GATE_STREAM = 4;
+constexpr unsigned long long COLOR_GATE_STREAM = 5;
+constexpr int ADA_ONE = 1 << 24;
+constexpr int ADA_MAX_INTERVAL = 1 << 16;
+constexpr int ADA_STATE_WORDS = 8;
+
 // GAN objectives of the loss / head kernels (misc.hip gan_loss_block). The first three are the
 // ids of the launchers and bindings; GAN_BCE_T is the kernel instance of bce with a smoothed
 // real target, which the launchers pick themselves (real_target != 1).

@@ -101,6 +101,19 @@ int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S
 // -2: a null pointer, x == y, N < 1, S outside 1..2^14, C outside 1..4, an empty or unknown policy / mode
 int DCG_API(dcg_d_color)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy, int mode,
                          uint64_t seed, const unsigned long long* step, hipStream_t s);
+// the same two with adaptive gates (kernels.h ADA): gates int32 [N], the effective policy per sample, written
+// in mode 0 from the Philox gate streams and p24 = ada[0], read in modes 1 and 2 (ada unused). gates ==
+// nullptr: the ungated kernels. -2 also: gates in mode 0 without ada, ada without gates
+int DCG_API(dcg_d_augment_gated)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy, int mode,
+                                 uint64_t seed, const unsigned long long* step, int* gates, const int* ada,
+                                 hipStream_t s);
+int DCG_API(dcg_d_color_gated)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy, int mode,
+                               uint64_t seed, const unsigned long long* step, int* gates, const int* ada,
+                               hipStream_t s);
+// one step of the ADA controller on state int32 [8] from the B real logits (fp32). -2: a null pointer, B < 1,
+// interval outside 1..2^16, B * interval >= 2^31, delta24 outside 1..2^24, |target_n| > B * interval, thr NaN
+int DCG_API(dcg_ada_update)(const float* logits, int B, int* state, float thr, int target_n, int delta24,
+                            int interval, hipStream_t s);
 int DCG_API(dcg_im2col_s2)(const elem_t* src, elem_t* dst, int B, int H, int W, int C, int Ho, int Wo, int pl_y, int pl_x,
                   int Kpad, hipStream_t s);
 int DCG_API(dcg_cast_to_bf16)(const void* src, int src_dtype, elem_t* dst, size_t n, float scale, float shift, hipStream_t s);

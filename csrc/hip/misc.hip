@@ -1026,13 +1026,30 @@ __global__ __launch_bounds__(256) void instance_noise_kernel(const E* __restrict
 // vec: one 16-byte store per thread over the row-flattened image (rows a multiple of 16 bytes and y
 // 16-byte aligned: a thread's V elements then share a row); else V element stores per thread,
 // strided by 256. Source loads are element loads (they sit tx * C elements off the output).
-template <typename U, int MODE>
-__global__ __launch_bounds__(256) void d_augment_kernel(const U* __restrict__ x, U* __restrict__ y,
-                                                        int* __restrict__ params, int S, int C, int policy,
-                                                        unsigned bpi, uint64_t seed,
-                                                        const unsigned long long* __restrict__ step, int vec) {
+// GATED (adaptive augmentation, kernels.h ADA): the image's effective policy is policy & gate mask.
+// MODE 0 draws the mask from words w0 (translation), w1 (cutout) of one more block, counter (n, t,
+// AUG_GATE_STREAM): bit i on iff (w_i >> 8) < p24 = ada[0], read once; the thread that records
+// params[n] records it in gates[n]. MODE 1 / 2 read gates[n]. The draws (ty, tx, oy, ox) are drawn and
+// recorded whatever the gates say. Workgroup-uniform: a workgroup never spans two images. The ungated
+// kernel inlines the same body with GATED = false: no load, no branch, its old arguments.
+template <typename U, int MODE, bool GATED>
+__device__ __forceinline__ void d_augment_body(const U* __restrict__ x, U* __restrict__ y, int* __restrict__ params,
+                                               int S, int C, int policy, unsigned bpi, uint64_t seed,
+                                               const unsigned long long* __restrict__ step, int vec,
+                                               int* __restrict__ gates, const int* __restrict__ ada) {
   constexpr int V = 16 / (int)sizeof(U);
   const unsigned n = blockIdx.x / bpi, chunk = blockIdx.x - n * bpi;
+  if (GATED) {
+    if (MODE == 0) {
+      uint32_t gw[4];
+      philox_block((size_t)n, seed, step[0], AUG_GATE_STREAM, gw);
+      const uint32_t p24 = (uint32_t)ada[0];
+      policy &= ((gw[0] >> 8) < p24 ? (int)AUG_TRANSLATION : 0) | ((gw[1] >> 8) < p24 ? (int)AUG_CUTOUT : 0);
+      if (chunk == 0 && threadIdx.x == 0) gates[n] = policy;
+    } else {
+      policy &= gates[n];
+    }
+  }
   const int k = (S + 1) / 2;
   int ty, tx, oy, ox;
   if (MODE == 0) {
@@ -1100,6 +1117,23 @@ __global__ __launch_bounds__(256) void d_augment_kernel(const U* __restrict__ x,
   }
 }
 
+template <typename U, int MODE>
+__global__ __launch_bounds__(256) void d_augment_kernel(const U* __restrict__ x, U* __restrict__ y,
+                                                        int* __restrict__ params, int S, int C, int policy,
+                                                        unsigned bpi, uint64_t seed,
+                                                        const unsigned long long* __restrict__ step, int vec) {
+  d_augment_body<U, MODE, false>(x, y, params, S, C, policy, bpi, seed, step, vec, nullptr, nullptr);
+}
+
+template <typename U, int MODE>
+__global__ __launch_bounds__(256) void d_augment_gated_kernel(const U* __restrict__ x, U* __restrict__ y,
+                                                              int* __restrict__ params, int S, int C, int policy,
+                                                              unsigned bpi, uint64_t seed,
+                                                              const unsigned long long* __restrict__ step, int vec,
+                                                              int* __restrict__ gates, const int* __restrict__ ada) {
+  d_augment_body<U, MODE, true>(x, y, params, S, C, policy, bpi, seed, step, vec, gates, ada);
+}
+
 // ---------------------------------------------------------------- DiffAugment's color policy on D's input
 // Brightness, saturation and contrast (kernels.h ColorPolicy) of x [N][S][S][C] into y, per sample n
 // from the words w0..w2 of the Philox block at counter (n, t = *step, COLOR_STREAM) of the step's z
@@ -1158,11 +1192,15 @@ __device__ __forceinline__ float color_block_sum(float acc, float* wsum) {
   return t;
 }
 
-template <typename E, int MODE, int C>
-__global__ __launch_bounds__(COLOR_THREADS) void d_color_kernel(const E* __restrict__ x, E* __restrict__ y,
-                                                                float* __restrict__ params, int S, int policy,
-                                                                uint64_t seed,
-                                                                const unsigned long long* __restrict__ step, int vec) {
+// GATED: as d_augment_body's. MODE 0 draws the gate mask from words w0 (brightness), w1 (saturation), w2
+// (contrast) of the block at counter (n, t, COLOR_GATE_STREAM) against p24 = ada[0] and thread 0 records
+// it in gates[n]; MODE 1 / 2 read gates[n]. One workgroup per image: every branch on the effective
+// policy -- the mean pass and the __syncthreads() in it included -- is taken by all its threads or none.
+template <typename E, int MODE, int C, bool GATED>
+__device__ __forceinline__ void d_color_body(const E* __restrict__ x, E* __restrict__ y, float* __restrict__ params,
+                                             int S, int policy, uint64_t seed,
+                                             const unsigned long long* __restrict__ step, int vec,
+                                             int* __restrict__ gates, const int* __restrict__ ada) {
 #pragma clang fp contract(off)
   constexpr int V = 16 / (int)sizeof(E);
   constexpr int GE = V * C;  // elements of a group
@@ -1186,6 +1224,18 @@ __global__ __launch_bounds__(COLOR_THREADS) void d_color_kernel(const E* __restr
     c = u2 + 0.5f;
   } else {
     b = p[0]; s = p[1]; c = p[2];
+  }
+  if (GATED) {
+    if (MODE == 0) {
+      uint32_t gw[4];
+      philox_block((size_t)n, seed, step[0], COLOR_GATE_STREAM, gw);
+      const uint32_t p24 = (uint32_t)ada[0];
+      policy &= ((gw[0] >> 8) < p24 ? (int)COLOR_BRIGHTNESS : 0) | ((gw[1] >> 8) < p24 ? (int)COLOR_SATURATION : 0) |
+                ((gw[2] >> 8) < p24 ? (int)COLOR_CONTRAST : 0);
+      if (tid == 0) gates[n] = policy;
+    } else {
+      policy &= gates[n];
+    }
   }
   const bool bri = MODE != 2 && (policy & COLOR_BRIGHTNESS) != 0;
   const bool sat = (policy & COLOR_SATURATION) != 0, con = (policy & COLOR_CONTRAST) != 0;
@@ -1272,6 +1322,60 @@ __global__ __launch_bounds__(COLOR_THREADS) void d_color_kernel(const E* __restr
     float v[GE];
     load(g, v);
     apply_store(g, v);
+  }
+}
+
+template <typename E, int MODE, int C>
+__global__ __launch_bounds__(COLOR_THREADS) void d_color_kernel(const E* __restrict__ x, E* __restrict__ y,
+                                                                float* __restrict__ params, int S, int policy,
+                                                                uint64_t seed,
+                                                                const unsigned long long* __restrict__ step, int vec) {
+  d_color_body<E, MODE, C, false>(x, y, params, S, policy, seed, step, vec, nullptr, nullptr);
+}
+
+template <typename E, int MODE, int C>
+__global__ __launch_bounds__(COLOR_THREADS) void d_color_gated_kernel(const E* __restrict__ x, E* __restrict__ y,
+                                                                      float* __restrict__ params, int S, int policy,
+                                                                      uint64_t seed,
+                                                                      const unsigned long long* __restrict__ step,
+                                                                      int vec, int* __restrict__ gates,
+                                                                      const int* __restrict__ ada) {
+  d_color_body<E, MODE, C, true>(x, y, params, S, policy, seed, step, vec, gates, ada);
+}
+
+// ---------------------------------------------------------------- adaptive augmentation: the controller
+// One step of kernels.h's ADA state machine on state int32 [8] = (p24, acc, cnt, r_acc, windows, 0, 0, 0)
+// from the B real logits x (fp32): a = sum_i ((x_i > thr) - (x_i < thr)), NaN counting 0. ONE workgroup
+// of 256 threads strides over x; the integer sum goes across the wave by xor shuffles and across the 4
+// waves through LDS -- integer addition: any order is bitwise the same, no atomics. Thread 0 then
+// updates the state. Everything else is a kernel argument; it reads no step counter.
+__global__ __launch_bounds__(256) void ada_update_kernel(const float* __restrict__ x, int B, int* __restrict__ state,
+                                                         float thr, int Tn, int delta24, int interval) {
+  __shared__ int wsum[4];
+  const int tid = threadIdx.x;
+  int a = 0;
+  for (int i = tid; i < B; i += 256) {
+    const float xi = x[i];
+    a += (int)(xi > thr) - (int)(xi < thr);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+  if ((tid & 63) == 0) wsum[tid >> 6] = a;
+  __syncthreads();
+  if (tid == 0) {
+    int p24 = state[0];
+    int acc = state[1] + wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    int cnt = state[2] + 1;
+    if (cnt == interval) {
+      const int d = (int)(acc > Tn) - (int)(acc < Tn);
+      p24 = min(max(p24 + d * delta24, 0), ADA_ONE);
+      state[0] = p24;
+      state[3] = acc;
+      state[4] = state[4] + 1;
+      acc = cnt = 0;
+    }
+    state[1] = acc;
+    state[2] = cnt;
   }
 }
 
@@ -1654,7 +1758,15 @@ extern "C" int DCG_API(dcg_instance_noise)(const elem_t* x, elem_t* y, size_t n,
 
 extern "C" int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy,
                                       int mode, uint64_t seed, const unsigned long long* step, hipStream_t s) {
+  return DCG_API(dcg_d_augment_gated)(x, y, params, N, S, C, policy, mode, seed, step, nullptr, nullptr, s);
+}
+
+// gates == nullptr: the ungated kernels, launched exactly as before
+extern "C" int DCG_API(dcg_d_augment_gated)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy,
+                                            int mode, uint64_t seed, const unsigned long long* step, int* gates,
+                                            const int* ada, hipStream_t s) {
   if (!x || !y || !params || x == y || (mode == 0 && !step)) return -2;
+  if (gates ? (mode == 0 && !ada) : ada != nullptr) return -2;
   if (N < 1 || S < 1 || S > AUG_MAX_SIZE || C < 1 || C > 4 || policy < 1 || policy > AUG_ALL || mode < 0 || mode > 2)
     return -2;
   typedef std::conditional<sizeof(elem_t) == 2, uint16_t, uint32_t>::type U;
@@ -1666,6 +1778,18 @@ extern "C" int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, i
   const dim3 grid((unsigned)(bpi * (size_t)N)), block(256);
   const U* xu = reinterpret_cast<const U*>(x);
   U* yu = reinterpret_cast<U*>(y);
+  if (gates) {
+    if (mode == 0)
+      hipLaunchKernelGGL((d_augment_gated_kernel<U, 0>), grid, block, 0, s, xu, yu, params, S, C, policy,
+                         (unsigned)bpi, seed, step, vec, gates, ada);
+    else if (mode == 1)
+      hipLaunchKernelGGL((d_augment_gated_kernel<U, 1>), grid, block, 0, s, xu, yu, params, S, C, policy,
+                         (unsigned)bpi, seed, step, vec, gates, ada);
+    else
+      hipLaunchKernelGGL((d_augment_gated_kernel<U, 2>), grid, block, 0, s, xu, yu, params, S, C, policy,
+                         (unsigned)bpi, seed, step, vec, gates, ada);
+    return (int)hipGetLastError();
+  }
   if (mode == 0)
     hipLaunchKernelGGL((d_augment_kernel<U, 0>), grid, block, 0, s, xu, yu, params, S, C, policy, (unsigned)bpi, seed,
                        step, vec);
@@ -1680,32 +1804,54 @@ extern "C" int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, i
 
 template <int MODE, int C>
 static void d_color_launch(const elem_t* x, elem_t* y, float* params, int N, int S, int policy, uint64_t seed,
-                           const unsigned long long* step, int vec, hipStream_t s) {
-  hipLaunchKernelGGL((d_color_kernel<elem_t, MODE, C>), dim3((unsigned)N), dim3(COLOR_THREADS), 0, s, x, y, params, S,
-                     policy, seed, step, vec);
+                           const unsigned long long* step, int vec, int* gates, const int* ada, hipStream_t s) {
+  if (gates)
+    hipLaunchKernelGGL((d_color_gated_kernel<elem_t, MODE, C>), dim3((unsigned)N), dim3(COLOR_THREADS), 0, s, x, y,
+                       params, S, policy, seed, step, vec, gates, ada);
+  else
+    hipLaunchKernelGGL((d_color_kernel<elem_t, MODE, C>), dim3((unsigned)N), dim3(COLOR_THREADS), 0, s, x, y, params,
+                       S, policy, seed, step, vec);
 }
 
 template <int MODE>
 static void d_color_launch_c(int C, const elem_t* x, elem_t* y, float* params, int N, int S, int policy, uint64_t seed,
-                             const unsigned long long* step, int vec, hipStream_t s) {
+                             const unsigned long long* step, int vec, int* gates, const int* ada, hipStream_t s) {
   switch (C) {
-    case 1: d_color_launch<MODE, 1>(x, y, params, N, S, policy, seed, step, vec, s); break;
-    case 2: d_color_launch<MODE, 2>(x, y, params, N, S, policy, seed, step, vec, s); break;
-    case 3: d_color_launch<MODE, 3>(x, y, params, N, S, policy, seed, step, vec, s); break;
-    default: d_color_launch<MODE, 4>(x, y, params, N, S, policy, seed, step, vec, s); break;
+    case 1: d_color_launch<MODE, 1>(x, y, params, N, S, policy, seed, step, vec, gates, ada, s); break;
+    case 2: d_color_launch<MODE, 2>(x, y, params, N, S, policy, seed, step, vec, gates, ada, s); break;
+    case 3: d_color_launch<MODE, 3>(x, y, params, N, S, policy, seed, step, vec, gates, ada, s); break;
+    default: d_color_launch<MODE, 4>(x, y, params, N, S, policy, seed, step, vec, gates, ada, s); break;
   }
 }
 
 extern "C" int DCG_API(dcg_d_color)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy,
                                     int mode, uint64_t seed, const unsigned long long* step, hipStream_t s) {
+  return DCG_API(dcg_d_color_gated)(x, y, params, N, S, C, policy, mode, seed, step, nullptr, nullptr, s);
+}
+
+// gates == nullptr: the ungated kernels, launched exactly as before
+extern "C" int DCG_API(dcg_d_color_gated)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy,
+                                          int mode, uint64_t seed, const unsigned long long* step, int* gates,
+                                          const int* ada, hipStream_t s) {
   if (!x || !y || !params || x == y || (mode == 0 && !step)) return -2;
+  if (gates ? (mode == 0 && !ada) : ada != nullptr) return -2;
   if (N < 1 || S < 1 || S > AUG_MAX_SIZE || C < 1 || C > 4 || policy < 1 || policy > COLOR_ALL || mode < 0 || mode > 2)
     return -2;
   constexpr size_t V = 16 / sizeof(elem_t);
   const int vec = ((size_t)S * S) % V == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
-  if (mode == 0) d_color_launch_c<0>(C, x, y, params, N, S, policy, seed, step, vec, s);
-  else if (mode == 1) d_color_launch_c<1>(C, x, y, params, N, S, policy, seed, step, vec, s);
-  else d_color_launch_c<2>(C, x, y, params, N, S, policy, seed, step, vec, s);
+  if (mode == 0) d_color_launch_c<0>(C, x, y, params, N, S, policy, seed, step, vec, gates, ada, s);
+  else if (mode == 1) d_color_launch_c<1>(C, x, y, params, N, S, policy, seed, step, vec, gates, ada, s);
+  else d_color_launch_c<2>(C, x, y, params, N, S, policy, seed, step, vec, gates, ada, s);
+  return (int)hipGetLastError();
+}
+
+extern "C" int DCG_API(dcg_ada_update)(const float* logits, int B, int* state, float thr, int target_n, int delta24,
+                                       int interval, hipStream_t s) {
+  if (!logits || !state || B < 1 || interval < 1 || interval > ADA_MAX_INTERVAL) return -2;
+  const long long span = (long long)B * interval;
+  if (span >= (1ll << 31) || delta24 < 1 || delta24 > ADA_ONE || target_n > span || target_n < -span || !(thr == thr))
+    return -2;
+  hipLaunchKernelGGL(ada_update_kernel, dim3(1), dim3(256), 0, s, logits, B, state, thr, target_n, delta24, interval);
   return (int)hipGetLastError();
 }
 

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import tf_bundle
+from ..ops.reference import ADA_KEYS
 
 INDEX_FILE = "checkpoint"
 
@@ -84,6 +85,8 @@ def latest_checkpoint(ckpt_dir: str) -> Optional[str]:
 BN_STEPS_KEYS = ("g_bn/ExponentialMovingAverage/local_step", "d_bn/ExponentialMovingAverage/local_step")
 
 
+ADA_PREFIX = "ada/"  # the adaptive-augmentation controller's int32 state: ada/p24, ada/acc, ... (ops.reference.ADA_KEYS)
+
 G_EMA_SUFFIX = "/ExponentialMovingAverage"  # shadow of a G variable (never a BN ".../moments/..." key)
 
 
@@ -117,6 +120,10 @@ def collect_state(engine) -> "OrderedDict[str, np.ndarray]":
     if sn is not None:  # D's spectral-norm state: <var>/sn_u, <var>/sn_v, <var>/sn_sigma
         for k, v in sn.tf_names().items():
             out[k] = v.detach().cpu().numpy().astype(np.float32)
+    ada = getattr(m, "ada", None)
+    if ada:  # the adaptive-augmentation controller's state (only with the controller on): int32 scalars
+        for k in ADA_KEYS:
+            out[ADA_PREFIX + k] = np.array(int(ada[k]), dtype=np.int32)
     return out
 
 
@@ -169,6 +176,22 @@ def apply_state(engine, sd: Dict[str, np.ndarray], strict: bool = True) -> Dict[
             else:
                 engine.reset_d_sn()
                 info["d_sn"] = "initialised from the loaded weights (the checkpoint has no sn_u / sn_v / sn_sigma)"
+    ada = getattr(engine, "ada", None)
+    if ada is not None and ada.adaptive:
+        # the adaptive-augmentation controller: the saved five words when all are there (an exact resume),
+        # else the initial p (a checkpoint written without the controller); after_state_load applies it
+        if all(ADA_PREFIX + k in sd for k in ADA_KEYS):
+            m.ada = {k: int(np.asarray(sd[ADA_PREFIX + k]).reshape(-1)[0]) for k in ADA_KEYS}
+            info["ada"] = "loaded (p = %.6f)" % (m.ada["p24"] / float(1 << 24))
+            if not 0 <= m.ada["cnt"] < ada.interval:
+                # written under a longer --ada_interval: the open window could never close (the controller
+                # tests cnt == interval), so it is dropped; p, r_acc and the window count are kept
+                info["ada"] += "; the open window of %d steps is dropped: it does not fit --ada_interval=%d" % (
+                    m.ada["cnt"], ada.interval)
+                m.ada["acc"] = m.ada["cnt"] = 0
+        else:
+            m.ada = None
+            info["ada"] = "starts from p = %g (the checkpoint has no ada/p24 ... ada/windows)" % ada.p
     if hasattr(engine, "after_state_load"):
         engine.after_state_load()
     return info

@@ -37,7 +37,9 @@ class ReferenceEngine:
                  instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
                  instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
                  d_color_augment: Optional[str] = None, g_topk: Optional[float] = None,
-                 g_topk_steps: Optional[int] = None, **_):
+                 g_topk_steps: Optional[int] = None, d_augment_p: Optional[float] = None,
+                 ada_target: Optional[float] = None, ada_interval: Optional[int] = None,
+                 ada_kimg: Optional[float] = None, **_):
         self.cfg = cfg
         self.batch_size = batch_size
         self.device = device
@@ -68,13 +70,16 @@ class ReferenceEngine:
         # DiffAugment of D's inputs: None = DCGAN_D_AUGMENT; drawn from the same seed as the noise
         self.aug = R.resolve_d_augment(d_augment)
         self.color = R.resolve_d_color(d_color_augment)  # its color policy; None = DCGAN_D_COLOR_AUGMENT
+        # adaptive augmentation probability: None = DCGAN_D_AUGMENT_P / DCGAN_ADA_TARGET / _INTERVAL / _KIMG
+        self.ada = R.resolve_ada(d_augment_p, ada_target, ada_interval, ada_kimg,
+                                 augmented=self.aug.active or self.color.active, batch_size=batch_size)
         # top-k generator updates: None = DCGAN_G_TOPK / DCGAN_G_TOPK_STEPS
         self.topk = R.resolve_g_topk(g_topk, g_topk_steps)
         zs = self.seed if z_seed is None else int(z_seed)
         self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None,
                                        instance_noise=self.noise, noise_seed=zs * 1000003 + 17 + 7919 * rank,
                                        d_augment=self.aug, d_color_augment=self.color, g_topk=self.topk,
-                                       g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth,
+                                       d_ada=self.ada, world=world, g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth,
                                        d_spectral_norm=bool(d_spectral_norm), seed=seed, d_steps=d_steps,
                                        beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=self.lr_sched)
         self.d_steps = self.step_impl.d_steps
@@ -188,8 +193,24 @@ class ReferenceEngine:
                                                 topk=False)
         return {"d_loss": float(out["d_loss"]), "g_loss": float(out["g_loss"])}
 
+    def ada_status(self):
+        """The adaptive-augmentation state {p24, acc, cnt, r_acc, windows, p, r_t}; None when off."""
+        if not self.ada.active:
+            return None
+        st = dict(zip(R.ADA_KEYS, self.step_impl.ada_state))
+        st["p"] = st["p24"] / float(R.ADA_ONE)
+        st["r_t"] = st["r_acc"] / float(self.batch_size * self.ada.interval)
+        return st
+
     def sync_state_for_checkpoint(self) -> None:
-        pass
+        self.model.ada = dict(zip(R.ADA_KEYS, self.step_impl.ada_state)) if self.ada.adaptive else None
+
+    def after_state_load(self) -> None:
+        """Adaptive augmentation: the controller's state from the loaded dictionary (None: the initial p)."""
+        if self.ada.adaptive:
+            st = getattr(self.model, "ada", None)
+            self.step_impl.ada_state = R.ada_state(R.ada_p24(self.ada.p)) if st is None else \
+                [int(st[k]) for k in R.ADA_KEYS] + [0] * (R.ADA_STATE_WORDS - len(R.ADA_KEYS))
 
     def sync_check_tensors(self):
         """What the cross-rank divergence check compares."""
@@ -220,7 +241,10 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                  instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
                  instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
                  d_color_augment: Optional[str] = None, g_topk: Optional[float] = None,
-                 g_topk_steps: Optional[int] = None):
+                 g_topk_steps: Optional[int] = None, d_augment_p: Optional[float] = None,
+                 ada_target: Optional[float] = None, ada_interval: Optional[int] = None,
+                 ada_kimg: Optional[float] = None):
+    ada_kw = dict(d_augment_p=d_augment_p, ada_target=ada_target, ada_interval=ada_interval, ada_kimg=ada_kimg)
     if engine == "auto":  # every dtype (bf16 / fp16 / fp32) runs on the HIP kernels on an MI355X
         engine = "hip" if device.type == "cuda" else "reference"
     if engine == "reference":
@@ -232,7 +256,7 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                                lr_warmup=lr_warmup, instance_noise=instance_noise,
                                instance_noise_end=instance_noise_end, instance_noise_steps=instance_noise_steps,
                                d_augment=d_augment, d_color_augment=d_color_augment, g_topk=g_topk,
-                               g_topk_steps=g_topk_steps)
+                               g_topk_steps=g_topk_steps, **ada_kw)
     if engine == "hip":
         from .hip_engine import HipEngine
         return HipEngine(cfg, batch_size, device, dtype=dtype, seed=seed, lr=lr, beta1=beta1,
@@ -244,5 +268,5 @@ def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine
                          lr_warmup=lr_warmup, instance_noise=instance_noise,
                          instance_noise_end=instance_noise_end, instance_noise_steps=instance_noise_steps,
                          d_augment=d_augment, d_color_augment=d_color_augment, g_topk=g_topk,
-                         g_topk_steps=g_topk_steps)
+                         g_topk_steps=g_topk_steps, **ada_kw)
     raise ValueError("unknown engine %r" % engine)

@@ -180,7 +180,9 @@ class HipEngineAux:
 
     def _step_progs(self):
         subs = [p for pair in self._sub for p in pair] + [self.progDU] * len(self._sub)
-        return [p for p in (self.progA, self.progB, self.progW, self.progC, getattr(self, "progSh", None))
+        ada = getattr(self, "progAda", None)  # (listed where the schedule issues it on the D chain's stream)
+        chain = (self.progB, ada) if self._schedule() == "fused" and self._ada_at_tail() else (ada, self.progB)
+        return [p for p in (self.progA,) + chain + (self.progW, self.progC, getattr(self, "progSh", None))
                 if p is not None] + subs
 
     def sub_op_names(self, k: int) -> List[str]:

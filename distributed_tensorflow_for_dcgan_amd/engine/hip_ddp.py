@@ -274,6 +274,8 @@ class HipDDPMixin:
         alt = ex.alt[0]
         ex.run(self.progA, [cs, ex.side], 0, self._a_fwd)
         ex.wait(alt, cs)
+        if self.progAda is not None:  # adaptive augmentation: the controller heads the D chain
+            ex.run(self.progAda, ex.alt)
         ex.run(self.progB, ex.alt, 0, self._b_split)
         self._ar_launch(ex, "dtop", alt)
         ex.run(self.progB, ex.alt, self._b_split, -1)

@@ -170,7 +170,9 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
                  instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
                  d_color_augment: Optional[str] = None, g_topk: Optional[float] = None,
-                 g_topk_steps: Optional[int] = None, **_):
+                 g_topk_steps: Optional[int] = None, d_augment_p: Optional[float] = None,
+                 ada_target: Optional[float] = None, ada_interval: Optional[int] = None,
+                 ada_kimg: Optional[float] = None, **_):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -222,6 +224,16 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # `d_color_bwd` applies transposed to the g_loss chain's image gradient, behind `d_aug_bwd` and
         # ahead of G's tanh backward. None: DCGAN_D_COLOR_AUGMENT. Off: no buffer, no op
         self.color = R.resolve_d_color(d_color_augment)
+        # adaptive augmentation probability (ops.reference.DAda): each selected policy of the two switches
+        # above applies to a sample with probability p = p24 * 2^-24. `d_color` / `d_aug` are then recorded
+        # as their gated kernels, which read p24 from the device state `ada_state` and record the per-sample
+        # gate masks that the two `_bwd` ops replay. With a target, one more recorded launch per full step
+        # (`ada_update`, on the D chain's stream) steers p24 from the real half of the logits, so graph
+        # and eager replays follow the live state with no host round trip. D sub-steps gate with the live
+        # p24 and record no controller op. None: DCGAN_D_AUGMENT_P / DCGAN_ADA_TARGET / _INTERVAL / _KIMG.
+        # Off (p = 1, no target): no buffer, no op, the ungated kernels
+        self.ada = R.resolve_ada(d_augment_p, ada_target, ada_interval, ada_kimg,
+                                 augmented=self.aug.active or self.color.active, batch_size=batch_size)
         # top-k generator updates (ops.reference.GTopK): the g_loss chain's seed keeps the k(t) fakes D
         # scores highest, times B / k, and is +0 on the others; one recorded launch (`g_topk`), the first
         # op behind the forward on the G chain's stream, selects them from the logits and the device step
@@ -290,6 +302,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.bucket_mb = bucket_mb
         self._exec = None
         self._alloc()
+        if self.ada.active and self.ddp and not self.dry:
+            D.broadcast_tensors([self.ada_state])  # rank 0's, as the parameters above
         self._build()
         if not self.dry:
             self._repack_weights_now()
@@ -337,6 +351,13 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # the color policy: the colored copy (shared the same way) and float32 [2B][4] = (b, s, c, Mx)
         self.d_colored = torch.zeros_like(self.d_in) if self.color.active else None
         self.color_params = t(B2, 4, dtype=torch.float32, zero=True) if self.color.active else None
+        # adaptive augmentation: the controller's state int32 [8] = (p24, acc, cnt, r_acc, windows, 0, 0, 0)
+        # and the gate masks int32 [2B] each gated kernel records (the effective policy per sample)
+        self.ada_state = self.aug_gates = self.color_gates = None
+        if self.ada.active:
+            self.ada_state = torch.tensor(R.ada_state(R.ada_p24(self.ada.p)), dtype=torch.int32, device=self.device)
+            self.aug_gates = t(B2, dtype=torch.int32, zero=True) if self.aug.active else None
+            self.color_gates = t(B2, dtype=torch.int32, zero=True) if self.color.active else None
         self.d_x, self.d_a = {}, {}
         for i, L in enumerate(self.dl):
             if L.bn:
@@ -443,6 +464,18 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self._a_fwd = self.progA.size()  # forward done: D's d_loss backward may start from here
         self._build_gloss_and_g_backward(self.progA, self.progW)
         self._build_d_backward_dloss(self.progB)  # sets self._b_split (top layer done)
+        # adaptive augmentation: the controller, one op on the D chain's stream (behind the head launch that
+        # wrote the logits, off the G chain's critical path): behind the chain in the fused step, ahead of
+        # it in the DDP schedules (_ada_at_tail). A program of its own: the D sub-steps share progB's
+        # layout and record no controller op
+        self.progAda = None
+        if self.ada.adaptive:
+            self.progAda = self._prog()
+            a, B = self.ada, self.B
+            self.progAda.ada_update("ada_update", _p(self.logits), B, _p(self.ada_state),
+                                    R.ada_threshold(self.gan_loss, self.label_smooth),
+                                    R.ada_target_n(a.target, B, a.interval),
+                                    R.ada_delta24(self.world, B, a.interval, a.kimg), a.interval, 0)
         # D-gradient slice final after the D chain's first segment: the top conv layer (+ its BN)
         # and the head, which the ParamSet lays out last
         self._d_top_off = self.model.d.offsets[self.dl[-1].name + "/w"][0]
@@ -779,13 +812,15 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # policy (stream 3) comes first: color, then translation / cutout, then noise
         prev = self._d_input(sub, noise)
         clean = d_in
+        # (adaptive augmentation: the gated kernels, gates from streams 5 / 4 against the live p24)
+        gate = lambda g: dict(gates=_p(g), ada_state=_p(self.ada_state)) if self.ada.active else {}  # noqa: E731
         if noise and self.color.active:
             prog.d_color("d_color", _p(d_in), _p(self.d_colored), _p(self.color_params), B2, cfg.output_size,
-                         cfg.c_dim, self.color.mask, zseed, _p(self.step_counter), 0)
+                         cfg.c_dim, self.color.mask, zseed, _p(self.step_counter), 0, **gate(self.color_gates))
             clean = self.d_colored
         if noise and self.aug.active:
             prog.d_augment("d_aug", _p(clean), _p(self.d_auged), _p(self.aug_params), B2, cfg.output_size, cfg.c_dim,
-                           self.aug.mask, zseed, _p(self.step_counter), 0)
+                           self.aug.mask, zseed, _p(self.step_counter), 0, **gate(self.aug_gates))
             clean = self.d_auged
         if prev is not clean:
             prog.instance_noise("d_noise", _p(clean), _p(prev), d_in.numel(), zseed, _p(self.step_counter),
@@ -1059,12 +1094,14 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             # DiffAugment: dL/d(augmented fake) -> dL/d(fake), the transposed gather over the draws the
             # forward recorded for the fake half (rows B..2B-1 of aug_params)
             prog.d_augment_bwd("d_aug_bwd", _p(self.img_grad), _p(self.img_grad_t), _p(self.aug_params[B:]), B,
-                               L.in_hw, L.cin, self.aug.mask, 0)
+                               L.in_hw, L.cin, self.aug.mask, 0,
+                               **(dict(gates=_p(self.aug_gates[B:])) if self.ada.active else {}))
         if self.color.active:
             # the color policy: dL/d(colored fake) -> dL/d(fake), its transposed map under (s, c) of the rows
             # the forward recorded for the fake half
             prog.d_color_bwd("d_color_bwd", _p(self.img_grad_t if self.aug.active else self.img_grad),
-                             _p(self.img_grad_c), _p(self.color_params[B:]), B, L.in_hw, L.cin, self.color.mask, 0)
+                             _p(self.img_grad_c), _p(self.color_params[B:]), B, L.in_hw, L.cin, self.color.mask, 0,
+                             **(dict(gates=_p(self.color_gates[B:])) if self.ada.active else {}))
         self._build_g_backward(prog, progw)
 
     def _build_g_backward(self, prog, progw):
@@ -1273,17 +1310,18 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         A, B, C, W = self.progA, self.progB, self.progC, self.progW
         M = self.MAIN
         lin = self._lin_segment
+        ada = [(self.progAda, 0, -1)] if self.progAda is not None else []  # the controller heads the D chain
         if sch in ("fused", "ddp"):
             run = (lambda ex, cs, sec: self._run_fused(ex, cs)) if sch == "fused" else \
                 (lambda ex, cs, sec: self._run_ddp(ex, cs))
             run.empty = False
             return [("step", run, M)]
         if sch == "concurrent" and self._sharded():
-            return [("fwd", lin([(A, 0, self._a_fwd)]), M), ("D_bwd_top", lin([(B, 0, self._b_split)]), self.ALT),
+            return [("fwd", lin([(A, 0, self._a_fwd)]), M), ("D_bwd_top", lin(ada + [(B, 0, self._b_split)]), self.ALT),
                     ("G_chain", lin([]), M), ("D_bwd_rest", lin([(B, self._b_split, -1)]), self.ALT),
                     ("G_tail", lin([]), M), ("update", lin([(C, 0, -1)]), M)]
         if sch == "serial":
-            return [("fwd+G_bwd", lin([(A, 0, -1), (W, 0, -1)]), M), ("D_bwd_top", lin([(B, 0, self._b_split)]), M),
+            return [("fwd+G_bwd", lin([(A, 0, -1), (W, 0, -1)]), M), ("D_bwd_top", lin(ada + [(B, 0, self._b_split)]), M),
                     ("D_bwd_rest", lin([(B, self._b_split, -1)]), M), ("adam_G", lin([(C, 0, self._c_split)]), M),
                     ("adam_D", lin([(C, self._c_split, -1)]), M)]
         # "concurrent": one graph per chain segment, each on its own stream; the collectives go
@@ -1301,7 +1339,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             g_chain = [(A, self._a_fwd, a_need), (W, wb, we)] + wx("g_a")
             g_tail = [(A, a_need, -1), (W, 0, wb), (W, we, -1)] + wx("g_b") + wx("g_c")
         segs = [("fwd", lin([(A, 0, self._a_fwd)]), M),
-                ("D_bwd_top", lin([(B, 0, self._b_split)] + wx("dtop")), self.ALT),
+                ("D_bwd_top", lin(ada + [(B, 0, self._b_split)] + wx("dtop")), self.ALT),
                 ("G_chain", lin(g_chain), M),
                 ("D_bwd_rest", lin([(B, self._b_split, -1)] + wx("drest")), self.ALT),
                 ("G_tail", lin(g_tail), M)]
@@ -1359,7 +1397,12 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         gradients run on the streams _gw_place() gives."""
         ex.run(self.progA, [cs, ex.side], 0, self._a_fwd)
         ex.wait(ex.alt[0], cs)
+        tail = self._ada_at_tail()
+        if self.progAda is not None and not tail:
+            ex.run(self.progAda, ex.alt)
         ex.run(self.progB, ex.alt)
+        if self.progAda is not None and tail:
+            ex.run(self.progAda, ex.alt)
         # the G chain: data gradients on cs; each G weight gradient on its _gw_place() stream once
         # cs has produced its operand (a mark after that progA position)
         if not self._g_wgrad_on_d_stream():  # every G gradient on cs
@@ -1393,6 +1436,14 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                 ex.run(self.progW, [cs, ex.side], lo, hi)
         ex.wait(cs, ex.alt[0])
         ex.run(self.progC, [cs, ex.side])
+
+    def _ada_at_tail(self) -> bool:
+        """The fused step's place for `ada_update` on the D chain's stream: behind the chain's last op, ahead
+        of the join (default), or with DCGAN_ADA_PLACE=head ahead of its first. Six interleaved pairs each
+        against the ungated step: +2.9 us at the tail, +10.3 us at the head, where the launch delays the
+        chain that ends the step (profiles/r18/ada_cost_r18.txt). The segmented and one-graph DDP schedules
+        keep it at the head of the chain's first segment."""
+        return os.environ.get("DCGAN_ADA_PLACE") != "head"
 
     def _gw_place(self) -> str:
         """Stream of each G weight-gradient segment in the fused step: "a" (default) the idle alt1
@@ -1610,8 +1661,22 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         """The bool mask [B] of the fakes G learned from in the last full step (None: top-k off)."""
         return self.topk_sel.ne(0) if self.topk.active else None
 
+    def ada_status(self):
+        """The adaptive-augmentation state as Python ints {p24, acc, cnt, r_acc, windows} plus p and r_t
+        (= r_acc / (B * interval), of the last finished window); None when no gate is recorded."""
+        if not self.ada.active:
+            return None
+        st = dict(zip(R.ADA_KEYS, (int(v) for v in self.ada_state.tolist())))
+        st["p"] = st["p24"] / float(R.ADA_ONE)
+        st["r_t"] = st["r_acc"] / float(self.B * self.ada.interval)
+        return st
+
     def sync_state_for_checkpoint(self) -> None:
         torch.cuda.synchronize(self.device)
+        # the controller's state for the checkpoint dictionary (only with the controller on)
+        self.model.ada = None
+        if self.ada.adaptive:
+            self.model.ada = {k: int(v) for k, v in zip(R.ADA_KEYS, self.ada_state.tolist())}
 
     def sync_bn_state(self) -> None:
         """Average BN moving averages over ranks (collective; see ReferenceEngine) -- and, after
@@ -1623,7 +1688,15 @@ class HipEngine(HipDDPMixin, HipEngineAux):
     def after_state_load(self) -> None:
         """Call after loading weights/slots from a checkpoint: refresh the 16-bit weight mirrors
         (the moving average's too) and, with spectral norm, the normalised copies from the loaded
-        state."""
+        state. Adaptive augmentation: the controller's state from the loaded dictionary (``model.ada``;
+        None = a checkpoint without one: the initial p), then rank 0's on every rank."""
+        if self.ada.adaptive and not self.dry:
+            st = getattr(self.model, "ada", None)
+            vals = R.ada_state(R.ada_p24(self.ada.p)) if st is None else \
+                [int(st[k]) for k in R.ADA_KEYS] + [0] * (R.ADA_STATE_WORDS - len(R.ADA_KEYS))
+            self.ada_state.copy_(torch.tensor(vals, dtype=torch.int32))
+            if self.ddp and D.is_initialized():
+                D.broadcast_tensors([self.ada_state])
         self._repack_weights_now()
 
     def reset_d_sn(self) -> None:

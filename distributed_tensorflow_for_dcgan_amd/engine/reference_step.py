@@ -28,7 +28,7 @@ class ReferenceStep:
                  lr_g: Optional[float] = None, lr_decay="none", lr_decay_start: int = 0, lr_decay_steps: int = 0,
                  lr_end: float = 0.0, lr_warmup: int = 0, instance_noise=0.0, instance_noise_end: float = 0.0,
                  instance_noise_steps: int = 0, noise_seed: int = 0, d_augment="", d_color_augment="",
-                 g_topk=1.0, g_topk_steps: int = 0):
+                 g_topk=1.0, g_topk_steps: int = 0, d_ada=None, world: int = 1):
         self.model = model
         # top-k generator updates (ops.reference.GTopK): g_loss is differentiated over the k(t) fakes D
         # scores highest only, k annealed from B to ceil(nu B) over the global step; D's losses and
@@ -41,6 +41,13 @@ class ReferenceStep:
         # its color policy (ops.reference.DColor), ahead of translation / cutout: brightness, saturation,
         # contrast per sample, (b, s, c) from Philox stream 3 of the same seed at the global step
         self.color = R.check_d_color(d_color_augment)
+        # adaptive augmentation probability (ops.reference.DAda): each selected policy applies to a sample
+        # iff its gate -- Philox streams 4 (translation, cutout) and 5 (color) of the same seed -- falls
+        # below p24; with a target, ``step`` steers p24 from its own real logits (ops.reference.ada_update),
+        # `world` entering the step size only. D sub-steps gate with the live p24 and leave the state alone
+        self.ada = R.check_ada(R.DAda() if d_ada is None else d_ada, augmented=self.aug.active or self.color.active)
+        self.ada_world = int(world)
+        self.ada_state = R.ada_state(R.ada_p24(self.ada.p))
         # instance noise (ops.reference.InstanceNoise): D sees [real | fake] + sigma(t) * eps, eps from
         # Philox stream 1 of `noise_seed` (the HIP engine's z seed) at the global step; D sub-step k
         # draws from ops.reference.substep_seed(noise_seed, k). G's gradient flows through it unchanged
@@ -109,9 +116,19 @@ class ReferenceStep:
             return None
         return R.color_params(shape[0], R.substep_seed(self.noise_seed, sub), self.global_step)
 
+    def draw_gates(self, n: int, sub: Optional[int] = None):
+        """(color gates, geometric gates), int32 [2B] each (None where that switch is off), at the current
+        global step and p24; None when no gate is active."""
+        if not self.ada.active:
+            return None
+        seed, p24 = R.substep_seed(self.noise_seed, sub), self.ada_state[0]
+        cg = R.gate_masks(n, seed, self.global_step, R.COLOR_GATE_STREAM, p24, self.color.mask) if self.color.active else None
+        ag = R.gate_masks(n, seed, self.global_step, R.AUG_GATE_STREAM, p24, self.aug.mask) if self.aug.active else None
+        return cg, ag
+
     def forward_losses(self, real: torch.Tensor, z: torch.Tensor, Pg=None, Pd=None, update_ema=True,
                        record=None, update_ema_g=None, noise=None, sub: Optional[int] = None, augment=None,
-                       color=None, topk=None):
+                       color=None, topk=None, gates=None):
         """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's). noise: the additive
         sigma * eps on D's input [2B, ...]; None = drawn (``draw_noise``, `sub` = the D sub-step) when
         instance noise is on; False = none (sample-time losses stay clean). augment: the params [2B, 4]
@@ -120,7 +137,9 @@ class ReferenceStep:
         (``draw_color``) when it is on; False = none. topk: the bool mask [B] of the fakes G learns from;
         None = the selection on this forward's own fake logits (``topk_k`` of them) when top-k is on; False
         = none. The result carries it as ``topk_sel`` (None when unused) beside ``g_loss_topk``, the mean
-        of G's loss over the selected (``g_loss`` itself when unused)."""
+        of G's loss over the selected (``g_loss`` itself when unused). gates: (color gates, geometric
+        gates) of adaptive augmentation, int [2B] each or None; None = drawn (``draw_gates``) when it is on;
+        False = none."""
         m = self.model
         if self.d_spectral_norm:  # D computes with W / sigma(W); autograd projects the gradient
             Pd = m.d_sn_weights(Pd)
@@ -128,14 +147,17 @@ class ReferenceStep:
                            record=record)
         B = real.shape[0]
         both = torch.cat([real, fake], 0)
+        if gates is None:
+            gates = self.draw_gates(both.shape[0], sub)
+        cg, ag = (None, None) if gates is None or gates is False else gates
         if color is None:
             color = self.draw_color(both.shape, sub)
         if color is not None and color is not False:
-            both = R.color_augment(both, color, self.color)
+            both = R.color_augment(both, color, self.color, gates=cg)
         if augment is None:
             augment = self.draw_augment(both.shape, sub)
         if augment is not None and augment is not False:
-            both = R.augment(both, augment, self.aug)
+            both = R.augment(both, augment, self.aug, gates=ag)
         if noise is None:
             noise = self.draw_noise(both.shape, sub)
         if noise is not None and noise is not False:
@@ -155,14 +177,14 @@ class ReferenceStep:
                 "d_loss_fake": d_fake, "g_loss": g_loss, "d_loss": d_loss, "g_loss_topk": g_topk, "topk_sel": topk}
 
     def compute_grads(self, real: torch.Tensor, z: torch.Tensor, update_ema: bool = True, noise=None, augment=None,
-                      color=None, topk=None):
+                      color=None, topk=None, gates=None):
         """Returns (losses dict, flat D grads, flat G grads) without applying them. G's gradients are
         those of ``g_loss_topk`` (which is ``g_loss`` without a top-k selection)."""
         m = self.model
         Pg = {k: v.detach().clone().requires_grad_(True) for k, v in m.g.tensors.items()}
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
         out = self.forward_losses(real, z, Pg, Pd, update_ema=update_ema, noise=noise, augment=augment, color=color,
-                                  topk=topk)
+                                  topk=topk, gates=gates)
         d_names, g_names = m.d.names(), m.g.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], retain_graph=True,
                                  allow_unused=True)
@@ -178,13 +200,14 @@ class ReferenceStep:
         return out, gd_flat.flat, gg_flat.flat
 
     def compute_d_grads(self, real: torch.Tensor, z: torch.Tensor, noise=None, sub: Optional[int] = None,
-                        augment=None, color=None):
+                        augment=None, color=None, gates=None):
         """(losses dict, flat D grads) of a D sub-step: G's forward in training mode on batch
         statistics with its BN moving averages left alone, only d_loss differentiated, through D."""
         m = self.model
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
         out = self.forward_losses(real, z, None, Pd, update_ema=True, update_ema_g=False, noise=noise,
-                                  sub=self._sub_k if sub is None else sub, augment=augment, color=color, topk=False)
+                                  sub=self._sub_k if sub is None else sub, augment=augment, color=color, topk=False,
+                                  gates=gates)
         d_names = m.d.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], allow_unused=True)
         gd_flat = m.d.like()
@@ -194,12 +217,12 @@ class ReferenceStep:
         return out, gd_flat.flat
 
     def d_step(self, real: torch.Tensor, z: torch.Tensor, noise=None, sub: Optional[int] = None,
-               augment=None, color=None) -> Dict[str, float]:
+               augment=None, color=None, gates=None) -> Dict[str, float]:
         """One D sub-step: a fresh z through G, D on [real | fake], the d_loss backward through D,
         TF-Adam(D) (D's beta powers advance) and the power step. Nothing of G changes -- parameters,
         Adam slots and powers, BN moving averages, weight EMA -- nor does the global step; D's BN
         moving averages (both slots) update as in a full step."""
-        out, gd = self.compute_d_grads(real, z, noise=noise, sub=sub, augment=augment, color=color)
+        out, gd = self.compute_d_grads(real, z, noise=noise, sub=sub, augment=augment, color=color, gates=gates)
         self._sub_k += 1
         for s in range(2):
             self.model.d_bn.count_step(s)
@@ -211,11 +234,22 @@ class ReferenceStep:
         self.last = out
         return {k: float(out[k].detach()) for k in ("d_loss_real", "d_loss_fake", "g_loss", "d_loss")}
 
+    def ada_step(self, real_logits: torch.Tensor) -> None:
+        """The controller's step of a full training step, from that step's real logits (no-op without a
+        target)."""
+        if not self.ada.adaptive:
+            return
+        a, B = self.ada, int(real_logits.numel())
+        self.ada_state = R.ada_update(self.ada_state, real_logits, R.ada_threshold(self.gan_loss, self.label_smooth),
+                                      R.ada_target_n(a.target, B, a.interval),
+                                      R.ada_delta24(self.ada_world, B, a.interval, a.kimg), a.interval)
+
     def step(self, real: torch.Tensor, z: torch.Tensor, noise=None, augment=None, color=None,
-             topk=None) -> Dict[str, float]:
+             topk=None, gates=None) -> Dict[str, float]:
         """topk: the mask of the fakes G learns from (an engine's recorded one); None = the reference's
         own selection when top-k is on; False = none."""
-        out, gd, gg = self.compute_grads(real, z, noise=noise, augment=augment, color=color, topk=topk)
+        out, gd, gg = self.compute_grads(real, z, noise=noise, augment=augment, color=color, topk=topk, gates=gates)
+        self.ada_step(out["logits_real"].detach())  # (follows the global step, whatever the update does)
         self._sub_k = 0
         for s in range(2):  # one EMA update per BN slot per step (as the HIP engine counts)
             self.model.d_bn.count_step(s)

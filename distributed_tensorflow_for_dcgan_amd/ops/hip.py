@@ -772,12 +772,31 @@ def _aug_images(op: str, x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.
     return out
 
 
+def _ada_state_arg(op: str, p24, device) -> torch.Tensor:
+    """The int32 [8] device state a gated launch reads p24 from: a given one, or a fresh one holding p24."""
+    if torch.is_tensor(p24):
+        if p24.dtype != torch.int32 or p24.numel() != 8 or not p24.is_contiguous() or p24.device != device:
+            raise TypeError("%s: the state must be a contiguous int32 [8] on x's device" % op)
+        return p24
+    if not 0 <= int(p24) <= 1 << 24:
+        raise ValueError("%s: p24 must satisfy 0 <= p24 <= 2^24, got %r" % (op, p24))
+    return torch.tensor([int(p24)] + [0] * 7, dtype=torch.int32, device=device)
+
+
+def _gates_arg(op: str, gates, N: int, device) -> torch.Tensor:
+    if not torch.is_tensor(gates) or gates.numel() != N or gates.is_floating_point():
+        raise TypeError("%s: gates must be an integer [N]" % op)
+    return gates.to(device=device, dtype=torch.int32).contiguous()
+
+
 def augment_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.Tensor] = None,
-                 params_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                 params_out: Optional[torch.Tensor] = None, p24=None, gates_out: Optional[torch.Tensor] = None):
     """DiffAugment of x [N, S, S, C] as the training step runs it (d_augment_kernel): sample n draws
     (ty, tx, oy, ox) from the Philox stream (seed, step, 2). Returns (y, params int32 [N, 4]); policy: a
     DAugment, a policy list ("translation,cutout") or the kernels' bitmask. Oracle: ops.reference.augment
-    over ops.reference.augment_params."""
+    over ops.reference.augment_params. p24 (an int, or the int32 [8] device state whose word 0 holds it):
+    the gated kernel of adaptive augmentation -- returns (y, params, gates int32 [N]), gates the
+    effective policy per sample (oracle: ops.reference.gate_masks on stream 4)."""
     out = _aug_images("augment_draw", x, out)
     if not torch.is_tensor(step):
         v = int(step) & 0xFFFFFFFFFFFFFFFF  # (the counter's 64 bits as the int64 that holds them)
@@ -789,6 +808,17 @@ def augment_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.T
     if params_out.dtype != torch.int32 or tuple(params_out.shape) != (N, 4) or not params_out.is_contiguous():
         raise TypeError("augment_draw: params_out must be a contiguous int32 [N, 4]")
     prog = ext().Program(_ELEM_DT[x.dtype])
+    if p24 is not None:
+        state = _ada_state_arg("augment_draw", p24, x.device)
+        if gates_out is None:
+            gates_out = torch.empty(N, device=x.device, dtype=torch.int32)
+        if gates_out.dtype != torch.int32 or tuple(gates_out.shape) != (N,) or not gates_out.is_contiguous():
+            raise TypeError("augment_draw: gates_out must be a contiguous int32 [N]")
+        prog.d_augment("d_augment", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0,
+                       _p(params_out) if N else 0, N, S, C, _aug_mask(policy), int(seed), _p(step), 0,
+                       _p(gates_out) if N else 0, _p(state))
+        run(prog)
+        return out, params_out, gates_out
     prog.d_augment("d_augment", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0, _p(params_out) if N else 0,
                    N, S, C, _aug_mask(policy), int(seed), _p(step))
     run(prog)
@@ -804,7 +834,7 @@ def augment_params(n: int, S: int, seed: int, step, device="cuda") -> torch.Tens
 
 
 def augment_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool = False,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, gates: Optional[torch.Tensor] = None) -> torch.Tensor:
     """DiffAugment of x [N, S, S, C] under given params [N, 4] = (ty, tx, oy, ox) (the kernel's probe
     entry), or with transpose=True its transposed gather, the backward (d_augment_bwd). Oracles:
     ops.reference.augment / augment_transpose."""
@@ -816,10 +846,15 @@ def augment_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool
     p = params.to(device=x.device, dtype=torch.int32).contiguous()
     prog = ext().Program(_ELEM_DT[x.dtype])
     px, po, pp = (_p(x), _p(out), _p(p)) if x.numel() else (0, 0, 0)
+    # gates: integer [N], the recorded gate masks -- the gated kernel's probe / transpose
+    pg = 0
+    if gates is not None:
+        gates = _gates_arg(op, gates, N, x.device)
+        pg = _p(gates) if N else 0
     if transpose:
-        prog.d_augment_bwd("d_augment_bwd", px, po, pp, N, S, C, _aug_mask(policy))
+        prog.d_augment_bwd("d_augment_bwd", px, po, pp, N, S, C, _aug_mask(policy), 0, pg)
     else:
-        prog.d_augment("d_augment", px, po, pp, N, S, C, _aug_mask(policy), 0, 0)
+        prog.d_augment("d_augment", px, po, pp, N, S, C, _aug_mask(policy), 0, 0, 0, pg, 0)
     run(prog)
     return out
 
@@ -830,11 +865,12 @@ def _color_mask(policy) -> int:
 
 
 def color_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.Tensor] = None,
-               params_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               params_out: Optional[torch.Tensor] = None, p24=None, gates_out: Optional[torch.Tensor] = None):
     """DiffAugment's color policy over x [N, S, S, C] as the training step runs it (d_color_kernel): sample
     n draws (b, s, c) from the Philox stream (seed, step, 3). Returns (y, params float32 [N, 4] = (b, s, c,
     Mx)); policy: a DColor, a policy list ("brightness,saturation,contrast") or the kernels' bitmask.
-    Oracle: ops.reference.color_augment over ops.reference.color_params."""
+    Oracle: ops.reference.color_augment over ops.reference.color_params. p24: as ``augment_draw`` -- the
+    gated kernel, returns (y, params, gates int32 [N]) (oracle: ops.reference.gate_masks on stream 5)."""
     out = _aug_images("color_draw", x, out)
     if not torch.is_tensor(step):
         v = int(step) & 0xFFFFFFFFFFFFFFFF  # (the counter's 64 bits as the int64 that holds them)
@@ -846,6 +882,16 @@ def color_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.Ten
     if params_out.dtype != torch.float32 or tuple(params_out.shape) != (N, 4) or not params_out.is_contiguous():
         raise TypeError("color_draw: params_out must be a contiguous float32 [N, 4]")
     prog = ext().Program(_ELEM_DT[x.dtype])
+    if p24 is not None:
+        state = _ada_state_arg("color_draw", p24, x.device)
+        if gates_out is None:
+            gates_out = torch.empty(N, device=x.device, dtype=torch.int32)
+        if gates_out.dtype != torch.int32 or tuple(gates_out.shape) != (N,) or not gates_out.is_contiguous():
+            raise TypeError("color_draw: gates_out must be a contiguous int32 [N]")
+        prog.d_color("d_color", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0, _p(params_out) if N else 0,
+                     N, S, C, _color_mask(policy), int(seed), _p(step), 0, _p(gates_out) if N else 0, _p(state))
+        run(prog)
+        return out, params_out, gates_out
     prog.d_color("d_color", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0, _p(params_out) if N else 0,
                  N, S, C, _color_mask(policy), int(seed), _p(step))
     run(prog)
@@ -861,7 +907,8 @@ def color_params(n: int, seed: int, step, device="cuda") -> torch.Tensor:
 
 
 def color_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool = False,
-                out: Optional[torch.Tensor] = None, params_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, params_out: Optional[torch.Tensor] = None,
+                gates: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The color policy over x [N, S, S, C] under given params [N, 3 or 4] = (b, s, c[, Mx]) (the kernel's
     probe entry: it computes Mx itself and leaves it in column 3 of params_out, a float32 [N, 4], when
     one is given), or with transpose=True its transpose, the backward (d_color_bwd). Oracles:
@@ -879,12 +926,45 @@ def color_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool =
     p[:, :3] = params[:, :3].to(device=x.device, dtype=torch.float32)
     prog = ext().Program(_ELEM_DT[x.dtype])
     px, po, pp = (_p(x), _p(out), _p(p)) if x.numel() else (0, 0, 0)
+    # gates: integer [N], the recorded gate masks -- the gated kernel's probe / transpose
+    pg = 0
+    if gates is not None:
+        gates = _gates_arg(op, gates, N, x.device)
+        pg = _p(gates) if N else 0
     if transpose:
-        prog.d_color_bwd("d_color_bwd", px, po, pp, N, S, C, _color_mask(policy))
+        prog.d_color_bwd("d_color_bwd", px, po, pp, N, S, C, _color_mask(policy), 0, pg)
     else:
-        prog.d_color("d_color", px, po, pp, N, S, C, _color_mask(policy), 0, 0)
+        prog.d_color("d_color", px, po, pp, N, S, C, _color_mask(policy), 0, 0, 0, pg, 0)
     run(prog)
     return out
+
+
+def gate_masks(n: int, seed: int, step, stream: int, p24, policy_mask: int, device="cuda") -> torch.Tensor:
+    """int32 [n]: the gate masks the gated kernels record for n samples at p24 under `policy_mask` --
+    stream 4: d_augment_kernel's (translation, cutout), stream 5: d_color_kernel's (brightness, saturation,
+    contrast) -- over dummy images of zeros. Oracle: ops.reference.gate_masks."""
+    if int(stream) == 4:
+        x = torch.zeros(int(n), 1, 1, 1, device=device, dtype=torch.bfloat16)
+        return augment_draw(x, seed, step, int(policy_mask), p24=p24)[2]
+    if int(stream) == 5:
+        x = torch.zeros(int(n), 1, 1, 1, device=device, dtype=torch.bfloat16)
+        return color_draw(x, seed, step, int(policy_mask), p24=p24)[2]
+    raise ValueError("gate_masks: stream must be 4 (translation / cutout) or 5 (color), got %r" % (stream,))
+
+
+def ada_update(state: torch.Tensor, real_logits: torch.Tensor, thr: float, target_n: int, delta24: int,
+               interval: int) -> torch.Tensor:
+    """One step of the adaptive-augmentation controller (ada_update_kernel), in place on state int32 [8] =
+    (p24, acc, cnt, r_acc, windows, 0, 0, 0), from the fp32 real logits [B]. Oracle: ops.reference.ada_update."""
+    if state.dtype != torch.int32 or state.numel() != 8 or not state.is_contiguous():
+        raise TypeError("ada_update: state must be a contiguous int32 [8]")
+    if real_logits.dtype != torch.float32 or real_logits.dim() != 1 or not real_logits.is_contiguous():
+        raise TypeError("ada_update: real_logits must be a contiguous float32 [B]")
+    prog = ext().Program()
+    prog.ada_update("ada_update", _p(real_logits) if real_logits.numel() else 0, real_logits.numel(), _p(state),
+                    float(thr), int(target_n), int(delta24), int(interval))
+    run(prog)
+    return state
 
 
 def adam_(w: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, powers: torch.Tensor, lr: float,

@@ -581,7 +581,15 @@ def augment_params(n: int, S: int, seed: int, step: int) -> torch.Tensor:
     return torch.from_numpy(out)
 
 
-def _augment_gather(x: torch.Tensor, params: torch.Tensor, aug: DAugment, transpose: bool) -> torch.Tensor:
+def _gate_rows(gates, N: int, mask: int, device) -> torch.Tensor:
+    """int64 [N]: the effective policy of each sample, `mask` & its recorded gate mask."""
+    g = torch.as_tensor(gates).to(device=device, dtype=torch.int64).reshape(-1)
+    if g.numel() != N:
+        raise ValueError("gates must hold one mask per sample (%d), got %d" % (N, g.numel()))
+    return g & int(mask)
+
+
+def _augment_gather(x: torch.Tensor, params: torch.Tensor, aug: DAugment, transpose: bool, gates=None) -> torch.Tensor:
     if x.dim() != 4 or x.shape[1] != x.shape[2]:
         raise ValueError("augment: x must be [N, S, S, C], got %s" % (tuple(x.shape),))
     N, S = x.shape[0], x.shape[1]
@@ -590,6 +598,10 @@ def _augment_gather(x: torch.Tensor, params: torch.Tensor, aug: DAugment, transp
         raise ValueError("augment: params must be [N, 4] = (ty, tx, oy, ox), got %s" % (tuple(p.shape),))
     zero = torch.zeros((), dtype=torch.int64, device=x.device)
     ty, tx = (p[:, 0], p[:, 1]) if aug.translation else (zero.expand(N), zero.expand(N))
+    eff = None if gates is None else _gate_rows(gates, N, aug.mask, x.device)
+    if eff is not None:  # a sample with translation gated off: ty = tx = 0, as under the smaller policy
+        on = (eff & 1) != 0
+        ty, tx = torch.where(on, ty, zero), torch.where(on, tx, zero)
     if transpose:
         ty, tx = -ty, -tx
     a = torch.arange(S, device=x.device)
@@ -600,13 +612,15 @@ def _augment_gather(x: torch.Tensor, params: torch.Tensor, aug: DAugment, transp
         by, bx = (si, sj) if transpose else (a[None, :].expand(N, S), a[None, :].expand(N, S))
         y0, x0 = (p[:, 2] - k // 2)[:, None], (p[:, 3] - k // 2)[:, None]
         box = ((by >= y0) & (by < y0 + k))[:, :, None] & ((bx >= x0) & (bx < x0 + k))[:, None, :]
+        if eff is not None:
+            box = box & ((eff & 2) != 0)[:, None, None]
         keep = keep & ~box
     g = x[torch.arange(N, device=x.device)[:, None, None], si.clamp(0, S - 1)[:, :, None],
           sj.clamp(0, S - 1)[:, None, :]]
     return torch.where(keep[..., None], g, torch.zeros((), dtype=x.dtype, device=x.device))
 
 
-def augment(x: torch.Tensor, params: torch.Tensor, aug: DAugment) -> torch.Tensor:
+def augment(x: torch.Tensor, params: torch.Tensor, aug: DAugment, gates=None) -> torch.Tensor:
     """The augmentation of x [N, S, S, C] (NHWC) under params [N, 4] = (ty, tx, oy, ox), k = (S + 1) // 2:
 
         y[n,i,j,c] = +0                     if cutout and oy - k//2 <= i < oy - k//2 + k (and j, ox alike)
@@ -614,14 +628,16 @@ def augment(x: torch.Tensor, params: torch.Tensor, aug: DAugment) -> torch.Tenso
                    = +0                     otherwise
 
     the published rand_translation followed by rand_cutout for those draws. A gather and a
-    torch.where: values pass through bit for bit, every zero is +0, and autograd gives the backward."""
-    return _augment_gather(x, params, aug, False)
+    torch.where: values pass through bit for bit, every zero is +0, and autograd gives the backward.
+    gates: int [N], the recorded gate masks of adaptive augmentation (``gate_masks``): sample n is
+    augmented under the policy ``aug.mask & gates[n]``. None: every sample under ``aug``."""
+    return _augment_gather(x, params, aug, False, gates)
 
 
-def augment_transpose(g: torch.Tensor, params: torch.Tensor, aug: DAugment) -> torch.Tensor:
+def augment_transpose(g: torch.Tensor, params: torch.Tensor, aug: DAugment, gates=None) -> torch.Tensor:
     """The transpose of ``augment`` as a gather of its own: gx[n,p,q,c] = g[n, p-ty, q-tx, c] if that
-    index is inside the image and outside the box, else +0."""
-    return _augment_gather(g, params, aug, True)
+    index is inside the image and outside the box, else +0. gates: as ``augment``."""
+    return _augment_gather(g, params, aug, True, gates)
 
 
 # --------------------------------------------------------------------------- DiffAugment's color policy
@@ -727,7 +743,27 @@ def color_mean(x: torch.Tensor) -> torch.Tensor:
     return _image_mean(x.to(ct))
 
 
-def color_augment(x: torch.Tensor, params: torch.Tensor, color: DColor) -> torch.Tensor:
+def _color_gated(x, params, color: DColor, eff: torch.Tensor) -> torch.Tensor:
+    """``color_augment`` with per-sample effective policies eff [N]: each stage computed as below and
+    kept only on the samples whose bit is set (a select: the others pass through bit for bit)."""
+    v, p, ct = _color_setup(x, params)
+    col = lambda i: p[:, i].reshape(-1, 1, 1, 1)  # noqa: E731
+    bit = lambda i: ((eff >> i) & 1).ne(0).reshape(-1, 1, 1, 1)  # noqa: E731
+    bri, sat, con = bit(0), bit(1), bit(2)
+    if color.brightness:
+        v = torch.where(bri, v + col(0), v)
+    if color.saturation:
+        m = _channel_mean(v)
+        v = torch.where(sat, col(1) * (v - m) + m, v)
+    if color.contrast:
+        M = (p[:, 3] if p.shape[1] == 4 else _image_mean(x.to(ct))).reshape(-1, 1, 1, 1)
+        if color.brightness:
+            M = torch.where(bri, M + col(0), M)
+        v = torch.where(con, col(2) * (v - M) + M, v)
+    return v.to(x.dtype)
+
+
+def color_augment(x: torch.Tensor, params: torch.Tensor, color: DColor, gates=None) -> torch.Tensor:
     """The color policy over x [N, S, S, C] (NHWC) under params [N, 3] = (b, s, c), every operation a
     separately rounded fp32 one (fp64 for an fp64 x), the stages that `color` switches off skipped:
 
@@ -737,7 +773,12 @@ def color_augment(x: torch.Tensor, params: torch.Tensor, color: DColor) -> torch
 
     M is the published mean of the image after brightness and saturation, in exact arithmetic
     (saturation keeps a pixel's channel mean): one reduction over the input serves. A fourth column of
-    params gives Mx (what the kernel recorded); else it is ``color_mean(x)``. Differentiable."""
+    params gives Mx (what the kernel recorded); else it is ``color_mean(x)``. Differentiable.
+    gates: int [N], the recorded gate masks of adaptive augmentation (``gate_masks``): sample n is
+    processed under the policy ``color.mask & gates[n]`` (brightness gated off: M = Mx; contrast gated
+    off: Mx is not read). None: every sample under ``color``."""
+    if gates is not None:
+        return _color_gated(x, params, color, _gate_rows(gates, x.shape[0], color.mask, x.device))
     v, p, ct = _color_setup(x, params)
     col = lambda i: p[:, i].reshape(-1, 1, 1, 1)  # noqa: E731
     if color.brightness:
@@ -753,7 +794,7 @@ def color_augment(x: torch.Tensor, params: torch.Tensor, color: DColor) -> torch
     return v.to(x.dtype)
 
 
-def color_augment_transpose(g: torch.Tensor, params: torch.Tensor, color: DColor, mean=None) -> torch.Tensor:
+def color_augment_transpose(g: torch.Tensor, params: torch.Tensor, color: DColor, mean=None, gates=None) -> torch.Tensor:
     """The transpose of ``color_augment``'s linear part over g = dL/dy: each stage is a symmetric map,
     so it is the same stage functions in reverse order on the gradient's own mean (brightness is the
     identity):
@@ -761,9 +802,19 @@ def color_augment_transpose(g: torch.Tensor, params: torch.Tensor, color: DColor
         contrast   : Gm = sum(g[n]) / (S*S*C);  v = c * (v - Gm) + Gm
         saturation : m over the channels of those values;  v = s * (v - m) + m
 
-    mean: Gm [N] given instead of summed here."""
+    mean: Gm [N] given instead of summed here. gates: as ``color_augment``."""
     v, p, ct = _color_setup(g, params)
     col = lambda i: p[:, i].reshape(-1, 1, 1, 1)  # noqa: E731
+    if gates is not None:
+        eff = _gate_rows(gates, g.shape[0], color.mask, g.device)
+        sat, con = (((eff >> i) & 1).ne(0).reshape(-1, 1, 1, 1) for i in (1, 2))
+        if color.contrast:
+            Gm = (_image_mean(v) if mean is None else torch.as_tensor(mean).to(device=v.device, dtype=ct)).reshape(-1, 1, 1, 1)
+            v = torch.where(con, col(2) * (v - Gm) + Gm, v)
+        if color.saturation:
+            m = _channel_mean(v)
+            v = torch.where(sat, col(1) * (v - m) + m, v)
+        return v.to(g.dtype)
     if color.contrast:
         Gm = (_image_mean(v) if mean is None else torch.as_tensor(mean).to(device=v.device, dtype=ct)).reshape(-1, 1, 1, 1)
         v = col(2) * (v - Gm) + Gm
@@ -771,6 +822,174 @@ def color_augment_transpose(g: torch.Tensor, params: torch.Tensor, color: DColor
         m = _channel_mean(v)
         v = col(1) * (v - m) + m
     return v.to(g.dtype)
+
+
+# --------------------------------------------------------------------------- adaptive augmentation (ADA)
+AUG_GATE_STREAM = 4    # Philox stream of the gates of translation (w0) and cutout (w1)
+COLOR_GATE_STREAM = 5  # ... and of brightness (w0), saturation (w1), contrast (w2)
+ADA_ONE = 1 << 24      # p24 of p = 1
+ADA_MAX_INTERVAL = 1 << 16
+ADA_STATE_WORDS = 8    # int32 (p24, acc, cnt, r_acc, windows, 0, 0, 0)
+ADA_KEYS = ("p24", "acc", "cnt", "r_acc", "windows")  # the checkpoint's ada/<key>
+
+
+class DAda(NamedTuple):
+    """Adaptive discriminator augmentation (Karras et al. 2020): every selected policy of DAugment /
+    DColor is applied to a sample with probability p, and p is steered by r_t = E[sign(D(real))] over
+    windows of `interval` steps: up by a fixed step while r_t is above `target`, down while below,
+    sized so that p can cross [0, 1] in `kimg` thousand real images. p is kept as the integer p24 = p *
+    2^24, so the gate, the controller and a resume are exact. target = 0: a fixed p (p = 1: off, no
+    gate at all). `p` here is the resolved start value."""
+    p: float = 1.0
+    target: float = 0.0
+    interval: int = 4
+    kimg: float = 500.0
+
+    @property
+    def adaptive(self) -> bool:
+        return self.target > 0.0
+
+    @property
+    def active(self) -> bool:
+        """Gated kernels and a device state are recorded."""
+        return self.adaptive or self.p < 1.0
+
+    def describe(self) -> str:
+        if not self.active:
+            return "off"
+        if not self.adaptive:
+            return "fixed p = %g" % self.p
+        return "adaptive p from %g, target r_t = %g, every %d steps, %g kimg from 0 to 1" % (
+            self.p, self.target, self.interval, self.kimg)
+
+
+def check_ada(p=-1.0, target=0.0, interval=4, kimg=500.0, augmented: Optional[bool] = None,
+              batch_size: Optional[int] = None) -> DAda:
+    """Validated DAda; errors name the flag. p = -1 resolves to 1 without a target (off) and to 0 with
+    one (the published start); else 0 <= p <= 1. 0 <= target < 1 (0 = no controller), interval in 1 ..
+    2^16, kimg > 0 and finite; batch_size (when given) * interval < 2^31. augmented=False: neither
+    d_augment nor d_color_augment selects a policy -- an error when a gate or the controller is on."""
+    if isinstance(p, DAda):
+        p, target, interval, kimg = p
+    try:
+        p, target, kimg = float(p), float(target), float(kimg)
+    except (TypeError, ValueError):
+        raise ValueError("d_augment_p, ada_target and ada_kimg must be numbers, got %r, %r, %r"
+                         % (p, target, kimg)) from None
+    if not (math.isfinite(target) and 0.0 <= target < 1.0):
+        raise ValueError("ada_target must satisfy 0 < ada_target < 1 (0 = off), got %r" % (target,))
+    if p == -1.0:
+        p = 0.0 if target > 0.0 else 1.0
+    if not (math.isfinite(p) and 0.0 <= p <= 1.0):
+        raise ValueError("d_augment_p must satisfy 0 <= d_augment_p <= 1 (or -1 = the default), got %r" % (p,))
+    interval = _lr_int("ada_interval", interval, 1, ADA_MAX_INTERVAL)
+    if not (math.isfinite(kimg) and kimg > 0.0):
+        raise ValueError("ada_kimg must be finite and > 0, got %r" % (kimg,))
+    ada = DAda(p, target, interval, kimg)
+    if batch_size is not None and int(batch_size) * interval >= 1 << 31:
+        raise ValueError("ada_interval: batch_size * ada_interval must stay below 2^31, got %d * %d"
+                         % (int(batch_size), interval))
+    if ada.active and augmented is False:
+        raise ValueError("d_augment_p / ada_target need a policy to gate: set d_augment and / or d_color_augment")
+    return ada
+
+
+def resolve_ada(p=None, target=None, interval=None, kimg=None, augmented: Optional[bool] = None,
+                batch_size: Optional[int] = None) -> DAda:
+    """check_ada over the engines' arguments: None = the environment default (DCGAN_D_AUGMENT_P,
+    DCGAN_ADA_TARGET, DCGAN_ADA_INTERVAL, DCGAN_ADA_KIMG), then -1 / 0 / 4 / 500. An explicit argument
+    wins. A DAda as `p` is validated as it is."""
+    import os
+    if isinstance(p, DAda):
+        return check_ada(p, augmented=augmented, batch_size=batch_size)
+
+    def env(name, conv):
+        v = os.environ.get(name)
+        if v is None or v.strip() == "":
+            return None
+        try:
+            return conv(v)
+        except ValueError:
+            raise ValueError("%s=%r is not a number" % (name, v)) from None
+    if p is None:
+        p = env("DCGAN_D_AUGMENT_P", float)
+    if target is None:
+        target = env("DCGAN_ADA_TARGET", float)
+    if interval is None:
+        interval = env("DCGAN_ADA_INTERVAL", int)
+    if kimg is None:
+        kimg = env("DCGAN_ADA_KIMG", float)
+    return check_ada(-1.0 if p is None else p, 0.0 if target is None else target, 4 if interval is None else interval,
+                     500.0 if kimg is None else kimg, augmented=augmented, batch_size=batch_size)
+
+
+def ada_p24(p: float) -> int:
+    """round_half_even(p * 2^24) in [0, 2^24]."""
+    p = float(p)
+    if not (0.0 <= p <= 1.0):
+        raise ValueError("ada_p24: p must satisfy 0 <= p <= 1, got %r" % (p,))
+    return int(round(p * ADA_ONE))
+
+
+def ada_delta24(world: int, B: int, interval: int, kimg: float) -> int:
+    """The controller's step of p24 per window: clamp(round_half_even(2^24 * W * B * interval / (1000
+    * kimg)), 1, 2^24) -- W * B * interval real images per window out of 1000 * kimg for the whole range."""
+    d = int(round(ADA_ONE * float(int(world) * int(B) * int(interval)) / (1000.0 * float(kimg))))
+    return max(1, min(ADA_ONE, d))
+
+
+def ada_target_n(target: float, B: int, interval: int) -> int:
+    """Tn = round_half_even(target * B * interval): the window's sum of signs at r_t = target."""
+    return int(round(float(target) * int(B) * int(interval)))
+
+
+def ada_threshold(kind: str = "bce", label_smooth: float = 0.0) -> float:
+    """The logit at which D calls a sample real, as the fp32 the kernel takes: 0 for bce and hinge,
+    (1 - label_smooth) / 2 for lsgan (halfway between its targets 0 and 1 - label_smooth)."""
+    import numpy as np
+    kind, label_smooth = check_gan_loss(kind, label_smooth)
+    return float(np.float32((1.0 - label_smooth) / 2.0)) if kind == "lsgan" else 0.0
+
+
+def ada_state(p24: int = 0) -> list:
+    """A fresh controller state (p24, acc, cnt, r_acc, windows, 0, 0, 0)."""
+    return [int(p24)] + [0] * (ADA_STATE_WORDS - 1)
+
+
+def gate_masks(n: int, seed: int, step: int, stream: int, p24: int, policy_mask: int) -> torch.Tensor:
+    """int32 [n]: the gate mask each gated kernel records for samples 0..n-1. Sample i draws the Philox
+    block at counter (i, step, stream) under `seed`; policy bit k is on iff (w_k >> 8) < p24, so p24 =
+    2^24 gates nothing off and p24 = 0 everything. Bits outside `policy_mask` are cleared: the mask is
+    the effective policy of the sample."""
+    import numpy as np
+    w = philox_words(4 * int(n), seed, step, stream)[:int(n)].astype(np.int64) >> 8
+    m = np.zeros(int(n), dtype=np.int64)
+    for k in range(3):
+        m |= (w[:, k] < int(p24)).astype(np.int64) << k
+    return torch.from_numpy((m & int(policy_mask)).astype(np.int32))
+
+
+def ada_sign_sum(real_logits, thr: float = 0.0) -> int:
+    """a = sum_i ((x_i > thr) - (x_i < thr)) over the fp32 logits, thr as fp32; NaN counts 0."""
+    import numpy as np
+    x = torch.as_tensor(real_logits).detach().to(torch.float32).cpu().numpy().reshape(-1)
+    t = np.float32(thr)
+    return int((x > t).sum()) - int((x < t).sum())
+
+
+def ada_update(state, real_logits, thr: float, target_n: int, delta24: int, interval: int) -> list:
+    """One controller step on Python ints: `state` = (p24, acc, cnt, r_acc, windows, ...) -> the new
+    state. The kernel (misc.hip ada_update_kernel) is this, word for word."""
+    s = [int(v) for v in state]
+    s += [0] * (ADA_STATE_WORDS - len(s))
+    p24, acc, cnt, r_acc, windows = s[:5]
+    acc += ada_sign_sum(real_logits, thr)
+    cnt += 1
+    if cnt == int(interval):
+        d = int(acc > int(target_n)) - int(acc < int(target_n))
+        p24 = max(0, min(ADA_ONE, p24 + d * int(delta24)))
+        r_acc, windows, acc, cnt = acc, windows + 1, 0, 0
+    return [p24, acc, cnt, r_acc, windows] + s[5:ADA_STATE_WORDS]
 
 
 # --------------------------------------------------------------------------- top-k generator updates

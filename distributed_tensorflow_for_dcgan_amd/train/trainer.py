@@ -232,6 +232,10 @@ def run(flags: Flags, out=None) -> int:
         if color is not None and color.active:
             print("color augmentation of D's inputs: %s (reals and fakes, ahead of translation / cutout, a fresh "
                   "draw per sample and step)" % color.describe(), file=out, flush=True)
+        ada = getattr(engine, "ada", None)
+        if ada is not None and ada.active:
+            print("augmentation probability of D's inputs: %s (each selected policy gated per sample)"
+                  % ada.describe(), file=out, flush=True)
         topk = getattr(engine, "topk", None)
         if topk is not None and topk.active:
             print("top-k generator updates: %s (of the global step; G learns from the k best-scored of its B "
@@ -252,6 +256,8 @@ def run(flags: Flags, out=None) -> int:
             print("generator weight EMA: %s" % info["g_ema"], file=out)
         if info and "d_sn" in info:
             print("discriminator spectral norm state: %s" % info["d_sn"], file=out)
+        if info and "ada" in info:
+            print("adaptive augmentation state: %s" % info["ada"], file=out)
 
     if sample_only:
         try:
@@ -339,6 +345,10 @@ def run(flags: Flags, out=None) -> int:
                         vals.append(SummaryWriter.scalar("g_topk/k", float(k)))
                         vals.append(SummaryWriter.scalar("g_topk/threshold", thr))
                         vals.append(SummaryWriter.scalar("g_loss_topk", g_topk_loss))
+                    ada = engine.ada_status() if hasattr(engine, "ada_status") else None
+                    if ada is not None:  # p after the step just taken, r_t of the last finished window
+                        vals.append(SummaryWriter.scalar("ada/p", ada["p"]))
+                        vals.append(SummaryWriter.scalar("ada/r_t", ada["r_t"]))
                     writer.add_summary_values(vals, step)
                     writer.flush()
                     print("Finished running Summary operation.", file=out)
@@ -417,7 +427,9 @@ def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps, instance_n
                         instance_noise_end=float(flags.instance_noise_end),
                         instance_noise_steps=int(instance_noise_steps), d_augment=str(flags.d_augment),
                         d_color_augment=str(flags.d_color_augment), g_topk=float(flags.g_topk),
-                        g_topk_steps=int(g_topk_steps))
+                        g_topk_steps=int(g_topk_steps), d_augment_p=float(flags.d_augment_p),
+                        ada_target=float(flags.ada_target), ada_interval=int(flags.ada_interval),
+                        ada_kimg=float(flags.ada_kimg))
 
 
 def _sample_ema(engine, flags) -> bool:

@@ -121,6 +121,14 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
     ("d_color_augment", "str", "", "DiffAugment's color policy on the discriminator's inputs, ahead of --d_augment: "
                                       "a comma-separated list of brightness, saturation and contrast, each drawn per "
                                       "sample and step; empty or none turns it off"),
+    ("d_augment_p", "float", -1.0, "probability of each policy selected by --d_augment / --d_color_augment per sample, "
+                                   "0 <= p <= 1. -1: 1 without --ada_target (every policy on every sample) and 0 with "
+                                   "it (the start of the adaptive run); a value below 1 without --ada_target is a fixed p"),
+    ("ada_target", "float", 0.0, "adaptive augmentation probability (ADA): the target for r_t = E[sign(D(real))], "
+                                 "0 < target < 1 (0.6 as published); p rises while r_t is above it and falls while "
+                                 "below. 0 turns the controller off"),
+    ("ada_interval", "int", 4, "steps per adjustment of p, 1..2^16"),
+    ("ada_kimg", "float", 500.0, "thousands of real images over which p can move from 0 to 1, > 0"),
     ("g_topk", "float", 1.0, "top-k generator updates: G learns only from the k fakes the discriminator scores "
                              "highest, k annealed linearly from the batch size down to ceil(g_topk * batch_size); "
                              "the final fraction, 0 < g_topk <= 1. 1 turns it off"),
@@ -237,6 +245,12 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         check_d_color(ns.d_color_augment)
     except ValueError as e:
         parser.error("--d_color_augment: %s" % e)
+    from ..ops.reference import check_ada
+    try:
+        check_ada(ns.d_augment_p, ns.ada_target, ns.ada_interval, ns.ada_kimg, batch_size=ns.batch_size,
+                  augmented=check_d_augment(ns.d_augment).active or check_d_color(ns.d_color_augment).active)
+    except (ValueError, TypeError, OverflowError) as e:
+        parser.error("--d_augment_p / --ada_target / --ada_interval / --ada_kimg: %s" % e)
     from ..ops.reference import check_g_topk
     try:  # (--g_topk_steps=0 with --g_topk < 1 stays open here: the trainer resolves it)
         check_g_topk(ns.g_topk, ns.g_topk_steps, open_ended=True)
