@@ -32,11 +32,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine  # noqa: E402
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig  # noqa: E402
+from distributed_tensorflow_for_dcgan_amd.ops.options import ENV_NAMES  # noqa: E402
 
 POSITIONS = ("_a_fwd", "_a_gd_end", "_b_split", "_b_top_dgrad", "_g_w", "_g_w_layer", "_c_split", "_c_split_a")
 ANONYMOUS = ("_keep", "_s_keep")  # engine attributes whose entries have no stable path
-ENV = ("DCGAN_D_BATCH_NORM", "DCGAN_DDP_SHARD", "DCGAN_D_AUGMENT", "DCGAN_D_COLOR_AUGMENT", "DCGAN_G_TOPK",
-       "DCGAN_G_TOPK_STEPS", "DCGAN_D_AUGMENT_P", "DCGAN_ADA_TARGET", "DCGAN_ADA_INTERVAL", "DCGAN_ADA_KIMG")
+ENV = ("DCGAN_D_BATCH_NORM", "DCGAN_DDP_SHARD") + ENV_NAMES  # cleared: a listing does not depend on the caller's shell
 MIN_PTR = 1 << 16  # smaller integers are sizes, counts and flags
 
 

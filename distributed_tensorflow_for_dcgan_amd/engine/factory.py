@@ -7,13 +7,13 @@ Both expose the same small interface used by the trainer and ``bench.py``:
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional
 
 import torch
 
 from ..models.config import DCGANConfig
 from ..models.dcgan import DCGAN
+from ..ops import options as O
 from ..ops import reference as R
 from ..parallel import dist as D
 from .reference_step import ReferenceStep
@@ -27,65 +27,28 @@ class ReferenceEngine:
 
     def __init__(self, cfg: DCGANConfig, batch_size: int, device: torch.device, seed: int = 0,
                  lr: float = 2e-4, beta1: float = 0.5, zero_debias: bool = False, rank: int = 0,
-                 world: int = 1, z_seed: Optional[int] = None, g_ema_decay: Optional[float] = None,
-                 gan_loss: Optional[str] = None, label_smooth: Optional[float] = None,
-                 d_spectral_norm: Optional[bool] = None, d_steps: Optional[int] = None,
-                 beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None,
-                 lr_decay: Optional[str] = None,
-                 lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
-                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
-                 instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
-                 instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
-                 d_color_augment: Optional[str] = None, g_topk: Optional[float] = None,
-                 g_topk_steps: Optional[int] = None, d_augment_p: Optional[float] = None,
-                 ada_target: Optional[float] = None, ada_interval: Optional[int] = None,
-                 ada_kimg: Optional[float] = None, **_):
+                 world: int = 1, z_seed: Optional[int] = None, **options):
         self.cfg = cfg
         self.batch_size = batch_size
         self.device = device
         self.seed = int(seed)
         self.model = DCGAN(cfg, device=device, seed=seed, zero_debias=zero_debias)
         self.world = world
-        if d_spectral_norm is None:
-            d_spectral_norm = R.env_spectral_norm()
-        if R.check_spectral_norm(d_spectral_norm):
+        # the training options (ops.options.TABLE; None = the environment's default, as the HIP engine),
+        # published as self.noise, self.aug, self.ada, self.d_steps, self.gan_loss, ...
+        self.options = O.resolve(batch_size, lr=lr, beta1=beta1, **O.known(options))
+        vars(self).update(self.options._asdict())
+        if self.d_spectral_norm:
             self.model.enable_d_spectral_norm(seed)
         if world > 1:
             D.broadcast_tensors([self.model.g.flat, self.model.d.flat, self.model.g_bn.flat,
                                  self.model.d_bn.flat] + ([self.model.d_sn.flat] if self.model.d_sn else []))
-        if g_ema_decay is None:  # (the HIP engine's switch, so both engines follow one environment)
-            g_ema_decay = float(os.environ.get("DCGAN_G_EMA_DECAY") or 0.0)
-        if gan_loss is None:
-            gan_loss = os.environ.get("DCGAN_GAN_LOSS") or "bce"
-        if label_smooth is None:
-            label_smooth = float(os.environ.get("DCGAN_LABEL_SMOOTH") or 0.0)
-        # D updates per G update, Adam's beta2, per-network learning rates: None = DCGAN_D_STEPS /
-        # DCGAN_BETA2 / DCGAN_LR_D / DCGAN_LR_G, as the HIP engine
-        d_steps, beta2, lr_d, lr_g = R.resolve_d_steps(d_steps, beta2, lr_d, lr_g, lr)
-        # learning-rate schedule: None = DCGAN_LR_DECAY / _START / _STEPS / DCGAN_LR_END / DCGAN_LR_WARMUP
-        self.lr_sched = R.resolve_lr_schedule(lr_decay, lr_decay_start, lr_decay_steps, lr_end, lr_warmup)
-        # instance noise: None = DCGAN_INSTANCE_NOISE / _END / _STEPS; drawn from the HIP engine's seed
-        # formula (HipEngine._zseed), so both engines add the same noise for the same flags
-        self.noise = R.resolve_instance_noise(instance_noise, instance_noise_end, instance_noise_steps)
-        # DiffAugment of D's inputs: None = DCGAN_D_AUGMENT; drawn from the same seed as the noise
-        self.aug = R.resolve_d_augment(d_augment)
-        self.color = R.resolve_d_color(d_color_augment)  # its color policy; None = DCGAN_D_COLOR_AUGMENT
-        # adaptive augmentation probability: None = DCGAN_D_AUGMENT_P / DCGAN_ADA_TARGET / _INTERVAL / _KIMG
-        self.ada = R.resolve_ada(d_augment_p, ada_target, ada_interval, ada_kimg,
-                                 augmented=self.aug.active or self.color.active, batch_size=batch_size)
-        # top-k generator updates: None = DCGAN_G_TOPK / DCGAN_G_TOPK_STEPS
-        self.topk = R.resolve_g_topk(g_topk, g_topk_steps)
+        # the instance noise and DiffAugment draw from the HIP engine's seed formula (HipEngine._zseed),
+        # so both engines add the same noise for the same flags
         zs = self.seed if z_seed is None else int(z_seed)
-        self.step_impl = ReferenceStep(self.model, lr, beta1, grad_hook=self._allreduce if world > 1 else None,
-                                       instance_noise=self.noise, noise_seed=zs * 1000003 + 17 + 7919 * rank,
-                                       d_augment=self.aug, d_color_augment=self.color, g_topk=self.topk,
-                                       d_ada=self.ada, world=world, g_ema_decay=g_ema_decay, gan_loss=gan_loss, label_smooth=label_smooth,
-                                       d_spectral_norm=bool(d_spectral_norm), seed=seed, d_steps=d_steps,
-                                       beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=self.lr_sched)
-        self.d_steps = self.step_impl.d_steps
-        self.d_spectral_norm = self.step_impl.d_spectral_norm
-        self.g_ema_decay = self.step_impl.g_ema_decay
-        self.gan_loss, self.label_smooth = self.step_impl.gan_loss, self.step_impl.label_smooth
+        self.step_impl = ReferenceStep(self.model, grad_hook=self._allreduce if world > 1 else None,
+                                       options=self.options, noise_seed=zs * 1000003 + 17 + 7919 * rank,
+                                       world=world, seed=seed)
         self.opt_d, self.opt_g = self.step_impl.opt_d, self.step_impl.opt_g
         self.z_gen = torch.Generator(device=device if device.type == "cuda" else "cpu")
         self.z_gen.manual_seed((z_seed if z_seed is not None else seed) + 7919 * rank + 1)
@@ -231,42 +194,16 @@ class ReferenceEngine:
 def build_engine(cfg: DCGANConfig, batch_size: int, device: torch.device, engine: str = "auto",
                  dtype: str = "bf16", seed: int = 0, rank: int = 0, world: int = 1, graph: bool = True,
                  allreduce_dtype: str = "fp32", lr: float = 2e-4, beta1: float = 0.5,
-                 zero_debias: bool = False, bucket_mb: float = 32.0, g_ema_decay: Optional[float] = None,
-                 gan_loss: Optional[str] = None, label_smooth: Optional[float] = None,
-                 d_spectral_norm: Optional[bool] = None, d_steps: Optional[int] = None,
-                 beta2: Optional[float] = None, lr_d: Optional[float] = None, lr_g: Optional[float] = None,
-                 lr_decay: Optional[str] = None,
-                 lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
-                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
-                 instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
-                 instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
-                 d_color_augment: Optional[str] = None, g_topk: Optional[float] = None,
-                 g_topk_steps: Optional[int] = None, d_augment_p: Optional[float] = None,
-                 ada_target: Optional[float] = None, ada_interval: Optional[int] = None,
-                 ada_kimg: Optional[float] = None):
-    ada_kw = dict(d_augment_p=d_augment_p, ada_target=ada_target, ada_interval=ada_interval, ada_kimg=ada_kimg)
+                 zero_debias: bool = False, bucket_mb: float = 32.0, **options):
+    """options: the training options (ops.options.TABLE), forwarded to the engine as they are."""
     if engine == "auto":  # every dtype (bf16 / fp16 / fp32) runs on the HIP kernels on an MI355X
         engine = "hip" if device.type == "cuda" else "reference"
     if engine == "reference":
         return ReferenceEngine(cfg, batch_size, device, seed=seed, lr=lr, beta1=beta1,
-                               zero_debias=zero_debias, rank=rank, world=world, g_ema_decay=g_ema_decay,
-                               gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm,
-                               d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=lr_decay,
-                               lr_decay_start=lr_decay_start, lr_decay_steps=lr_decay_steps, lr_end=lr_end,
-                               lr_warmup=lr_warmup, instance_noise=instance_noise,
-                               instance_noise_end=instance_noise_end, instance_noise_steps=instance_noise_steps,
-                               d_augment=d_augment, d_color_augment=d_color_augment, g_topk=g_topk,
-                               g_topk_steps=g_topk_steps, **ada_kw)
+                               zero_debias=zero_debias, rank=rank, world=world, **options)
     if engine == "hip":
         from .hip_engine import HipEngine
         return HipEngine(cfg, batch_size, device, dtype=dtype, seed=seed, lr=lr, beta1=beta1,
                          zero_debias=zero_debias, rank=rank, world=world, graph=graph,
-                         allreduce_dtype=allreduce_dtype, bucket_mb=bucket_mb, g_ema_decay=g_ema_decay,
-                         gan_loss=gan_loss, label_smooth=label_smooth, d_spectral_norm=d_spectral_norm,
-                         d_steps=d_steps, beta2=beta2, lr_d=lr_d, lr_g=lr_g, lr_decay=lr_decay,
-                         lr_decay_start=lr_decay_start, lr_decay_steps=lr_decay_steps, lr_end=lr_end,
-                         lr_warmup=lr_warmup, instance_noise=instance_noise,
-                         instance_noise_end=instance_noise_end, instance_noise_steps=instance_noise_steps,
-                         d_augment=d_augment, d_color_augment=d_color_augment, g_topk=g_topk,
-                         g_topk_steps=g_topk_steps, **ada_kw)
+                         allreduce_dtype=allreduce_dtype, bucket_mb=bucket_mb, **options)
     raise ValueError("unknown engine %r" % engine)

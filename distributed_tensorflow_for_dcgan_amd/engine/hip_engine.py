@@ -57,6 +57,7 @@ from ..models.config import DCGANConfig, same_pads
 from ..models.dcgan import DCGAN
 from ..optim.adam import TFAdam
 from ..ops import hip as H
+from ..ops import options as O
 from ..ops import reference as R
 from ..parallel import dist as D
 from .hip_aux import HipEngineAux
@@ -161,18 +162,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                  seed: int = 0, lr: float = 2e-4, beta1: float = 0.5, zero_debias: bool = False, rank: int = 0,
                  world: int = 1, graph: bool = True, allreduce_dtype: str = "fp32", bucket_mb: float = 32.0,
                  rank_seeded_z: bool = True, schedule: Optional[str] = None, dry_run: bool = False,
-                 ddp: Optional[bool] = None, g_ema_decay: Optional[float] = None, gan_loss: Optional[str] = None,
-                 label_smooth: Optional[float] = None, d_spectral_norm: Optional[bool] = None,
-                 z_seed: Optional[int] = None, d_steps: Optional[int] = None, beta2: Optional[float] = None,
-                 lr_d: Optional[float] = None, lr_g: Optional[float] = None, lr_decay: Optional[str] = None,
-                 lr_decay_start: Optional[int] = None, lr_decay_steps: Optional[int] = None,
-                 lr_end: Optional[float] = None, lr_warmup: Optional[int] = None,
-                 instance_noise: Optional[float] = None, instance_noise_end: Optional[float] = None,
-                 instance_noise_steps: Optional[int] = None, d_augment: Optional[str] = None,
-                 d_color_augment: Optional[str] = None, g_topk: Optional[float] = None,
-                 g_topk_steps: Optional[int] = None, d_augment_p: Optional[float] = None,
-                 ada_target: Optional[float] = None, ada_interval: Optional[int] = None,
-                 ada_kimg: Optional[float] = None, **_):
+                 ddp: Optional[bool] = None, z_seed: Optional[int] = None, **options):
         if dtype not in DTYPES:
             raise ValueError("HIP engine dtype must be one of %s" % sorted(DTYPES))
         self.dtype_name = dtype
@@ -194,75 +184,55 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # seed of the in-kernel z stream (as ReferenceEngine's z_seed): None = the model seed
         self.z_seed = self.seed if z_seed is None else int(z_seed)
         self.rank_seeded_z = bool(rank_seeded_z)  # False only in equivalence tests
-        self.lr, self.beta1 = float(lr), float(beta1)
-        # discriminator updates per generator update (d_steps - 1 recorded D-only sub-steps before
-        # each full step), Adam's beta2 and the per-network learning rates. None: DCGAN_D_STEPS /
-        # DCGAN_BETA2 / DCGAN_LR_D / DCGAN_LR_G, then 1 / TFAdam's beta2 / lr. All at their defaults:
-        # no buffer, launch or Program beyond the full step's
-        self.d_steps, self.beta2, self.lr_d, self.lr_g = R.resolve_d_steps(d_steps, beta2, lr_d, lr_g, lr)
-        # learning-rate schedule (ops.reference.LrSchedule), evaluated by every recorded Adam launch
-        # from the device step counter: replays follow the live counter, a resume needs no new state.
-        # None: DCGAN_LR_DECAY / _START / _STEPS / DCGAN_LR_END / DCGAN_LR_WARMUP. Off: the Adam ops
-        # are recorded exactly as without it and never read the counter
-        self.lr_sched = R.resolve_lr_schedule(lr_decay, lr_decay_start, lr_decay_steps, lr_end, lr_warmup)
-        # instance noise (ops.reference.InstanceNoise): D's layer 0 reads x + sigma(t) * eps, a noisy copy
-        # of [real | fake] that one recorded launch (`d_noise`) writes from the device step counter; the
-        # g_loss chain and G keep reading the clean fake. None: DCGAN_INSTANCE_NOISE / _END / _STEPS.
-        # Off: no buffer, no op
-        self.noise = R.resolve_instance_noise(instance_noise, instance_noise_end, instance_noise_steps)
-        # DiffAugment (ops.reference.DAugment): D sees augment([real | fake]), translation and / or cutout
-        # per sample, which one recorded launch (`d_aug`) draws from stream 2 of the step's z seed and the
-        # device step counter and writes, with its draws, behind G's RGB layer -- before the noise when
-        # both are on. Its Jacobian is not the identity: the g_loss chain's image gradient passes through
-        # the transposed gather (`d_aug_bwd`, from the recorded draws) before G's tanh backward, which
-        # therefore runs unfused. None: DCGAN_D_AUGMENT. Off: no buffer, no op
-        self.aug = R.resolve_d_augment(d_augment)
-        # DiffAugment's color policy (ops.reference.DColor), a switch of its own: D sees noise(geometric(
-        # color([real | fake]))), the published order. One recorded launch (`d_color`) ahead of `d_aug`
-        # draws (b, s, c) per sample from stream 3 of the step's z seed and the device step counter and
-        # writes the colored copy with (b, s, c, Mx); its Jacobian is a dense linear map per image, which
-        # `d_color_bwd` applies transposed to the g_loss chain's image gradient, behind `d_aug_bwd` and
-        # ahead of G's tanh backward. None: DCGAN_D_COLOR_AUGMENT. Off: no buffer, no op
-        self.color = R.resolve_d_color(d_color_augment)
-        # adaptive augmentation probability (ops.reference.DAda): each selected policy of the two switches
-        # above applies to a sample with probability p = p24 * 2^-24. `d_color` / `d_aug` are then recorded
-        # as their gated kernels, which read p24 from the device state `ada_state` and record the per-sample
-        # gate masks that the two `_bwd` ops replay. With a target, one more recorded launch per full step
-        # (`ada_update`, on the D chain's stream) steers p24 from the real half of the logits, so graph
-        # and eager replays follow the live state with no host round trip. D sub-steps gate with the live
-        # p24 and record no controller op. None: DCGAN_D_AUGMENT_P / DCGAN_ADA_TARGET / _INTERVAL / _KIMG.
-        # Off (p = 1, no target): no buffer, no op, the ungated kernels
-        self.ada = R.resolve_ada(d_augment_p, ada_target, ada_interval, ada_kimg,
-                                 augmented=self.aug.active or self.color.active, batch_size=batch_size)
-        # top-k generator updates (ops.reference.GTopK): the g_loss chain's seed keeps the k(t) fakes D
-        # scores highest, times B / k, and is +0 on the others; one recorded launch (`g_topk`), the first
+        # The training options (ops.options.TABLE), resolved once -- an explicit keyword, else (None) the
+        # option's environment variable, else its default -- and published under their field names. Each
+        # at its default: no buffer, launch or Program beyond the plain full step's.
+        # d_steps, beta2, lr_d, lr_g: discriminator updates per generator update (d_steps - 1 recorded
+        # D-only sub-steps before each full step), Adam's beta2 and the per-network learning rates.
+        # lr_sched (ops.reference.LrSchedule): evaluated by every recorded Adam launch from the device step
+        # counter: replays follow the live counter, a resume needs no new state. Off: the Adam ops are
+        # recorded exactly as without it and never read the counter.
+        # noise (ops.reference.InstanceNoise): D's layer 0 reads x + sigma(t) * eps, a noisy copy of
+        # [real | fake] that one recorded launch (`d_noise`) writes from the device step counter; the
+        # g_loss chain and G keep reading the clean fake.
+        # aug, DiffAugment (ops.reference.DAugment): D sees augment([real | fake]), translation and / or
+        # cutout per sample, which one recorded launch (`d_aug`) draws from stream 2 of the step's z seed
+        # and the device step counter and writes, with its draws, behind G's RGB layer -- before the noise
+        # when both are on. Its Jacobian is not the identity: the g_loss chain's image gradient passes
+        # through the transposed gather (`d_aug_bwd`, from the recorded draws) before G's tanh backward,
+        # which therefore runs unfused.
+        # color, DiffAugment's color policy (ops.reference.DColor), a switch of its own: D sees noise(
+        # geometric(color([real | fake]))), the published order. One recorded launch (`d_color`) ahead of
+        # `d_aug` draws (b, s, c) per sample from stream 3 of the step's z seed and the device step counter
+        # and writes the colored copy with (b, s, c, Mx); its Jacobian is a dense linear map per image,
+        # which `d_color_bwd` applies transposed to the g_loss chain's image gradient, behind `d_aug_bwd`
+        # and ahead of G's tanh backward.
+        # ada, adaptive augmentation probability (ops.reference.DAda): each selected policy of the two
+        # switches above applies to a sample with probability p = p24 * 2^-24. `d_color` / `d_aug` are then
+        # recorded as their gated kernels, which read p24 from the device state `ada_state` and record the
+        # per-sample gate masks that the two `_bwd` ops replay. With a target, one more recorded launch per
+        # full step (`ada_update`, on the D chain's stream) steers p24 from the real half of the logits, so
+        # graph and eager replays follow the live state with no host round trip. D sub-steps gate with the
+        # live p24 and record no controller op. Off (p = 1, no target): the ungated kernels.
+        # topk, top-k generator updates (ops.reference.GTopK): the g_loss chain's seed keeps the k(t) fakes
+        # D scores highest, times B / k, and is +0 on the others; one recorded launch (`g_topk`), the first
         # op behind the forward on the G chain's stream, selects them from the logits and the device step
         # counter into buffers of its own. D's losses, seeds and chain are untouched, D sub-steps record
-        # no such op. None: DCGAN_G_TOPK / DCGAN_G_TOPK_STEPS. Off (nu = 1): no buffer, no op
-        self.topk = R.resolve_g_topk(g_topk, g_topk_steps)
+        # no such op.
+        # g_ema_decay: moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates =
+        # the global step); 0 = off.
+        # gan_loss, label_smooth: objective of the fused head / loss kernel: bce | lsgan | hinge, D's real
+        # target = 1 - label_smooth.
+        # d_spectral_norm: spectral normalisation of D's conv kernels and head: D computes with W /
+        # sigma(W), one power-iteration step after each Adam(D).
+        self.options = O.resolve(batch_size, lr=lr, beta1=beta1, **O.known(options))
+        vars(self).update(self.options._asdict())
         if self.topk.active and batch_size > R.TOPK_MAX_B:
             raise ValueError("g_topk needs batch_size <= %d (the selection ranks one batch in one workgroup), "
                              "got %d" % (R.TOPK_MAX_B, batch_size))
-        # moving average of G's weights (tf.train.ExponentialMovingAverage with num_updates = the
-        # global step); 0 = off: no buffers, no op. None: DCGAN_G_EMA_DECAY (A/B of its cost)
-        if g_ema_decay is None:
-            g_ema_decay = float(os.environ.get("DCGAN_G_EMA_DECAY") or 0.0)
-        self.g_ema_decay = R.check_ema_decay(g_ema_decay)
         if self.g_ema_decay > 0 and os.environ.get("DCGAN_DDP_SHARD", "0") == "1":
             raise ValueError("g_ema_decay > 0 is not supported with DCGAN_DDP_SHARD=1: under the sharded update "
                              "each rank holds only 1/W of G's fp32 masters when the average would be taken")
-        # objective of the fused head / loss kernel: bce | lsgan | hinge, D's real target = 1 -
-        # label_smooth. None: DCGAN_GAN_LOSS / DCGAN_LABEL_SMOOTH (A/B on the benchmark)
-        if gan_loss is None:
-            gan_loss = os.environ.get("DCGAN_GAN_LOSS") or "bce"
-        if label_smooth is None:
-            label_smooth = float(os.environ.get("DCGAN_LABEL_SMOOTH") or 0.0)
-        self.gan_loss, self.label_smooth = R.check_gan_loss(gan_loss, label_smooth)
-        # spectral normalisation of D's conv kernels and head: D computes with W / sigma(W), one
-        # power-iteration step after each Adam(D). Off: no buffer, no launch. None: DCGAN_D_SPECTRAL_NORM
-        if d_spectral_norm is None:
-            d_spectral_norm = R.env_spectral_norm()
-        self.d_spectral_norm = R.check_spectral_norm(d_spectral_norm)
         if self.d_spectral_norm and os.environ.get("DCGAN_DDP_SHARD", "0") == "1":
             raise ValueError("d_spectral_norm is not supported with DCGAN_DDP_SHARD=1: sigma needs the whole "
                              "matrix, and under the sharded update each rank holds only 1/W of D's fp32 masters")

@@ -16,66 +16,69 @@ from typing import Callable, Dict, Optional
 import torch
 
 from ..models.dcgan import DCGAN
+from ..ops import options as O
 from ..ops import reference as R
 from ..optim.adam import TFAdam
 
 
 class ReferenceStep:
     def __init__(self, model: DCGAN, lr: float = 2e-4, beta1: float = 0.5,
-                 grad_hook: Optional[Callable[[str, torch.Tensor], None]] = None, g_ema_decay: float = 0.0,
-                 gan_loss: str = "bce", label_smooth: float = 0.0, d_spectral_norm: bool = False, seed: int = 0,
-                 d_steps: int = 1, beta2: float = R.ADAM_BETA2, lr_d: Optional[float] = None,
-                 lr_g: Optional[float] = None, lr_decay="none", lr_decay_start: int = 0, lr_decay_steps: int = 0,
-                 lr_end: float = 0.0, lr_warmup: int = 0, instance_noise=0.0, instance_noise_end: float = 0.0,
-                 instance_noise_steps: int = 0, noise_seed: int = 0, d_augment="", d_color_augment="",
-                 g_topk=1.0, g_topk_steps: int = 0, d_ada=None, world: int = 1):
+                 grad_hook: Optional[Callable[[str, torch.Tensor], None]] = None,
+                 options: Optional[O.StepOptions] = None, noise_seed: int = 0, seed: int = 0, world: int = 1,
+                 d_ada=None, **keywords):
+        """options: the resolved record; else `keywords` are the training options (ops.options.TABLE;
+        d_ada: the ADA group as an ops.reference.DAda), at their defaults where not given -- the
+        environment is never read here."""
         self.model = model
+        if options is None:
+            if d_ada is not None:
+                keywords["d_augment_p"] = d_ada
+            options = O.resolve(env=False, lr=lr, beta1=beta1, **keywords)
+        o = self.options = options
         # top-k generator updates (ops.reference.GTopK): g_loss is differentiated over the k(t) fakes D
         # scores highest only, k annealed from B to ceil(nu B) over the global step; D's losses and
         # gradients and the reported g_loss stay those of all B samples
-        self.topk = R.check_g_topk(*g_topk) if isinstance(g_topk, R.GTopK) else R.check_g_topk(g_topk, g_topk_steps)
+        self.topk = o.topk
         # DiffAugment (ops.reference.DAugment): D sees augment([real | fake]) -- translation and / or
         # cutout, drawn per sample from Philox stream 2 of `noise_seed` at the global step (D sub-step
         # k: substep_seed(noise_seed, k)) -- before the additive noise; G's gradient flows through it
-        self.aug = R.check_d_augment(d_augment)
+        self.aug = o.aug
         # its color policy (ops.reference.DColor), ahead of translation / cutout: brightness, saturation,
         # contrast per sample, (b, s, c) from Philox stream 3 of the same seed at the global step
-        self.color = R.check_d_color(d_color_augment)
+        self.color = o.color
         # adaptive augmentation probability (ops.reference.DAda): each selected policy applies to a sample
         # iff its gate -- Philox streams 4 (translation, cutout) and 5 (color) of the same seed -- falls
         # below p24; with a target, ``step`` steers p24 from its own real logits (ops.reference.ada_update),
         # `world` entering the step size only. D sub-steps gate with the live p24 and leave the state alone
-        self.ada = R.check_ada(R.DAda() if d_ada is None else d_ada, augmented=self.aug.active or self.color.active)
+        self.ada = o.ada
         self.ada_world = int(world)
         self.ada_state = R.ada_state(R.ada_p24(self.ada.p))
         # instance noise (ops.reference.InstanceNoise): D sees [real | fake] + sigma(t) * eps, eps from
         # Philox stream 1 of `noise_seed` (the HIP engine's z seed) at the global step; D sub-step k
         # draws from ops.reference.substep_seed(noise_seed, k). G's gradient flows through it unchanged
-        self.noise = R.check_instance_noise(*instance_noise) if isinstance(instance_noise, R.InstanceNoise) else \
-            R.check_instance_noise(instance_noise, instance_noise_end, instance_noise_steps)
+        self.noise = o.noise
         self.noise_seed = int(noise_seed)
         self._sub_k = 0  # D sub-steps taken since the last full step
         # learning-rate schedule (ops.reference.LrSchedule): both Adam rates times lr_factor at the
         # global step before its increment; the D sub-steps see the step of the full step after them
-        self.lr_sched = R.check_lr_schedule(*lr_decay) if isinstance(lr_decay, R.LrSchedule) else \
-            R.check_lr_schedule(lr_decay, lr_decay_start, lr_decay_steps, lr_end, lr_warmup)
+        self.lr_sched = o.lr_sched
         # discriminator updates per generator update (d_steps - 1 D sub-steps, ``d_step``, before
         # each full ``step``), Adam's beta2 and the per-network learning rates (TTUR)
-        self.d_steps, self.beta2, self.lr_d, self.lr_g = R.check_d_steps(d_steps, beta2, lr_d, lr_g, lr)
+        self.d_steps, self.beta2, self.lr_d, self.lr_g = o.d_steps, o.beta2, o.lr_d, o.lr_g
         # spectral normalisation of D's conv kernels and head (model.d_sn; ops.reference.sn_power /
         # spectral_normalize): D computes with W / sigma(W), one power step after each Adam(D)
-        self.d_spectral_norm = R.check_spectral_norm(d_spectral_norm)
+        self.d_spectral_norm = o.d_spectral_norm
         if self.d_spectral_norm and model.d_sn is None:
             model.enable_d_spectral_norm(seed)
         # objective (ops.reference.gan_losses): bce | lsgan | hinge, D's real target = 1 - label_smooth
-        self.gan_loss, self.label_smooth = R.check_gan_loss(gan_loss, label_smooth)
+        self.gan_loss, self.label_smooth = o.gan_loss, o.label_smooth
         # moving average of G's weights (model.g_ema; ops.reference.ema_update_), 0 = none kept
-        self.g_ema_decay = R.check_ema_decay(g_ema_decay)
+        self.g_ema_decay = o.g_ema_decay
         if self.g_ema_decay > 0:
             model.g_ema = model.g.like()
             model.g_ema.flat.copy_(model.g.flat)
-        self.opt_d = TFAdam(model.d, self.lr_d, beta1, self.beta2, power_suffix="")
-        self.opt_g = TFAdam(model.g, self.lr_g, beta1, self.beta2, power_suffix="_1")
+        self.opt_d = TFAdam(model.d, self.lr_d, o.beta1, self.beta2, power_suffix="")
+        self.opt_g = TFAdam(model.g, self.lr_g, o.beta1, self.beta2, power_suffix="_1")
         self.global_step = 0
         self.grad_hook = grad_hook  # e.g. DDP all-reduce of the flat grad buffer
         self.last: Dict[str, torch.Tensor] = {}

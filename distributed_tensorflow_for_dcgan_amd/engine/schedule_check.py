@@ -167,9 +167,7 @@ def check_engine(eng, steps: int = 2) -> Tuple[List[Hazard], int]:
 
 
 def check(cfg=None, batch_size: int = 8, dtype: str = "bf16", world: int = 1, schedule: Optional[str] = None,
-          timing: bool = False, steps: int = 2, allreduce_dtype: str = "fp32", g_ema_decay: float = 0.0,
-          gan_loss: str = "bce", label_smooth: float = 0.0, d_spectral_norm: bool = False, d_steps: int = 1,
-          **engine_kw):
+          timing: bool = False, steps: int = 2, allreduce_dtype: str = "fp32", **engine_kw):
     """Build a dry-run engine on the CPU and check one schedule. Returns (schedule, hazards, ops).
     engine_kw: further HipEngine arguments (the learning-rate schedule's lr_decay, lr_decay_steps, ...:
     with one on, every Adam op reads the step counter that step_end / adam2 writes; instance_noise,
@@ -184,8 +182,7 @@ def check(cfg=None, batch_size: int = 8, dtype: str = "bf16", world: int = 1, sc
     from .hip_engine import HipEngine
     cfg = cfg or DCGANConfig()
     eng = HipEngine(cfg, batch_size, torch.device("cpu"), dtype=dtype, world=world, schedule=schedule, dry_run=True,
-                    graph=False, allreduce_dtype=allreduce_dtype, g_ema_decay=g_ema_decay, gan_loss=gan_loss,
-                    label_smooth=label_smooth, d_spectral_norm=d_spectral_norm, d_steps=d_steps, **engine_kw)
+                    graph=False, allreduce_dtype=allreduce_dtype, **engine_kw)
     if timing:  # (enable_timing without its CUDA events)
         eng._timing = True
         eng._build_updates()

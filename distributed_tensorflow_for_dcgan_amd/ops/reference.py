@@ -14,6 +14,7 @@ is tested against. They reproduce, with explicit padding/cropping:
 from __future__ import annotations
 
 import math
+import os
 from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -140,6 +141,17 @@ def tf_adam_update(param: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: 
     param.sub_(lr_t * m / (v.sqrt() + eps))
 
 
+def env_value(name, conv):
+    """conv(environment variable `name`); None when it is unset or empty. Read at call time."""
+    v = os.environ.get(name)
+    if v is None or v.strip() == "":
+        return None
+    try:
+        return conv(v)
+    except ValueError:
+        raise ValueError("%s=%r is not a number" % (name, v)) from None
+
+
 ADAM_BETA2 = 0.999   # TF-Adam's beta2 where none is given (optim.adam.TFAdam's default)
 MAX_D_STEPS = 16
 
@@ -167,25 +179,8 @@ def check_d_steps(d_steps=1, beta2=ADAM_BETA2, lr_d=None, lr_g=None, lr=2e-4):
 def resolve_d_steps(d_steps=None, beta2=None, lr_d=None, lr_g=None, lr=2e-4):
     """check_d_steps over the engines' arguments: None = the environment default (DCGAN_D_STEPS,
     DCGAN_BETA2, DCGAN_LR_D, DCGAN_LR_G), then 1 / ADAM_BETA2 / `lr`. An explicit argument wins."""
-    import os
-
-    def env(name, conv):
-        v = os.environ.get(name)
-        if v is None or v.strip() == "":
-            return None
-        try:
-            return conv(v)
-        except ValueError:
-            raise ValueError("%s=%r is not a number" % (name, v)) from None
-    if d_steps is None:
-        d_steps = env("DCGAN_D_STEPS", int)
-    if beta2 is None:
-        beta2 = env("DCGAN_BETA2", float)
-    if lr_d is None:
-        lr_d = env("DCGAN_LR_D", float)
-    if lr_g is None:
-        lr_g = env("DCGAN_LR_G", float)
-    return check_d_steps(1 if d_steps is None else d_steps, ADAM_BETA2 if beta2 is None else beta2, lr_d, lr_g, lr)
+    from .options import resolve_group
+    return resolve_group("d_steps", (d_steps, beta2, lr_d, lr_g), lr=lr)
 
 
 def check_d_steps_schedule(d_steps: int, schedule: str, sharded: bool) -> None:
@@ -280,31 +275,8 @@ def resolve_lr_schedule(kind=None, start=None, steps=None, end=None, warmup=None
     """check_lr_schedule over the engines' arguments: None = the environment default (DCGAN_LR_DECAY,
     DCGAN_LR_DECAY_START, DCGAN_LR_DECAY_STEPS, DCGAN_LR_END, DCGAN_LR_WARMUP), then none / 0 / 0 /
     0.0 / 0. An explicit argument wins. An LrSchedule as `kind` is validated as it is."""
-    import os
-    if isinstance(kind, LrSchedule):
-        return check_lr_schedule(*kind, total_steps=total_steps)
-
-    def env(name, conv):
-        v = os.environ.get(name)
-        if v is None or v.strip() == "":
-            return None
-        try:
-            return conv(v)
-        except ValueError:
-            raise ValueError("%s=%r is not a number" % (name, v)) from None
-    if kind is None:
-        kind = env("DCGAN_LR_DECAY", str)
-    if start is None:
-        start = env("DCGAN_LR_DECAY_START", int)
-    if steps is None:
-        steps = env("DCGAN_LR_DECAY_STEPS", int)
-    if end is None:
-        end = env("DCGAN_LR_END", float)
-    if warmup is None:
-        warmup = env("DCGAN_LR_WARMUP", int)
-    return check_lr_schedule("none" if kind is None else kind, 0 if start is None else start,
-                             0 if steps is None else steps, 0.0 if end is None else end,
-                             0 if warmup is None else warmup, total_steps=total_steps)
+    from .options import resolve_group
+    return resolve_group("lr_sched", (kind, start, steps, end, warmup), total_steps=total_steps)
 
 
 def lr_factor(sched: LrSchedule, t, dtype=torch.float32) -> torch.Tensor:
@@ -394,26 +366,8 @@ def resolve_instance_noise(sigma0=None, sigma1=None, steps=None, total_steps=Non
     """check_instance_noise over the engines' arguments: None = the environment default
     (DCGAN_INSTANCE_NOISE, DCGAN_INSTANCE_NOISE_END, DCGAN_INSTANCE_NOISE_STEPS), then 0 / 0 / 0. An
     explicit argument wins. An InstanceNoise as `sigma0` is validated as it is."""
-    import os
-    if isinstance(sigma0, InstanceNoise):
-        return check_instance_noise(*sigma0, total_steps=total_steps)
-
-    def env(name, conv):
-        v = os.environ.get(name)
-        if v is None or v.strip() == "":
-            return None
-        try:
-            return conv(v)
-        except ValueError:
-            raise ValueError("%s=%r is not a number" % (name, v)) from None
-    if sigma0 is None:
-        sigma0 = env("DCGAN_INSTANCE_NOISE", float)
-    if sigma1 is None:
-        sigma1 = env("DCGAN_INSTANCE_NOISE_END", float)
-    if steps is None:
-        steps = env("DCGAN_INSTANCE_NOISE_STEPS", int)
-    return check_instance_noise(0.0 if sigma0 is None else sigma0, 0.0 if sigma1 is None else sigma1,
-                                0 if steps is None else steps, total_steps=total_steps)
+    from .options import resolve_group
+    return resolve_group("noise", (sigma0, sigma1, steps), total_steps=total_steps)
 
 
 def noise_sigma(t, sigma0: float, sigma1: float, steps: int, dtype=torch.float32) -> torch.Tensor:
@@ -556,10 +510,8 @@ def check_d_augment(spec="") -> DAugment:
 def resolve_d_augment(spec=None) -> DAugment:
     """check_d_augment over the engines' argument: None = the environment default DCGAN_D_AUGMENT,
     then off. An explicit argument wins."""
-    import os
-    if spec is None:
-        spec = os.environ.get("DCGAN_D_AUGMENT") or ""
-    return check_d_augment(spec)
+    from .options import resolve_group
+    return resolve_group("aug", (spec,))
 
 
 def augment_params(n: int, S: int, seed: int, step: int) -> torch.Tensor:
@@ -689,10 +641,8 @@ def check_d_color(spec="") -> DColor:
 def resolve_d_color(spec=None) -> DColor:
     """check_d_color over the engines' argument: None = the environment default
     DCGAN_D_COLOR_AUGMENT, then off. An explicit argument wins."""
-    import os
-    if spec is None:
-        spec = os.environ.get("DCGAN_D_COLOR_AUGMENT") or ""
-    return check_d_color(spec)
+    from .options import resolve_group
+    return resolve_group("color", (spec,))
 
 
 def color_params(n: int, seed: int, step: int) -> torch.Tensor:
@@ -899,28 +849,8 @@ def resolve_ada(p=None, target=None, interval=None, kimg=None, augmented: Option
     """check_ada over the engines' arguments: None = the environment default (DCGAN_D_AUGMENT_P,
     DCGAN_ADA_TARGET, DCGAN_ADA_INTERVAL, DCGAN_ADA_KIMG), then -1 / 0 / 4 / 500. An explicit argument
     wins. A DAda as `p` is validated as it is."""
-    import os
-    if isinstance(p, DAda):
-        return check_ada(p, augmented=augmented, batch_size=batch_size)
-
-    def env(name, conv):
-        v = os.environ.get(name)
-        if v is None or v.strip() == "":
-            return None
-        try:
-            return conv(v)
-        except ValueError:
-            raise ValueError("%s=%r is not a number" % (name, v)) from None
-    if p is None:
-        p = env("DCGAN_D_AUGMENT_P", float)
-    if target is None:
-        target = env("DCGAN_ADA_TARGET", float)
-    if interval is None:
-        interval = env("DCGAN_ADA_INTERVAL", int)
-    if kimg is None:
-        kimg = env("DCGAN_ADA_KIMG", float)
-    return check_ada(-1.0 if p is None else p, 0.0 if target is None else target, 4 if interval is None else interval,
-                     500.0 if kimg is None else kimg, augmented=augmented, batch_size=batch_size)
+    from .options import resolve_group
+    return resolve_group("ada", (p, target, interval, kimg), augmented=augmented, batch_size=batch_size)
 
 
 def ada_p24(p: float) -> int:
@@ -1047,23 +977,8 @@ def check_g_topk(nu=1.0, steps=0, total_steps=None, open_ended=False) -> GTopK:
 def resolve_g_topk(nu=None, steps=None, total_steps=None) -> GTopK:
     """check_g_topk over the engines' arguments: None = the environment default (DCGAN_G_TOPK,
     DCGAN_G_TOPK_STEPS), then 1 / 0. An explicit argument wins. A GTopK as `nu` is validated as it is."""
-    import os
-    if isinstance(nu, GTopK):
-        return check_g_topk(*nu, total_steps=total_steps)
-
-    def env(name, conv):
-        v = os.environ.get(name)
-        if v is None or v.strip() == "":
-            return None
-        try:
-            return conv(v)
-        except ValueError:
-            raise ValueError("%s=%r is not a number" % (name, v)) from None
-    if nu is None:
-        nu = env("DCGAN_G_TOPK", float)
-    if steps is None:
-        steps = env("DCGAN_G_TOPK_STEPS", int)
-    return check_g_topk(1.0 if nu is None else nu, 0 if steps is None else steps, total_steps=total_steps)
+    from .options import resolve_group
+    return resolve_group("topk", (nu, steps), total_steps=total_steps)
 
 
 def topk_kmin(B: int, nu: float) -> int:
@@ -1224,8 +1139,3 @@ def check_spectral_norm(flag) -> bool:
         return bool(flag)
     raise ValueError("d_spectral_norm must be a boolean, got %r" % (flag,))
 
-
-def env_spectral_norm() -> bool:
-    """The engines' default where none is given: DCGAN_D_SPECTRAL_NORM."""
-    import os
-    return check_spectral_norm(os.environ.get("DCGAN_D_SPECTRAL_NORM") or "0")

@@ -30,6 +30,7 @@ from ..models.config import config_from_flags
 from ..obs import images as IM
 from ..obs import summaries as SUM
 from ..obs.events import SummaryWriter
+from ..ops import options as O
 from ..ops import reference as R
 from ..parallel import dist as D
 from ..utils.flags import Flags, apply_dataset_preset, cluster_from_flags
@@ -154,53 +155,33 @@ def run(flags: Flags, out=None) -> int:
         print("device %s rank %d/%d local_rank %d (%s) engine %s" % (device, rank, world, cl["local_rank"],
                                                                    cl["source"], flags.engine), file=out, flush=True)
 
-    # --lr_decay_steps=0 with a decay: "until the end of training". The recorded Adam launches take
-    # the length as a constant, so the data source (whose size caps max_steps through --epoch) is
-    # opened ahead of the engine in that case alone
+    # An annealed option's --*_steps=0 (--lr_decay_steps with a decay, --instance_noise_steps with
+    # --instance_noise != --instance_noise_end, --g_topk_steps with --g_topk < 1) means "until the end of
+    # training". The recorded launches take the length as a constant, so the data source (whose size
+    # caps max_steps through --epoch) is opened ahead of the engine in that case alone
     source = None
     sample_only = flags.explicitly_set("is_train") and not flags.is_train
-    lr_steps = int(flags.lr_decay_steps)
-    lr_open = str(flags.lr_decay).strip().lower() != "none" and lr_steps == 0
-    # --instance_noise_steps=0 with an anneal (--instance_noise != --instance_noise_end) likewise: the
-    # recorded noise launch takes the length as a constant
-    noise_steps = int(flags.instance_noise_steps)
-    noise_open = float(flags.instance_noise) != float(flags.instance_noise_end) and noise_steps == 0
-    # --g_topk_steps=0 with --g_topk < 1 likewise: the recorded top-k launch takes the length as a constant
-    topk_steps = int(flags.g_topk_steps)
-    topk_open = float(flags.g_topk) < 1.0 and topk_steps == 0
-    if lr_open or noise_open or topk_open:
+    options = O.from_flags(flags)
+    pending = O.open_ended(options)
+    if pending:
         total = None  # sample-only mode never steps: any valid length
         if not sample_only:
             hip_engine = flags.engine == "hip" or (flags.engine == "auto" and device.type == "cuda")
             source = make_source(flags, B, shape, device, rank=rank, world=world,
                                  engine_dtype=flags.dtype if hip_engine else "fp32")
             total = _step_budget(flags, source.num_examples, int(flags.d_steps), B, world)[1]
-        try:
-            if lr_open:
-                lr_steps = R.check_lr_schedule(flags.lr_decay, flags.lr_decay_start, 0, flags.lr_end,
-                                               flags.lr_warmup_steps,
-                                               total_steps=int(flags.lr_decay_start) + 1 if total is None else total).steps
-        except ValueError as e:
-            if source is not None:
-                source.close()
-            raise SystemExit("--lr_decay_steps: %s" % e)
-        try:
-            if noise_open:
-                noise_steps = R.check_instance_noise(flags.instance_noise, flags.instance_noise_end, 0,
-                                                     total_steps=1 if total is None else total).steps
-        except ValueError as e:
-            if source is not None:
-                source.close()
-            raise SystemExit("--instance_noise_steps: %s" % e)
-        try:
-            if topk_open:
-                topk_steps = R.check_g_topk(flags.g_topk, 0, total_steps=1 if total is None else total).steps
-        except ValueError as e:
-            if source is not None:
-                source.close()
-            raise SystemExit("--g_topk_steps: %s" % e)
+        for group in pending:
+            try:
+                options[group.steps] = group.until_end(options, total)
+            except ValueError as e:
+                if source is not None:
+                    source.close()
+                raise SystemExit("--%s: %s" % (group.steps_flag, e))
     try:
-        engine = _build_engine(flags, cfg, B, device, rank, world, lr_steps, noise_steps, topk_steps)
+        engine = build_engine(cfg, B, device, engine=flags.engine, dtype=flags.dtype, seed=int(flags.seed),
+                              rank=rank, world=world, graph=bool(flags.graph),
+                              allreduce_dtype=flags.allreduce_dtype, zero_debias=bool(flags.bn_zero_debias),
+                              bucket_mb=float(flags.bucket_mb), **options)
     except BaseException:
         if source is not None:
             source.close()
@@ -410,26 +391,6 @@ def _step_budget(flags, n_ex: int, n_d: int, B: int, world: int):
     if flags.epoch and int(flags.epoch) > 0:
         max_steps = min(max_steps, int(flags.epoch) * step_per_epoch)
     return step_per_epoch, max_steps
-
-
-def _build_engine(flags, cfg, B, device, rank, world, lr_decay_steps, instance_noise_steps, g_topk_steps):
-    return build_engine(cfg, B, device, engine=flags.engine, dtype=flags.dtype, seed=int(flags.seed), rank=rank,
-                        world=world, graph=bool(flags.graph), allreduce_dtype=flags.allreduce_dtype,
-                        lr=float(flags.learning_rate), beta1=float(flags.beta1),
-                        zero_debias=bool(flags.bn_zero_debias), bucket_mb=float(flags.bucket_mb),
-                        g_ema_decay=float(flags.g_ema_decay), gan_loss=str(flags.gan_loss),
-                        label_smooth=float(flags.label_smooth), d_spectral_norm=bool(flags.d_spectral_norm),
-                        d_steps=int(flags.d_steps), beta2=float(flags.beta2),
-                        lr_d=float(flags.d_learning_rate), lr_g=float(flags.g_learning_rate),
-                        lr_decay=str(flags.lr_decay), lr_decay_start=int(flags.lr_decay_start),
-                        lr_decay_steps=int(lr_decay_steps), lr_end=float(flags.lr_end),
-                        lr_warmup=int(flags.lr_warmup_steps), instance_noise=float(flags.instance_noise),
-                        instance_noise_end=float(flags.instance_noise_end),
-                        instance_noise_steps=int(instance_noise_steps), d_augment=str(flags.d_augment),
-                        d_color_augment=str(flags.d_color_augment), g_topk=float(flags.g_topk),
-                        g_topk_steps=int(g_topk_steps), d_augment_p=float(flags.d_augment_p),
-                        ada_target=float(flags.ada_target), ada_interval=int(flags.ada_interval),
-                        ada_kimg=float(flags.ada_kimg))
 
 
 def _sample_ema(engine, flags) -> bool:

@@ -214,48 +214,8 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
     ns = parser.parse_args(argv)
     if not 0.0 <= float(ns.g_ema_decay) < 1.0:
         parser.error("--g_ema_decay must satisfy 0 <= decay < 1, got %r" % (ns.g_ema_decay,))
-    from ..ops.reference import check_gan_loss
-    try:
-        check_gan_loss(ns.gan_loss, ns.label_smooth)
-    except ValueError as e:
-        parser.error("--gan_loss / --label_smooth: %s" % e)
-    from ..ops.reference import check_d_steps
-    try:
-        check_d_steps(ns.d_steps, ns.beta2, ns.d_learning_rate, ns.g_learning_rate, ns.learning_rate)
-    except (ValueError, TypeError, OverflowError) as e:
-        parser.error("--d_steps / --beta2 / --d_learning_rate / --g_learning_rate: %s" % e)
-    from ..ops.reference import check_lr_schedule
-    try:  # (--lr_decay_steps=0 with a decay stays open here: the trainer resolves it)
-        check_lr_schedule(ns.lr_decay, ns.lr_decay_start, ns.lr_decay_steps, ns.lr_end, ns.lr_warmup_steps,
-                          open_ended=True)
-    except (ValueError, TypeError, OverflowError) as e:
-        parser.error("--lr_decay / --lr_decay_start / --lr_decay_steps / --lr_end / --lr_warmup_steps: %s" % e)
-    from ..ops.reference import check_instance_noise
-    try:  # (--instance_noise_steps=0 with an anneal stays open here: the trainer resolves it)
-        check_instance_noise(ns.instance_noise, ns.instance_noise_end, ns.instance_noise_steps, open_ended=True)
-    except (ValueError, TypeError, OverflowError) as e:
-        parser.error("--instance_noise / --instance_noise_end / --instance_noise_steps: %s" % e)
-    from ..ops.reference import check_d_augment
-    try:
-        check_d_augment(ns.d_augment)
-    except ValueError as e:
-        parser.error("--d_augment: %s" % e)
-    from ..ops.reference import check_d_color
-    try:
-        check_d_color(ns.d_color_augment)
-    except ValueError as e:
-        parser.error("--d_color_augment: %s" % e)
-    from ..ops.reference import check_ada
-    try:
-        check_ada(ns.d_augment_p, ns.ada_target, ns.ada_interval, ns.ada_kimg, batch_size=ns.batch_size,
-                  augmented=check_d_augment(ns.d_augment).active or check_d_color(ns.d_color_augment).active)
-    except (ValueError, TypeError, OverflowError) as e:
-        parser.error("--d_augment_p / --ada_target / --ada_interval / --ada_kimg: %s" % e)
-    from ..ops.reference import check_g_topk
-    try:  # (--g_topk_steps=0 with --g_topk < 1 stays open here: the trainer resolves it)
-        check_g_topk(ns.g_topk, ns.g_topk_steps, open_ended=True)
-    except (ValueError, TypeError, OverflowError) as e:
-        parser.error("--g_topk / --g_topk_steps: %s" % e)
+    from ..ops.options import validate_flags  # (an open-ended --*_steps=0 stays open here: the trainer resolves it)
+    validate_flags(ns, parser.error)
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
