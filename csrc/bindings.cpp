@@ -97,6 +97,23 @@ struct AccList {
   AccList& w(uintptr_t p, size_t n) { if (p && n) v.push_back({p, n, true}); return *this; }
 };
 
+// A DiffAugment stage on D's input as Program's two recorders of it (stage_fwd, stage_bwd) see it: they
+// are the same code for every stage. PT: the element type of its params rows [N][4]
+template <class PT>
+struct DStage {
+  typedef int (*Launcher)(const elem_t*, elem_t*, PT*, int, int, int, int, int, uint64_t, const unsigned long long*,
+                          int*, const int*, hipStream_t);
+  const char* name;           // of the forward op in messages; the transpose's is name + "_bwd"
+  int all;                    // the largest policy mask ...
+  const char* policies;       // ... spelled out for the message that rejects another
+  Launcher launch[3];         // by the Program's element type: bf16, fp16, fp32
+  bool probe_writes_params;   // the probe (step == 0) writes params as well as reading them
+};
+static const DStage<int> D_AUGMENT = {"d_augment", AUG_ALL, "translation (1) | cutout (2)",
+                                      {dcg_d_augment, dcg_d_augment_f16, dcg_d_augment_f32}, false};
+static const DStage<float> D_COLOR = {"d_color", COLOR_ALL, "brightness (1) | saturation (2) | contrast (4)",
+                                      {dcg_d_color, dcg_d_color_f16, dcg_d_color_f32}, true};  // (color's probe: Mx)
+
 class Program {
  public:
   explicit Program(int dtype = 0, bool dry = false) : dt_(dtype), dry_(dry) {
@@ -1185,101 +1202,80 @@ class Program {
       throw std::runtime_error(o + ": ada_state must be a buffer of its own");
   }
   // the checks the DiffAugment ops share: a rejected call throws before anything is recorded
-  void aug_check(const char* op, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy) const {
-    const std::string o(op);
+  template <class PT>
+  void stage_check(const DStage<PT>& st, const std::string& o, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S,
+                   int C, int policy) const {
     if (!x || !y || !params) throw std::runtime_error(o + ": the image buffers and params must be non-null");
     if (x == y) throw std::runtime_error(o + ": the output must be a buffer of its own");
-    if (policy < 1 || policy > (int)AUG_ALL)
-      throw std::runtime_error(o + ": policy must be a non-empty mask of translation (1) | cutout (2), got " +
+    if (policy < 1 || policy > st.all)
+      throw std::runtime_error(o + ": policy must be a non-empty mask of " + st.policies + ", got " +
                                std::to_string(policy));
     if (N < 1) throw std::runtime_error(o + ": N must be >= 1, got " + std::to_string(N));
     if (S < 1 || S > AUG_MAX_SIZE) throw std::runtime_error(o + ": S must satisfy 1 <= S <= 2^14, got " + std::to_string(S));
     if (C < 1 || C > 4) throw std::runtime_error(o + ": C must satisfy 1 <= C <= 4, got " + std::to_string(C));
   }
-  // DiffAugment of D's input x [N][S][S][C] -> y (d_augment_kernel). step != 0: the draws come from
-  // the Philox stream (seed, *step, AUG_STREAM) and land in params int32 [N][4]: reads x and the
-  // 8-byte counter, writes y and params. step == 0 (the probe): reads x and params, writes y
-  // gates != 0 (adaptive augmentation): the gated kernel. step != 0 also reads the 4 bytes of p24 at
-  // ada_state and writes gates int32 [N]; the probe reads gates
-  int d_augment(std::string name, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy,
-                uint64_t seed, uintptr_t step, int stream, uintptr_t gates, uintptr_t ada_state) {
-    aug_check("d_augment", x, y, params, N, S, C, policy);
+  // a stage of x [N][S][S][C] -> y. step != 0: reads x and the 8-byte counter, writes y and the draws
+  // params [N][4]. step == 0 (the probe): reads x and params (and writes params where the stage says so),
+  // writes y. gates != 0 (adaptive augmentation): the gated kernel. step != 0 also reads the 4 bytes of
+  // p24 at ada_state and writes gates int32 [N]; the probe reads gates
+  template <class PT>
+  int stage_fwd(const DStage<PT>& st, std::string name, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C,
+                int policy, uint64_t seed, uintptr_t step, int stream, uintptr_t gates, uintptr_t ada_state) {
+    stage_check(st, st.name, x, y, params, N, S, C, policy);
     const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * 16, gbytes = (size_t)N * 4;
     const int mode = step ? 0 : 1;
-    gate_check("d_augment", gates, mode == 0 ? ada_state : 0, mode == 0, x, y, bytes, params, pbytes, gbytes);
+    gate_check(st.name, gates, mode == 0 ? ada_state : 0, mode == 0, x, y, bytes, params, pbytes, gbytes);
     AccList acc;
     acc.r(x, bytes).w(y, bytes);
     if (mode == 0) acc.r(step, 8).w(params, pbytes); else acc.r(params, pbytes);
+    if (mode == 1 && st.probe_writes_params) acc.w(params, pbytes);
     if (gates && mode == 0) acc.r(ada_state, 4).w(gates, gbytes);
     else if (gates) acc.r(gates, gbytes);
+    const auto launch = st.launch[dt_];
     return add(name, stream, [=](hipStream_t s) {
-      return KF(dcg_d_augment_gated)(P<const elem_t>(x), P<elem_t>(y), P<int>(params), N, S, C, policy, mode, seed,
-                                     P<const unsigned long long>(step), P<int>(gates),
-                                     mode == 0 ? P<const int>(ada_state) : nullptr, s);
+      return launch(P<const elem_t>(x), P<elem_t>(y), P<PT>(params), N, S, C, policy, mode, seed,
+                    P<const unsigned long long>(step), P<int>(gates), mode == 0 ? P<const int>(ada_state) : nullptr, s);
     }, acc.v);
   }
   // its transpose: gy [N][S][S][C] -> gx through the recorded params rows; reads gy and params, writes gx
   // gates != 0: under the recorded gate rows int32 [N], which it reads too
+  template <class PT>
+  int stage_bwd(const DStage<PT>& st, std::string name, uintptr_t gy, uintptr_t gx, uintptr_t params, int N, int S,
+                int C, int policy, int stream, uintptr_t gates) {
+    const std::string o = std::string(st.name) + "_bwd";
+    stage_check(st, o, gy, gx, params, N, S, C, policy);
+    const size_t bytes = (size_t)N * S * S * C * es_, gbytes = (size_t)N * 4;
+    gate_check(o.c_str(), gates, 0, false, gy, gx, bytes, params, (size_t)N * 16, gbytes);
+    AccList acc;
+    acc.r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes);
+    if (gates) acc.r(gates, gbytes);
+    const auto launch = st.launch[dt_];
+    return add(name, stream, [=](hipStream_t s) {
+      return launch(P<const elem_t>(gy), P<elem_t>(gx), P<PT>(params), N, S, C, policy, 2, 0,
+                    (const unsigned long long*)nullptr, P<int>(gates), (const int*)nullptr, s);
+    }, acc.v);
+  }
+  // DiffAugment of D's input (d_augment_kernel): the draws come from the Philox stream (seed, *step,
+  // AUG_STREAM) and land in params int32 [N][4]; the probe only reads them
+  int d_augment(std::string name, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy,
+                uint64_t seed, uintptr_t step, int stream, uintptr_t gates, uintptr_t ada_state) {
+    return stage_fwd(D_AUGMENT, name, x, y, params, N, S, C, policy, seed, step, stream, gates, ada_state);
+  }
+  // its transpose: the transposed gather through the recorded params rows
   int d_augment_bwd(std::string name, uintptr_t gy, uintptr_t gx, uintptr_t params, int N, int S, int C, int policy,
                     int stream, uintptr_t gates) {
-    aug_check("d_augment_bwd", gy, gx, params, N, S, C, policy);
-    const size_t bytes = (size_t)N * S * S * C * es_, gbytes = (size_t)N * 4;
-    gate_check("d_augment_bwd", gates, 0, false, gy, gx, bytes, params, (size_t)N * 16, gbytes);
-    AccList acc;
-    acc.r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes);
-    if (gates) acc.r(gates, gbytes);
-    return add(name, stream, [=](hipStream_t s) {
-      return KF(dcg_d_augment_gated)(P<const elem_t>(gy), P<elem_t>(gx), P<int>(params), N, S, C, policy, 2, 0,
-                                     (const unsigned long long*)nullptr, P<int>(gates), (const int*)nullptr, s);
-    }, acc.v);
+    return stage_bwd(D_AUGMENT, name, gy, gx, params, N, S, C, policy, stream, gates);
   }
-  // the checks the color ops share, in the style of aug_check: a rejected call throws before anything is recorded
-  void color_check(const char* op, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy) const {
-    const std::string o(op);
-    if (!x || !y || !params) throw std::runtime_error(o + ": the image buffers and params must be non-null");
-    if (x == y) throw std::runtime_error(o + ": the output must be a buffer of its own");
-    if (policy < 1 || policy > (int)COLOR_ALL)
-      throw std::runtime_error(o + ": policy must be a non-empty mask of brightness (1) | saturation (2) | contrast (4), got " +
-                               std::to_string(policy));
-    if (N < 1) throw std::runtime_error(o + ": N must be >= 1, got " + std::to_string(N));
-    if (S < 1 || S > AUG_MAX_SIZE) throw std::runtime_error(o + ": S must satisfy 1 <= S <= 2^14, got " + std::to_string(S));
-    if (C < 1 || C > 4) throw std::runtime_error(o + ": C must satisfy 1 <= C <= 4, got " + std::to_string(C));
-  }
-  // DiffAugment's color policy on D's input x [N][S][S][C] -> y (d_color_kernel), params float [N][4] = (b, s,
-  // c, Mx). step != 0: (b, s, c) come from the Philox stream (seed, *step, COLOR_STREAM): reads x and the
-  // 8-byte counter, writes y and params. step == 0 (the probe): reads x, reads (b, s, c) of and writes Mx to params
-  // gates != 0 (adaptive augmentation): the gated kernel, as d_augment's
+  // DiffAugment's color policy on D's input (d_color_kernel), params float [N][4] = (b, s, c, Mx): (b, s, c)
+  // come from the Philox stream (seed, *step, COLOR_STREAM); the probe reads (b, s, c) of and writes Mx to params
   int d_color(std::string name, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy,
               uint64_t seed, uintptr_t step, int stream, uintptr_t gates, uintptr_t ada_state) {
-    color_check("d_color", x, y, params, N, S, C, policy);
-    const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * 16, gbytes = (size_t)N * 4;
-    const int mode = step ? 0 : 1;
-    gate_check("d_color", gates, mode == 0 ? ada_state : 0, mode == 0, x, y, bytes, params, pbytes, gbytes);
-    AccList acc;
-    acc.r(x, bytes).w(y, bytes);
-    if (mode == 0) acc.r(step, 8).w(params, pbytes); else acc.r(params, pbytes).w(params, pbytes);
-    if (gates && mode == 0) acc.r(ada_state, 4).w(gates, gbytes);
-    else if (gates) acc.r(gates, gbytes);
-    return add(name, stream, [=](hipStream_t s) {
-      return KF(dcg_d_color_gated)(P<const elem_t>(x), P<elem_t>(y), P<float>(params), N, S, C, policy, mode, seed,
-                                   P<const unsigned long long>(step), P<int>(gates),
-                                   mode == 0 ? P<const int>(ada_state) : nullptr, s);
-    }, acc.v);
+    return stage_fwd(D_COLOR, name, x, y, params, N, S, C, policy, seed, step, stream, gates, ada_state);
   }
-  // its transpose: gy [N][S][S][C] -> gx under (s, c) of the recorded params rows; reads gy and params, writes gx
-  // gates != 0: under the recorded gate rows int32 [N], which it reads too
+  // its transpose: the transposed map under (s, c) of the recorded params rows
   int d_color_bwd(std::string name, uintptr_t gy, uintptr_t gx, uintptr_t params, int N, int S, int C, int policy,
                   int stream, uintptr_t gates) {
-    color_check("d_color_bwd", gy, gx, params, N, S, C, policy);
-    const size_t bytes = (size_t)N * S * S * C * es_, gbytes = (size_t)N * 4;
-    gate_check("d_color_bwd", gates, 0, false, gy, gx, bytes, params, (size_t)N * 16, gbytes);
-    AccList acc;
-    acc.r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes);
-    if (gates) acc.r(gates, gbytes);
-    return add(name, stream, [=](hipStream_t s) {
-      return KF(dcg_d_color_gated)(P<const elem_t>(gy), P<elem_t>(gx), P<float>(params), N, S, C, policy, 2, 0,
-                                   (const unsigned long long*)nullptr, P<int>(gates), (const int*)nullptr, s);
-    }, acc.v);
+    return stage_bwd(D_COLOR, name, gy, gx, params, N, S, C, policy, stream, gates);
   }
   // one step of the adaptive-augmentation controller (ada_update_kernel): reads the B fp32 real logits,
   // reads and writes the 32 bytes of state int32 [8] = (p24, acc, cnt, r_acc, windows, 0, 0, 0)

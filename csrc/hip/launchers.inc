@@ -91,25 +91,19 @@ int DCG_API(dcg_noise_sigma)(const unsigned long long* steps, float* out, size_t
 // DiffAugment (translation / cutout, kernels.h AugPolicy) of x [N][S][S][C] into y, params int32 [N][4]
 // = (ty, tx, oy, ox). mode 0: drawn from the Philox stream (seed, *step, AUG_STREAM) and written to
 // params; 1: read from params; 2: the transposed gather (backward) of the rows in params.
-// -2: a null pointer, x == y, N < 1, S outside 1..2^14, C outside 1..4, an empty or unknown policy / mode
-int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy, int mode,
-                           uint64_t seed, const unsigned long long* step, hipStream_t s);
 // DiffAugment's color policy (brightness / saturation / contrast, kernels.h ColorPolicy) of x [N][S][S][C]
 // into y, params float [N][4] = (b, s, c, Mx). mode 0: (b, s, c) drawn from the Philox stream (seed, *step,
 // COLOR_STREAM), all four written; 1: (b, s, c) read from params, Mx written; 2: the transpose (backward)
 // under (s, c) of params, which it only reads.
-// -2: a null pointer, x == y, N < 1, S outside 1..2^14, C outside 1..4, an empty or unknown policy / mode
+// Both with adaptive gates (kernels.h ADA): gates int32 [N], the effective policy per sample, written in mode
+// 0 from the Philox gate streams and p24 = ada[0], read in modes 1 and 2 (ada unused). gates == nullptr: the
+// ungated kernels.
+// -2: a null pointer, x == y, N < 1, S outside 1..2^14, C outside 1..4, an empty or unknown policy / mode,
+// gates in mode 0 without ada, ada without gates
+int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy, int mode,
+                           uint64_t seed, const unsigned long long* step, int* gates, const int* ada, hipStream_t s);
 int DCG_API(dcg_d_color)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy, int mode,
-                         uint64_t seed, const unsigned long long* step, hipStream_t s);
-// the same two with adaptive gates (kernels.h ADA): gates int32 [N], the effective policy per sample, written
-// in mode 0 from the Philox gate streams and p24 = ada[0], read in modes 1 and 2 (ada unused). gates ==
-// nullptr: the ungated kernels. -2 also: gates in mode 0 without ada, ada without gates
-int DCG_API(dcg_d_augment_gated)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy, int mode,
-                                 uint64_t seed, const unsigned long long* step, int* gates, const int* ada,
-                                 hipStream_t s);
-int DCG_API(dcg_d_color_gated)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy, int mode,
-                               uint64_t seed, const unsigned long long* step, int* gates, const int* ada,
-                               hipStream_t s);
+                         uint64_t seed, const unsigned long long* step, int* gates, const int* ada, hipStream_t s);
 // one step of the ADA controller on state int32 [8] from the B real logits (fp32). -2: a null pointer, B < 1,
 // interval outside 1..2^16, B * interval >= 2^31, delta24 outside 1..2^24, |target_n| > B * interval, thr NaN
 int DCG_API(dcg_ada_update)(const float* logits, int B, int* state, float thr, int target_n, int delta24,

@@ -1756,49 +1756,54 @@ extern "C" int DCG_API(dcg_instance_noise)(const elem_t* x, elem_t* y, size_t n,
   return (int)hipGetLastError();
 }
 
-extern "C" int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy,
-                                      int mode, uint64_t seed, const unsigned long long* step, hipStream_t s) {
-  return DCG_API(dcg_d_augment_gated)(x, y, params, N, S, C, policy, mode, seed, step, nullptr, nullptr, s);
+// what the two DiffAugment entry points below accept alike (all: the stage's full policy mask)
+static bool d_stage_args_ok(const void* x, const void* y, const void* params, int N, int S, int C, int policy, int all,
+                            int mode, const void* step, const void* gates, const void* ada) {
+  if (!x || !y || !params || x == y || (mode == 0 && !step)) return false;
+  if (gates ? (mode == 0 && !ada) : ada != nullptr) return false;
+  return !(N < 1 || S < 1 || S > AUG_MAX_SIZE || C < 1 || C > 4 || policy < 1 || policy > all || mode < 0 || mode > 2);
 }
 
-// gates == nullptr: the ungated kernels, launched exactly as before
-extern "C" int DCG_API(dcg_d_augment_gated)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy,
-                                            int mode, uint64_t seed, const unsigned long long* step, int* gates,
-                                            const int* ada, hipStream_t s) {
-  if (!x || !y || !params || x == y || (mode == 0 && !step)) return -2;
-  if (gates ? (mode == 0 && !ada) : ada != nullptr) return -2;
-  if (N < 1 || S < 1 || S > AUG_MAX_SIZE || C < 1 || C > 4 || policy < 1 || policy > AUG_ALL || mode < 0 || mode > 2)
-    return -2;
+// GATED false (gates == nullptr): the ungated kernel. The switch is the outer level of the dispatch, the mode
+// the inner one: the kernel instances are emitted in the order these helpers first name them, and that
+// order -- gated 0, 1, 2, then ungated 0, 1, 2 -- keeps the code object's layout what it was
+template <typename U, bool GATED, int MODE>
+static void d_augment_launch(dim3 grid, const U* x, U* y, int* params, int S, int C, int policy, unsigned bpi,
+                             uint64_t seed, const unsigned long long* step, int vec, int* gates, const int* ada,
+                             hipStream_t s) {
+  if constexpr (GATED)
+    hipLaunchKernelGGL((d_augment_gated_kernel<U, MODE>), grid, dim3(256), 0, s, x, y, params, S, C, policy, bpi, seed,
+                       step, vec, gates, ada);
+  else
+    hipLaunchKernelGGL((d_augment_kernel<U, MODE>), grid, dim3(256), 0, s, x, y, params, S, C, policy, bpi, seed, step,
+                       vec);
+}
+
+template <typename U, bool GATED>
+static void d_augment_launch_m(int mode, dim3 grid, const U* x, U* y, int* params, int S, int C, int policy,
+                               unsigned bpi, uint64_t seed, const unsigned long long* step, int vec, int* gates,
+                               const int* ada, hipStream_t s) {
+  if (mode == 0) d_augment_launch<U, GATED, 0>(grid, x, y, params, S, C, policy, bpi, seed, step, vec, gates, ada, s);
+  else if (mode == 1) d_augment_launch<U, GATED, 1>(grid, x, y, params, S, C, policy, bpi, seed, step, vec, gates, ada, s);
+  else d_augment_launch<U, GATED, 2>(grid, x, y, params, S, C, policy, bpi, seed, step, vec, gates, ada, s);
+}
+
+extern "C" int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S, int C, int policy,
+                                      int mode, uint64_t seed, const unsigned long long* step, int* gates,
+                                      const int* ada, hipStream_t s) {
+  if (!d_stage_args_ok(x, y, params, N, S, C, policy, AUG_ALL, mode, step, gates, ada)) return -2;
   typedef std::conditional<sizeof(elem_t) == 2, uint16_t, uint32_t>::type U;
   constexpr size_t V = 16 / sizeof(U);
   const size_t hwc = (size_t)S * S * C;
   const size_t bpi = (hwc + 256 * V - 1) / (256 * V);
   if (bpi * (size_t)N > 0x7FFFFFFFull) return -2;
   const int vec = ((size_t)S * C * sizeof(U)) % 16 == 0 && ((uintptr_t)y & 15) == 0;
-  const dim3 grid((unsigned)(bpi * (size_t)N)), block(256);
+  const dim3 grid((unsigned)(bpi * (size_t)N));
   const U* xu = reinterpret_cast<const U*>(x);
   U* yu = reinterpret_cast<U*>(y);
-  if (gates) {
-    if (mode == 0)
-      hipLaunchKernelGGL((d_augment_gated_kernel<U, 0>), grid, block, 0, s, xu, yu, params, S, C, policy,
-                         (unsigned)bpi, seed, step, vec, gates, ada);
-    else if (mode == 1)
-      hipLaunchKernelGGL((d_augment_gated_kernel<U, 1>), grid, block, 0, s, xu, yu, params, S, C, policy,
-                         (unsigned)bpi, seed, step, vec, gates, ada);
-    else
-      hipLaunchKernelGGL((d_augment_gated_kernel<U, 2>), grid, block, 0, s, xu, yu, params, S, C, policy,
-                         (unsigned)bpi, seed, step, vec, gates, ada);
-    return (int)hipGetLastError();
-  }
-  if (mode == 0)
-    hipLaunchKernelGGL((d_augment_kernel<U, 0>), grid, block, 0, s, xu, yu, params, S, C, policy, (unsigned)bpi, seed,
-                       step, vec);
-  else if (mode == 1)
-    hipLaunchKernelGGL((d_augment_kernel<U, 1>), grid, block, 0, s, xu, yu, params, S, C, policy, (unsigned)bpi, seed,
-                       step, vec);
-  else
-    hipLaunchKernelGGL((d_augment_kernel<U, 2>), grid, block, 0, s, xu, yu, params, S, C, policy, (unsigned)bpi, seed,
-                       step, vec);
+  const unsigned b = (unsigned)bpi;
+  if (gates) d_augment_launch_m<U, true>(mode, grid, xu, yu, params, S, C, policy, b, seed, step, vec, gates, ada, s);
+  else d_augment_launch_m<U, false>(mode, grid, xu, yu, params, S, C, policy, b, seed, step, vec, gates, ada, s);
   return (int)hipGetLastError();
 }
 
@@ -1825,18 +1830,9 @@ static void d_color_launch_c(int C, const elem_t* x, elem_t* y, float* params, i
 }
 
 extern "C" int DCG_API(dcg_d_color)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy,
-                                    int mode, uint64_t seed, const unsigned long long* step, hipStream_t s) {
-  return DCG_API(dcg_d_color_gated)(x, y, params, N, S, C, policy, mode, seed, step, nullptr, nullptr, s);
-}
-
-// gates == nullptr: the ungated kernels, launched exactly as before
-extern "C" int DCG_API(dcg_d_color_gated)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy,
-                                          int mode, uint64_t seed, const unsigned long long* step, int* gates,
-                                          const int* ada, hipStream_t s) {
-  if (!x || !y || !params || x == y || (mode == 0 && !step)) return -2;
-  if (gates ? (mode == 0 && !ada) : ada != nullptr) return -2;
-  if (N < 1 || S < 1 || S > AUG_MAX_SIZE || C < 1 || C > 4 || policy < 1 || policy > COLOR_ALL || mode < 0 || mode > 2)
-    return -2;
+                                    int mode, uint64_t seed, const unsigned long long* step, int* gates,
+                                    const int* ada, hipStream_t s) {
+  if (!d_stage_args_ok(x, y, params, N, S, C, policy, COLOR_ALL, mode, step, gates, ada)) return -2;
   constexpr size_t V = 16 / sizeof(elem_t);
   const int vec = ((size_t)S * S) % V == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
   if (mode == 0) d_color_launch_c<0>(C, x, y, params, N, S, policy, seed, step, vec, gates, ada, s);

@@ -152,6 +152,30 @@ class _DChain(NamedTuple):
     grads: Optional[object]       # D's gradient set, or None: data gradients only
 
 
+class _DStage(NamedTuple):
+    """One stage between G's RGB layer and D's layer 0: a launch that writes a copy of [real | fake]
+    of its own from the copy before it. It names engine attributes and holds no tensor: a buffer
+    exists only while the stage's option is on (None otherwise) and keeps its one attribute path."""
+    opt: str                            # the option that switches it on: self.<opt>.active
+    out: str                            # its copy of [real | fake]
+    name: str                           # its recorded name
+    # a DiffAugment stage: its Jacobian is not the identity, so the launch records what its transpose
+    # (Program.<op>_bwd, recorded as <name>_bwd on the g_loss chain) replays for the fake half
+    op: Optional[str] = None            # Program.<op>
+    params: Optional[str] = None        # its draws [2B][4] ...
+    pdtype: Optional[torch.dtype] = None  # ... of this type
+    gates: Optional[str] = None         # under adaptive augmentation, its gate masks int32 [2B]
+    grad: Optional[str] = None          # the image gradient [B] behind its transpose
+
+
+# in the order they run, the published one: color, then translation / cutout, then noise
+D_STAGES = (
+    _DStage("color", "d_colored", "d_color", "d_color", "color_params", torch.float32, "color_gates", "img_grad_c"),
+    _DStage("aug", "d_auged", "d_aug", "d_augment", "aug_params", torch.int32, "aug_gates", "img_grad_t"),
+    _DStage("noise", "d_noisy", "d_noise"),
+)
+
+
 class HipEngine(HipDDPMixin, HipEngineAux):
     name = "hip"
     dtype_name = "bf16"
@@ -310,24 +334,28 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # staging area of d_steps real batches: D sub-step k reads (and G writes the fake half of)
         # its own [real_k | fake] buffer; the last slot is the full step's d_in
         self.d_ins = [t(B2, s, s, cfg.c_dim, zero=True) for _ in range(self.d_steps - 1)] + [self.d_in]
-        # instance noise: the noisy copy D's layer 0 reads. ONE buffer for the sub-steps and the full
-        # step: each ends with its D chain (the last reader) joined back into the main stream, where
-        # the next forward rewrites it (schedule_check proves it: tests/test_instance_noise.py)
-        self.d_noisy = torch.zeros_like(self.d_in) if self.noise.active else None
-        # DiffAugment: the augmented copy (shared the same way), the draws int32 [2B][4] = (ty, tx, oy,
-        # ox) that `d_aug` records, and the image gradient taken back through the fake half's rows
-        self.d_auged = torch.zeros_like(self.d_in) if self.aug.active else None
-        self.aug_params = t(B2, 4, dtype=torch.int32, zero=True) if self.aug.active else None
-        # the color policy: the colored copy (shared the same way) and float32 [2B][4] = (b, s, c, Mx)
-        self.d_colored = torch.zeros_like(self.d_in) if self.color.active else None
-        self.color_params = t(B2, 4, dtype=torch.float32, zero=True) if self.color.active else None
+        # the stages on D's input (D_STAGES), each switched on its own: the copy the next stage or D's
+        # layer 0 reads. ONE buffer for the sub-steps and the full step: each ends with its D chain (the
+        # last reader) joined back into the main stream, where the next forward rewrites it
+        # (schedule_check proves it: tests/test_instance_noise.py). A DiffAugment stage also keeps the
+        # draws [2B][4] its launch records -- int32 (ty, tx, oy, ox) of `d_aug`, float32 (b, s, c, Mx)
+        # of `d_color` -- and, under adaptive augmentation, the gate masks int32 [2B] its gated kernel
+        # records (the effective policy per sample). Allocated last stage first, the controller's state
+        # ahead of the gates: the order these buffers have always been allocated in, so that every buffer
+        # of the process, this engine's and any later one's, keeps the address it had
+        for st in reversed(D_STAGES):
+            on = getattr(self, st.opt).active
+            setattr(self, st.out, torch.zeros_like(self.d_in) if on else None)
+            if st.op:
+                setattr(self, st.params, t(B2, 4, dtype=st.pdtype, zero=True) if on else None)
         # adaptive augmentation: the controller's state int32 [8] = (p24, acc, cnt, r_acc, windows, 0, 0, 0)
-        # and the gate masks int32 [2B] each gated kernel records (the effective policy per sample)
-        self.ada_state = self.aug_gates = self.color_gates = None
+        self.ada_state = None
         if self.ada.active:
             self.ada_state = torch.tensor(R.ada_state(R.ada_p24(self.ada.p)), dtype=torch.int32, device=self.device)
-            self.aug_gates = t(B2, dtype=torch.int32, zero=True) if self.aug.active else None
-            self.color_gates = t(B2, dtype=torch.int32, zero=True) if self.color.active else None
+        for st in reversed(D_STAGES):
+            if st.op:
+                on = getattr(self, st.opt).active and self.ada.active
+                setattr(self, st.gates, t(B2, dtype=torch.int32, zero=True) if on else None)
         self.d_x, self.d_a = {}, {}
         for i, L in enumerate(self.dl):
             if L.bn:
@@ -360,8 +388,10 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         self.gc_dx = {L.name: t(B, L.out_hw, L.out_hw, L.cout) for L in self.dl}
         self.img_grad = t(B, s, s, cfg.c_dim)
         self.img_g = t(B, s, s, cfg.c_dim)
-        self.img_grad_t = t(B, s, s, cfg.c_dim) if self.aug.active else None
-        self.img_grad_c = t(B, s, s, cfg.c_dim) if self.color.active else None  # ... and back through the color map
+        # ... and taken back through each DiffAugment stage's transpose (the fake half's rows), in the order it passes
+        for st in reversed(D_STAGES):
+            if st.grad:
+                setattr(self, st.grad, t(B, s, s, cfg.c_dim) if getattr(self, st.opt).active else None)
         Lg = self.gl[-1]
         self.kp_g = _kpad(cfg.c_dim)
         self.g_last_col = t(B * Lg.in_hw ** 2, self.kp_g)
@@ -661,7 +691,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         (narrow.hip DACT): 16-bit, 64-channel D layer 0, <= 4 image channels. Not under DiffAugment
         (either switch): the image gradient is then taken at the augmented pixels, tanh' at the clean ones."""
         L = self.dl[0]
-        return not self.aug.active and not self.color.active and not self.f32 and L.cin <= 4 and L.cout == 64 and self.gl[-1].cout == L.cin
+        return not self._d_stages(transposed=True) and not self.f32 and L.cin <= 4 and L.cout == 64 and self.gl[-1].cout == L.cin
 
     def _g_out_direct(self) -> bool:
         """G's 1..4-channel output layer backward on narrow2.hip (nconv data gradient + nwgrad)."""
@@ -705,18 +735,20 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             return zseed
         return (zseed + (sub + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
 
+    def _d_stages(self, transposed: bool = False) -> List[_DStage]:
+        """The stages on D's input that are switched on, in the order they run. transposed: those among
+        them with a transpose, in the order the g_loss chain's image gradient passes back through them."""
+        on = [st for st in D_STAGES if getattr(self, st.opt).active]
+        return [st for st in reversed(on) if st.grad] if transposed else on
+
     def _d_input(self, sub: Optional[int] = None, noise: bool = True) -> torch.Tensor:
         """What D's layer 0 reads (forward and weight gradient): [real | fake] of the full step or
-        of D sub-step `sub`, or its perturbed copy: the noisy one under instance noise (the noise of
-        the augmented copy when both are on), else the augmented one under DiffAugment, else the colored
-        one under its color policy (each stage reads the one before it). noise=False: the clean input
-        whatever is switched on."""
-        if noise and self.noise.active:
-            return self.d_noisy
-        if noise and self.aug.active:
-            return self.d_auged
-        if noise and self.color.active:
-            return self.d_colored
+        of D sub-step `sub`, or its perturbed copy: the output of the last stage that is on (each
+        stage reads the one before it: the noise lands on the augmented copy when both are on).
+        noise=False: the clean input whatever is switched on."""
+        stages = self._d_stages() if noise else []
+        if stages:
+            return getattr(self, stages[-1].out)
         return self.d_in if sub is None else self.d_ins[sub]
 
     def noise_sigma(self) -> float:
@@ -780,21 +812,18 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # written here -- behind the op that wrote the fake half, on the main stream -- from streams
         # 2 / 1 of the step's z seed; the noise lands on the augmented copy when both are on. The color
         # policy (stream 3) comes first: color, then translation / cutout, then noise
-        prev = self._d_input(sub, noise)
-        clean = d_in
-        # (adaptive augmentation: the gated kernels, gates from streams 5 / 4 against the live p24)
-        gate = lambda g: dict(gates=_p(g), ada_state=_p(self.ada_state)) if self.ada.active else {}  # noqa: E731
-        if noise and self.color.active:
-            prog.d_color("d_color", _p(d_in), _p(self.d_colored), _p(self.color_params), B2, cfg.output_size,
-                         cfg.c_dim, self.color.mask, zseed, _p(self.step_counter), 0, **gate(self.color_gates))
-            clean = self.d_colored
-        if noise and self.aug.active:
-            prog.d_augment("d_aug", _p(clean), _p(self.d_auged), _p(self.aug_params), B2, cfg.output_size, cfg.c_dim,
-                           self.aug.mask, zseed, _p(self.step_counter), 0, **gate(self.aug_gates))
-            clean = self.d_auged
-        if prev is not clean:
-            prog.instance_noise("d_noise", _p(clean), _p(prev), d_in.numel(), zseed, _p(self.step_counter),
-                                R.NOISE_STREAM, self.noise.sigma0, self.noise.sigma1, self.noise.steps, 0)
+        prev = d_in
+        for st in self._d_stages() if noise else []:
+            dst = getattr(self, st.out)
+            if st.op:
+                # (adaptive augmentation: the gated kernels, gates from streams 5 / 4 against the live p24)
+                gate = dict(gates=_p(getattr(self, st.gates)), ada_state=_p(self.ada_state)) if self.ada.active else {}
+                getattr(prog, st.op)(st.name, _p(prev), _p(dst), _p(getattr(self, st.params)), B2, cfg.output_size,
+                                     cfg.c_dim, getattr(self, st.opt).mask, zseed, _p(self.step_counter), 0, **gate)
+            else:
+                prog.instance_noise(st.name, _p(prev), _p(dst), d_in.numel(), zseed, _p(self.step_counter),
+                                    R.NOISE_STREAM, self.noise.sigma0, self.noise.sigma1, self.noise.steps, 0)
+            prev = dst
         for i, L in enumerate(self.dl):
             w = Wd[L.name + "/w"]  # HWIO [5,5,ci,co] = [tap][K][N]
             pad = same_pads(L.in_hw)[0]
@@ -1060,31 +1089,29 @@ class HipEngine(HipDDPMixin, HipEngineAux):
                                L.out_hw, L.out_hw, L.cout, L.in_hw, L.in_hw, L.cin, pad, NONE, 0.0, 0)
         else:
             self._igemm(prog, "g." + L.name + ".dgrad_img", H.GemmShape.dgrad(L, B), dx, nat, self.img_grad, pad)
-        if self.aug.active:
-            # DiffAugment: dL/d(augmented fake) -> dL/d(fake), the transposed gather over the draws the
-            # forward recorded for the fake half (rows B..2B-1 of aug_params)
-            prog.d_augment_bwd("d_aug_bwd", _p(self.img_grad), _p(self.img_grad_t), _p(self.aug_params[B:]), B,
-                               L.in_hw, L.cin, self.aug.mask, 0,
-                               **(dict(gates=_p(self.aug_gates[B:])) if self.ada.active else {}))
-        if self.color.active:
-            # the color policy: dL/d(colored fake) -> dL/d(fake), its transposed map under (s, c) of the rows
-            # the forward recorded for the fake half
-            prog.d_color_bwd("d_color_bwd", _p(self.img_grad_t if self.aug.active else self.img_grad),
-                             _p(self.img_grad_c), _p(self.color_params[B:]), B, L.in_hw, L.cin, self.color.mask, 0,
-                             **(dict(gates=_p(self.color_gates[B:])) if self.ada.active else {}))
-        self._build_g_backward(prog, progw)
+        img_grad = self.img_grad
+        for st in self._d_stages(transposed=True):
+            # DiffAugment: dL/d(the stage's copy of the fake) -> dL/d(its input), the stage's transpose --
+            # the transposed gather of `d_aug`, the transposed color map under (s, c) of `d_color` -- over
+            # the draws (and gates) the forward recorded for the fake half (rows B..2B-1)
+            gx = getattr(self, st.grad)
+            gate = dict(gates=_p(getattr(self, st.gates)[B:])) if self.ada.active else {}
+            getattr(prog, st.op + "_bwd")(st.name + "_bwd", _p(img_grad), _p(gx), _p(getattr(self, st.params)[B:]), B,
+                                          L.in_hw, L.cin, getattr(self, st.opt).mask, 0, **gate)
+            img_grad = gx
+        self._build_g_backward(prog, progw, img_grad)
 
-    def _build_g_backward(self, prog, progw):
+    def _build_g_backward(self, prog, progw, img_grad):
         """G's backward from the image gradient img_g (G's tanh backward already applied when the
-        image-gradient kernel fused it): data gradients into prog, weight gradients into progw."""
+        image-gradient kernel fused it; else taken here from img_grad, the g_loss chain's gradient at
+        the clean pixels): data gradients into prog, weight gradients into progw."""
         cfg, B = self.cfg, self.B
         Pg, gG = self.model.g, self.grad_g
         self._a_gd_end = prog.size()  # the g_loss chain is done with D's weights / BN parameters
         n = len(self.gl)
         Lg = self.gl[-1]
         if not self._img_dact():  # (else fused into the image-gradient kernel above)
-            # (DiffAugment: the gradient at the clean pixels, where tanh' is taken)
-            img_grad = self.img_grad_c if self.color.active else self.img_grad_t if self.aug.active else self.img_grad
+            # (DiffAugment: behind the last transpose, at the clean pixels, where tanh' is taken)
             self._act_bwd_dbias(prog, "g_out.tanh_bwd", img_grad, self.fake, self.img_g, B * Lg.out_hw ** 2,
                                 Lg.cout, TANH, gG[Lg.name + "/biases"], "g")
 

@@ -755,11 +755,6 @@ def instance_noise(x: torch.Tensor, y: torch.Tensor, seed: int, step: torch.Tens
     return y
 
 
-def _aug_mask(policy) -> int:
-    from . import reference as R
-    return policy if isinstance(policy, int) and not isinstance(policy, bool) else R.check_d_augment(policy).mask
-
-
 def _aug_images(op: str, x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
     if x.dtype not in _ELEM_DT or x.dim() != 4 or x.shape[1] != x.shape[2]:
         raise TypeError("%s: x must be [N, S, S, C] in bf16, fp16 or fp32" % op)
@@ -789,6 +784,94 @@ def _gates_arg(op: str, gates, N: int, device) -> torch.Tensor:
     return gates.to(device=device, dtype=torch.int32).contiguous()
 
 
+def _int_rows(op: str, params: torch.Tensor, params_out, N: int, device) -> torch.Tensor:
+    if tuple(params.shape) != (N, 4) or params.dtype not in (torch.int32, torch.int64):
+        raise TypeError("%s: params must be an integer [N, 4]" % op)
+    return params.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _color_rows(op: str, params: torch.Tensor, params_out, N: int, device) -> torch.Tensor:
+    if params.dim() != 2 or params.shape[0] != N or params.shape[1] not in (3, 4) or not params.is_floating_point():
+        raise TypeError("%s: params must be a floating-point [N, 3] or [N, 4]" % op)
+    p = params_out
+    if p is None:
+        p = torch.zeros(N, 4, device=device, dtype=torch.float32)
+    if p.dtype != torch.float32 or tuple(p.shape) != (N, 4) or not p.is_contiguous() or p.device != device:
+        raise TypeError("%s: params_out must be a contiguous float32 [N, 4] on x's device" % op)
+    p[:, :3] = params[:, :3].to(device=device, dtype=torch.float32)
+    return p
+
+
+class _DStage(NamedTuple):
+    """A DiffAugment stage on D's input as the one-shot wrappers below see it: the draw and apply
+    helpers read this and are the same code for every stage."""
+    name: str           # of the wrappers in messages: <name>_draw, <name>_apply
+    op: str             # Program.<op> / Program.<op>_bwd, recorded under the same names
+    dtype: torch.dtype  # of the params rows [N, 4]
+    check: str          # ops.reference's parser of a policy that is not yet the kernels' bitmask
+    rows: object        # (op, params, params_out, N, device) -> the validated rows a probe / transpose reads
+    gate_stream: int    # Philox stream of its gates (ops.reference.gate_masks)
+
+    def mask(self, policy) -> int:
+        from . import reference as R
+        if isinstance(policy, int) and not isinstance(policy, bool):
+            return policy
+        return getattr(R, self.check)(policy).mask
+
+
+_AUGMENT = _DStage("augment", "d_augment", torch.int32, "check_d_augment", _int_rows, 4)
+_COLOR = _DStage("color", "d_color", torch.float32, "check_d_color", _color_rows, 5)
+
+
+def _stage_draw(st: _DStage, x, seed, step, policy, out, params_out, p24, gates_out):
+    op = st.name + "_draw"
+    out = _aug_images(op, x, out)
+    if not torch.is_tensor(step):
+        v = int(step) & 0xFFFFFFFFFFFFFFFF  # (the counter's 64 bits as the int64 that holds them)
+        step = torch.tensor([v - (1 << 64) if v >> 63 else v], dtype=torch.int64, device=x.device)
+    _check_step(op, step)
+    N, S, C = x.shape[0], x.shape[1], x.shape[3]
+    if params_out is None:
+        params_out = torch.empty(N, 4, device=x.device, dtype=st.dtype)
+    if params_out.dtype != st.dtype or tuple(params_out.shape) != (N, 4) or not params_out.is_contiguous():
+        raise TypeError("%s: params_out must be a contiguous %s [N, 4]" % (op, str(st.dtype).split(".")[-1]))
+    prog = ext().Program(_ELEM_DT[x.dtype])
+    px, po = (_p(x), _p(out)) if x.numel() else (0, 0)
+    record, pp = getattr(prog, st.op), _p(params_out) if N else 0
+    if p24 is None:
+        record(st.op, px, po, pp, N, S, C, st.mask(policy), int(seed), _p(step))
+        run(prog)
+        return out, params_out
+    state = _ada_state_arg(op, p24, x.device)
+    if gates_out is None:
+        gates_out = torch.empty(N, device=x.device, dtype=torch.int32)
+    if gates_out.dtype != torch.int32 or tuple(gates_out.shape) != (N,) or not gates_out.is_contiguous():
+        raise TypeError("%s: gates_out must be a contiguous int32 [N]" % op)
+    record(st.op, px, po, pp, N, S, C, st.mask(policy), int(seed), _p(step), 0, _p(gates_out) if N else 0, _p(state))
+    run(prog)
+    return out, params_out, gates_out
+
+
+def _stage_apply(st: _DStage, x, params, policy, transpose, out, params_out, gates):
+    op = st.name + "_apply"
+    out = _aug_images(op, x, out)
+    N, S, C = x.shape[0], x.shape[1], x.shape[3]
+    p = st.rows(op, params, params_out, N, x.device)
+    prog = ext().Program(_ELEM_DT[x.dtype])
+    px, po, pp = (_p(x), _p(out), _p(p)) if x.numel() else (0, 0, 0)
+    # gates: integer [N], the recorded gate masks -- the gated kernel's probe / transpose
+    pg = 0
+    if gates is not None:
+        gates = _gates_arg(op, gates, N, x.device)
+        pg = _p(gates) if N else 0
+    if transpose:
+        getattr(prog, st.op + "_bwd")(st.op + "_bwd", px, po, pp, N, S, C, st.mask(policy), 0, pg)
+    else:
+        getattr(prog, st.op)(st.op, px, po, pp, N, S, C, st.mask(policy), 0, 0, 0, pg, 0)
+    run(prog)
+    return out
+
+
 def augment_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.Tensor] = None,
                  params_out: Optional[torch.Tensor] = None, p24=None, gates_out: Optional[torch.Tensor] = None):
     """DiffAugment of x [N, S, S, C] as the training step runs it (d_augment_kernel): sample n draws
@@ -797,32 +880,7 @@ def augment_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.T
     over ops.reference.augment_params. p24 (an int, or the int32 [8] device state whose word 0 holds it):
     the gated kernel of adaptive augmentation -- returns (y, params, gates int32 [N]), gates the
     effective policy per sample (oracle: ops.reference.gate_masks on stream 4)."""
-    out = _aug_images("augment_draw", x, out)
-    if not torch.is_tensor(step):
-        v = int(step) & 0xFFFFFFFFFFFFFFFF  # (the counter's 64 bits as the int64 that holds them)
-        step = torch.tensor([v - (1 << 64) if v >> 63 else v], dtype=torch.int64, device=x.device)
-    _check_step("augment_draw", step)
-    N, S, C = x.shape[0], x.shape[1], x.shape[3]
-    if params_out is None:
-        params_out = torch.empty(N, 4, device=x.device, dtype=torch.int32)
-    if params_out.dtype != torch.int32 or tuple(params_out.shape) != (N, 4) or not params_out.is_contiguous():
-        raise TypeError("augment_draw: params_out must be a contiguous int32 [N, 4]")
-    prog = ext().Program(_ELEM_DT[x.dtype])
-    if p24 is not None:
-        state = _ada_state_arg("augment_draw", p24, x.device)
-        if gates_out is None:
-            gates_out = torch.empty(N, device=x.device, dtype=torch.int32)
-        if gates_out.dtype != torch.int32 or tuple(gates_out.shape) != (N,) or not gates_out.is_contiguous():
-            raise TypeError("augment_draw: gates_out must be a contiguous int32 [N]")
-        prog.d_augment("d_augment", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0,
-                       _p(params_out) if N else 0, N, S, C, _aug_mask(policy), int(seed), _p(step), 0,
-                       _p(gates_out) if N else 0, _p(state))
-        run(prog)
-        return out, params_out, gates_out
-    prog.d_augment("d_augment", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0, _p(params_out) if N else 0,
-                   N, S, C, _aug_mask(policy), int(seed), _p(step))
-    run(prog)
-    return out, params_out
+    return _stage_draw(_AUGMENT, x, seed, step, policy, out, params_out, p24, gates_out)
 
 
 def augment_params(n: int, S: int, seed: int, step, device="cuda") -> torch.Tensor:
@@ -838,30 +896,7 @@ def augment_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool
     """DiffAugment of x [N, S, S, C] under given params [N, 4] = (ty, tx, oy, ox) (the kernel's probe
     entry), or with transpose=True its transposed gather, the backward (d_augment_bwd). Oracles:
     ops.reference.augment / augment_transpose."""
-    op = "augment_apply"
-    out = _aug_images(op, x, out)
-    N, S, C = x.shape[0], x.shape[1], x.shape[3]
-    if tuple(params.shape) != (N, 4) or params.dtype not in (torch.int32, torch.int64):
-        raise TypeError("%s: params must be an integer [N, 4]" % op)
-    p = params.to(device=x.device, dtype=torch.int32).contiguous()
-    prog = ext().Program(_ELEM_DT[x.dtype])
-    px, po, pp = (_p(x), _p(out), _p(p)) if x.numel() else (0, 0, 0)
-    # gates: integer [N], the recorded gate masks -- the gated kernel's probe / transpose
-    pg = 0
-    if gates is not None:
-        gates = _gates_arg(op, gates, N, x.device)
-        pg = _p(gates) if N else 0
-    if transpose:
-        prog.d_augment_bwd("d_augment_bwd", px, po, pp, N, S, C, _aug_mask(policy), 0, pg)
-    else:
-        prog.d_augment("d_augment", px, po, pp, N, S, C, _aug_mask(policy), 0, 0, 0, pg, 0)
-    run(prog)
-    return out
-
-
-def _color_mask(policy) -> int:
-    from . import reference as R
-    return policy if isinstance(policy, int) and not isinstance(policy, bool) else R.check_d_color(policy).mask
+    return _stage_apply(_AUGMENT, x, params, policy, transpose, out, None, gates)
 
 
 def color_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.Tensor] = None,
@@ -871,31 +906,7 @@ def color_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.Ten
     Mx)); policy: a DColor, a policy list ("brightness,saturation,contrast") or the kernels' bitmask.
     Oracle: ops.reference.color_augment over ops.reference.color_params. p24: as ``augment_draw`` -- the
     gated kernel, returns (y, params, gates int32 [N]) (oracle: ops.reference.gate_masks on stream 5)."""
-    out = _aug_images("color_draw", x, out)
-    if not torch.is_tensor(step):
-        v = int(step) & 0xFFFFFFFFFFFFFFFF  # (the counter's 64 bits as the int64 that holds them)
-        step = torch.tensor([v - (1 << 64) if v >> 63 else v], dtype=torch.int64, device=x.device)
-    _check_step("color_draw", step)
-    N, S, C = x.shape[0], x.shape[1], x.shape[3]
-    if params_out is None:
-        params_out = torch.empty(N, 4, device=x.device, dtype=torch.float32)
-    if params_out.dtype != torch.float32 or tuple(params_out.shape) != (N, 4) or not params_out.is_contiguous():
-        raise TypeError("color_draw: params_out must be a contiguous float32 [N, 4]")
-    prog = ext().Program(_ELEM_DT[x.dtype])
-    if p24 is not None:
-        state = _ada_state_arg("color_draw", p24, x.device)
-        if gates_out is None:
-            gates_out = torch.empty(N, device=x.device, dtype=torch.int32)
-        if gates_out.dtype != torch.int32 or tuple(gates_out.shape) != (N,) or not gates_out.is_contiguous():
-            raise TypeError("color_draw: gates_out must be a contiguous int32 [N]")
-        prog.d_color("d_color", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0, _p(params_out) if N else 0,
-                     N, S, C, _color_mask(policy), int(seed), _p(step), 0, _p(gates_out) if N else 0, _p(state))
-        run(prog)
-        return out, params_out, gates_out
-    prog.d_color("d_color", _p(x) if x.numel() else 0, _p(out) if x.numel() else 0, _p(params_out) if N else 0,
-                 N, S, C, _color_mask(policy), int(seed), _p(step))
-    run(prog)
-    return out, params_out
+    return _stage_draw(_COLOR, x, seed, step, policy, out, params_out, p24, gates_out)
 
 
 def color_params(n: int, seed: int, step, device="cuda") -> torch.Tensor:
@@ -913,42 +924,17 @@ def color_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool =
     probe entry: it computes Mx itself and leaves it in column 3 of params_out, a float32 [N, 4], when
     one is given), or with transpose=True its transpose, the backward (d_color_bwd). Oracles:
     ops.reference.color_augment / color_augment_transpose."""
-    op = "color_apply"
-    out = _aug_images(op, x, out)
-    N, S, C = x.shape[0], x.shape[1], x.shape[3]
-    if params.dim() != 2 or params.shape[0] != N or params.shape[1] not in (3, 4) or not params.is_floating_point():
-        raise TypeError("%s: params must be a floating-point [N, 3] or [N, 4]" % op)
-    p = params_out
-    if p is None:
-        p = torch.zeros(N, 4, device=x.device, dtype=torch.float32)
-    if p.dtype != torch.float32 or tuple(p.shape) != (N, 4) or not p.is_contiguous() or p.device != x.device:
-        raise TypeError("%s: params_out must be a contiguous float32 [N, 4] on x's device" % op)
-    p[:, :3] = params[:, :3].to(device=x.device, dtype=torch.float32)
-    prog = ext().Program(_ELEM_DT[x.dtype])
-    px, po, pp = (_p(x), _p(out), _p(p)) if x.numel() else (0, 0, 0)
-    # gates: integer [N], the recorded gate masks -- the gated kernel's probe / transpose
-    pg = 0
-    if gates is not None:
-        gates = _gates_arg(op, gates, N, x.device)
-        pg = _p(gates) if N else 0
-    if transpose:
-        prog.d_color_bwd("d_color_bwd", px, po, pp, N, S, C, _color_mask(policy), 0, pg)
-    else:
-        prog.d_color("d_color", px, po, pp, N, S, C, _color_mask(policy), 0, 0, 0, pg, 0)
-    run(prog)
-    return out
+    return _stage_apply(_COLOR, x, params, policy, transpose, out, params_out, gates)
 
 
 def gate_masks(n: int, seed: int, step, stream: int, p24, policy_mask: int, device="cuda") -> torch.Tensor:
     """int32 [n]: the gate masks the gated kernels record for n samples at p24 under `policy_mask` --
     stream 4: d_augment_kernel's (translation, cutout), stream 5: d_color_kernel's (brightness, saturation,
     contrast) -- over dummy images of zeros. Oracle: ops.reference.gate_masks."""
-    if int(stream) == 4:
-        x = torch.zeros(int(n), 1, 1, 1, device=device, dtype=torch.bfloat16)
-        return augment_draw(x, seed, step, int(policy_mask), p24=p24)[2]
-    if int(stream) == 5:
-        x = torch.zeros(int(n), 1, 1, 1, device=device, dtype=torch.bfloat16)
-        return color_draw(x, seed, step, int(policy_mask), p24=p24)[2]
+    for st in (_AUGMENT, _COLOR):
+        if st.gate_stream == int(stream):
+            x = torch.zeros(int(n), 1, 1, 1, device=device, dtype=torch.bfloat16)
+            return _stage_draw(st, x, seed, step, int(policy_mask), None, None, p24, None)[2]
     raise ValueError("gate_masks: stream must be 4 (translation / cutout) or 5 (color), got %r" % (stream,))
 
 

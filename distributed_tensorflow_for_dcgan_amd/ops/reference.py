@@ -488,23 +488,29 @@ class DAugment(NamedTuple):
         return ",".join(n for n, on in zip(AUG_POLICIES, self) if on) or "off"
 
 
-def check_d_augment(spec="") -> DAugment:
-    """Validated DAugment from a comma-separated policy list: "", "none", "translation", "cutout" or
-    both in any order. Anything else is a ValueError naming the offending token."""
-    if isinstance(spec, DAugment):
-        return DAugment(bool(spec.translation), bool(spec.cutout))
+def _check_policy_list(option: str, cls, names, spec):
+    """The policy tuple `cls` (one bool per name of `names`) from a comma-separated list, any subset in
+    any order; "", None and "none" mean off. Anything else is a ValueError naming the offending token."""
+    if isinstance(spec, cls):
+        return cls(*(bool(v) for v in spec))
     if spec is None:
         spec = ""
     if not isinstance(spec, str):
-        raise ValueError("d_augment must be a comma-separated list of %s, got %r" % (AUG_POLICIES, spec))
+        raise ValueError("%s must be a comma-separated list of %s, got %r" % (option, names, spec))
     toks = [t.strip().lower() for t in spec.split(",")]
     toks = [t for t in toks if t]
     if toks == ["none"]:
         toks = []
     for t in toks:
-        if t not in AUG_POLICIES:
-            raise ValueError("d_augment: unknown policy %r (known: %s, or none)" % (t, ", ".join(AUG_POLICIES)))
-    return DAugment("translation" in toks, "cutout" in toks)
+        if t not in names:
+            raise ValueError("%s: unknown policy %r (known: %s, or none)" % (option, t, ", ".join(names)))
+    return cls(*(n in toks for n in names))
+
+
+def check_d_augment(spec="") -> DAugment:
+    """Validated DAugment from a comma-separated policy list: "", "none", "translation", "cutout" or
+    both in any order. Anything else is a ValueError naming the offending token."""
+    return _check_policy_list("d_augment", DAugment, AUG_POLICIES, spec)
 
 
 def resolve_d_augment(spec=None) -> DAugment:
@@ -622,20 +628,7 @@ class DColor(NamedTuple):
 def check_d_color(spec="") -> DColor:
     """Validated DColor from a comma-separated list of brightness, saturation, contrast (any subset, any
     order); "" and "none" mean off. Anything else is a ValueError naming the offending token."""
-    if isinstance(spec, DColor):
-        return DColor(*(bool(v) for v in spec))
-    if spec is None:
-        spec = ""
-    if not isinstance(spec, str):
-        raise ValueError("d_color_augment must be a comma-separated list of %s, got %r" % (COLOR_POLICIES, spec))
-    toks = [t.strip().lower() for t in spec.split(",")]
-    toks = [t for t in toks if t]
-    if toks == ["none"]:
-        toks = []
-    for t in toks:
-        if t not in COLOR_POLICIES:
-            raise ValueError("d_color_augment: unknown policy %r (known: %s, or none)" % (t, ", ".join(COLOR_POLICIES)))
-    return DColor(*(n in toks for n in COLOR_POLICIES))
+    return _check_policy_list("d_color_augment", DColor, COLOR_POLICIES, spec)
 
 
 def resolve_d_color(spec=None) -> DColor:

@@ -543,6 +543,85 @@ def test_bindings_record_the_byte_ranges_and_reject_bad_calls():
     assert prog.size() == 0
 
 
+# (recorded name, output attribute, gates attribute, image-gradient attribute behind its transpose), in running order
+WIRING = (("d_color", "d_colored", "color_gates", "img_grad_c"), ("d_aug", "d_auged", "aug_gates", "img_grad_t"),
+          ("d_noise", "d_noisy", None, None))
+WIRING_CASES = [(c, g, n, ada) for ada in (False, True) for c, g, n in itertools.product((False, True), repeat=3)
+                if c or g or not ada]  # (a probability gates a policy: no ADA case where none is on)
+
+
+@pytest.mark.parametrize("color,geo,noise,ada", WIRING_CASES,
+                         ids=["color%d-geo%d-noise%d-ada%d" % c for c in WIRING_CASES])
+def test_stages_on_ds_input_chain_buffer_to_buffer_forward_and_back(color, geo, noise, ada):
+    """Every on / off combination of the three stages on D's input, without and with a fixed augmentation
+    probability: each forward stage reads exactly the buffer the one before it wrote, from d_in on, and D's
+    layer 0 (forward and weight gradient) reads the last; the transposes run in reverse from img_grad, and G's
+    tanh backward reads the last -- or stays fused into the image gradient where there is no transpose."""
+    kw = dict(ON if color else {}, **(GEO if geo else {}), **(NOISE if noise else {}))
+    eng = _hip(**kw, **(dict(d_augment_p=0.5) if ada else {}))
+    B, nbytes = eng.B, eng.d_in.numel() * 2
+    half = nbytes // 2
+    info = lambda prog: [prog.op_info(i) for i in range(prog.size())]  # noqa: E731  (name, stream, kind, event, acc)
+    opsA, opsB = info(eng.progA), info(eng.progB)
+    names = [o[0] for o in opsA]
+    on = [w for w, flag in zip(WIRING, (color, geo, noise)) if flag]
+    for w, flag in zip(WIRING, (color, geo, noise)):
+        if not flag:
+            assert all(getattr(eng, a) is None for a in w[1:] if a) and w[0] not in names and w[0] + "_bwd" not in names
+    assert (eng.ada_state is not None) == ada
+    copies = [eng.d_in] + [getattr(eng, w[1]) for w in on]
+
+    def only_reads(op, buf, n, among):  # of the buffers `among`, op reads `buf` (n bytes from its start) and no other
+        assert (buf.data_ptr(), n, False) in op[4], op
+        assert not any(a == o.data_ptr() and not wr for a, _, wr in op[4] for o in among if o is not buf), op
+
+    # forward: consecutive ops, each from the copy before it into its own
+    i, prev = None, eng.d_in
+    for name, out, gates, _ in on:
+        assert names.count(name) == 1 and (i is None or names.index(name) == i + 1)
+        i, dst = names.index(name), getattr(eng, out)
+        only_reads(opsA[i], prev, nbytes, copies)
+        assert (dst.data_ptr(), nbytes, True) in opsA[i][4]
+        if ada and gates:  # the gated kernel: p24 from the state, the gate masks of all 2B samples out
+            assert (eng.ada_state.data_ptr(), 4, False) in opsA[i][4]
+            assert (getattr(eng, gates).data_ptr(), 2 * B * 4, True) in opsA[i][4]
+        elif ada:
+            assert not any(a == eng.ada_state.data_ptr() for a, _, _ in opsA[i][4])
+        elif gates:
+            assert getattr(eng, gates) is None
+        prev = dst
+    assert prev is eng._d_input()
+    d0 = [o for o in opsA + opsB if o[0].startswith(("d0.", eng.dl[0].name))
+          and any(a == c.data_ptr() and not wr for a, _, wr in o[4] for c in copies)]
+    assert any(o in opsA for o in d0) and any(o in opsB for o in d0)  # layer 0's forward, and its weight gradient
+    for o in d0:
+        only_reads(o, prev, nbytes, copies)
+    if on:
+        assert opsA[i + 1] in d0
+
+    # backward: the transposes in reverse order, behind the image gradient and ahead of G's tanh backward
+    back = [w for w in reversed(on) if w[3]]
+    if not back:
+        assert sum("dgrad_img+tanh_bwd" in n for n in names) >= 1 and "g_out.tanh_bwd" not in names
+        assert not any(n.endswith(".dgrad_img") for n in names)
+        return
+    assert not any("dgrad_img+tanh_bwd" in n for n in names) and names.count("g_out.tanh_bwd") == 1
+    grads = [eng.img_grad] + [getattr(eng, w[3]) for w in back]
+    j = [k for k, n in enumerate(names) if n.endswith(".dgrad_img")]
+    assert len(j) == 1 and (eng.img_grad.data_ptr(), half, True) in opsA[j[0]][4]
+    j, prev = j[0], eng.img_grad
+    for name, _, gates, grad in back:
+        j += 1
+        assert names[j] == name + "_bwd" and names.count(names[j]) == 1
+        only_reads(opsA[j], prev, half, grads)
+        assert (getattr(eng, grad).data_ptr(), half, True) in opsA[j][4]
+        if ada:  # the gate rows the forward recorded for the fake half
+            assert (getattr(eng, gates).data_ptr() + B * 4, B * 4, False) in opsA[j][4]
+        prev = getattr(eng, grad)
+    assert names[j + 1] == "g_out.tanh_bwd"
+    only_reads(opsA[j + 1], prev, half, grads)
+
+
 # ------------------------------------------------------------------ 6. trainer / CLI
 def test_cli_runs_with_the_color_policy_on_the_reference_engine(tmp_path):
     env = dict(os.environ, OMP_NUM_THREADS="4")
