@@ -2,34 +2,26 @@
 ``d_augment_kernel`` / ``d_color_kernel`` against the gated oracles (every build, the 16-byte and the
 element paths, canaries around every output, params and gate buffer), ``ada_update_kernel`` against
 ``ops.reference.ada_update``, and the engine: gated buffers and gate rows per step and sub-step, steps
-against ``ReferenceStep`` with the oracle's draws and gates passed in (the comparison and tolerances of
-test_hip_d_steps.py, as test_hip_d_color.py uses them), the controller's state after each of 9 steps, graph
+against ``ReferenceStep`` with the oracle's draws and gates passed in (``check_piece`` of
+hip_harness.py, as test_hip_d_color.py uses it), the controller's state after each of 9 steps, graph
 replay on the live state, an fp16 overflow step, the switch off, clean sample-time losses, one-rank RCCL
 DDP and a resume through the trainer in the middle of a window.
 
 Color inputs are the exact-sum ones of test_hip_d_color.py (bitwise, the mean included); on general inputs
 the forward is compared at the recorded Mx, as there."""
-import io
-import itertools
-import os
-
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import test_ada as TA
-import test_hip_d_color as HC
-import test_hip_d_spectral_norm as SNT
-import test_hip_d_steps as TD
+import hip_harness as HH
+import test_ada as TA  # the CPU twin: its policies and its hand-written controller table
+import test_hip_d_color as HC  # the color policy's own oracle helpers, which the gated tests extend
+from hip_harness import BUILDS, H, PAD, dev, small
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
 from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
 
-dev = torch.device("cuda", 0)
-BUILDS = SNT.BUILDS
-PAD = SNT.PAD
-ENV = HC.ENV + TA.ADA_ENV
+ENV = HH.ENV + HH.env_of("color", "aug", "noise", "lr_sched", "ada")
 ONE = 1 << 24
 P24S = [0, 1, 1 << 23, ONE - 1, ONE]
 N = 5
@@ -38,32 +30,17 @@ SEED, T = 0xFEDCBA9876543210, (1 << 32) + 3
 AUG, COL = TA.AUG, TA.COL
 ON = TA.ON
 FIXED = TA.FIXED
-_slot, _intact, _same_bits, _exact = HC._slot, HC._intact, HC._same_bits, HC._exact
+_slot, _intact, _same_bits, _exact = HH.slot, HH.intact, HH.same_bits, HC._exact
+_clean_env = HH.clean_env(ENV)
 
 
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
+def _islot(n):
+    """int32 [n] between PAD canaries of -3: (buffer, view)."""
+    return _slot(n, torch.int32, fill=-3)
 
 
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
-
-
-def small():
-    return DCGANConfig(output_size=28, c_dim=1)
-
-
-def _islot(n, fill=-3):
-    """int32 [n] between PAD canaries: (buffer, view)."""
-    buf = torch.full((n + 2 * PAD,), fill, dtype=torch.int32, device=dev)
-    return buf, buf[PAD:PAD + n]
-
-
-def _iintact(buf, fill=-3):
-    return bool((buf[:PAD] == fill).all()) and bool((buf[-PAD:] == fill).all())
+def _iintact(buf):
+    return _intact(buf, fill=-3)
 
 
 # ------------------------------------------------------------------ 1. the gates
@@ -275,8 +252,8 @@ def _check_gated(eng, d_in, k, t, tag):
 @pytest.mark.parametrize("dtype,size,c_dim", [("bf16", 28, 1), ("fp16", 28, 1), ("fp32", 28, 1), ("bf16", 64, 3)])
 def test_engine_gated_buffers_and_gate_rows_are_the_oracles_and_z_is_untouched(dtype, size, c_dim):
     cfg = DCGANConfig(output_size=size, c_dim=c_dim)
-    eng = TD._engine(cfg, 8, 2, dtype=dtype, seed=3, **FIXED)
-    off = TD._engine(cfg, 8, 2, dtype=dtype, seed=3, **ON)
+    eng = HH.engine(cfg, 8, 2, dtype=dtype, seed=3, **FIXED)
+    off = HH.engine(cfg, 8, 2, dtype=dtype, seed=3, **ON)
     assert eng.ada == R.DAda(0.5, 0.0, 4, 500.0) and eng.progAda is None and off.ada_state is None
     assert eng.ada_state.tolist() == R.ada_state(ONE // 2) and eng.op_names() == off.op_names()
     assert eng.color_gates.dtype == eng.aug_gates.dtype == torch.int32 and tuple(eng.aug_gates.shape) == (16,)
@@ -322,10 +299,10 @@ def test_four_gated_steps_track_the_reference(dtype, size, c_dim, seed=3):
     """Four steps after one warm-up step, as test_hip_d_color.py's colored and augmented steps (step 0 sits on
     the LeakyReLU kink over the zero-filled pixels)."""
     cfg, B = DCGANConfig(output_size=size, c_dim=c_dim), 8
-    eng = TD._engine(cfg, B, 1, dtype=dtype, seed=seed, **FIXED)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, False, d_ada=R.check_ada(0.5), **ON)
+    eng = HH.engine(cfg, B, 1, dtype=dtype, seed=seed, **FIXED)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, False, d_ada=R.check_ada(0.5), **ON)
     ref = _WithGates(ref)
-    real = TD._reals(B, cfg, dtype, 1)[0].to(rdev)
+    real = HH.reals(B, cfg, dtype, 1)[0].to(rdev)
     eng.train_step()
     for s in range(1, 5):
         _gated_piece(eng, ref, ref_model, cfg, real, dtype, False, None, eng.train_full_step, "step %d" % s, rdev)
@@ -335,10 +312,10 @@ def test_four_gated_steps_track_the_reference(dtype, size, c_dim, seed=3):
 @pytest.mark.parametrize("size,c_dim", [(28, 1), (64, 3)])
 def test_gated_cycle_with_sub_steps_and_spectral_norm_tracks_the_reference(size, c_dim, seed=4):
     cfg, B, dtype = DCGANConfig(output_size=size, c_dim=c_dim, d_bn=False), 8, "bf16"
-    eng = TD._engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, **FIXED)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2, d_ada=R.check_ada(0.5), **ON)
+    eng = HH.engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, **FIXED)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2, d_ada=R.check_ada(0.5), **ON)
     ref = _WithGates(ref)
-    reals = [x.to(rdev) for x in TD._reals(B, cfg, dtype, 2)]
+    reals = [x.to(rdev) for x in HH.reals(B, cfg, dtype, 2)]
     eng.train_step()  # (warm-up, as above)
     _gated_piece(eng, ref, ref_model, cfg, reals[0], dtype, True, 0, lambda: eng.train_d_step(0), "sub-step", rdev)
     _gated_piece(eng, ref, ref_model, cfg, reals[1], dtype, True, None, eng.train_full_step, "full", rdev)
@@ -360,7 +337,7 @@ def _ada_consts(eng):
 def test_adaptive_state_follows_the_oracle_fed_the_engines_own_logits(dtype, size, c_dim, extra):
     cfg = DCGANConfig(output_size=size, c_dim=c_dim)
     d_steps = extra.pop("d_steps", 1)
-    eng = TD._engine(cfg, 8, d_steps, dtype=dtype, seed=3, **ADAPT, **extra)
+    eng = HH.engine(cfg, 8, d_steps, dtype=dtype, seed=3, **ADAPT, **extra)
     assert eng.op_names().count("ada_update") == 1 and eng.ada_state.tolist() == R.ada_state(0)
     assert all("ada_update" not in eng.sub_op_names(k) for k in range(d_steps - 1))
     want, ps = R.ada_state(0), []
@@ -385,14 +362,13 @@ def test_adaptive_state_follows_the_oracle_fed_the_engines_own_logits(dtype, siz
 def test_graph_replay_equals_eager_on_the_live_state(dtype, d_steps):
     """A p24 baked in at capture time would keep the gates of the first replay's probability."""
     kw = dict(dtype=dtype, seed=1, **ADAPT)
-    e1 = TD._engine(small(), 8, d_steps, **kw)
-    e2 = TD._engine(small(), 8, d_steps, graph=True, **kw)
+    e1 = HH.engine(small(), 8, d_steps, **kw)
+    e2 = HH.engine(small(), 8, d_steps, graph=True, **kw)
     ps = []
     for t in range(6):
         e1.train_step()
         e2.train_step()
-        for x, y in zip(TD._snap(e1), TD._snap(e2)):
-            assert torch.equal(x, y)
+        HH.snap_equal(e1, e2)
         assert torch.equal(e1.ada_state, e2.ada_state) and torch.equal(e1.color_gates, e2.color_gates)
         assert torch.equal(e1.aug_gates, e2.aug_gates) and _same_bits(e1.d_auged, e2.d_auged)
         assert _same_bits(e1.img_grad_c, e2.img_grad_c)
@@ -402,7 +378,7 @@ def test_graph_replay_equals_eager_on_the_live_state(dtype, d_steps):
 
 
 def test_an_fp16_overflow_step_still_advances_the_controller():
-    eng = TD._engine(small(), 8, 1, dtype="fp16", seed=1, **dict(ADAPT, ada_interval=1))
+    eng = HH.engine(small(), 8, 1, dtype="fp16", seed=1, **dict(ADAPT, ada_interval=1))
     eng.train_step()
     torch.cuda.synchronize()
     before, w0 = eng.ada_state.tolist(), eng.model.d.flat.clone()
@@ -416,38 +392,36 @@ def test_an_fp16_overflow_step_still_advances_the_controller():
 
 def test_the_switch_off_is_todays_engine():
     cfg = small()
-    a = TD._engine(cfg, 8, 2, seed=2, d_augment_p=-1.0, ada_target=0.0, **ON)
-    b = TD._engine(cfg, 8, 2, seed=2, **ON)
-    c = TD._engine(cfg, 8, 2, seed=2, d_augment_p=1.0, **ON)
+    a = HH.engine(cfg, 8, 2, seed=2, d_augment_p=-1.0, ada_target=0.0, **ON)
+    b = HH.engine(cfg, 8, 2, seed=2, **ON)
+    c = HH.engine(cfg, 8, 2, seed=2, d_augment_p=1.0, **ON)
     for e in (a, b, c):
         assert not e.ada.active and e.ada_state is None and e.aug_gates is None and e.color_gates is None and e.progAda is None
     assert a.op_names() == b.op_names() == c.op_names() and a.kernel_count() == b.kernel_count()
     for _ in range(3):
         for e in (a, b, c):
             e.train_step()
-    for x, y, w in zip(TD._snap(a), TD._snap(b), TD._snap(c)):
-        assert torch.equal(x, y) and torch.equal(x, w)
+    HH.snap_equal(a, b, c)
     assert _same_bits(a.d_auged, b.d_auged) and torch.equal(a.color_params, b.color_params)
     # and p24 = 2^24 through the gated kernels is the same model, bitwise
-    d = TD._engine(cfg, 8, 2, seed=2, d_augment_p=0.5, **ON)
+    d = HH.engine(cfg, 8, 2, seed=2, d_augment_p=0.5, **ON)
     d.ada_state[0] = ONE
     for _ in range(3):
         d.train_step()
-    for x, y in zip(TD._snap(d), TD._snap(b)):
-        assert torch.equal(x, y)
+    HH.snap_equal(d, b)
     assert bool((d.aug_gates == 3).all()) and bool((d.color_gates == 7).all())
 
 
 def test_eval_losses_stay_clean_and_leave_the_state_alone():
     cfg, B = small(), 8
-    on = TD._engine(cfg, B, 1, seed=2, **ADAPT)
-    off = TD._engine(cfg, B, 1, seed=7)
+    on = HH.engine(cfg, B, 1, seed=2, **ADAPT)
+    off = HH.engine(cfg, B, 1, seed=7)
     on.train_step()
     torch.cuda.synchronize()
     for name in ("g", "d"):
         getattr(off.model, name).flat.copy_(getattr(on.model, name).flat)
     off.after_state_load()
-    real = TD._reals(B, cfg, "bf16", 3)[2]
+    real = HH.reals(B, cfg, "bf16", 3)[2]
     z = torch.rand(B, cfg.z_dim, generator=torch.Generator().manual_seed(11)) * 2 - 1
     before = (on.ada_state.clone(), on.aug_gates.clone(), on.color_gates.clone(), on.d_auged.clone())
     a, b = on.eval_losses(real, z), off.eval_losses(real, z)
@@ -464,7 +438,7 @@ STEPS = 5
 
 
 def _ddp_engine(graph):
-    return TD._engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, **ADAPT)
+    return HH.engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, **ADAPT)
 
 
 def _result(eng):
@@ -475,55 +449,22 @@ def _result(eng):
             "img_grad_c": eng.img_grad_c.cpu()}
 
 
-def _rccl_worker(out_dir, schedule, port):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["DCGAN_FORCE_DDP"] = "1"
-    os.environ["DCGAN_DDP_SCHEDULE"] = schedule
-    os.environ["DCGAN_DDP_SHARD"] = "0"
-    os.environ.pop("DCGAN_DIST_BACKEND", None)
-    torch.cuda.set_device(0)
-    from distributed_tensorflow_for_dcgan_amd.parallel import dist as D
-    import torch.distributed as tdist
-    D.init_distributed(1, 0, torch.device("cuda", 0))
-    eng = _ddp_engine(True)
-    assert eng.ddp and eng._schedule() == schedule and eng.ada.adaptive
-    for _ in range(STEPS):
-        eng.train_step()
-    out = _result(eng)
-    out.update({"step": eng.global_step, "backend": tdist.get_backend(), "graph": eng.graph_enabled, "ops": eng.op_names()})
-    torch.save(out, os.path.join(out_dir, "rccl.pt"))
-    D.barrier()
-    D.shutdown()
+def _active(eng):
+    return eng.ada.adaptive
+
+
+DDP = HH.Ddp(_ddp_engine, _result, STEPS, active=_active)
 
 
 @pytest.fixture(scope="module")
 def fused_run():
-    old = {k: os.environ.pop(k, None) for k in ENV}
-    try:
-        eng = _ddp_engine(True)
-        assert not eng.ddp and eng._schedule() == "fused"
-        for _ in range(STEPS):
-            eng.train_step()
-        return _result(eng)
-    finally:
-        for k, v in old.items():
-            if v is not None:
-                os.environ[k] = v
+    return HH.fused_result(DDP, ENV)
 
 
 @pytest.mark.parametrize("schedule", ["concurrent", "ddp"])
 def test_rccl_single_rank_ddp_matches_fused_state_included(tmp_path, schedule, fused_run):
-    ctx = mp.get_context("spawn")
-    p = ctx.Process(target=_rccl_worker, args=(str(tmp_path), schedule, SNT._free_port()))
-    p.start()
-    p.join(timeout=600)
-    assert p.exitcode == 0, "RCCL rank exited with %s" % p.exitcode
-    r = torch.load(tmp_path / "rccl.pt", weights_only=True)
-    assert r["backend"] == "nccl" and r["step"] == STEPS and r["graph"]
+    r = HH.rccl_run(tmp_path, DDP, schedule, True, fused_run)
     assert r["ops"].count("ada_update") == 1
-    for k, v in fused_run.items():
-        assert torch.equal(r[k], v), k
     assert fused_run["state"].tolist()[4] == 2 and fused_run["state"].tolist()[2] == 1
 
 
@@ -533,64 +474,21 @@ def test_trainer_resume_is_exact_in_the_middle_of_a_window(tmp_path, monkeypatch
     source alternates two batches, so an even split keeps them aligned) -- every saved tensor bitwise, the five
     ada/ keys among them; a run with a fixed p writes none of them."""
     from distributed_tensorflow_for_dcgan_amd.ckpt import checkpoint as CK
-    from distributed_tensorflow_for_dcgan_amd.data import pipeline as P
-    from distributed_tensorflow_for_dcgan_amd.train import trainer as T
-    from distributed_tensorflow_for_dcgan_amd.utils import flags as F
-
-    def source(flags, batch, shape, device, **kw):
-        class Two:
-            num_examples = 1 << 20
-
-            def __init__(self):
-                self.i = 0
-                self.x = [P.SyntheticSource(batch, shape, device, seed=s).next().to(torch.bfloat16) for s in (1, 2)]
-
-            def next(self):
-                self.i += 1
-                return self.x[self.i % 2]
-
-            def stats(self):
-                return {"source": "test"}
-
-            def close(self):
-                pass
-        return Two()
-    monkeypatch.setattr(T, "make_source", source)
     AF = ["--d_color_augment=contrast,saturation,brightness", "--d_augment=translation,cutout", "--ada_target=0.6",
           "--ada_interval=4", "--ada_kimg=0.05", "--d_augment_p=0.5"]
-
-    def run(ck, steps, af=AF):
-        fl = F.parse_flags(["--synthetic", "--engine=hip", "--device=cuda", "--dtype=bf16", "--output_size=28",
-                            "--c_dim=1", "--batch_size=8", "--max_steps=%d" % steps, "--sample_every=0", "--nosummaries",
-                            "--save_model_secs=1e9", "--checkpoint_dir=%s" % ck, "--sample_dir=%s" % (tmp_path / "s"),
-                            "--nolog_device_placement", "--seed=5"] + af)
-        out = io.StringIO()
-        assert T.run(fl, out=out) == 0, out.getvalue()
-        return out.getvalue()
-
-    def load(ck):
-        from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
-        eng = HipEngine(small(), 8, dev, seed=99, graph=False, d_augment_p=0.5, ada_target=0.6, ada_interval=4,
-                        ada_kimg=0.05, **ON)
-        info = CK.CheckpointManager(str(ck)).restore_latest(eng)
-        torch.cuda.synchronize()
-        return info, CK.collect_state(eng), eng.ada_state.tolist()
-    text = run(tmp_path / "a", 6)
-    assert "augmentation probability of D's inputs: adaptive p from 0.5, target r_t = 0.6, every 4 steps" in text
-    text = run(tmp_path / "b", 2)
-    assert "load failed" in text
-    text = run(tmp_path / "b", 6)
-    assert "load success!" in text and "global_step 2" in text and "adaptive augmentation state: loaded" in text
-    (ia, sa, ta), (ib, sb, tb) = load(tmp_path / "a"), load(tmp_path / "b")
-    assert ia["global_step"] == ib["global_step"] == 6 and list(sa) == list(sb) and ta == tb
+    r = HH.trainer_resume(tmp_path, monkeypatch, AF, load_kw=dict(ON, d_augment_p=0.5, ada_target=0.6, ada_interval=4, ada_kimg=0.05),
+                          log_line="augmentation probability of D's inputs: adaptive p from 0.5, target r_t = 0.6, every 4 steps",
+                          steps=(6, 2))
+    assert "load failed" in r.texts[1] and "adaptive augmentation state: loaded" in r.texts[2]
+    (ia, sa, ea), (ib, sb, eb) = r.a, r.b
+    ta, tb = ea.ada_state.tolist(), eb.ada_state.tolist()
+    assert ta == tb
     assert [k for k in sa if k.startswith("ada/")] == ["ada/" + k for k in R.ADA_KEYS]
     assert int(sa["ada/cnt"]) == 2 and int(sa["ada/windows"]) == 1 and ta[:5] == [int(sa["ada/" + k]) for k in R.ADA_KEYS]
-    for k in sa:
-        assert (sa[k] == sb[k]).all(), k
-    text = run(tmp_path / "c", 2, af=AF[:2] + ["--d_augment_p=0.5"])  # a fixed p: no key, and the controller's load says so
+    text = r.run(tmp_path / "c", 2, AF[:2] + ["--d_augment_p=0.5"])  # a fixed p: no key, and the controller's load says so
     assert "fixed p = 0.5" in text
-    ic, sc, tc = load(tmp_path / "c")
-    assert "starts from p = 0.5" in ic["ada"] and tc == R.ada_state(ONE // 2)
+    ic, sc, ec = r.load(tmp_path / "c")
+    assert "starts from p = 0.5" in ic["ada"] and ec.ada_state.tolist() == R.ada_state(ONE // 2)
     from distributed_tensorflow_for_dcgan_amd.ckpt import tf_bundle
     ckc = CK.latest_checkpoint(str(tmp_path / "c"))
     assert ckc is not None and not any(k.startswith("ada/") for k in tf_bundle.read_bundle(ckc))

@@ -3,7 +3,7 @@ draws against the oracle, the forward and the transpose against ``ops.reference.
 ``color_augment_transpose`` (bf16 / fp16 / fp32 builds, canary-padded buffers, the 16-byte and the element
 path), the engine's colored buffer and recorded params (full step and D sub-steps), the three stages in
 order, the g_loss chain stage by stage, steps against ``ReferenceStep`` with the oracle's draws passed in
-(the comparison and tolerances of test_hip_d_steps.py, as test_hip_d_augment.py uses them), hipGraph
+(``check_piece`` of hip_harness.py, as test_hip_d_augment.py uses it), hipGraph
 replay, the switch off, clean sample-time losses, one-rank RCCL DDP and resume through the trainer.
 
 Exact-sum inputs (values k/128, |k| <= 128, at most 49,152 per image) sum exactly in fp32 in any order
@@ -12,27 +12,19 @@ included. On general inputs the recorded mean is held to Higham's bound for a su
 division's rounding, the forward is bitwise the oracle at the recorded mean, and the transpose -- whose
 mean is not recorded -- to half an ulp of the element type plus the mean's bound scaled by |1 - c| plus
 eight fp32 roundings of the largest value. Measured on an MI355X (profiles/r16/d_color_r16.txt)."""
-import io
 import itertools
-import os
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import test_hip_d_spectral_norm as SNT
-import test_hip_d_steps as TD
+import hip_harness as HH
+from hip_harness import BUILDS, H, PAD, dev, small
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
 from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
 
-dev = torch.device("cuda", 0)
-BUILDS = SNT.BUILDS
-PAD = SNT.PAD
-ENV = TD.ENV + ("DCGAN_D_COLOR_AUGMENT", "DCGAN_D_AUGMENT", "DCGAN_INSTANCE_NOISE", "DCGAN_INSTANCE_NOISE_END",
-                "DCGAN_INSTANCE_NOISE_STEPS", "DCGAN_LR_DECAY", "DCGAN_LR_DECAY_START", "DCGAN_LR_DECAY_STEPS",
-                "DCGAN_LR_END", "DCGAN_LR_WARMUP")
+ENV = HH.ENV + HH.env_of("color", "aug", "noise", "lr_sched")
 SEEDS = [1000020, 0xFEDCBA9876543210]
 STEPS_T = [0, 1, (1 << 32) + 3]
 SHAPES = [(3, 8, 3), (1, 5, 3), (2, 6, 4), (2, 28, 1), (2, 28, 3), (2, 64, 3), (1, 128, 3)]  # (N, S, C)
@@ -41,45 +33,9 @@ SUBSETS = [R.DColor(*bits) for bits in itertools.product((False, True), repeat=3
 COLOR = dict(d_color_augment="brightness,saturation,contrast")
 GEO = dict(d_augment="translation,cutout")
 NOISE = dict(instance_noise=0.2, instance_noise_end=0.05, instance_noise_steps=4)
-FILL = 7.0
 MANT = {torch.bfloat16: (7, -126), torch.float16: (10, -14), torch.float32: (23, -126)}  # (fraction bits, min exponent)
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
-
-
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
-
-
-def small():
-    return DCGANConfig(output_size=28, c_dim=1)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16).cpu()
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _slot(shape, dtype, off=0):
-    """A view of `shape` `off` elements past a 16-byte boundary, PAD canaries on both sides: (buffer, view)."""
-    n = 1
-    for d in shape:
-        n *= d
-    buf = torch.full((n + 2 * PAD + off,), FILL, dtype=dtype, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    return buf, buf[PAD + off:PAD + off + n].view(shape)
-
-
-def _intact(buf, off=0):
-    return bool((buf[:PAD + off] == FILL).all()) and bool((buf[-PAD:] == FILL).all())
+_same_bits, _slot, _intact = HH.same_bits, HH.slot, HH.intact
+_clean_env = HH.clean_env(ENV)
 
 
 def _exact(N, S, C, seed):
@@ -314,8 +270,8 @@ def _acc(prog, name):
 @pytest.mark.parametrize("dtype,size,c_dim", [("bf16", 28, 1), ("fp16", 28, 1), ("fp32", 28, 1), ("bf16", 64, 3)])
 def test_engine_colored_buffer_is_the_oracles_and_z_is_untouched(dtype, size, c_dim):
     cfg = DCGANConfig(output_size=size, c_dim=c_dim)
-    eng = TD._engine(cfg, 8, 1, dtype=dtype, seed=3, **COLOR)
-    off = TD._engine(cfg, 8, 1, dtype=dtype, seed=3)
+    eng = HH.engine(cfg, 8, 1, dtype=dtype, seed=3, **COLOR)
+    off = HH.engine(cfg, 8, 1, dtype=dtype, seed=3)
     assert eng.color == ALL and eng.d_colored.shape == eng.d_in.shape and eng.d_colored.dtype == eng.d_in.dtype
     assert eng.color_params.dtype == torch.float32 and tuple(eng.color_params.shape) == (16, 4)
     assert off.d_colored is None and off.color_params is None and off.img_grad_c is None
@@ -344,7 +300,7 @@ def test_engine_colored_buffer_is_the_oracles_and_z_is_untouched(dtype, size, c_
 
 
 def test_sub_steps_draw_their_own_params():
-    eng = TD._engine(small(), 8, 3, seed=6, **COLOR)
+    eng = HH.engine(small(), 8, 3, seed=6, **COLOR)
     assert eng.op_names().count("d_color") == 3 and eng.op_names().count("d_color_bwd") == 1
     assert all(eng.sub_op_names(k).count("d_color") == 1 and "d_color_bwd" not in eng.sub_op_names(k) for k in range(2))
     seen = []
@@ -363,7 +319,7 @@ def test_sub_steps_draw_their_own_params():
 @pytest.mark.parametrize("dtype", ["bf16", "fp32"])
 def test_the_three_stages_land_in_order(dtype):
     """color, then translation / cutout of the colored copy, then the noise on that."""
-    eng = TD._engine(small(), 8, 1, dtype=dtype, seed=3, **COLOR, **GEO, **NOISE)
+    eng = HH.engine(small(), 8, 1, dtype=dtype, seed=3, **COLOR, **GEO, **NOISE)
     es = 4 if dtype == "fp32" else 2
     nb = eng.d_in.numel() * es
     step = (eng.step_counter.data_ptr(), 8, False)
@@ -396,7 +352,7 @@ def test_the_g_loss_chain_stage_by_stage(dtype, size, c_dim, geo):
     tolerance, as test_hip_d_augment.py takes it: 8e-3 x max |ref|); G's output bias gradient is the column
     sum of img_g (that test's bound)."""
     cfg, B = DCGANConfig(output_size=size, c_dim=c_dim), 8
-    eng = TD._engine(cfg, B, 1, dtype=dtype, seed=3, **COLOR, **(GEO if geo else {}))
+    eng = HH.engine(cfg, B, 1, dtype=dtype, seed=3, **COLOR, **(GEO if geo else {}))
     edt = BUILDS[dtype]
     nb = eng.img_grad.numel() * (4 if dtype == "fp32" else 2)
     src = eng.img_grad_t if geo else eng.img_grad
@@ -462,7 +418,7 @@ def _color_piece(eng, ref, ref_model, cfg, real, dtype, sn, k, run, tag, rdev):
         ref.params = R.augment_params(2 * eng.B, cfg.output_size, eng._zseed(k), eng.global_step)
     if eng.noise.active:
         ref.noise = R.instance_noise(tuple(eng.d_in.shape), eng.noise, eng._zseed(k), eng.global_step).to(rdev)
-    TD._check_piece(eng, ref, ref_model, cfg, real, dtype, sn, k is None, run, tag)
+    HH.check_piece(eng, ref, ref_model, cfg, real, dtype, sn, k is None, run, tag)
     assert torch.equal(eng.color_params[:, :3].cpu(), ref.color), tag
     if eng.aug.active:
         assert torch.equal(eng.aug_params.cpu().long(), ref.params), tag
@@ -471,10 +427,10 @@ def _color_piece(eng, ref, ref_model, cfg, real, dtype, sn, k, run, tag, rdev):
 @pytest.mark.parametrize("dtype,size,c_dim", [("fp32", 28, 1), ("bf16", 28, 1), ("fp16", 28, 1), ("bf16", 64, 3)])
 def test_four_colored_steps_track_the_reference(dtype, size, c_dim, seed=3):
     cfg, B = DCGANConfig(output_size=size, c_dim=c_dim), 8
-    eng = TD._engine(cfg, B, 1, dtype=dtype, seed=seed, **COLOR)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, False, **COLOR)
+    eng = HH.engine(cfg, B, 1, dtype=dtype, seed=seed, **COLOR)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, False, **COLOR)
     ref = _WithColor(ref)
-    real = TD._reals(B, cfg, dtype, 1)[0].to(rdev)
+    real = HH.reals(B, cfg, dtype, 1)[0].to(rdev)
     for s in range(4):
         _color_piece(eng, ref, ref_model, cfg, real, dtype, False, None, eng.train_full_step, "step %d" % s, rdev)
     assert eng.global_step == 4
@@ -485,10 +441,10 @@ def test_four_colored_and_augmented_steps_track_the_reference(dtype, size, c_dim
     """Four steps after one warm-up step: with translation / cutout on, step 0 sits on the LeakyReLU kink
     over the zero-filled pixels (test_hip_d_augment.py documents and measures it)."""
     cfg, B = DCGANConfig(output_size=size, c_dim=c_dim), 8
-    eng = TD._engine(cfg, B, 1, dtype=dtype, seed=seed, **COLOR, **GEO)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, False, **COLOR, **GEO)
+    eng = HH.engine(cfg, B, 1, dtype=dtype, seed=seed, **COLOR, **GEO)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, False, **COLOR, **GEO)
     ref = _WithColor(ref)
-    real = TD._reals(B, cfg, dtype, 1)[0].to(rdev)
+    real = HH.reals(B, cfg, dtype, 1)[0].to(rdev)
     eng.train_step()
     for s in range(1, 5):
         _color_piece(eng, ref, ref_model, cfg, real, dtype, False, None, eng.train_full_step, "step %d" % s, rdev)
@@ -497,10 +453,10 @@ def test_four_colored_and_augmented_steps_track_the_reference(dtype, size, c_dim
 
 def test_colored_cycle_with_sub_steps_and_spectral_norm_tracks_the_reference(seed=4):
     cfg, B, dtype = DCGANConfig(output_size=28, c_dim=1, d_bn=False), 8, "bf16"
-    eng = TD._engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, **COLOR)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2, **COLOR)
+    eng = HH.engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, **COLOR)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2, **COLOR)
     ref = _WithColor(ref)
-    reals = [x.to(rdev) for x in TD._reals(B, cfg, dtype, 2)]
+    reals = [x.to(rdev) for x in HH.reals(B, cfg, dtype, 2)]
     _color_piece(eng, ref, ref_model, cfg, reals[0], dtype, True, 0, lambda: eng.train_d_step(0), "sub-step", rdev)
     _color_piece(eng, ref, ref_model, cfg, reals[1], dtype, True, None, eng.train_full_step, "full", rdev)
     assert eng.global_step == 1
@@ -511,14 +467,13 @@ def test_colored_cycle_with_sub_steps_and_spectral_norm_tracks_the_reference(see
 def test_graph_replay_follows_the_live_counter(dtype, d_steps, geo):
     """A step baked in at capture time would repeat the first replay's draws."""
     kw = dict(dtype=dtype, seed=1, **COLOR, **(GEO if geo else {}))
-    e1 = TD._engine(small(), 8, d_steps, **kw)
-    e2 = TD._engine(small(), 8, d_steps, graph=True, **kw)
+    e1 = HH.engine(small(), 8, d_steps, **kw)
+    e2 = HH.engine(small(), 8, d_steps, graph=True, **kw)
     prev = None
     for t in range(4):
         e1.train_step()
         e2.train_step()
-        for x, y in zip(TD._snap(e1), TD._snap(e2)):
-            assert torch.equal(x, y)
+        HH.snap_equal(e1, e2)
         assert _same_bits(e1.d_colored, e2.d_colored) and torch.equal(e1.color_params, e2.color_params)
         assert _same_bits(e1.img_grad_c, e2.img_grad_c)
         assert torch.equal(e2.color_params[:, :3].cpu(), R.color_params(16, e2._zseed(None), t))
@@ -529,10 +484,10 @@ def test_graph_replay_follows_the_live_counter(dtype, d_steps, geo):
 
 def test_the_switch_off_is_todays_engine():
     cfg = small()
-    a = TD._engine(cfg, 8, 2, seed=2, d_color_augment="")
+    a = HH.engine(cfg, 8, 2, seed=2, d_color_augment="")
     from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
     b = HipEngine(cfg, 8, dev, seed=2, graph=False, d_steps=2)  # built without the argument
-    for k, x in enumerate(TD._reals(8, cfg, "bf16", 2)):
+    for k, x in enumerate(HH.reals(8, cfg, "bf16", 2)):
         b.set_batch(x.to(dev), k)
     assert not a.color.active and a.d_colored is None and b.d_colored is None and b.color_params is None
     assert a.op_names() == b.op_names() and not any("d_color" in n for n in a.op_names())
@@ -541,21 +496,20 @@ def test_the_switch_off_is_todays_engine():
     for _ in range(3):
         a.train_step()
         b.train_step()
-    for x, y in zip(TD._snap(a), TD._snap(b)):
-        assert torch.equal(x, y)
+    HH.snap_equal(a, b)
 
 
 # ------------------------------------------------------------------ 9. eval_losses
 def test_eval_losses_stay_clean():
     cfg, B = small(), 8
-    on = TD._engine(cfg, B, 1, seed=2, **COLOR, **NOISE)
-    off = TD._engine(cfg, B, 1, seed=7)
+    on = HH.engine(cfg, B, 1, seed=2, **COLOR, **NOISE)
+    off = HH.engine(cfg, B, 1, seed=7)
     on.train_step()
     torch.cuda.synchronize()
     for name in ("g", "d"):
         getattr(off.model, name).flat.copy_(getattr(on.model, name).flat)
     off.after_state_load()
-    real = TD._reals(B, cfg, "bf16", 3)[2]
+    real = HH.reals(B, cfg, "bf16", 3)[2]
     z = torch.rand(B, cfg.z_dim, generator=torch.Generator().manual_seed(11)) * 2 - 1
     before = (on.d_colored.clone(), on.color_params.clone(), on.d_noisy.clone())
     a, b = on.eval_losses(real, z), off.eval_losses(real, z)
@@ -571,7 +525,7 @@ STEPS = 3
 
 
 def _ddp_engine(graph):
-    return TD._engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, **COLOR, **GEO)
+    return HH.engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, **COLOR, **GEO)
 
 
 def _result(eng):
@@ -582,113 +536,32 @@ def _result(eng):
             "auged": eng.d_auged.cpu(), "img_grad_c": eng.img_grad_c.cpu()}
 
 
-def _rccl_worker(out_dir, schedule, port):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["DCGAN_FORCE_DDP"] = "1"
-    os.environ["DCGAN_DDP_SCHEDULE"] = schedule
-    os.environ["DCGAN_DDP_SHARD"] = "0"
-    os.environ.pop("DCGAN_DIST_BACKEND", None)
-    torch.cuda.set_device(0)
-    from distributed_tensorflow_for_dcgan_amd.parallel import dist as D
-    import torch.distributed as tdist
-    D.init_distributed(1, 0, torch.device("cuda", 0))
-    eng = _ddp_engine(True)
-    assert eng.ddp and eng._schedule() == schedule and eng.color.active
-    for _ in range(STEPS):
-        eng.train_step()
-    out = _result(eng)
-    out.update({"step": eng.global_step, "backend": tdist.get_backend(), "graph": eng.graph_enabled,
-                "ops": eng.op_names()})
-    torch.save(out, os.path.join(out_dir, "rccl.pt"))
-    D.barrier()
-    D.shutdown()
+def _active(eng):
+    return eng.color.active
+
+
+DDP = HH.Ddp(_ddp_engine, _result, STEPS, active=_active)
 
 
 @pytest.fixture(scope="module")
 def fused_run():
-    old = {k: os.environ.pop(k, None) for k in ENV}
-    try:
-        eng = _ddp_engine(True)
-        assert not eng.ddp and eng._schedule() == "fused"
-        for _ in range(STEPS):
-            eng.train_step()
-        return _result(eng)
-    finally:
-        for k, v in old.items():
-            if v is not None:
-                os.environ[k] = v
+    return HH.fused_result(DDP, ENV)
 
 
 @pytest.mark.parametrize("schedule", ["concurrent", "ddp"])
 def test_rccl_single_rank_ddp_matches_fused_with_the_color_policy(tmp_path, schedule, fused_run):
-    ctx = mp.get_context("spawn")
-    p = ctx.Process(target=_rccl_worker, args=(str(tmp_path), schedule, SNT._free_port()))
-    p.start()
-    p.join(timeout=600)
-    assert p.exitcode == 0, "RCCL rank exited with %s" % p.exitcode
-    r = torch.load(tmp_path / "rccl.pt", weights_only=True)
-    assert r["backend"] == "nccl" and r["step"] == STEPS and r["graph"]
+    r = HH.rccl_run(tmp_path, DDP, schedule, True, fused_run)
     assert r["ops"].count("d_color") == 1 and r["ops"].count("d_color_bwd") == 1
-    for k, v in fused_run.items():
-        assert torch.equal(r[k], v), k
 
 
 # ------------------------------------------------------------------ 11. resume through the trainer
 def test_trainer_resume_is_exact(tmp_path, monkeypatch):
     """bf16: 4 steps in one run == 2 steps, a restart from the checkpoint, 2 more -- every saved tensor
     bitwise, and no key beyond the run's without the switch (the draws are a function of seed and step)."""
-    from distributed_tensorflow_for_dcgan_amd.ckpt import checkpoint as CK
-    from distributed_tensorflow_for_dcgan_amd.data import pipeline as P
-    from distributed_tensorflow_for_dcgan_amd.train import trainer as T
-    from distributed_tensorflow_for_dcgan_amd.utils import flags as F
-
-    def source(flags, batch, shape, device, **kw):
-        class Two:
-            num_examples = 1 << 20
-
-            def __init__(self):
-                self.i = 0
-                self.x = [P.SyntheticSource(batch, shape, device, seed=s).next().to(torch.bfloat16) for s in (1, 2)]
-
-            def next(self):
-                self.i += 1
-                return self.x[self.i % 2]
-
-            def stats(self):
-                return {"source": "test"}
-
-            def close(self):
-                pass
-        return Two()
-    monkeypatch.setattr(T, "make_source", source)
     AF = ["--d_color_augment=contrast,saturation,brightness"]
-
-    def run(ck, steps, af=AF):
-        fl = F.parse_flags(["--synthetic", "--engine=hip", "--device=cuda", "--dtype=bf16", "--output_size=28",
-                            "--c_dim=1", "--batch_size=8", "--max_steps=%d" % steps, "--sample_every=0", "--nosummaries",
-                            "--save_model_secs=1e9", "--checkpoint_dir=%s" % ck, "--sample_dir=%s" % (tmp_path / "s"),
-                            "--nolog_device_placement", "--seed=5"] + af)
-        out = io.StringIO()
-        assert T.run(fl, out=out) == 0, out.getvalue()
-        return out.getvalue()
-
-    def load(ck):
-        from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
-        eng = HipEngine(small(), 8, dev, seed=99, graph=False)
-        info = CK.CheckpointManager(str(ck)).restore_latest(eng)
-        torch.cuda.synchronize()
-        return info, CK.collect_state(eng)
-    text = run(tmp_path / "a", 4)
-    assert "color augmentation of D's inputs: brightness,saturation,contrast" in text
-    run(tmp_path / "b", 2)
-    text = run(tmp_path / "b", 4)
-    assert "load success!" in text and "global_step 2" in text
-    (ia, sa), (ib, sb) = load(tmp_path / "a"), load(tmp_path / "b")
-    assert ia["global_step"] == ib["global_step"] == 4 and list(sa) == list(sb)
-    for k in sa:
-        assert (sa[k] == sb[k]).all(), k
-    text = run(tmp_path / "c", 4, af=[])  # without the switch: another model, under the same keys
+    r = HH.trainer_resume(tmp_path, monkeypatch, AF, log_line="color augmentation of D's inputs: brightness,saturation,contrast")
+    sa = r.a[1]
+    text = r.run(tmp_path / "c", 4, [])  # without the switch: another model, under the same keys
     assert "color augmentation" not in text
-    ic, sc = load(tmp_path / "c")
+    ic, sc, _ = r.load(tmp_path / "c")
     assert list(sc) == list(sa) and any(not (sa[k] == sc[k]).all() for k in sa)

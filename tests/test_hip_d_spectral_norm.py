@@ -22,14 +22,13 @@ the weights 3e-6..1e-5; bound 1e-3); bf16 largest per-tensor error 0.27 on g_h4/
 (excluded as in test_hip_engine.py), otherwise <= 0.18 (bound 0.25 / 0.35); fp16 D <= 0.035,
 G <= 0.056 (bounds 0.1 / 0.15). The cases without spectral norm read the same, so the standard
 tolerances hold and no wider one is used."""
-import contextlib
 import os
-import socket
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
+import hip_harness as HH
+from hip_harness import BUILDS, H, dev, rel
 from distributed_tensorflow_for_dcgan_amd.engine.reference_step import ReferenceStep
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
 from distributed_tensorflow_for_dcgan_amd.models.dcgan import DCGAN
@@ -37,34 +36,11 @@ from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
 
-dev = torch.device("cuda", 0)
 SHAPES = [(25, 64), (75, 64), (1600, 128), (6400, 512), (2048, 1)]
-BUILDS = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}
 HALF_ULP = 2.0 ** -24
-PAD = 64  # canary elements around every slice the kernels write
-
-
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
-
-
-def rel(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
-
-
-def _padded(x, dtype=None, fill=7.0):
-    """x inside a buffer with PAD canaries on both sides: (buffer, view of x)."""
-    dtype = dtype or x.dtype
-    buf = torch.full((x.numel() + 2 * PAD,), fill, dtype=dtype, device=dev)
-    view = buf[PAD:PAD + x.numel()]
-    view.copy_(x.flatten().to(dtype))
-    return buf, view
-
-
-def _canaries_intact(buf, fill=7.0):
-    return bool((buf[:PAD] == fill).all()) and bool((buf[-PAD:] == fill).all())
+_padded, _canaries_intact, _ulps_apart = HH.padded, HH.intact, HH.ulps_apart
+_engine, _real, _copies_match_state = HH.engine, HH.real, HH.copies_match_state
+_engine_signs, _recording, _engine_masks, KINK_MAX_INPUT = HH.engine_signs, HH.recording, HH.engine_masks, HH.KINK_MAX_INPUT
 
 
 @pytest.fixture(scope="module")
@@ -104,13 +80,6 @@ def _run_power(m, build, ls=None):
     for b in (ub, vb, sb, hb):
         assert _canaries_intact(b)
     return u.cpu().clone(), v.cpu().clone(), s.cpu().clone(), hat.cpu().clone()
-
-
-def _ulps_apart(a, b):
-    """Distance in units of the last place between two 16-bit tensors of one dtype."""
-    ia, ib = a.view(torch.int16).int(), b.view(torch.int16).int()
-    key = lambda x: torch.where(x < 0, -(x & 0x7FFF), x)  # noqa: E731  sign-magnitude -> ordered
-    return (key(ia) - key(ib)).abs()
 
 
 @pytest.mark.parametrize("build", list(BUILDS))
@@ -241,90 +210,6 @@ def test_wrappers_reject_bad_arguments():
 
 
 # ------------------------------------------------------------------ the whole step
-def _real(B, cfg, edt=None):
-    real = torch.rand(B, cfg.output_size, cfg.output_size, cfg.c_dim, generator=torch.Generator().manual_seed(5)) * 2 - 1
-    if edt is not None and edt != torch.float32:
-        real = real.to(edt).float()
-    return real
-
-
-def _engine(cfg, B=8, **kw):
-    from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
-    kw.setdefault("graph", False)
-    eng = HipEngine(cfg, B, dev, **kw)
-    eng.set_batch(_real(B, cfg, BUILDS[kw.get("dtype", "bf16")]).to(dev))
-    return eng
-
-
-def _copies_match_state(eng):
-    """Every normalised copy is W * (1 / sigma) of the stored sigma, rounded to its dtype."""
-    sn = eng.model.d_sn
-    for name, K, C in sn.shapes:
-        exp = eng.model.d[name].flatten() * (1.0 / sn.sigma[name])
-        if name.endswith("/Matrix"):
-            got = eng.sn_head
-        else:
-            got = eng.wbf_d[name].flatten()
-        if got.dtype == torch.float32:
-            assert torch.allclose(got, exp, rtol=2 * 2.0 ** -24, atol=0), name
-        else:
-            assert int(_ulps_apart(got.cpu(), exp.to(got.dtype).cpu()).max()) <= 1, name
-
-
-def _engine_signs(eng, cfg):
-    """Sign masks of the engine's activations, in the order the reference calls ReLU (G) and
-    LeakyReLU (D)."""
-    acts = [eng.g_h0] + [eng.g_a[L.name] for L in cfg.g_layers()[:-1]] + [eng.d_a[L.name] for L in cfg.d_layers()]
-    return [(m.float() > 0).cpu() for m in acts]
-
-
-@contextlib.contextmanager
-def _recording(inputs):
-    """Within the block every input of the reference's ReLU / LeakyReLU is appended to `inputs`;
-    the reference itself is unchanged."""
-    relu, lrelu = torch.relu, R.lrelu
-
-    def relu_r(x):
-        inputs.append(x.detach())
-        return relu(x)
-
-    def lrelu_r(x, leak=0.2):
-        inputs.append(x.detach())
-        return lrelu(x, leak)
-    torch.relu, R.lrelu = relu_r, lrelu_r
-    try:
-        yield
-    finally:
-        torch.relu, R.lrelu = relu, lrelu
-
-
-KINK_MAX_INPUT = 1e-6
-
-
-@contextlib.contextmanager
-def _engine_masks(eng, cfg):
-    """Within the block the reference's ReLU (G) and LeakyReLU (D) select their branch by the sign
-    of the engine's activation instead of their own input's: the same values (the two differ only
-    where the input is zero to within rounding) and, at such a kink, the engine's derivative. Only
-    used for a step whose differing signs were shown to be kinks (see the test)."""
-    masks = _engine_signs(eng, cfg)
-    n_g = len(cfg.g_layers())
-    it = iter(masks)
-    relu, lrelu = torch.relu, R.lrelu
-
-    def relu_m(x):
-        return torch.where(next(it).reshape(x.shape), x, torch.zeros_like(x))
-
-    def lrelu_m(x, leak=0.2):
-        return torch.where(next(it).reshape(x.shape), x, leak * x)
-    torch.relu, R.lrelu = relu_m, lrelu_m
-    try:
-        yield
-        assert next(it, None) is None and n_g + len(cfg.d_layers()) == len(masks)  # every mask was used
-    finally:
-        torch.relu, R.lrelu = relu, lrelu
-
-
 @pytest.mark.parametrize("size,c_dim", [(28, 1), (64, 3)])
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
 @pytest.mark.parametrize("sn,bn", [(True, True), (True, False), (False, False), (False, True)])
@@ -536,62 +421,25 @@ def test_checkpoint_resume_is_exact(tmp_path, dtype):
 STEPS = 4
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _ddp_engine(graph):
     return _engine(DCGANConfig(d_bn=False), 16, seed=3, graph=graph, rank_seeded_z=False, d_spectral_norm=True)
 
 
-def _rccl_worker(out_dir, graph, port):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["DCGAN_FORCE_DDP"] = "1"
-    os.environ["DCGAN_DDP_SCHEDULE"] = "concurrent"
-    os.environ["DCGAN_DDP_SHARD"] = "0"
-    os.environ.pop("DCGAN_DIST_BACKEND", None)
-    torch.cuda.set_device(0)
-    from distributed_tensorflow_for_dcgan_amd.parallel import dist as D
-    import torch.distributed as tdist
-    D.init_distributed(1, 0, torch.device("cuda", 0))
-    eng = _ddp_engine(graph)
-    assert eng.ddp and eng._schedule() == "concurrent"
-    for _ in range(STEPS):
-        eng.train_step()
-    torch.cuda.synchronize()
-    torch.save({"g": eng.model.g.flat.cpu(), "d": eng.model.d.flat.cpu(), "sn": eng.model.d_sn.flat.cpu(),
-                "mirror": eng.wbf_d.flat.cpu(), "head": eng.sn_head.cpu(), "step": eng.global_step,
-                "backend": tdist.get_backend(), "graph": eng.graph_enabled, "ops": eng.op_names()},
-               os.path.join(out_dir, "rccl.pt"))
-    D.barrier()
-    D.shutdown()
-
-
-@pytest.fixture(scope="module")
-def fused_run():
-    eng = _ddp_engine(True)
-    assert not eng.ddp and eng._schedule() == "fused"
-    for _ in range(STEPS):
-        eng.train_step()
+def _result(eng):
     torch.cuda.synchronize()
     return {"g": eng.model.g.flat.cpu(), "d": eng.model.d.flat.cpu(), "sn": eng.model.d_sn.flat.cpu(),
             "mirror": eng.wbf_d.flat.cpu(), "head": eng.sn_head.cpu()}
 
 
+DDP = HH.Ddp(_ddp_engine, _result, STEPS)
+
+
+@pytest.fixture(scope="module")
+def fused_run():
+    return HH.fused_result(DDP, ())  # (this module clears no switch around its tests either)
+
+
 @pytest.mark.parametrize("graph", [False, True])
 def test_rccl_single_rank_ddp_matches_fused(tmp_path, graph, fused_run):
-    ctx = mp.get_context("spawn")
-    p = ctx.Process(target=_rccl_worker, args=(str(tmp_path), graph, _free_port()))
-    p.start()
-    p.join(timeout=600)
-    assert p.exitcode == 0, "RCCL rank exited with %s" % p.exitcode
-    r = torch.load(tmp_path / "rccl.pt", weights_only=True)
-    assert r["backend"] == "nccl" and r["step"] == STEPS and r["graph"] == graph
+    r = HH.rccl_run(tmp_path, DDP, "concurrent", graph, fused_run)
     assert r["ops"].count("sn_power.wu") == 1 and r["ops"].index("sn_power.wu") == r["ops"].index("adam_d") + 1
-    for k, v in fused_run.items():
-        assert torch.equal(r[k], v), k

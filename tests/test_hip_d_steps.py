@@ -5,7 +5,7 @@ against ``ReferenceStep`` (bf16 / fp16 / fp32), the z of the sub-steps, hipGraph
 the trainer, and that the defaults change nothing.
 
 Comparisons with the reference are those of ``test_step_matches_reference`` in
-test_hip_d_spectral_norm.py (its helpers are imported, its tolerances repeated in ``_check_piece``):
+test_hip_d_spectral_norm.py (``check_piece`` of hip_harness.py repeats its tolerances):
 fp32 against the CPU reference, losses 1e-5, every live gradient 1e-3, activations at a kink
 compared on the engine's side after showing that they are kinks; bf16 losses 3e-2, gradients 0.25
 (biases 0.35), mean 0.15; fp16 losses 2e-2, D 0.1, G 0.15. Parameters: the engine's new D weights
@@ -17,37 +17,21 @@ gradient error 9.9e-5 (d_h3_lin/bias; otherwise 1e-6..1e-5; bound 1e-3), 3 of 17
 activation on the other side of a kink, largest |input| 4.1e-7 (bound 1e-6); bf16 largest per-tensor
 error 0.16 (g_bn2/beta in a full step; sub-steps <= 0.14; bounds 0.25 / 0.35); fp16 D <= 0.031,
 G <= 0.012 (bounds 0.1 / 0.15)."""
-import os
-
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import test_hip_d_spectral_norm as SNT  # the full step's comparison helpers
-from distributed_tensorflow_for_dcgan_amd.engine.reference_step import ReferenceStep
+import hip_harness as HH
+from hip_harness import BUILDS, H, PAD, dev
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
-from distributed_tensorflow_for_dcgan_amd.models.dcgan import DCGAN
 from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
 
-dev = torch.device("cuda", 0)
-BUILDS = SNT.BUILDS
-PAD = SNT.PAD
-rel, _padded, _canaries_intact = SNT.rel, SNT._padded, SNT._canaries_intact
-ENV = ("DCGAN_D_STEPS", "DCGAN_BETA2", "DCGAN_LR_D", "DCGAN_LR_G", "DCGAN_D_UPDATE", "DCGAN_D_SPECTRAL_NORM",
-       "DCGAN_G_EMA_DECAY", "DCGAN_GAN_LOSS")
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
-
-
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
+_padded, _canaries_intact = HH.padded, HH.intact
+_engine, _reals, _ref_for, _check_piece, _copies_match_state = HH.engine, HH.reals, HH.ref_for, HH.check_piece, HH.copies_match_state
+_g_state, _d_state, _snap = HH.g_state, HH.d_state, HH.snap
+ENV = HH.ENV
+_clean_env = HH.clean_env(ENV)
 
 
 # ------------------------------------------------------------------ kernels
@@ -161,136 +145,6 @@ def _check_step_end(ls0, want_ls, advance, with_g_and_step):
 
 
 # ------------------------------------------------------------------ a sub-step / the cycle vs the reference
-def _reals(B, cfg, dtype, n):
-    out = []
-    for k in range(n):
-        x = torch.rand(B, cfg.output_size, cfg.output_size, cfg.c_dim, generator=torch.Generator().manual_seed(5 + k)) * 2 - 1
-        out.append(x.to(BUILDS[dtype]).float())
-    return out
-
-
-def _engine(cfg, B=8, d_steps=2, **kw):
-    from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
-    kw.setdefault("graph", False)
-    eng = HipEngine(cfg, B, dev, d_steps=d_steps, **kw)
-    for k, x in enumerate(_reals(B, cfg, kw.get("dtype", "bf16"), d_steps)):
-        eng.set_batch(x.to(dev), k)
-    return eng
-
-
-def _g_state(eng):
-    t = [eng.model.g.flat, eng.wbf_g.flat, eng.opt_g.m.flat, eng.opt_g.v.flat, eng.opt_g.powers, eng.model.g_bn.flat,
-         torch.as_tensor(eng.model.g_bn.steps), eng.step_counter]
-    if eng.g_ema is not None:
-        t += [eng.g_ema.flat, eng.wbf_g_ema.flat]
-    return [x.detach().cpu().clone() for x in t]
-
-
-def _d_state(eng):
-    t = [eng.model.d.flat, eng.wbf_d.flat, eng.opt_d.m.flat, eng.opt_d.v.flat, eng.opt_d.powers]
-    if eng.d_spectral_norm:
-        t += [eng.model.d_sn.flat, eng.sn_head]
-    return [x.detach().cpu().clone() for x in t]
-
-
-def _sync_ref(ref_model, eng, sn):
-    ref_model.g.flat.copy_(eng.model.g.flat)
-    ref_model.d.flat.copy_(eng.model.d.flat)
-    if sn:
-        ref_model.d_sn.flat.copy_(eng.model.d_sn.flat)
-
-
-def _check_piece(eng, ref, ref_model, cfg, real, dtype, sn, full, run, tag):
-    """Run one piece of the cycle on the engine (`run`: a D sub-step, or the full step) from the
-    engine's own state and compare its losses, gradients and -- for D -- the parameters it wrote
-    with the reference on the engine's z. full: compare G's gradients too."""
-    rdev = next(iter(ref_model.d.tensors.values())).device
-    _sync_ref(ref_model, eng, sn)
-    scale = float(eng.loss_scale[0]) if dtype == "fp16" else 1.0
-    od = eng.opt_d
-    w0, m0, v0 = od.params.flat.cpu().clone(), od.m.flat.cpu().clone(), od.v.flat.cpu().clone()
-    p0 = od.powers.cpu().clone()
-    run()
-    torch.cuda.synchronize()
-    z = eng.z.to(rdev)
-    grads = (lambda: ref.compute_grads(real, z, update_ema=False)) if full else \
-        (lambda: ref.compute_d_grads(real, z) + (None,))
-    bn_keep = (ref_model.d_bn.flat.clone(), ref_model.g_bn.flat.clone())  # (compute_d_grads moves D's averages)
-    if dtype == "fp32":
-        ins = []
-        with SNT._recording(ins):  # the unmodified reference
-            out, gd, gg = grads()
-        signs = SNT._engine_signs(eng, cfg)
-        assert len(ins) == len(signs)
-        at_kink = [x.flatten()[(m.flatten() != (x.flatten() > 0))].abs() for x, m in zip(ins, signs)]
-        flips = sum(k.numel() for k in at_kink)
-        far = max([float(k.max()) for k in at_kink if k.numel()], default=0.0)
-        near = sum(int((x.abs() < SNT.KINK_MAX_INPUT).sum()) for x in ins)
-        print("%s fp32: %d activation(s) with another sign than the reference's, largest |input| %.2e; %d reference "
-              "inputs below %.0e" % (tag, flips, far, near, SNT.KINK_MAX_INPUT))
-        assert flips <= near and far < SNT.KINK_MAX_INPUT, (tag, flips, near, far)
-        if flips:  # the same piece on the engine's side of those kinks
-            with SNT._engine_masks(eng, cfg):
-                out, gd, gg = grads()
-    else:
-        out, gd, gg = grads()
-    ref_model.d_bn.flat.copy_(bn_keep[0])
-    ref_model.g_bn.flat.copy_(bn_keep[1])
-    L = eng.last_losses()
-    ltol = {"fp32": 1e-5, "bf16": 3e-2, "fp16": 2e-2}[dtype]
-    for k in ("d_loss_real", "d_loss_fake", "g_loss", "d_loss"):
-        r = float(out[k].detach())
-        assert abs(L[k] - r) <= ltol * max(1.0, abs(r)), (tag, k, L[k], r)
-    gl_last = cfg.g_layers()[-1].name
-    dead = {L_.name + "/biases" for L_ in cfg.d_layers() if L_.bn} | {L_.name + "/biases" for L_ in cfg.g_layers() if L_.bn}
-    if dtype == "fp16":
-        e_d = rel(eng.grad_d.flat / scale, gd)
-        e_g = rel(eng.grad_g.flat / scale, gg) if full else 0.0
-        print("%s fp16 relative grad error: D %.4f G %.4f" % (tag, e_d, e_g))
-        assert e_d < 0.1 and e_g < 0.15
-    else:
-        gdref = ref_model.d.like()
-        gdref.flat.copy_(gd)
-        errs = {n: rel(eng.grad_d[n], gdref[n]) for n in ref_model.d.names() if n not in dead}
-        if full:
-            ggref = ref_model.g.like()
-            ggref.flat.copy_(gg)
-            for n in ref_model.g.names():
-                if n not in dead and not (dtype == "fp32" and n == "g_h0_lin/bias"):
-                    errs[n] = rel(eng.grad_g[n], ggref[n])
-        print("%s %s max rel grad error %.3e (%s)" % (tag, dtype, max(errs.values()), max(errs, key=errs.get)))
-        if dtype == "fp32":
-            bad = {k: v for k, v in errs.items() if v > 1e-3}
-        else:
-            bad = {k: v for k, v in errs.items()
-                   if v > (0.35 if k.endswith("/biases") else 0.25) and k != gl_last + "/biases"}
-            assert sum(errs.values()) / len(errs) < 0.15
-        assert not bad, (tag, bad)
-    # D's parameters: TF-Adam(lr_d, beta1, beta2) of the engine's gradient from the pre-step state
-    b1p, b2p = float(p0[0]), float(p0[1])
-    R.tf_adam_update(w0, eng.grad_d.flat.cpu() / scale, m0, v0, b1p, b2p, od.lr, od.beta1, od.beta2, od.eps)
-    assert torch.allclose(od.params.flat.cpu(), w0, atol=1e-6, rtol=1e-5), tag
-    assert torch.allclose(od.powers.cpu(), torch.tensor([b1p * od.beta1, b2p * od.beta2]), rtol=1e-6), tag
-    if not eng.f32:  # the 16-bit mirror (with spectral norm its kernel slices hold W / sigma: checked below)
-        name = "d_h0_conv/biases"
-        got, want = (eng.wbf_d[name], eng.model.d[name]) if sn else (eng.wbf_d.flat, eng.model.d.flat)
-        assert torch.equal(got, want.to(eng.edt)), tag
-    if sn:  # one power step on the new weights from the stored u, copies rewritten
-        snr = ref_model.d_sn
-        snr.power_step_({k: v.to(rdev) for k, v in eng.model.d.tensors.items()})
-        for name, _, _ in snr.shapes:
-            for a, b in ((eng.model.d_sn.u[name], snr.u[name]), (eng.model.d_sn.v[name], snr.v[name]),
-                         (eng.model.d_sn.sigma[name], snr.sigma[name])):
-                assert rel(a, b) < 1e-5, (tag, name)
-        SNT._copies_match_state(eng)
-
-
-def _ref_for(cfg, dtype, seed, sn, **kw):
-    rdev = torch.device("cpu") if dtype == "fp32" else dev
-    ref_model = DCGAN(cfg, device=rdev, seed=seed)
-    return ref_model, ReferenceStep(ref_model, d_spectral_norm=sn, seed=seed, **kw), rdev
-
-
 @pytest.mark.parametrize("size,c_dim", [(28, 1), (64, 3)])
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
 @pytest.mark.parametrize("sn,bn", [(True, True), (True, False), (False, False), (False, True)])
@@ -383,12 +237,6 @@ def test_z_of_the_sub_steps():
 
 
 # ------------------------------------------------------------------ graph == eager, defaults, fp16 skip
-def _snap(eng):
-    torch.cuda.synchronize()
-    return _g_state(eng) + _d_state(eng) + [eng.model.d_bn.flat.cpu().clone(), eng.model.g_bn.flat.cpu().clone(),
-                                             eng.losses.cpu().clone()]
-
-
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_graph_replay_matches_eager(dtype):
     cfg = DCGANConfig(d_bn=False)
@@ -397,8 +245,7 @@ def test_graph_replay_matches_eager(dtype):
     for _ in range(4):
         e1.train_step()
         e2.train_step()
-        for x, y in zip(_snap(e1), _snap(e2)):
-            assert torch.equal(x, y)
+        HH.snap_equal(e1, e2)
     assert e2.graph_enabled and not e1.graph_enabled and e1.global_step == e2.global_step == 4
     assert [len(g) for g in e2._sub_graphs] == [1, 1]  # one captured graph per sub-step
 
@@ -418,8 +265,7 @@ def test_defaults_change_nothing():
     for _ in range(3):
         bare.train_step()
         dflt.train_step()
-        for x, y in zip(_snap(bare), _snap(dflt)):
-            assert torch.equal(x, y)
+        HH.snap_equal(bare, dflt)
     other = _engine(cfg, 16, 1, seed=1, beta2=0.9)
     other.train_step()
     other.train_step()
@@ -447,7 +293,7 @@ def test_fp16_overflow_sub_step_leaves_the_state():
     assert not any(torch.equal(x, y) for x, y in zip(d0, _d_state(eng)))
     for x, y in zip(g0, _g_state(eng)):
         assert torch.equal(x, y)
-    SNT._copies_match_state(eng)
+    _copies_match_state(eng)
 
 
 # ------------------------------------------------------------------ one-rank RCCL DDP
@@ -466,57 +312,23 @@ def _result(eng):
             "pg": eng.opt_g.powers.cpu(), "losses": eng.losses.cpu()}
 
 
-def _rccl_worker(out_dir, graph, port):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["DCGAN_FORCE_DDP"] = "1"
-    os.environ["DCGAN_DDP_SCHEDULE"] = "concurrent"
-    os.environ["DCGAN_DDP_SHARD"] = "0"
-    os.environ.pop("DCGAN_DIST_BACKEND", None)
-    torch.cuda.set_device(0)
-    from distributed_tensorflow_for_dcgan_amd.parallel import dist as D
-    import torch.distributed as tdist
-    D.init_distributed(1, 0, torch.device("cuda", 0))
-    eng = _ddp_engine(graph)
-    assert eng.ddp and eng._schedule() == "concurrent"
-    for _ in range(STEPS):
-        eng.train_step()
-    out = _result(eng)
-    out.update({"step": eng.global_step, "backend": tdist.get_backend(), "graph": eng.graph_enabled,
-                "ops": eng.sub_op_names(0), "sub_graphs": [len(g) for g in eng._sub_graphs]})
-    torch.save(out, os.path.join(out_dir, "rccl.pt"))
-    D.barrier()
-    D.shutdown()
+def _sub_ops(eng):
+    return {"ops": eng.sub_op_names(0), "sub_graphs": [len(g) for g in eng._sub_graphs]}
+
+
+DDP = HH.Ddp(_ddp_engine, _result, STEPS, extras=_sub_ops)
 
 
 @pytest.fixture(scope="module")
 def fused_run():
-    old = {k: os.environ.pop(k, None) for k in ENV}
-    try:
-        eng = _ddp_engine(True)
-        assert not eng.ddp and eng._schedule() == "fused"
-        for _ in range(STEPS):
-            eng.train_step()
-        return _result(eng)
-    finally:
-        for k, v in old.items():
-            if v is not None:
-                os.environ[k] = v
+    return HH.fused_result(DDP, ENV)
 
 
 @pytest.mark.parametrize("graph", [False, True])
 def test_rccl_single_rank_ddp_matches_fused(tmp_path, graph, fused_run):
-    ctx = mp.get_context("spawn")
-    p = ctx.Process(target=_rccl_worker, args=(str(tmp_path), graph, SNT._free_port()))
-    p.start()
-    p.join(timeout=600)
-    assert p.exitcode == 0, "RCCL rank exited with %s" % p.exitcode
-    r = torch.load(tmp_path / "rccl.pt", weights_only=True)
-    assert r["backend"] == "nccl" and r["step"] == STEPS and r["graph"] == graph
+    r = HH.rccl_run(tmp_path, DDP, "concurrent", graph, fused_run)
     assert "adam_d" in r["ops"] and "d_step_end" in r["ops"] and "adam_d1" not in r["ops"]
     assert r["sub_graphs"] == ([4] if graph else [])
-    for k, v in fused_run.items():
-        assert torch.equal(r[k], v), k
 
 
 # ------------------------------------------------------------------ checkpoint resume through the trainer
@@ -524,60 +336,11 @@ def test_trainer_resume_is_exact_with_d_steps(tmp_path, monkeypatch):
     """bf16, d_steps = 2: 4 steps in one run == 2 steps, a restart from the checkpoint, 2 more --
     every saved tensor bitwise (D's powers after 8 updates included), and no key beyond the
     default run's."""
-    import io
-    from distributed_tensorflow_for_dcgan_amd.ckpt import checkpoint as CK
-    from distributed_tensorflow_for_dcgan_amd.data import pipeline as P
-    from distributed_tensorflow_for_dcgan_amd.train import trainer as T
-    from distributed_tensorflow_for_dcgan_amd.utils import flags as F
-    made = []
-
-    def source(flags, batch, shape, device, **kw):  # two alternating batches, restarted with every run
-        class Two:
-            num_examples = 1 << 20
-
-            def __init__(self):
-                self.i = 0
-                self.x = [P.SyntheticSource(batch, shape, device, seed=s).next().to(torch.bfloat16) for s in (1, 2)]
-
-            def next(self):
-                self.i += 1
-                return self.x[self.i % 2]
-
-            def stats(self):
-                return {"source": "test"}
-
-            def close(self):
-                pass
-        made.append(Two())
-        return made[-1]
-    monkeypatch.setattr(T, "make_source", source)
-
-    def run(ck, steps, d_steps=2):
-        fl = F.parse_flags(["--synthetic", "--engine=hip", "--device=cuda", "--dtype=bf16", "--output_size=28",
-                            "--c_dim=1", "--batch_size=8", "--d_steps=%d" % d_steps, "--beta2=0.9",
-                            "--max_steps=%d" % steps, "--sample_every=0", "--nosummaries", "--save_model_secs=1e9",
-                            "--checkpoint_dir=%s" % ck, "--sample_dir=%s" % (tmp_path / "s"),
-                            "--nolog_device_placement", "--seed=5"])
-        out = io.StringIO()
-        assert T.run(fl, out=out) == 0, out.getvalue()
-        return out.getvalue()
-
-    def load(ck, d_steps=2):
-        from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
-        eng = HipEngine(DCGANConfig(output_size=28, c_dim=1), 8, dev, seed=99, graph=False, d_steps=d_steps, beta2=0.9)
-        info = CK.CheckpointManager(str(ck)).restore_latest(eng)
-        torch.cuda.synchronize()
-        return info, CK.collect_state(eng)
-    run(tmp_path / "a", 4)
-    run(tmp_path / "b", 2)
-    text = run(tmp_path / "b", 4)
-    assert "load success!" in text and "global_step 2" in text
-    assert [m.i for m in made] == [8, 4, 4]  # two real batches per training step
-    (ia, sa), (ib, sb) = load(tmp_path / "a"), load(tmp_path / "b")
-    assert ia["global_step"] == ib["global_step"] == 4 and list(sa) == list(sb)
-    for k in sa:
-        assert (sa[k] == sb[k]).all(), k
+    kw = dict(d_steps=2, beta2=0.9)
+    r = HH.trainer_resume(tmp_path, monkeypatch, ["--d_steps=2", "--beta2=0.9"], load_kw=kw)
+    assert [m.i for m in r.made] == [8, 4, 4]  # two real batches per training step
+    sa = r.a[1]
     assert float(sa["beta2_power"].reshape(-1)[0]) == pytest.approx(0.9 ** 9, rel=1e-5)
     assert float(sa["beta2_power_1"].reshape(-1)[0]) == pytest.approx(0.9 ** 5, rel=1e-5)
-    run(tmp_path / "c", 1, d_steps=1)
-    assert list(load(tmp_path / "c", 1)[1]) == list(sa)
+    r.run(tmp_path / "c", 1, ["--d_steps=1", "--beta2=0.9"])
+    assert list(r.load(tmp_path / "c", d_steps=1, beta2=0.9)[1]) == list(sa)

@@ -15,17 +15,13 @@ Two kinds of checks:
 import pytest
 import torch
 
+from hip_harness import rel
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig, same_pads
 from distributed_tensorflow_for_dcgan_amd.models.dcgan import DCGAN
 from distributed_tensorflow_for_dcgan_amd.engine.reference_step import ReferenceStep
 from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
-
-
-def rel(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
 
 
 def d64(t):

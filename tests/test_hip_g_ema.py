@@ -2,30 +2,19 @@
 (ops.reference.ema_update_), the ``ema_g`` op inside the HIP engine's step (bf16 / fp16 / fp32,
 eager and hipGraph, one-rank RCCL DDP), the EMA sampler, and that decay 0 changes nothing."""
 import os
-import socket
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
+import hip_harness as HH
+from hip_harness import H, dev, rel
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
 from distributed_tensorflow_for_dcgan_amd.models.dcgan import DCGAN
 from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
 
-dev = torch.device("cuda", 0)
 DECAY = 0.999
-
-
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
-
-
-def rel(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
 
 
 def _engine(**kw):
@@ -264,62 +253,24 @@ def test_fp32_engine_shadow_follows_the_oracle():
 STEPS = 4
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _ddp_engine(graph):
     return _engine(B=16, seed=3, graph=graph, rank_seeded_z=False, g_ema_decay=DECAY)
 
 
-def _rccl_worker(out_dir, graph, port):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["DCGAN_FORCE_DDP"] = "1"
-    os.environ["DCGAN_DDP_SCHEDULE"] = "concurrent"
-    os.environ["DCGAN_DDP_SHARD"] = "0"
-    os.environ.pop("DCGAN_DIST_BACKEND", None)
-    torch.cuda.set_device(0)
-    from distributed_tensorflow_for_dcgan_amd.parallel import dist as D
-    import torch.distributed as tdist
-    D.init_distributed(1, 0, torch.device("cuda", 0))
-    eng = _ddp_engine(graph)
-    assert eng.ddp and eng._schedule() == "concurrent"
-    for _ in range(STEPS):
-        eng.train_step()
+def _result(eng):
     torch.cuda.synchronize()
-    torch.save({"g": eng.model.g.flat.cpu(), "ema": eng.g_ema.flat.cpu(), "mirror": eng.wbf_g_ema.flat.cpu(),
-                "step": eng.global_step, "backend": tdist.get_backend(), "graph": eng.graph_enabled,
-                "ops": eng.op_names()}, os.path.join(out_dir, "rccl.pt"))
-    D.barrier()
-    D.shutdown()
+    return {"g": eng.model.g.flat.cpu(), "ema": eng.g_ema.flat.cpu(), "mirror": eng.wbf_g_ema.flat.cpu()}
+
+
+DDP = HH.Ddp(_ddp_engine, _result, STEPS)
 
 
 @pytest.fixture(scope="module")
 def fused_run():
-    eng = _ddp_engine(True)
-    assert not eng.ddp and eng._schedule() == "fused"
-    for _ in range(STEPS):
-        eng.train_step()
-    torch.cuda.synchronize()
-    return eng.model.g.flat.cpu(), eng.g_ema.flat.cpu(), eng.wbf_g_ema.flat.cpu()
+    return HH.fused_result(DDP, ())  # (this module clears no switch around its tests either)
 
 
 @pytest.mark.parametrize("graph", [False, True])
 def test_rccl_single_rank_ddp_shadow_matches_fused(tmp_path, graph, fused_run):
-    ctx = mp.get_context("spawn")
-    p = ctx.Process(target=_rccl_worker, args=(str(tmp_path), graph, _free_port()))
-    p.start()
-    p.join(timeout=600)
-    assert p.exitcode == 0, "RCCL rank exited with %s" % p.exitcode
-    r = torch.load(tmp_path / "rccl.pt", weights_only=True)
-    assert r["backend"] == "nccl" and r["step"] == STEPS and r["graph"] == graph
+    r = HH.rccl_run(tmp_path, DDP, "concurrent", graph, fused_run)
     assert r["ops"].count("ema_g") == 1 and {"adam_g_a", "adam_g_b", "adam_g_c"} <= set(r["ops"])
-    g, ema, mirror = fused_run
-    assert torch.equal(r["g"], g)
-    assert torch.equal(r["ema"], ema), (r["ema"] - ema).abs().max()
-    assert torch.equal(r["mirror"], mirror)

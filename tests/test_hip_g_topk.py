@@ -12,48 +12,27 @@ error against the fp64 oracle over all the kernel cases with a finite loss, |got
 |want|), is at most 4 x that of the fp32 oracle on the same inputs; where the fp64 loss is not finite
 (a selected +-inf or NaN) the device's is the same infinity or NaN.
 
-The step comparison is ``_check_piece`` of tests/test_hip_d_steps.py with its tolerances, unchanged; a
+The step comparison is ``check_piece`` of tests/hip_harness.py with its tolerances, unchanged; a
 sample the reference itself would have selected differently must lie within the comparison's loss
 tolerance (relative to max(1, |threshold|)) of the reference's threshold logit."""
-import io
-import os
-
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import test_hip_d_spectral_norm as SNT
-import test_hip_d_steps as TD
+import hip_harness as HH
+from hip_harness import H, dev, small
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
 from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
 
-dev = torch.device("cuda", 0)
-PAD = SNT.PAD
-_padded, _canaries_intact = SNT._padded, SNT._canaries_intact
-ENV = TD.ENV + ("DCGAN_G_TOPK", "DCGAN_G_TOPK_STEPS", "DCGAN_INSTANCE_NOISE", "DCGAN_INSTANCE_NOISE_END",
-                "DCGAN_INSTANCE_NOISE_STEPS", "DCGAN_D_AUGMENT", "DCGAN_D_COLOR_AUGMENT", "DCGAN_LR_DECAY")
+_padded, _canaries_intact = HH.padded, HH.intact
+ENV = HH.ENV + HH.env_of("topk", "noise", "aug", "color") + ("DCGAN_LR_DECAY",)
 TOPK = dict(g_topk=0.5, g_topk_steps=4)
 BS = [1, 2, 5, 256, 257, 1000]
 KINDS = ("bce", "lsgan", "hinge")
 INPUTS = ("normal", "equal", "dups", "zeros", "special", "up", "down")
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
-
-
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
-
-
-def small():
-    return DCGANConfig(output_size=28, c_dim=1)
+_clean_env = HH.clean_env(ENV)
 
 
 def _step(t):
@@ -264,8 +243,8 @@ def _check_recorded(eng, t, tag):
                                               ("fp32", 64, 3)])
 def test_engine_selection_is_the_oracles_and_d_is_untouched(dtype, size, c_dim):
     cfg = DCGANConfig(output_size=size, c_dim=c_dim)
-    eng = TD._engine(cfg, 8, 1, dtype=dtype, seed=3, **TOPK)
-    off = TD._engine(cfg, 8, 1, dtype=dtype, seed=3)
+    eng = HH.engine(cfg, 8, 1, dtype=dtype, seed=3, **TOPK)
+    off = HH.engine(cfg, 8, 1, dtype=dtype, seed=3)
     assert off.dl_g_k is None and off.topk_sel is None and off.topk_info is None and off.last_topk() is None
     assert off.topk_selection() is None
     names = eng.op_names()
@@ -305,7 +284,7 @@ def _topk_piece(eng, ref, ref_model, cfg, real, dtype, sn, tag, rdev):
     the same (pre-step) weights and z: where the two differ, the reference logit is at its threshold."""
     t = eng.global_step
     sn0 = eng.model.d_sn.flat.to(rdev, copy=True) if sn else None  # (_check_piece ends with the power step)
-    TD._check_piece(eng, _WithMask(ref, eng, rdev), ref_model, cfg, real, dtype, sn, True, eng.train_full_step, tag)
+    HH.check_piece(eng, _WithMask(ref, eng, rdev), ref_model, cfg, real, dtype, sn, True, eng.train_full_step, tag)
     _check_recorded(eng, t, tag)
     ref.global_step = t
     if sn:
@@ -339,9 +318,9 @@ def test_four_topk_steps_track_the_reference(dtype, kind, size, c_dim, seed=3):
     tests/test_hip_gan_objectives.py describes, and a skipped step has no finite gradients to compare; lsgan
     runs in fp32 and bf16 here.)"""
     cfg, B = DCGANConfig(output_size=size, c_dim=c_dim), 8
-    eng = TD._engine(cfg, B, 1, dtype=dtype, seed=seed, gan_loss=kind, **TOPK)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, False, gan_loss=kind, **TOPK)
-    real = TD._reals(B, cfg, dtype, 1)[0].to(rdev)
+    eng = HH.engine(cfg, B, 1, dtype=dtype, seed=seed, gan_loss=kind, **TOPK)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, False, gan_loss=kind, **TOPK)
+    real = HH.reals(B, cfg, dtype, 1)[0].to(rdev)
     ks = [_topk_piece(eng, ref, ref_model, cfg, real, dtype, False, "step %d" % s, rdev) for s in range(4)]
     assert ks == [8, 7, 6, 5] and eng.global_step == 4
 
@@ -350,13 +329,13 @@ def test_cycle_with_sub_steps_spectral_norm_and_hinge(seed=4):
     """d_steps = 2, spectral norm, BN-free D, hinge: the sub-step records no g_topk and leaves the top-k
     buffers untouched; the full step behind it tracks the reference."""
     cfg, B, dtype = DCGANConfig(output_size=28, c_dim=1, d_bn=False), 8, "bf16"
-    eng = TD._engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, gan_loss="hinge", **TOPK)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2, gan_loss="hinge", **TOPK)
-    reals = [x.to(rdev) for x in TD._reals(B, cfg, dtype, 2)]
+    eng = HH.engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, gan_loss="hinge", **TOPK)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2, gan_loss="hinge", **TOPK)
+    reals = [x.to(rdev) for x in HH.reals(B, cfg, dtype, 2)]
     assert "g_topk" not in eng.sub_op_names(0) and eng.op_names().count("g_topk") == 1
     for t in range(2):
         before = [b.clone() for b in (eng.dl_g_k, eng.topk_sel, eng.topk_info)]
-        TD._check_piece(eng, _WithMask(ref, eng, rdev), ref_model, cfg, reals[0], dtype, True, False,
+        HH.check_piece(eng, _WithMask(ref, eng, rdev), ref_model, cfg, reals[0], dtype, True, False,
                         lambda: eng.train_d_step(0), "step %d sub-step" % t)
         for a, b in zip(before, (eng.dl_g_k, eng.topk_sel, eng.topk_info)):
             assert torch.equal(a, b)
@@ -370,8 +349,8 @@ def test_composed_with_augmentations_and_noise():
     kw = dict(seed=5, d_augment="translation,cutout", d_color_augment="brightness,saturation,contrast",
               instance_noise=0.2, instance_noise_end=0.05, instance_noise_steps=4)
     cfg = DCGANConfig(output_size=64, c_dim=3)
-    eng = TD._engine(cfg, 8, 1, **kw, **TOPK)
-    off = TD._engine(cfg, 8, 1, **kw)
+    eng = HH.engine(cfg, 8, 1, **kw, **TOPK)
+    off = HH.engine(cfg, 8, 1, **kw)
     assert [n for n in eng.op_names() if n != "g_topk"] == off.op_names()
     for t in range(3):
         eng.train_step()
@@ -389,14 +368,13 @@ def test_composed_with_augmentations_and_noise():
 def test_graph_replay_follows_the_live_counter(dtype, d_steps):
     """A k baked in at capture time would stay at the first replay's."""
     kw = dict(dtype=dtype, seed=1, **TOPK)
-    e1 = TD._engine(small(), 8, d_steps, **kw)
-    e2 = TD._engine(small(), 8, d_steps, graph=True, **kw)
+    e1 = HH.engine(small(), 8, d_steps, **kw)
+    e2 = HH.engine(small(), 8, d_steps, graph=True, **kw)
     ks = []
     for t in range(6):
         e1.train_step()
         e2.train_step()
-        for x, y in zip(TD._snap(e1), TD._snap(e2)):
-            assert torch.equal(x, y)
+        HH.snap_equal(e1, e2)
         for a, b in ((e1.dl_g_k, e2.dl_g_k), (e1.topk_sel, e2.topk_sel), (e1.topk_info, e2.topk_info)):
             assert torch.equal(a, b)
         ks.append(_check_recorded(e2, t, "replay %d" % t))
@@ -405,10 +383,10 @@ def test_graph_replay_follows_the_live_counter(dtype, d_steps):
 
 def test_nu_one_is_the_engine_without_the_arguments():
     cfg = small()
-    a = TD._engine(cfg, 8, 2, seed=2, g_topk=1.0, g_topk_steps=1000)
+    a = HH.engine(cfg, 8, 2, seed=2, g_topk=1.0, g_topk_steps=1000)
     from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
     b = HipEngine(cfg, 8, dev, seed=2, graph=False, d_steps=2)  # built without the arguments
-    for k, x in enumerate(TD._reals(8, cfg, "bf16", 2)):
+    for k, x in enumerate(HH.reals(8, cfg, "bf16", 2)):
         b.set_batch(x.to(dev), k)
     assert not a.topk.active and a.dl_g_k is None and b.dl_g_k is None
     assert a.op_names() == b.op_names() and "g_topk" not in a.op_names() and a.kernel_count() == b.kernel_count()
@@ -416,21 +394,20 @@ def test_nu_one_is_the_engine_without_the_arguments():
     for _ in range(3):
         a.train_step()
         b.train_step()
-    for x, y in zip(TD._snap(a), TD._snap(b)):
-        assert torch.equal(x, y)
+    HH.snap_equal(a, b)
 
 
 def test_eval_losses_stay_clean():
     cfg, B = small(), 8
-    on = TD._engine(cfg, B, 1, seed=2, **TOPK)
-    off = TD._engine(cfg, B, 1, seed=7)
+    on = HH.engine(cfg, B, 1, seed=2, **TOPK)
+    off = HH.engine(cfg, B, 1, seed=7)
     on.train_step()
     on.train_step()
     torch.cuda.synchronize()
     for name in ("g", "d"):
         getattr(off.model, name).flat.copy_(getattr(on.model, name).flat)
     off.after_state_load()
-    real = TD._reals(B, cfg, "bf16", 3)[2]
+    real = HH.reals(B, cfg, "bf16", 3)[2]
     z = torch.rand(B, cfg.z_dim, generator=torch.Generator().manual_seed(11)) * 2 - 1
     before = [b.clone() for b in (on.dl_g_k, on.topk_sel, on.topk_info)]
     a, b = on.eval_losses(real, z), off.eval_losses(real, z)
@@ -454,7 +431,7 @@ STEPS = 3
 
 
 def _ddp_engine(graph):
-    return TD._engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, **TOPK)
+    return HH.engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, **TOPK)
 
 
 def _result(eng):
@@ -465,113 +442,32 @@ def _result(eng):
             "dl_g_k": eng.dl_g_k.cpu()}
 
 
-def _rccl_worker(out_dir, schedule, port):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["DCGAN_FORCE_DDP"] = "1"
-    os.environ["DCGAN_DDP_SCHEDULE"] = schedule
-    os.environ["DCGAN_DDP_SHARD"] = "0"
-    os.environ.pop("DCGAN_DIST_BACKEND", None)
-    torch.cuda.set_device(0)
-    from distributed_tensorflow_for_dcgan_amd.parallel import dist as D
-    import torch.distributed as tdist
-    D.init_distributed(1, 0, torch.device("cuda", 0))
-    eng = _ddp_engine(True)
-    assert eng.ddp and eng._schedule() == schedule and eng.topk.active
-    for _ in range(STEPS):
-        eng.train_step()
-    out = _result(eng)
-    out.update({"step": eng.global_step, "backend": tdist.get_backend(), "graph": eng.graph_enabled,
-                "ops": eng.op_names()})
-    torch.save(out, os.path.join(out_dir, "rccl.pt"))
-    D.barrier()
-    D.shutdown()
+def _active(eng):
+    return eng.topk.active
+
+
+DDP = HH.Ddp(_ddp_engine, _result, STEPS, active=_active)
 
 
 @pytest.fixture(scope="module")
 def fused_run():
-    old = {k: os.environ.pop(k, None) for k in ENV}
-    try:
-        eng = _ddp_engine(True)
-        assert not eng.ddp and eng._schedule() == "fused"
-        for _ in range(STEPS):
-            eng.train_step()
-        return _result(eng)
-    finally:
-        for k, v in old.items():
-            if v is not None:
-                os.environ[k] = v
+    return HH.fused_result(DDP, ENV)
 
 
 @pytest.mark.parametrize("schedule", ["concurrent", "ddp"])
 def test_rccl_single_rank_ddp_matches_fused_with_topk(tmp_path, schedule, fused_run):
-    ctx = mp.get_context("spawn")
-    p = ctx.Process(target=_rccl_worker, args=(str(tmp_path), schedule, SNT._free_port()))
-    p.start()
-    p.join(timeout=600)
-    assert p.exitcode == 0, "RCCL rank exited with %s" % p.exitcode
-    r = torch.load(tmp_path / "rccl.pt", weights_only=True)
-    assert r["backend"] == "nccl" and r["step"] == STEPS and r["graph"]
+    r = HH.rccl_run(tmp_path, DDP, schedule, True, fused_run)
     assert r["ops"].count("g_topk") == 1
     assert float(fused_run["topk_info"][3]) == 6.0  # k(2) of 8 -> 4 over 4 steps
-    for k, v in fused_run.items():
-        assert torch.equal(r[k], v), k
 
 
 # ------------------------------------------------------------------ 6. resume through the trainer
 def test_trainer_resume_is_exact_mid_anneal(tmp_path, monkeypatch):
     """bf16: 4 steps in one run == 2 steps, a restart from the checkpoint, 2 more, with the anneal of k
     under way at the restart -- every saved tensor bitwise, and no key beyond the run without top-k."""
-    from distributed_tensorflow_for_dcgan_amd.ckpt import checkpoint as CK
-    from distributed_tensorflow_for_dcgan_amd.data import pipeline as P
-    from distributed_tensorflow_for_dcgan_amd.train import trainer as T
-    from distributed_tensorflow_for_dcgan_amd.utils import flags as F
-
-    def source(flags, batch, shape, device, **kw):
-        class Two:
-            num_examples = 1 << 20
-
-            def __init__(self):
-                self.i = 0
-                self.x = [P.SyntheticSource(batch, shape, device, seed=s).next().to(torch.bfloat16) for s in (1, 2)]
-
-            def next(self):
-                self.i += 1
-                return self.x[self.i % 2]
-
-            def stats(self):
-                return {"source": "test"}
-
-            def close(self):
-                pass
-        return Two()
-    monkeypatch.setattr(T, "make_source", source)
     TF = ["--g_topk=0.5", "--g_topk_steps=6"]
-
-    def run(ck, steps, tf=TF):
-        fl = F.parse_flags(["--synthetic", "--engine=hip", "--device=cuda", "--dtype=bf16", "--output_size=28",
-                            "--c_dim=1", "--batch_size=8", "--max_steps=%d" % steps, "--sample_every=0", "--nosummaries",
-                            "--save_model_secs=1e9", "--checkpoint_dir=%s" % ck, "--sample_dir=%s" % (tmp_path / "s"),
-                            "--nolog_device_placement", "--seed=5"] + tf)
-        out = io.StringIO()
-        assert T.run(fl, out=out) == 0, out.getvalue()
-        return out.getvalue()
-
-    def load(ck):
-        from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
-        eng = HipEngine(small(), 8, dev, seed=99, graph=False)
-        info = CK.CheckpointManager(str(ck)).restore_latest(eng)
-        torch.cuda.synchronize()
-        return info, CK.collect_state(eng)
-    text = run(tmp_path / "a", 4)
-    assert "top-k generator updates: k from B to ceil(0.5 B) over 6 steps" in text
-    run(tmp_path / "b", 2)
-    text = run(tmp_path / "b", 4)
-    assert "load success!" in text and "global_step 2" in text
-    (ia, sa), (ib, sb) = load(tmp_path / "a"), load(tmp_path / "b")
-    assert ia["global_step"] == ib["global_step"] == 4 and list(sa) == list(sb)
-    for k in sa:
-        assert (sa[k] == sb[k]).all(), k
-    run(tmp_path / "c", 4, tf=[])  # without top-k: another model, under the same keys
-    ic, sc = load(tmp_path / "c")
+    r = HH.trainer_resume(tmp_path, monkeypatch, TF, log_line="top-k generator updates: k from B to ceil(0.5 B) over 6 steps")
+    sa = r.a[1]
+    r.run(tmp_path / "c", 4, [])  # without top-k: another model, under the same keys
+    ic, sc, _ = r.load(tmp_path / "c")
     assert list(sc) == list(sa) and any(not (sa[k] == sc[k]).all() for k in sa)

@@ -2,13 +2,13 @@
 the stand-alone loss kernel against the fp32 oracle, the head GEMV's fused loss block against head
 + stand-alone loss, the default instance against today's calls, and whole steps of the fp32 /
 bf16 / fp16 engines (eager, hipGraph, eval_losses, one-rank RCCL DDP)."""
-import os
-import socket
+import functools
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
+import hip_harness as HH
+from hip_harness import H, bf, dev, rel, rnd
 from distributed_tensorflow_for_dcgan_amd.engine.reference_step import ReferenceStep
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
 from distributed_tensorflow_for_dcgan_amd.models.dcgan import DCGAN
@@ -16,46 +16,15 @@ from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
 
-dev = torch.device("cuda", 0)
 LOSS_SCALE = 32768.0  # HipEngine.INIT_LOSS_SCALE, the scale of the fp16 engine tests
 KINDS = [("bce", 0.0), ("bce", 0.1), ("lsgan", 0.0), ("lsgan", 0.1), ("hinge", 0.0)]
 NON_DEFAULT = [("hinge", 0.0), ("lsgan", 0.1)]
-
-
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
+_p = HH.ptr
+close = functools.partial(HH.close, show=True)  # (this module prints every comparison)
 
 
 def _prog(dt=0):
-    return H().ext().Program(dt)
-
-
-def _p(t):
-    return 0 if t is None else t.data_ptr()
-
-
-def bf(t):
-    return t.to(torch.bfloat16).contiguous()
-
-
-def close(out, ref, rel=1.5e-2, name=""):  # (tests/test_hip_kernels.py)
-    out = out.float()
-    ref = ref.float()
-    scale = ref.abs().max().item() + 1e-6
-    err = (out - ref).abs().max().item()
-    print("%s: max err %.3e vs scale %.3e" % (name, err, scale))
-    assert err <= rel * scale, "%s: max err %.3e vs scale %.3e" % (name, err, scale)
-
-
-def rel(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
-
-
-def rnd(*shape, scale=1.0, seed=0):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return (torch.rand(*shape, generator=g) * 2 - 1).mul(scale).to(dev)
+    return HH.prog(dt)
 
 
 def oracle(logits, kind, s):
@@ -419,60 +388,29 @@ def test_eval_losses_with_hinge():
 STEPS = 3
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _ddp_engine():
+def _ddp_engine(graph):
     cfg, B = DCGANConfig(), 16
-    eng = _engine(cfg, B, seed=3, graph=False, rank_seeded_z=False, gan_loss="lsgan", label_smooth=0.1)
+    eng = _engine(cfg, B, seed=3, graph=graph, rank_seeded_z=False, gan_loss="lsgan", label_smooth=0.1)
     eng.set_batch(_real(B, cfg))
     return eng
 
 
-def _rccl_worker(out_dir, port):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["DCGAN_FORCE_DDP"] = "1"
-    os.environ["DCGAN_DDP_SCHEDULE"] = "concurrent"
-    os.environ["DCGAN_DDP_SHARD"] = "0"
-    os.environ.pop("DCGAN_DIST_BACKEND", None)
-    torch.cuda.set_device(0)
-    from distributed_tensorflow_for_dcgan_amd.parallel import dist as D
-    import torch.distributed as tdist
-    D.init_distributed(1, 0, torch.device("cuda", 0))
-    eng = _ddp_engine()
-    assert eng.ddp and eng._schedule() == "concurrent"
-    for _ in range(STEPS):
-        eng.train_step()
+def _result(eng):
     torch.cuda.synchronize()
-    torch.save({"g": eng.model.g.flat.cpu(), "d": eng.model.d.flat.cpu(), "losses": eng.losses.cpu(),
-                "step": eng.global_step, "backend": tdist.get_backend(), "kind": eng.gan_loss,
-                "s": eng.label_smooth}, os.path.join(out_dir, "rccl.pt"))
-    D.barrier()
-    D.shutdown()
+    return {"g": eng.model.g.flat.cpu(), "d": eng.model.d.flat.cpu(), "losses": eng.losses.cpu()}
+
+
+def _objective(eng):
+    return {"kind": eng.gan_loss, "s": eng.label_smooth}
+
+
+DDP = HH.Ddp(_ddp_engine, _result, STEPS, extras=_objective)
 
 
 def test_rccl_single_rank_ddp_lsgan_matches_fused(tmp_path):
-    eng = _ddp_engine()
-    assert not eng.ddp and eng._schedule() == "fused"
-    for _ in range(STEPS):
-        eng.train_step()
-    torch.cuda.synchronize()
-    ctx = mp.get_context("spawn")
-    p = ctx.Process(target=_rccl_worker, args=(str(tmp_path), _free_port()))
-    p.start()
-    p.join(timeout=600)
-    assert p.exitcode == 0, "RCCL rank exited with %s" % p.exitcode
-    r = torch.load(tmp_path / "rccl.pt", weights_only=True)
-    assert r["backend"] == "nccl" and r["step"] == STEPS and (r["kind"], r["s"]) == ("lsgan", 0.1)
-    assert torch.equal(r["g"], eng.model.g.flat.cpu())
-    assert torch.equal(r["d"], eng.model.d.flat.cpu())
-    assert torch.equal(r["losses"], eng.losses.cpu())
+    eng = HH.fused_engine(DDP, (), graph=False)
+    r = HH.rccl_run(tmp_path, DDP, "concurrent", False, _result(eng))
+    assert (r["kind"], r["s"]) == ("lsgan", 0.1)
     # ... and it is the least-squares objective that trained: the losses are the oracle's on the last logits
     losses, _, _ = oracle(eng.logits, "lsgan", 0.1)
     close(eng.losses, losses, 1e-5, "fused losses")

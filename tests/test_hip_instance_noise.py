@@ -1,7 +1,7 @@
 """GPU tests of the instance noise on D's inputs: the normals and sigma probes against the fp64 oracle,
 the noise kernel (bf16 / fp16 / fp32 builds) against x + sigma * eps in fp64, the engine's noisy
 buffer against the oracle (full step and D sub-steps), steps against ``ReferenceStep`` with the
-oracle's noise passed in (the comparison and tolerances of test_hip_d_steps.py, unchanged), hipGraph
+oracle's noise passed in (``check_piece`` of hip_harness.py, its comparison and tolerances unchanged), hipGraph
 replay, the end of the anneal, an inactive 0 -> 0 anneal, clean sample-time losses, one-rank RCCL DDP
 and resume through the trainer.
 
@@ -15,46 +15,25 @@ normals' own bound, scaled.
 Shapes: n in {5, 8, 1027, 12544}: less than one 16-byte access, exactly one, body + scalar tail over
 several blocks, D's stacked 28x28x1 input at B = 8; plus a view one element off 16-byte alignment
 (the all-scalar path). Engines at 28x28x1 and 64x64x3, B = 8."""
-import io
 import math
-import os
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import test_hip_d_spectral_norm as SNT
-import test_hip_d_steps as TD
+import hip_harness as HH
+from hip_harness import BUILDS, H, PAD, dev, small
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
 from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
 
-dev = torch.device("cuda", 0)
-BUILDS = SNT.BUILDS
-PAD = SNT.PAD
-_padded, _canaries_intact = SNT._padded, SNT._canaries_intact
-ENV = TD.ENV + ("DCGAN_INSTANCE_NOISE", "DCGAN_INSTANCE_NOISE_END", "DCGAN_INSTANCE_NOISE_STEPS", "DCGAN_LR_DECAY",
-                "DCGAN_LR_DECAY_START", "DCGAN_LR_DECAY_STEPS", "DCGAN_LR_END", "DCGAN_LR_WARMUP")
+_padded, _canaries_intact = HH.padded, HH.intact
+ENV = HH.ENV + HH.env_of("noise", "lr_sched")
 SIZES = [5, 8, 1027, 2 * 8 * 28 * 28]
 SEEDS = [1000020, 0xFEDCBA9876543210]
 STEPS_T = [0, 1, (1 << 32) + 3]
 NOISE = dict(instance_noise=0.2, instance_noise_end=0.05, instance_noise_steps=4)
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
-
-
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
-
-
-def small():
-    return DCGANConfig(output_size=28, c_dim=1)
+_clean_env = HH.clean_env(ENV)
 
 
 def _step(t):
@@ -277,8 +256,8 @@ def _check_noisy(eng, d_in, seed, t, dtype, oracle_err, tag):
                                               ("fp32", 64, 3)])
 def test_engine_noisy_buffer_is_the_oracles_and_z_is_untouched(dtype, size, c_dim, oracle_err):
     cfg = DCGANConfig(output_size=size, c_dim=c_dim)
-    eng = TD._engine(cfg, 8, 1, dtype=dtype, seed=3, **NOISE)
-    off = TD._engine(cfg, 8, 1, dtype=dtype, seed=3)
+    eng = HH.engine(cfg, 8, 1, dtype=dtype, seed=3, **NOISE)
+    off = HH.engine(cfg, 8, 1, dtype=dtype, seed=3)
     assert eng.d_noisy is not None and eng.d_noisy.shape == eng.d_in.shape and eng.d_noisy.dtype == eng.d_in.dtype
     assert off.d_noisy is None and off.noise_sigma() == 0.0
     assert [n for n in eng.op_names() if n != "d_noise"] == off.op_names() and eng.op_names().count("d_noise") == 1
@@ -296,7 +275,7 @@ def test_engine_noisy_buffer_is_the_oracles_and_z_is_untouched(dtype, size, c_di
 
 
 def test_sub_steps_draw_their_own_noise(oracle_err):
-    eng = TD._engine(small(), 8, 3, seed=6, **NOISE)
+    eng = HH.engine(small(), 8, 3, seed=6, **NOISE)
     assert eng.op_names().count("d_noise") == 3 and all(eng.sub_op_names(k).count("d_noise") == 1 for k in range(2))
     seen = []
     for t in range(2):
@@ -330,16 +309,16 @@ class _WithNoise:
 def _noisy_piece(eng, ref, ref_model, cfg, real, dtype, sn, k, run, tag, rdev):
     ref.noise = R.instance_noise(tuple(eng.d_in.shape), eng.noise, eng._zseed(k), eng.global_step).to(rdev)
     assert float(ref.noise.abs().max()) > 0
-    TD._check_piece(eng, ref, ref_model, cfg, real, dtype, sn, k is None, run, tag)
+    HH.check_piece(eng, ref, ref_model, cfg, real, dtype, sn, k is None, run, tag)
 
 
 @pytest.mark.parametrize("dtype,size,c_dim", [("fp32", 28, 1), ("bf16", 28, 1), ("fp16", 28, 1), ("bf16", 64, 3)])
 def test_four_noisy_steps_track_the_reference(dtype, size, c_dim, seed=3):
     cfg, B = DCGANConfig(output_size=size, c_dim=c_dim), 8
-    eng = TD._engine(cfg, B, 1, dtype=dtype, seed=seed, **NOISE)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, False)
+    eng = HH.engine(cfg, B, 1, dtype=dtype, seed=seed, **NOISE)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, False)
     ref = _WithNoise(ref)
-    real = TD._reals(B, cfg, dtype, 1)[0].to(rdev)
+    real = HH.reals(B, cfg, dtype, 1)[0].to(rdev)
     for s in range(4):
         _noisy_piece(eng, ref, ref_model, cfg, real, dtype, False, None, eng.train_full_step, "step %d" % s, rdev)
     assert eng.global_step == 4 and eng.noise_sigma() == float(torch.tensor(0.05))
@@ -347,10 +326,10 @@ def test_four_noisy_steps_track_the_reference(dtype, size, c_dim, seed=3):
 
 def test_noisy_cycle_with_sub_steps_and_spectral_norm_tracks_the_reference(seed=4):
     cfg, B, dtype = DCGANConfig(output_size=28, c_dim=1, d_bn=False), 8, "bf16"
-    eng = TD._engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, **NOISE)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2)
+    eng = HH.engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, **NOISE)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2)
     ref = _WithNoise(ref)
-    reals = [x.to(rdev) for x in TD._reals(B, cfg, dtype, 2)]
+    reals = [x.to(rdev) for x in HH.reals(B, cfg, dtype, 2)]
     _noisy_piece(eng, ref, ref_model, cfg, reals[0], dtype, True, 0, lambda: eng.train_d_step(0), "sub-step", rdev)
     _noisy_piece(eng, ref, ref_model, cfg, reals[1], dtype, True, None, eng.train_full_step, "full", rdev)
     assert eng.global_step == 1
@@ -361,14 +340,13 @@ def test_noisy_cycle_with_sub_steps_and_spectral_norm_tracks_the_reference(seed=
 def test_graph_replay_follows_the_live_counter(dtype, d_steps):
     """A step baked in at capture time would repeat the first replay's noise."""
     kw = dict(dtype=dtype, seed=1, **NOISE)
-    e1 = TD._engine(small(), 8, d_steps, **kw)
-    e2 = TD._engine(small(), 8, d_steps, graph=True, **kw)
+    e1 = HH.engine(small(), 8, d_steps, **kw)
+    e2 = HH.engine(small(), 8, d_steps, graph=True, **kw)
     prev = None
     for _ in range(4):
         e1.train_step()
         e2.train_step()
-        for x, y in zip(TD._snap(e1), TD._snap(e2)):
-            assert torch.equal(x, y)
+        HH.snap_equal(e1, e2)
         assert torch.equal(e1.d_noisy, e2.d_noisy)
         eps = (e2.d_noisy.float() - e2.d_in.float()).cpu()
         assert prev is None or not torch.equal(eps[:8], prev[:8])  # (the real half: the same clean batch every step)
@@ -378,7 +356,7 @@ def test_graph_replay_follows_the_live_counter(dtype, d_steps):
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp32"])
 def test_after_the_anneal_ends_at_zero_the_input_is_clean(dtype):
-    eng = TD._engine(small(), 8, 1, dtype=dtype, seed=2, instance_noise=0.2, instance_noise_end=0.0,
+    eng = HH.engine(small(), 8, 1, dtype=dtype, seed=2, instance_noise=0.2, instance_noise_end=0.0,
                      instance_noise_steps=2)
     for t in range(4):
         eng.train_step()
@@ -390,10 +368,10 @@ def test_after_the_anneal_ends_at_zero_the_input_is_clean(dtype):
 
 def test_an_anneal_from_zero_to_zero_is_inactive():
     cfg = small()
-    a = TD._engine(cfg, 8, 2, seed=2, instance_noise=0.0, instance_noise_end=0.0, instance_noise_steps=1000)
+    a = HH.engine(cfg, 8, 2, seed=2, instance_noise=0.0, instance_noise_end=0.0, instance_noise_steps=1000)
     from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
     b = HipEngine(cfg, 8, dev, seed=2, graph=False, d_steps=2)  # built without the arguments
-    for k, x in enumerate(TD._reals(8, cfg, "bf16", 2)):
+    for k, x in enumerate(HH.reals(8, cfg, "bf16", 2)):
         b.set_batch(x.to(dev), k)
     assert not a.noise.active and a.d_noisy is None and b.d_noisy is None
     assert a.op_names() == b.op_names() and "d_noise" not in a.op_names() and a.kernel_count() == b.kernel_count()
@@ -401,20 +379,19 @@ def test_an_anneal_from_zero_to_zero_is_inactive():
     for _ in range(3):
         a.train_step()
         b.train_step()
-    for x, y in zip(TD._snap(a), TD._snap(b)):
-        assert torch.equal(x, y)
+    HH.snap_equal(a, b)
 
 
 def test_eval_losses_stay_clean():
     cfg, B = small(), 8
-    on = TD._engine(cfg, B, 1, seed=2, instance_noise=0.5, instance_noise_end=0.5)
-    off = TD._engine(cfg, B, 1, seed=7)
+    on = HH.engine(cfg, B, 1, seed=2, instance_noise=0.5, instance_noise_end=0.5)
+    off = HH.engine(cfg, B, 1, seed=7)
     on.train_step()
     torch.cuda.synchronize()
     for name in ("g", "d"):
         getattr(off.model, name).flat.copy_(getattr(on.model, name).flat)
     off.after_state_load()
-    real = TD._reals(B, cfg, "bf16", 3)[2]
+    real = HH.reals(B, cfg, "bf16", 3)[2]
     z = torch.rand(B, cfg.z_dim, generator=torch.Generator().manual_seed(11)) * 2 - 1
     noisy_before = on.d_noisy.clone()
     a, b = on.eval_losses(real, z), off.eval_losses(real, z)
@@ -429,7 +406,7 @@ STEPS = 3
 
 
 def _ddp_engine(graph):
-    return TD._engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, **NOISE)
+    return HH.engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, **NOISE)
 
 
 def _result(eng):
@@ -439,112 +416,31 @@ def _result(eng):
             "losses": eng.losses.cpu(), "noisy": eng.d_noisy.cpu()}
 
 
-def _rccl_worker(out_dir, schedule, port):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["DCGAN_FORCE_DDP"] = "1"
-    os.environ["DCGAN_DDP_SCHEDULE"] = schedule
-    os.environ["DCGAN_DDP_SHARD"] = "0"
-    os.environ.pop("DCGAN_DIST_BACKEND", None)
-    torch.cuda.set_device(0)
-    from distributed_tensorflow_for_dcgan_amd.parallel import dist as D
-    import torch.distributed as tdist
-    D.init_distributed(1, 0, torch.device("cuda", 0))
-    eng = _ddp_engine(True)
-    assert eng.ddp and eng._schedule() == schedule and eng.noise.active
-    for _ in range(STEPS):
-        eng.train_step()
-    out = _result(eng)
-    out.update({"step": eng.global_step, "backend": tdist.get_backend(), "graph": eng.graph_enabled,
-                "ops": eng.op_names()})
-    torch.save(out, os.path.join(out_dir, "rccl.pt"))
-    D.barrier()
-    D.shutdown()
+def _active(eng):
+    return eng.noise.active
+
+
+DDP = HH.Ddp(_ddp_engine, _result, STEPS, active=_active)
 
 
 @pytest.fixture(scope="module")
 def fused_run():
-    old = {k: os.environ.pop(k, None) for k in ENV}
-    try:
-        eng = _ddp_engine(True)
-        assert not eng.ddp and eng._schedule() == "fused"
-        for _ in range(STEPS):
-            eng.train_step()
-        return _result(eng)
-    finally:
-        for k, v in old.items():
-            if v is not None:
-                os.environ[k] = v
+    return HH.fused_result(DDP, ENV)
 
 
 @pytest.mark.parametrize("schedule", ["concurrent", "ddp"])
 def test_rccl_single_rank_ddp_matches_fused_with_noise(tmp_path, schedule, fused_run):
-    ctx = mp.get_context("spawn")
-    p = ctx.Process(target=_rccl_worker, args=(str(tmp_path), schedule, SNT._free_port()))
-    p.start()
-    p.join(timeout=600)
-    assert p.exitcode == 0, "RCCL rank exited with %s" % p.exitcode
-    r = torch.load(tmp_path / "rccl.pt", weights_only=True)
-    assert r["backend"] == "nccl" and r["step"] == STEPS and r["graph"]
+    r = HH.rccl_run(tmp_path, DDP, schedule, True, fused_run)
     assert r["ops"].count("d_noise") == 1
-    for k, v in fused_run.items():
-        assert torch.equal(r[k], v), k
 
 
 # ------------------------------------------------------------------ 7. resume through the trainer
 def test_trainer_resume_is_exact_mid_anneal(tmp_path, monkeypatch):
     """bf16: 4 steps in one run == 2 steps, a restart from the checkpoint, 2 more, with the anneal under
     way at the restart -- every saved tensor bitwise, and no key beyond the noise-free run's."""
-    from distributed_tensorflow_for_dcgan_amd.ckpt import checkpoint as CK
-    from distributed_tensorflow_for_dcgan_amd.data import pipeline as P
-    from distributed_tensorflow_for_dcgan_amd.train import trainer as T
-    from distributed_tensorflow_for_dcgan_amd.utils import flags as F
-
-    def source(flags, batch, shape, device, **kw):
-        class Two:
-            num_examples = 1 << 20
-
-            def __init__(self):
-                self.i = 0
-                self.x = [P.SyntheticSource(batch, shape, device, seed=s).next().to(torch.bfloat16) for s in (1, 2)]
-
-            def next(self):
-                self.i += 1
-                return self.x[self.i % 2]
-
-            def stats(self):
-                return {"source": "test"}
-
-            def close(self):
-                pass
-        return Two()
-    monkeypatch.setattr(T, "make_source", source)
     NF = ["--instance_noise=0.3", "--instance_noise_end=0.1", "--instance_noise_steps=6"]
-
-    def run(ck, steps, nf=NF):
-        fl = F.parse_flags(["--synthetic", "--engine=hip", "--device=cuda", "--dtype=bf16", "--output_size=28",
-                            "--c_dim=1", "--batch_size=8", "--max_steps=%d" % steps, "--sample_every=0", "--nosummaries",
-                            "--save_model_secs=1e9", "--checkpoint_dir=%s" % ck, "--sample_dir=%s" % (tmp_path / "s"),
-                            "--nolog_device_placement", "--seed=5"] + nf)
-        out = io.StringIO()
-        assert T.run(fl, out=out) == 0, out.getvalue()
-        return out.getvalue()
-
-    def load(ck):
-        from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
-        eng = HipEngine(small(), 8, dev, seed=99, graph=False)
-        info = CK.CheckpointManager(str(ck)).restore_latest(eng)
-        torch.cuda.synchronize()
-        return info, CK.collect_state(eng)
-    text = run(tmp_path / "a", 4)
-    assert "instance noise on D's inputs: sigma 0.3 to 0.1 over 6 steps" in text
-    run(tmp_path / "b", 2)
-    text = run(tmp_path / "b", 4)
-    assert "load success!" in text and "global_step 2" in text
-    (ia, sa), (ib, sb) = load(tmp_path / "a"), load(tmp_path / "b")
-    assert ia["global_step"] == ib["global_step"] == 4 and list(sa) == list(sb)
-    for k in sa:
-        assert (sa[k] == sb[k]).all(), k
-    run(tmp_path / "c", 4, nf=[])  # without the noise: another model, under the same keys
-    ic, sc = load(tmp_path / "c")
+    r = HH.trainer_resume(tmp_path, monkeypatch, NF, log_line="instance noise on D's inputs: sigma 0.3 to 0.1 over 6 steps")
+    sa = r.a[1]
+    r.run(tmp_path / "c", 4, [])  # without the noise: another model, under the same keys
+    ic, sc, _ = r.load(tmp_path / "c")
     assert list(sc) == list(sa) and any(not (sa[k] == sc[k]).all() for k in sa)

@@ -9,34 +9,11 @@ import math
 import pytest
 import torch
 
+from hip_harness import H, bf, close, dev, rnd
+from hip_harness import prog as _prog, ptr as _p
 from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
-
-dev = "cuda"
-
-
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
-
-
-def bf(t):
-    return t.to(torch.bfloat16).contiguous()
-
-
-def close(out, ref, rel=1.5e-2, name=""):
-    out = out.float()
-    ref = ref.float()
-    scale = ref.abs().max().item() + 1e-6
-    err = (out - ref).abs().max().item()
-    assert err <= rel * scale, "%s: max err %.3e vs scale %.3e" % (name, err, scale)
-
-
-def rnd(*shape, scale=1.0, seed=0):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return (torch.rand(*shape, generator=g) * 2 - 1).mul(scale).to(dev)
-
 
 @pytest.mark.parametrize("B,Hs,Ci,Co", [(4, 16, 64, 128), (2, 8, 128, 256), (3, 7, 64, 64), (2, 32, 64, 128)])
 def test_conv2d_same_fwd(B, Hs, Ci, Co):
@@ -462,14 +439,6 @@ def test_wgrad_plain_im2col():
     close(out[:75].reshape(5, 5, C, Co), gw, 2e-3, "plain wgrad")
 
 
-def _prog():
-    return H().ext().Program()
-
-
-def _p(t):
-    return 0 if t is None else t.data_ptr()
-
-
 def test_bn_forward_backward_groups():
     """colstats -> finalize (+EMA) -> apply(act) and the backward chain vs autograd (2 groups)."""
     h = H()
@@ -548,7 +517,7 @@ def test_adam2_equals_two_adams_plus_step_end(nA, nD, build):
     """Three updates of the one-launch adam2 against adam_bf(A) + adam_bf(D) + step_end on the same
     inputs, bitwise: weights, mirrors, slots, both beta-power pairs and the step counter. The last
     size gives set A's (at most 512) blocks a third grid-stride pass with one vector in it."""
-    from test_hip_d_spectral_norm import PAD, _canaries_intact, _padded
+    from hip_harness import PAD, intact as _canaries_intact, padded as _padded
     h = H()
     edt, dt = (torch.float16, 1) if build == "fp16" else (torch.bfloat16, 0)
     gen = torch.Generator().manual_seed(50)

@@ -1,46 +1,26 @@
 """GPU tests of the learning-rate schedule the Adam kernels evaluate from the device step counter:
 the factor probe against the fp64 closed form, scheduled Adam == plain Adam at lr * f (bitwise, every
 Adam kernel), the zero step, a decay that has not started, the engine against ``ReferenceStep``
-(the comparison and tolerances of test_hip_d_steps.py), hipGraph replay, one-rank RCCL DDP, resume
+(``check_piece`` of hip_harness.py, its comparison and tolerances), hipGraph replay, one-rank RCCL DDP, resume
 through the trainer and the bindings' argument checks.
 
 Shapes: adam_ n = 4100 (float4 body + scalar tail, 5 blocks), adam1 / adam2 n = 2052 and 1028
 (% 4 == 0, more than one block), canaries around every buffer; engines at 28x28x1, batch 8."""
-import io
-import os
-
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-import test_hip_d_spectral_norm as SNT
-import test_hip_d_steps as TD
+import hip_harness as HH
+from hip_harness import BUILDS, H, PAD, dev, small
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
 from distributed_tensorflow_for_dcgan_amd.ops import reference as R
 
 pytestmark = pytest.mark.gpu
 
-dev = torch.device("cuda", 0)
-BUILDS = SNT.BUILDS
-_padded, _canaries_intact = SNT._padded, SNT._canaries_intact
-ENV = TD.ENV + ("DCGAN_LR_DECAY", "DCGAN_LR_DECAY_START", "DCGAN_LR_DECAY_STEPS", "DCGAN_LR_END", "DCGAN_LR_WARMUP")
+_padded, _canaries_intact = HH.padded, HH.intact
+ENV = HH.ENV + HH.env_of("lr_sched")
 KINDS = ("linear", "cosine", "exponential")
 F32 = torch.float32
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
-
-
-def H():
-    from distributed_tensorflow_for_dcgan_amd.ops import hip
-    return hip
-
-
-def small():
-    return DCGANConfig(output_size=28, c_dim=1)
+_clean_env = HH.clean_env(ENV)
 
 
 # ------------------------------------------------------------------ 1. the factor probe
@@ -195,7 +175,7 @@ def test_scheduled_adam2_is_adam2_at_lr_times_f(case):
     _same(bA, vA, ("w", "wbf", "m", "v", "p"), case)
     _same(bD, vD, ("w", "wbf", "m", "v", "p"), case)
     for side in ("sched", "plain"):
-        assert int(steps[side][1]) == t + 1 and bool((steps[side][0][:SNT.PAD] == 0).all())
+        assert int(steps[side][1]) == t + 1 and bool((steps[side][0][:PAD] == 0).all())
     assert float(vA["sched", "p"][0]) == pytest.approx(B1 ** 4, rel=1e-6)
     assert float(vD["sched", "p"][1]) == pytest.approx(B2 ** 3 * 0.99, rel=1e-6)
 
@@ -240,7 +220,7 @@ def _slots(eng):
 def test_the_zero_step_moves_no_weight(dtype):
     """linear, start 0, steps 2, end 0: factors 1, 0.5, 0 -- the third step leaves every parameter
     and 16-bit mirror of G and D bitwise alone while m, v, the beta powers and the step advance."""
-    eng = TD._engine(small(), 8, 1, dtype=dtype, seed=2, lr_decay="linear", lr_decay_start=0, lr_decay_steps=2,
+    eng = HH.engine(small(), 8, 1, dtype=dtype, seed=2, lr_decay="linear", lr_decay_start=0, lr_decay_steps=2,
                      lr_end=0.0)
     assert eng.lr_sched == R.LrSchedule("linear", 0, 2, 0.0, 0)
     for _ in range(2):
@@ -258,16 +238,15 @@ def test_the_zero_step_moves_no_weight(dtype):
 
 
 def test_before_the_decay_starts_nothing_changes():
-    a = TD._engine(small(), 8, 1, seed=2, lr_decay="cosine", lr_decay_start=1000, lr_decay_steps=50)
+    a = HH.engine(small(), 8, 1, seed=2, lr_decay="cosine", lr_decay_start=1000, lr_decay_steps=50)
     from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
     b = HipEngine(small(), 8, dev, seed=2, graph=False)  # built without the arguments
-    b.set_batch(TD._reals(8, small(), "bf16", 1)[0].to(dev))
+    b.set_batch(HH.reals(8, small(), "bf16", 1)[0].to(dev))
     assert a.lr_sched.active and not b.lr_sched.active and a.op_names() == b.op_names()
     for _ in range(3):
         a.train_step()
         b.train_step()
-    for x, y in zip(TD._snap(a), TD._snap(b)):
-        assert torch.equal(x, y)
+    HH.snap_equal(a, b)
 
 
 # ------------------------------------------------------------------ 5. the engine against ReferenceStep
@@ -275,7 +254,7 @@ LRKW = dict(lr_decay_start=0, lr_decay_steps=4, lr_end=0.1, lr_warmup=2)
 
 
 def _scheduled_piece(eng, ref, ref_model, cfg, real, dtype, sn, full, run, tag):
-    """test_hip_d_steps._check_piece with its Adam oracle at lr * f, f = ReferenceStep's factor at
+    """hip_harness.check_piece with its Adam oracle at lr * f, f = ReferenceStep's factor at
     the engine's global step; for a full step G's parameters get the same check as D's."""
     ref.global_step = eng.global_step
     f = ref.lr_factor()
@@ -285,7 +264,7 @@ def _scheduled_piece(eng, ref, ref_model, cfg, real, dtype, sn, full, run, tag):
     keep = (od.lr, og.lr)
     od.lr, og.lr = keep[0] * f, keep[1] * f  # (the recorded launches hold their own copy of lr)
     try:
-        TD._check_piece(eng, ref, ref_model, cfg, real, dtype, sn, full, run, tag)
+        HH.check_piece(eng, ref, ref_model, cfg, real, dtype, sn, full, run, tag)
         if full:
             scale = float(eng.loss_scale[0]) if dtype == "fp16" else 1.0
             w0, m0, v0, p0 = g0
@@ -301,9 +280,9 @@ def _scheduled_piece(eng, ref, ref_model, cfg, real, dtype, sn, full, run, tag):
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
 def test_four_scheduled_steps_track_the_reference(dtype, kind, seed=3):
     cfg, B = small(), 8
-    eng = TD._engine(cfg, B, 1, dtype=dtype, seed=seed, lr_decay=kind, **LRKW)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, False, lr_decay=kind, **LRKW)
-    real = TD._reals(B, cfg, dtype, 1)[0].to(rdev)
+    eng = HH.engine(cfg, B, 1, dtype=dtype, seed=seed, lr_decay=kind, **LRKW)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, False, lr_decay=kind, **LRKW)
+    real = HH.reals(B, cfg, dtype, 1)[0].to(rdev)
     fs = [_scheduled_piece(eng, ref, ref_model, cfg, real, dtype, False, True, eng.train_full_step,
                            "%s step %d" % (kind, s)) for s in range(4)]
     assert fs[0] == 0.5 and fs[1] < 1.0 and fs[3] < fs[2] < fs[1] and eng.global_step == 4
@@ -311,9 +290,9 @@ def test_four_scheduled_steps_track_the_reference(dtype, kind, seed=3):
 
 def test_scheduled_cycle_with_sub_steps_and_spectral_norm_tracks_the_reference(seed=4):
     cfg, B, dtype = DCGANConfig(output_size=28, c_dim=1, d_bn=False), 8, "bf16"
-    eng = TD._engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, lr_decay="linear", **LRKW)
-    ref_model, ref, rdev = TD._ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2, lr_decay="linear", **LRKW)
-    reals = [x.to(rdev) for x in TD._reals(B, cfg, dtype, 2)]
+    eng = HH.engine(cfg, B, 2, dtype=dtype, seed=seed, d_spectral_norm=True, beta2=0.9, lr_decay="linear", **LRKW)
+    ref_model, ref, rdev = HH.ref_for(cfg, dtype, seed, True, beta2=0.9, d_steps=2, lr_decay="linear", **LRKW)
+    reals = [x.to(rdev) for x in HH.reals(B, cfg, dtype, 2)]
     for s in range(4):
         fa = _scheduled_piece(eng, ref, ref_model, cfg, reals[0], dtype, True, False, lambda: eng.train_d_step(0),
                               "step %d sub-step" % s)
@@ -328,13 +307,12 @@ def test_scheduled_cycle_with_sub_steps_and_spectral_norm_tracks_the_reference(s
 def test_graph_replay_follows_the_live_counter(dtype, d_steps):
     """A factor baked in at capture time would repeat the first replayed step's rate."""
     kw = dict(dtype=dtype, seed=1, lr_decay="linear", **LRKW)
-    e1 = TD._engine(small(), 8, d_steps, **kw)
-    e2 = TD._engine(small(), 8, d_steps, graph=True, **kw)
+    e1 = HH.engine(small(), 8, d_steps, **kw)
+    e2 = HH.engine(small(), 8, d_steps, graph=True, **kw)
     for _ in range(4):
         e1.train_step()
         e2.train_step()
-        for x, y in zip(TD._snap(e1), TD._snap(e2)):
-            assert torch.equal(x, y)
+        HH.snap_equal(e1, e2)
     assert e2.graph_enabled and not e1.graph_enabled and e1.global_step == e2.global_step == 4
 
 
@@ -343,7 +321,7 @@ STEPS = 4
 
 
 def _ddp_engine(graph):
-    return TD._engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, lr_decay="cosine", **LRKW)
+    return HH.engine(small(), 8, 1, seed=3, graph=graph, rank_seeded_z=False, lr_decay="cosine", **LRKW)
 
 
 def _result(eng):
@@ -353,114 +331,34 @@ def _result(eng):
             "losses": eng.losses.cpu()}
 
 
-def _rccl_worker(out_dir, schedule, port):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    os.environ["DCGAN_FORCE_DDP"] = "1"
-    os.environ["DCGAN_DDP_SCHEDULE"] = schedule
-    os.environ["DCGAN_DDP_SHARD"] = "0"
-    os.environ.pop("DCGAN_DIST_BACKEND", None)
-    torch.cuda.set_device(0)
-    from distributed_tensorflow_for_dcgan_amd.parallel import dist as D
-    import torch.distributed as tdist
-    D.init_distributed(1, 0, torch.device("cuda", 0))
-    eng = _ddp_engine(True)
-    assert eng.ddp and eng._schedule() == schedule and eng.lr_sched.active
-    for _ in range(STEPS):
-        eng.train_step()
-    out = _result(eng)
-    out.update({"step": eng.global_step, "backend": tdist.get_backend(), "graph": eng.graph_enabled,
-                "ops": eng.op_names()})
-    torch.save(out, os.path.join(out_dir, "rccl.pt"))
-    D.barrier()
-    D.shutdown()
+def _active(eng):
+    return eng.lr_sched.active
+
+
+DDP = HH.Ddp(_ddp_engine, _result, STEPS, active=_active)
 
 
 @pytest.fixture(scope="module")
 def fused_run():
-    old = {k: os.environ.pop(k, None) for k in ENV}
-    try:
-        eng = _ddp_engine(True)
-        assert not eng.ddp and eng._schedule() == "fused"
-        for _ in range(STEPS):
-            eng.train_step()
-        return _result(eng)
-    finally:
-        for k, v in old.items():
-            if v is not None:
-                os.environ[k] = v
+    return HH.fused_result(DDP, ENV)
 
 
 @pytest.mark.parametrize("schedule", ["concurrent", "ddp"])
 def test_rccl_single_rank_ddp_matches_fused_with_a_schedule(tmp_path, schedule, fused_run):
-    ctx = mp.get_context("spawn")
-    p = ctx.Process(target=_rccl_worker, args=(str(tmp_path), schedule, SNT._free_port()))
-    p.start()
-    p.join(timeout=600)
-    assert p.exitcode == 0, "RCCL rank exited with %s" % p.exitcode
-    r = torch.load(tmp_path / "rccl.pt", weights_only=True)
-    assert r["backend"] == "nccl" and r["step"] == STEPS and r["graph"]
+    r = HH.rccl_run(tmp_path, DDP, schedule, True, fused_run)
     assert "adam_gd" not in r["ops"]  # (the DDP steps update with adam_bf + step_end)
-    for k, v in fused_run.items():
-        assert torch.equal(r[k], v), k
 
 
 # ------------------------------------------------------------------ 8. resume through the trainer
 def test_trainer_resume_is_exact_mid_decay(tmp_path, monkeypatch):
     """bf16: 4 steps in one run == 2 steps, a restart from the checkpoint, 2 more, with the decay
     (and the warm-up) under way at the restart -- every saved tensor bitwise, no new key."""
-    from distributed_tensorflow_for_dcgan_amd.ckpt import checkpoint as CK
-    from distributed_tensorflow_for_dcgan_amd.data import pipeline as P
-    from distributed_tensorflow_for_dcgan_amd.train import trainer as T
-    from distributed_tensorflow_for_dcgan_amd.utils import flags as F
-
-    def source(flags, batch, shape, device, **kw):
-        class Two:
-            num_examples = 1 << 20
-
-            def __init__(self):
-                self.i = 0
-                self.x = [P.SyntheticSource(batch, shape, device, seed=s).next().to(torch.bfloat16) for s in (1, 2)]
-
-            def next(self):
-                self.i += 1
-                return self.x[self.i % 2]
-
-            def stats(self):
-                return {"source": "test"}
-
-            def close(self):
-                pass
-        return Two()
-    monkeypatch.setattr(T, "make_source", source)
     LRF = ["--lr_decay=cosine", "--lr_decay_start=1", "--lr_decay_steps=6", "--lr_end=0.1", "--lr_warmup_steps=3"]
-
-    def run(ck, steps, lrf=LRF):
-        fl = F.parse_flags(["--synthetic", "--engine=hip", "--device=cuda", "--dtype=bf16", "--output_size=28",
-                            "--c_dim=1", "--batch_size=8", "--max_steps=%d" % steps, "--sample_every=0", "--nosummaries",
-                            "--save_model_secs=1e9", "--checkpoint_dir=%s" % ck, "--sample_dir=%s" % (tmp_path / "s"),
-                            "--nolog_device_placement", "--seed=5"] + lrf)
-        out = io.StringIO()
-        assert T.run(fl, out=out) == 0, out.getvalue()
-        return out.getvalue()
-
-    def load(ck):
-        from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine
-        eng = HipEngine(small(), 8, dev, seed=99, graph=False)
-        info = CK.CheckpointManager(str(ck)).restore_latest(eng)
-        torch.cuda.synchronize()
-        return info, CK.collect_state(eng)
-    text = run(tmp_path / "a", 4)
-    assert "learning-rate schedule: cosine to 0.1 x over steps 1..7, linear warm-up over 3 steps" in text
-    run(tmp_path / "b", 2)
-    text = run(tmp_path / "b", 4)
-    assert "load success!" in text and "global_step 2" in text
-    (ia, sa), (ib, sb) = load(tmp_path / "a"), load(tmp_path / "b")
-    assert ia["global_step"] == ib["global_step"] == 4 and list(sa) == list(sb)
-    for k in sa:
-        assert (sa[k] == sb[k]).all(), k
-    run(tmp_path / "c", 4, lrf=[])  # the constant rate trains another model, under the same keys
-    ic, sc = load(tmp_path / "c")
+    r = HH.trainer_resume(tmp_path, monkeypatch, LRF, log_line="learning-rate schedule: cosine to 0.1 x over steps 1..7, "
+                          "linear warm-up over 3 steps")
+    sa = r.a[1]
+    r.run(tmp_path / "c", 4, [])  # the constant rate trains another model, under the same keys
+    ic, sc, _ = r.load(tmp_path / "c")
     assert list(sc) == list(sa) and any(not (sa[k] == sc[k]).all() for k in sa)
 
 

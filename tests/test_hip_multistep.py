@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from hip_harness import rel
 from distributed_tensorflow_for_dcgan_amd.engine.reference_step import ReferenceStep
 from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig
 from distributed_tensorflow_for_dcgan_amd.models.dcgan import DCGAN
@@ -24,11 +25,6 @@ from distributed_tensorflow_for_dcgan_amd.models.dcgan import DCGAN
 pytestmark = pytest.mark.gpu
 
 LOSS_KEYS = ("d_loss_real", "d_loss_fake", "g_loss", "d_loss")
-
-
-def rel(a, b):
-    a, b = a.double().flatten().cpu(), b.double().flatten().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
 
 
 def _live(model, names, cfg):
