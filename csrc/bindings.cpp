@@ -34,6 +34,7 @@
 
 #include "hip/kernels.h"
 #include "comm.h"
+#include "hip/swd.h"
 extern "C" {
 #include "hip/narrow2.inc"
 }
@@ -1356,6 +1357,63 @@ class Program {
   }
   static int summary_blocks(size_t n) { return (int)std::max<size_t>(1, std::min<size_t>(256, (n + 8191) / 8192)); }
 
+  // ---- sliced Wasserstein distance (swd.hip, swd.h): fp32 whatever the Program's element type. One set is
+  // x [n][s][s][C]; N = n * P descriptors per level, J directions; an argument out of range fails the run (-2)
+  int swd_down(std::string name, uintptr_t g, uintptr_t out, int n, int s, int C, int stream) {
+    const size_t b = (size_t)n * s * s * C * 4;
+    return add(name, stream, [=](hipStream_t st) { return dcg_swd_down(P<const float>(g), P<float>(out), n, s, C, st); },
+               AccList().r(g, b).w(out, b / 4).v);
+  }
+  int swd_laplace(std::string name, uintptr_t g, uintptr_t gn, uintptr_t l, int n, int s, int C, int stream) {
+    const size_t b = (size_t)n * s * s * C * 4;
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_swd_laplace(P<const float>(g), P<const float>(gn), P<float>(l), n, s, C, st);
+    }, AccList().r(g, b).r(gn, b / 4).w(l, b).v);
+  }
+  int swd_centres(std::string name, uintptr_t cen, int n, int Pn, int s, int level, uint64_t seed, int stream) {
+    return add(name, stream, [=](hipStream_t st) { return dcg_swd_centres(P<int>(cen), n, Pn, s, level, seed, st); },
+               AccList().w(cen, (size_t)n * Pn * 8).v);
+  }
+  // stats float [2][C] = per-channel (mean, std) of the sampled windows; the fp64 partials are the Program's
+  int swd_stats(std::string name, uintptr_t l, uintptr_t cen, int n, int Pn, int s, int C, uintptr_t stats, int stream) {
+    const size_t N = (size_t)n * Pn, pb = ((N + SWD_STAT_ROWS - 1) / SWD_STAT_ROWS) * 2 * SWD_MAX_CH * sizeof(double);
+    double* part = reinterpret_cast<double*>(dev_alloc(pb));
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_swd_stats(P<const float>(l), P<const int>(cen), n, Pn, s, C, part, P<float>(stats), st);
+    }, AccList().r(l, (size_t)n * s * s * C * 4).r(cen, N * 8).w((uintptr_t)part, pb).w(stats, (size_t)2 * C * 4).v);
+  }
+  // theta [J][49 C] -> thetap [J][swd_kpad(C)], bias [J]: unit length and the normalisation of `stats` folded in
+  int swd_prepare(std::string name, uintptr_t theta, uintptr_t stats, uintptr_t thetap, uintptr_t bias, int J, int C,
+                  int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_swd_prepare(P<const float>(theta), P<const float>(stats), P<float>(thetap), P<float>(bias), J, C, st);
+    }, AccList().r(theta, (size_t)J * 49 * C * 4).r(stats, (size_t)2 * C * 4).w(thetap, (size_t)J * swd_kpad(C) * 4)
+           .w(bias, (size_t)J * 4).v);
+  }
+  int swd_project(std::string name, uintptr_t l, uintptr_t cen, uintptr_t thetap, uintptr_t bias, uintptr_t proj, int n,
+                  int Pn, int s, int C, int J, int stream) {
+    const size_t N = (size_t)n * Pn;
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_swd_project(P<const float>(l), P<const int>(cen), P<const float>(thetap), P<const float>(bias),
+                             P<float>(proj), n, Pn, s, C, J, st);
+    }, AccList().r(l, (size_t)n * s * s * C * 4).r(cen, N * 8).r(thetap, (size_t)J * swd_kpad(C) * 4)
+           .r(bias, (size_t)J * 4).w(proj, (size_t)J * N * 4).v);
+  }
+  // columns [J][N]: src0 sorted into dst0 and, with src1 (N <= 16384), src1 into dst1; partial double [J] = sum_i
+  // |sorted0 - sorted1|, or against the stored sorted columns `ref`. dst0, dst1, partial may be 0
+  int swd_sort_distance(std::string name, uintptr_t src0, uintptr_t dst0, uintptr_t src1, uintptr_t dst1, uintptr_t ref,
+                        uintptr_t partial, int N, int J, int stream) {
+    const size_t b = (size_t)J * N * 4;
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_swd_sort_distance(P<const float>(src0), P<float>(dst0), P<const float>(src1), P<float>(dst1),
+                                   P<const float>(ref), P<double>(partial), N, J, st);
+    }, AccList().r(src0, b).w(dst0, b).r(src1, b).w(dst1, b).r(ref, b).w(partial, (size_t)J * 8).v);
+  }
+  int swd_mean(std::string name, uintptr_t partial, uintptr_t out, int N, int J, int stream) {
+    return add(name, stream, [=](hipStream_t st) { return dcg_swd_mean(P<const double>(partial), P<double>(out), N, J, st); },
+               AccList().r(partial, (size_t)J * 8).w(out, 8).v);
+  }
+
  private:
   int add(const std::string& name, int stream, std::function<int(hipStream_t)> fn, std::vector<Acc> acc,
           int kind = OP_LAUNCH, int ev = -1) {
@@ -1432,6 +1490,8 @@ PYBIND11_MODULE(_dcgan_hip, m) {
     if (!p.nrb) throw std::runtime_error("sn_plan: matrix shape out of range");
     return py::make_tuple(p.nrb, p.rpb, p.nct, p.ncb, p.ws_floats);
   });
+  m.def("swd_kpad", &swd_kpad);  // k depth of the projection's theta' rows for C channels
+  m.attr("SWD_FUSED_ROWS") = (int)SWD_FUSED_ROWS;
   m.attr("OP_LAUNCH") = (int)OP_LAUNCH;
   m.attr("OP_RECORD") = (int)OP_RECORD;
   m.attr("OP_WAIT") = (int)OP_WAIT;
@@ -1581,5 +1641,13 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("cast_to_bf16", &Program::cast_to_bf16)
       .def("cast_bf16_f32", &Program::cast_bf16_f32)
       .def("splitk_reduce", &Program::splitk_reduce)
-      .def("tensor_summary", &Program::tensor_summary);
+      .def("tensor_summary", &Program::tensor_summary)
+      .def("swd_down", &Program::swd_down)
+      .def("swd_laplace", &Program::swd_laplace)
+      .def("swd_centres", &Program::swd_centres)
+      .def("swd_stats", &Program::swd_stats)
+      .def("swd_prepare", &Program::swd_prepare)
+      .def("swd_project", &Program::swd_project)
+      .def("swd_sort_distance", &Program::swd_sort_distance)
+      .def("swd_mean", &Program::swd_mean);
 }

@@ -74,6 +74,8 @@ def _run(cmd):
     return r.stdout
 
 
+# per-file compiler flags. swd.hip: no packed fp32 instructions (v_pk_*_f32) in its element-wise fp32 kernels
+FILE_FLAGS = {"swd.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 VARIANTS = {"bf16": ("", []), "f16": (".f16", ["-DDCG_F16"]), "f32": (".f32", ["-DDCG_F32"])}
 
 
@@ -118,7 +120,7 @@ def build_hip(verbose: bool = False, jobs: int = 8) -> str:
         for tag, defs in _variants(s):
             o = os.path.join(BUILD, os.path.basename(s) + tag + ".o")
             objs.append(o)
-            cmd = [HIPCC] + common + defs + ["-c", s, "-o", o]
+            cmd = [HIPCC] + common + FILE_FLAGS.get(os.path.basename(s), []) + defs + ["-c", s, "-o", o]
             if _stale(deps, o, cmd):
                 jobs_list.append((cmd, deps, o))
     binding = os.path.join(CSRC, "bindings.cpp")

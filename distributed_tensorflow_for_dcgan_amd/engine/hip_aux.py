@@ -158,6 +158,31 @@ class HipEngineAux:
         self.losses.copy_(saved_losses)
         return {"d_loss": l[3], "g_loss": l[2]}
 
+    # ------------------------------------------------------------------ sliced Wasserstein distance
+    def swd(self, real: Optional[torch.Tensor], z: torch.Tensor, patches: int, seed: int, ema: Optional[bool] = None,
+            refresh: bool = False) -> List[float]:
+        """Sliced Wasserstein distance x 1000 between `real` [n, S, S, C] and the n samples of z, per
+        Laplacian-pyramid level, finest first (swd.hip; ops.hip.Swd). Programs of their own, recorded on
+        first use: nothing of the training step is touched. The fakes come from ``sampler(z, ema=ema)`` in
+        chunks of the batch size. The real side (its sorted projections per level) is computed on the first
+        call and kept: later calls do not read `real` (None is fine) unless refresh is set or the set's
+        size, `patches` or `seed` changed."""
+        n, B = int(z.shape[0]), self.B
+        key = (n, int(patches), int(seed))
+        sw = getattr(self, "_swd", None)
+        if sw is None or self._swd_key != key or refresh:
+            if real is None or int(real.shape[0]) != n:
+                raise ValueError("swd: the first evaluation needs the n = %d real images" % n)
+            sw = H.Swd(n, self.cfg.output_size, self.cfg.c_dim, int(patches), int(seed), device=self.device)
+            sw.set_real(real.to(self.device, torch.float32))
+            self._swd, self._swd_key = sw, key
+        z = z.to(self.device, torch.float32)
+        for i in range(0, n, B):
+            m = min(B, n - i)
+            zc = z[i:i + m] if m == B else torch.cat([z[i:], z.new_zeros(B - m, z.shape[1])])
+            sw.x[i:i + m].copy_(self.sampler(zc, ema=ema)[:m])
+        return sw.distance()
+
     def placement(self) -> List[str]:
         """--log_device_placement lines: every recorded op of the step runs on this rank's HIP
         device; which stream slots / graphs carry it."""

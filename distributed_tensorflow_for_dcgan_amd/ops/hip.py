@@ -1161,3 +1161,199 @@ def sn_project_(mats, grads, build: str = "fp32") -> None:
     prog = ext().Program(dt)
     prog.sn_project("sn_project", tup, 0)
     run(prog)
+
+
+# --------------------------------------------------------------------------- sliced Wasserstein distance
+def _f32_images(op: str, x: torch.Tensor) -> torch.Tensor:
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != x.shape[2] or not x.is_contiguous():
+        raise TypeError("%s: images must be contiguous float32 [n, S, S, C], got %s %s" % (op, x.dtype, tuple(x.shape)))
+    return x
+
+
+def _swd_pyramid(prog, g, l, n: int, sizes, C: int) -> None:
+    """Record the Laplacian pyramid of g[0] (swd.hip): g[k + 1] = down(g[k]), l[k] = g[k] - up(g[k + 1]); the
+    caller makes l[-1] the tensor g[-1]."""
+    for k, s in enumerate(sizes[:-1]):
+        prog.swd_down("swd.down%d" % s, _p(g[k]), _p(g[k + 1]), n, s, C, 0)
+        prog.swd_laplace("swd.laplace%d" % s, _p(g[k]), _p(g[k + 1]), _p(l[k]), n, s, C, 0)
+
+
+def swd_laplacian(x: torch.Tensor, out=None):
+    """The Laplacian pyramid of x [n, S, S, C] float32 (oracle: ops.reference.swd_laplacian): one tensor per
+    level of reference.swd_levels(S), the last the coarsest Gaussian level. out: the tensors to write."""
+    from . import reference as R
+    n, S, _, C = _f32_images("swd_laplacian", x).shape
+    sizes = R.swd_levels(S)
+    new = lambda s: torch.empty(n, s, s, C, dtype=torch.float32, device=x.device)  # noqa: E731
+    out = [new(s) for s in sizes] if out is None else list(out)
+    if [tuple(o.shape) for o in out] != [(n, s, s, C) for s in sizes]:
+        raise ValueError("swd_laplacian: out must hold one [n, s, s, C] tensor per level %s" % (sizes,))
+    g = [x] + [new(s) for s in sizes[1:-1]] + ([out[-1]] if len(sizes) > 1 else [])
+    if len(sizes) == 1:
+        out[0].copy_(x)
+        return out
+    prog = ext().Program()
+    _swd_pyramid(prog, g, out, n, sizes, C)
+    run(prog)
+    return out
+
+
+def swd_patch_centres(n: int, patches: int, s: int, level: int, seed: int, device="cuda") -> torch.Tensor:
+    """int32 [n * patches, 2] = (cy, cx) of every descriptor of pyramid level `level` at size s, as the
+    kernels draw them (oracle: ops.reference.swd_patch_centres)."""
+    from . import reference as R
+    N = R.check_swd(n, patches, s)
+    cen = torch.empty(N, 2, dtype=torch.int32, device=device)
+    prog = ext().Program()
+    prog.swd_centres("swd.centres", _p(cen), int(n), int(patches), int(s), int(level), int(seed) & (2 ** 64 - 1), 0)
+    run(prog)
+    return cen
+
+
+def swd_project(l: torch.Tensor, centres: torch.Tensor, mean: torch.Tensor, std: torch.Tensor,
+                theta: torch.Tensor) -> torch.Tensor:
+    """float32 [J, N]: the 7x7xC windows of l [n, s, s, C] around centres int32 [N, 2], normalised per
+    channel by (mean, std) and projected on the directions theta [J, 49 C] scaled to unit length. J: a
+    multiple of 128 up to 1024. The normalised descriptors are never written out."""
+    from . import reference as R
+    n, s, _, C = _f32_images("swd_project", l).shape
+    N = centres.shape[0]
+    R.check_swd(n, N // n, s)
+    J = theta.shape[0]
+    if centres.dtype != torch.int32 or tuple(centres.shape) != (N, 2) or N % n:
+        raise TypeError("swd_project: centres must be int32 [N, 2], N a multiple of the image count")
+    if int(centres.min()) < 3 or int(centres.max()) > s - 4:
+        raise ValueError("swd_project: centres must lie in [3, s - 4]")
+    if theta.dtype != torch.float32 or tuple(theta.shape) != (J, 49 * C) or J % 128 or not 128 <= J <= 1024:
+        raise ValueError("swd_project: theta must be float32 [J, 49 C], J a multiple of 128 up to 1024")
+    dev = l.device
+    stats = torch.stack([mean.reshape(C), std.reshape(C)]).to(dev, torch.float32).contiguous()
+    thetap = torch.empty(J, ext().swd_kpad(C), dtype=torch.float32, device=dev)
+    bias = torch.empty(J, dtype=torch.float32, device=dev)
+    proj = torch.empty(J, N, dtype=torch.float32, device=dev)
+    centres, theta = centres.contiguous(), theta.contiguous()
+    prog = ext().Program()
+    prog.swd_prepare("swd.prepare", _p(theta), _p(stats), _p(thetap), _p(bias), J, C, 0)
+    prog.swd_project("swd.project", _p(l), _p(centres), _p(thetap), _p(bias), _p(proj), n, N // n, s, C, J, 0)
+    run(prog)
+    return proj
+
+
+def swd_sorted_distance(a: torch.Tensor, b: torch.Tensor):
+    """(sort(a), sort(b), float64 mean_i |sort(a)[i] - sort(b)[i]|) of the columns a, b float32 [J, N] (row j = the
+    column of direction j), sorted by the monotone key (-0 < +0). N a power of two in [16, 32768]: up to
+    16384 both columns are sorted in one launch, above it each in a launch of its own."""
+    if a.dtype != torch.float32 or a.dim() != 2 or b.dtype != a.dtype or b.shape != a.shape:
+        raise TypeError("swd_sorted_distance: a and b must be float32 [J, N] of one shape")
+    J, N = a.shape
+    if N < 16 or N > 32768 or N & (N - 1) or not 1 <= J <= 1024:
+        raise ValueError("swd_sorted_distance: N must be a power of two in [16, 32768] and J at most 1024, got "
+                         "[%d, %d]" % (J, N))
+    a, b = a.contiguous(), b.contiguous()
+    sa, sb = torch.empty_like(a), torch.empty_like(b)
+    part = torch.empty(J, dtype=torch.float64, device=a.device)
+    prog = ext().Program()
+    if N <= ext().SWD_FUSED_ROWS:
+        prog.swd_sort_distance("swd.sort2", _p(b), _p(sb), _p(a), _p(sa), 0, _p(part), N, J, 0)
+    else:
+        prog.swd_sort_distance("swd.sort", _p(a), _p(sa), 0, 0, 0, 0, N, J, 0)
+        prog.swd_sort_distance("swd.sort_dist", _p(b), _p(sb), 0, 0, _p(sa), _p(part), N, J, 0)
+    run(prog)
+    return sa, sb, part / N
+
+
+class Swd:
+    """The sliced Wasserstein distance of image sets [n, S, S, C] against one real set, on the device
+    (swd.hip; oracle: ops.reference.swd). ``set_real`` projects the real set and keeps its sorted columns
+    per level -- the reals, the patch centres and the directions never change -- so every ``distance`` costs
+    the evaluated set's side only. Everything is recorded once: the side's Program and the two sort Programs."""
+
+    def __init__(self, n: int, S: int, C: int, patches: int, seed: int, repeats: int = 4, dirs: int = 128,
+                 device="cuda"):
+        from . import reference as R
+        self.N = N = R.check_swd(n, patches, S)
+        self.J = J = int(repeats) * int(dirs)
+        if J % 128 or not 128 <= J <= 1024 or not 1 <= C <= 4:
+            raise ValueError("swd: repeats * dirs must be a multiple of 128 up to 1024 and C at most 4")
+        self.sizes = sizes = R.swd_levels(S)
+        seed = int(seed) & (2 ** 64 - 1)
+        new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=device)  # noqa: E731
+        K, nl = 49 * C, len(sizes)
+        self.theta = new(J, K)  # the normals of the directions; swd_prepare scales them to unit length
+        step = torch.empty(1, dtype=torch.int64, device=device)
+        for r in range(int(repeats)):
+            step.fill_(R.SWD_DIR_STEP + r)
+            self.theta[r * dirs:(r + 1) * dirs] = philox_normal(dirs * K, seed, step, R.SWD_STREAM).view(dirs, K)
+        self.x = new(n, S, S, C)  # the set under evaluation
+        self.g = [self.x] + [new(n, s, s, C) for s in sizes[1:]]
+        self.l = [new(n, s, s, C) for s in sizes[:-1]] + [self.g[-1]]
+        self.cen = [new(N, 2, dt=torch.int32) for _ in sizes]
+        self.stats = [new(2, C) for _ in sizes]
+        self.thetap = [new(J, ext().swd_kpad(C)) for _ in sizes]
+        self.bias, self.partial = [new(J) for _ in sizes], [new(J, dt=torch.float64) for _ in sizes]
+        self.proj = [new(J, N) for _ in sizes]
+        self.real_sorted = [new(J, N) for _ in sizes]
+        self.out = new(nl, dt=torch.float64)
+        self.fused = N <= ext().SWD_FUSED_ROWS
+        self.real_proj = None  # (fused: the reals' unsorted columns until the first distance sorts them)
+        self.has_real = False
+        init, side, first, cached = (ext().Program() for _ in range(4))
+        _swd_pyramid(side, self.g, self.l, n, sizes, C)
+        for k, s in enumerate(sizes):
+            init.swd_centres("swd.centres%d" % s, _p(self.cen[k]), n, patches, s, k, seed, 0)
+            side.swd_stats("swd.stats%d" % s, _p(self.l[k]), _p(self.cen[k]), n, patches, s, C, _p(self.stats[k]), 0)
+            side.swd_prepare("swd.prepare%d" % s, _p(self.theta), _p(self.stats[k]), _p(self.thetap[k]),
+                             _p(self.bias[k]), J, C, 0)
+            side.swd_project("swd.project%d" % s, _p(self.l[k]), _p(self.cen[k]), _p(self.thetap[k]), _p(self.bias[k]),
+                             _p(self.proj[k]), n, patches, s, C, J, 0)
+        run(init)
+        if self.fused:
+            self.real_proj = [new(J, N) for _ in sizes]
+        for k, s in enumerate(sizes):
+            if self.fused:  # the first distance: both sets' columns in one launch, the reals' kept
+                first.swd_sort_distance("swd.sort2_%d" % s, _p(self.proj[k]), 0, _p(self.real_proj[k]),
+                                        _p(self.real_sorted[k]), 0, _p(self.partial[k]), N, J, 0)
+            else:           # the reals' columns, sorted when they are set
+                first.swd_sort_distance("swd.sort%d" % s, _p(self.proj[k]), _p(self.real_sorted[k]), 0, 0, 0, 0, N, J, 0)
+            cached.swd_sort_distance("swd.sort_dist%d" % s, _p(self.proj[k]), 0, 0, 0, _p(self.real_sorted[k]),
+                                     _p(self.partial[k]), N, J, 0)
+        for p in (first, cached) if self.fused else (cached,):
+            for k in range(nl):
+                p.swd_mean("swd.mean%d" % sizes[k], _p(self.partial[k]), _p(self.out[k]), N, J, 0)
+        self.prog_side, self.prog_first, self.prog_cached = side, first, cached
+
+    def set_real(self, real: torch.Tensor) -> None:
+        self.x.copy_(real)
+        run(self.prog_side)
+        if self.fused:
+            for dst, src in zip(self.real_proj, self.proj):
+                dst.copy_(src)
+        else:
+            run(self.prog_first)
+        self.has_real = True
+
+    def distance(self, x: Optional[torch.Tensor] = None):
+        """Per-level distances x 1000 (finest level first) of x -- None: of what the caller wrote into
+        ``self.x`` -- against the real set."""
+        if not self.has_real:
+            raise RuntimeError("swd: set_real() first")
+        if x is not None:
+            self.x.copy_(x)
+        run(self.prog_side)
+        if self.fused and self.real_proj is not None:
+            run(self.prog_first)
+            self.real_proj = None
+        else:
+            run(self.prog_cached)
+        return self.out.tolist()
+
+
+def swd(A: torch.Tensor, B: torch.Tensor, patches: int, seed: int, repeats: int = 4, dirs: int = 128):
+    """Sliced Wasserstein distance x 1000 between the image sets A (real) and B (fake), float32 [n, S, S, C]
+    on the device, per pyramid level (oracle: ops.reference.swd)."""
+    n, S, _, C = _f32_images("swd", A).shape
+    if _f32_images("swd", B).shape != A.shape:
+        raise ValueError("swd: A and B must share a shape")
+    sw = Swd(n, S, C, int(patches), seed, repeats, dirs, device=A.device)
+    sw.set_real(A)
+    return sw.distance(B)

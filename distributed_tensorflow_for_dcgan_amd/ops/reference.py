@@ -1132,3 +1132,136 @@ def check_spectral_norm(flag) -> bool:
         return bool(flag)
     raise ValueError("d_spectral_norm must be a boolean, got %r" % (flag,))
 
+
+
+# --------------------------------------------------------------------------- sliced Wasserstein distance
+# The quality metric of Karras et al. 2018 (Progressive GANs, section 5): the sliced Wasserstein distance
+# between 7x7 patch descriptors of the Laplacian pyramids of a real and a generated image set, per level.
+SWD_STREAM = 6             # Philox stream of the patch centres and directions (0..5 are taken)
+SWD_DIR_STEP = 1 << 16     # counter word 2 of the directions of repeat r: 2^16 + r (the levels use 0, 1, ...)
+SWD_MIN_ROWS, SWD_MAX_ROWS = 16, 32768  # descriptors per set and level the device sort holds in LDS
+SWD_TAPS = (1.0, 4.0, 6.0, 4.0, 1.0)   # / 16
+
+
+def swd_levels(S: int):
+    """Pyramid sizes: S, then halved while even and the half is at least 16."""
+    out = [int(S)]
+    while out[-1] % 2 == 0 and out[-1] // 2 >= 16:
+        out.append(out[-1] // 2)
+    return out
+
+
+def check_swd(n: int, patches: int, S: int, names=("n", "patches", "output size")) -> int:
+    """Validated N = n * patches descriptors per set: a power of two in [16, 32768], S >= 16. `names`: how
+    the caller spells the three in its message (the flag parser passes its flags)."""
+    n, patches, S = int(n), int(patches), int(S)
+    N = n * patches
+    if n < 1 or patches < 1 or N < SWD_MIN_ROWS or N > SWD_MAX_ROWS or N & (N - 1):
+        raise ValueError("%s * %s must be a power of two in [%d, %d] (larger sets need a global merge sort), got "
+                         "%d * %d" % (names[0], names[1], SWD_MIN_ROWS, SWD_MAX_ROWS, n, patches))
+    if S < 16:
+        raise ValueError("%s must be at least 16 for the sliced Wasserstein distance, got %d" % (names[2], S))
+    return N
+
+
+def _swd_filter(x: torch.Tensor, gain: float) -> torch.Tensor:
+    """The 5x5 binomial filter times `gain` over x [n, s, s, C], borders reflected (reflect-101)."""
+    C = x.shape[3]
+    w = torch.tensor(SWD_TAPS, dtype=x.dtype, device=x.device) / 16.0
+    k = (torch.outer(w, w) * gain).expand(C, 1, 5, 5).contiguous()
+    y = F.conv2d(F.pad(x.permute(0, 3, 1, 2), (2, 2, 2, 2), mode="reflect"), k, groups=C)
+    return y.permute(0, 2, 3, 1)
+
+
+def swd_down(g: torch.Tensor) -> torch.Tensor:
+    """g_{k+1}: the filtered image at every second pixel, [n, s, s, C] -> [n, s / 2, s / 2, C]."""
+    return _swd_filter(g, 1.0)[:, ::2, ::2].contiguous()
+
+
+def swd_up(g: torch.Tensor) -> torch.Tensor:
+    """The zero-stuffed image filtered with gain 4, [n, s, s, C] -> [n, 2 s, 2 s, C]."""
+    n, s, _, C = g.shape
+    z = g.new_zeros(n, 2 * s, 2 * s, C)
+    z[:, ::2, ::2] = g
+    return _swd_filter(z, 4.0).contiguous()
+
+
+def swd_laplacian(x: torch.Tensor, dtype=torch.float64):
+    """The Laplacian pyramid [l_0, ..., l_last] of x [n, S, S, C]: l_k = g_k - up(g_{k+1}), l_last = g_last."""
+    g = x.to(dtype)
+    out = []
+    for _ in swd_levels(x.shape[1])[1:]:
+        nxt = swd_down(g)
+        out.append(g - swd_up(nxt))
+        g = nxt
+    return out + [g]
+
+
+def swd_patch_centres(n: int, patches: int, s: int, level: int, seed: int) -> torch.Tensor:
+    """int64 [n * patches, 2] = (cy, cx) of patch p of image i at row i * patches + p: words w0, w1 of the
+    Philox block at counter (p, i, level, SWD_STREAM) under `seed`, c = 3 + mulhi(w, s - 6) in [3, s - 4]."""
+    import numpy as np
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.empty((int(n), int(patches), 4), dtype=np.uint64)
+    ctr[..., 0] = np.arange(int(patches), dtype=np.uint64)[None, :]
+    ctr[..., 1] = np.arange(int(n), dtype=np.uint64)[:, None]
+    ctr[..., 2] = int(level)
+    ctr[..., 3] = SWD_STREAM
+    w = philox4x32_10(ctr.reshape(-1, 4), np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)).astype(np.uint64)
+    c = 3 + ((w[:, :2] * np.uint64(int(s) - 6)) >> np.uint64(32)).astype(np.int64)
+    return torch.from_numpy(c)
+
+
+def swd_descriptors(l: torch.Tensor, centres: torch.Tensor) -> torch.Tensor:
+    """[N, 49 C]: row r is the 7x7xC window of image r // (N / n) of l [n, s, s, C] around centres[r]."""
+    n, C = l.shape[0], l.shape[3]
+    cen = centres.to(l.device)
+    N = cen.shape[0]
+    img = torch.arange(N, device=l.device) // (N // n)
+    o = torch.arange(-3, 4, device=l.device)
+    d = l[img[:, None, None], cen[:, 0, None, None] + o[None, :, None], cen[:, 1, None, None] + o[None, None, :]]
+    return d.reshape(N, 49 * C)
+
+
+def swd_stats(d: torch.Tensor, C: int):
+    """(mu_c, sigma_c) over all N * 49 values of channel c (population; accumulated in fp64), in d's dtype."""
+    v = d.double().reshape(-1, C)
+    mu = v.mean(0)
+    return mu.to(d.dtype), ((v - mu) ** 2).mean(0).sqrt().to(d.dtype)
+
+
+def swd_directions(K: int, seed: int, repeats: int = 4, dirs: int = 128, dtype=torch.float64) -> torch.Tensor:
+    """[repeats * dirs, K] unit vectors: repeat r draws dirs * K normals of the Philox stream (seed,
+    2^16 + r, SWD_STREAM), direction j the K values from j * K, each scaled to unit L2 norm."""
+    out = []
+    for r in range(int(repeats)):
+        t = philox_normal(int(dirs) * int(K), seed, SWD_DIR_STEP + r, SWD_STREAM, dtype).reshape(int(dirs), int(K))
+        out.append(t / t.norm(dim=1, keepdim=True))
+    return torch.cat(out, 0)
+
+
+def swd_sorted_distance(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """mean_i |sort(a)[i] - sort(b)[i]| along the last dimension: the 1-D Wasserstein-1 distance."""
+    return (a.sort(-1).values - b.sort(-1).values).abs().mean(-1)
+
+
+def swd(A: torch.Tensor, B: torch.Tensor, patches: int, seed: int, repeats: int = 4, dirs: int = 128,
+        dtype=torch.float64):
+    """Sliced Wasserstein distance x 1000 between the image sets A (real) and B (fake), both [n, S, S, C] in
+    [-1, 1], per pyramid level (a list of floats, finest level first). A channel that is constant over a
+    set has sigma = 0 and makes that level non-finite."""
+    if A.shape != B.shape or A.dim() != 4 or A.shape[1] != A.shape[2]:
+        raise ValueError("swd: A and B must share a shape [n, S, S, C], got %s and %s" % (tuple(A.shape), tuple(B.shape)))
+    n, S, _, C = A.shape
+    check_swd(n, patches, S)
+    theta = swd_directions(49 * C, seed, repeats, dirs, dtype).to(A.device)
+    out = []
+    for k, (la, lb) in enumerate(zip(swd_laplacian(A, dtype), swd_laplacian(B, dtype))):
+        cen = swd_patch_centres(n, patches, la.shape[1], k, seed)
+        proj = []
+        for l in (la, lb):
+            d = swd_descriptors(l, cen)
+            mu, sigma = swd_stats(d, C)
+            proj.append((((d.reshape(-1, 49, C) - mu) / sigma).reshape(d.shape) @ theta.t()).t())
+        out.append(1000.0 * float(swd_sorted_distance(proj[0], proj[1]).mean()))
+    return out

@@ -277,6 +277,7 @@ def run(flags: Flags, out=None) -> int:
     next_summary = start_time + float(flags.save_summaries_secs)
     last_rate_t, last_rate_step = start_time, step
     losslog = AsyncLossLog(engine, device)
+    swd_every, swd_at, swd_state = int(flags.swd_every), -1, {}
 
     def emit(entries):
         for (st, t, ips), L in entries:
@@ -351,6 +352,9 @@ def run(flags: Flags, out=None) -> int:
                 _sample(engine, flags, sample_source, source, sample_z, step, step_per_epoch, out)
             if chief and save_now:
                 ckpt.save(engine)
+            if chief and swd_every > 0 and step % swd_every == 0:
+                swd_at = step
+                _swd(engine, flags, swd_state, sample_source or source, cfg, device, step, out, writer)
             if int(flags.check_sync_every) > 0 and world > 1 and step % int(flags.check_sync_every) == 0:
                 tens = (engine.sync_check_tensors() if hasattr(engine, "sync_check_tensors")
                         else [engine.model.g.flat, engine.model.d.flat])
@@ -364,6 +368,8 @@ def run(flags: Flags, out=None) -> int:
         emit(losslog.ready(flush=True))
         if world > 1:
             engine.sync_bn_state()
+        if chief and swd_every > 0 and swd_at != step:  # once at the end of training
+            _swd(engine, flags, swd_state, sample_source or source, cfg, device, step, out, writer)
         if chief:
             path = ckpt.save(engine)
             print("saved %s" % path, file=out)
@@ -420,6 +426,14 @@ def _test_mode(engine, flags, cfg, B, device, info, chief, out) -> int:
     path = os.path.join(flags.sample_dir, "test_%06d.png" % step)
     IM.save_images(arr, (8, 8) if n == 64 else IM.grid_size(n), path)
     print("[Test] wrote %d samples to %s" % (n, path), file=out, flush=True)
+    if int(flags.swd_images) > 0 and (flags.explicitly_set("swd_images") or int(flags.swd_every) > 0) and (
+            flags.synthetic or os.path.isdir(flags.data_dir)):  # the restored checkpoint's distance
+        shape = (cfg.output_size, cfg.output_size, cfg.c_dim)
+        src = make_source(flags, B, shape, device, rank=0, world=1, engine_dtype=getattr(engine, "dtype_name", None))
+        try:
+            _swd(engine, flags, {}, src, cfg, device, step, out, None)
+        finally:
+            src.close()
     if flags.visualize:
         base = (torch.rand(1, cfg.z_dim, generator=gen) * 2 - 1).repeat(B, 1)
         sweep = torch.linspace(-1.0, 1.0, B)
@@ -448,3 +462,29 @@ def _sample(engine, flags, sample_source, source, sample_z, step, step_per_epoch
                                                                           step % step_per_epoch))
     IM.save_images(samples.detach().float().cpu().numpy(), grid, path)
     print("[Sample] d_loss: %.8f, g_loss: %.8f" % (losses["d_loss"], losses["g_loss"]), file=out, flush=True)
+
+
+def _swd(engine, flags, state, source, cfg, device, step, out, writer) -> None:
+    """Chief side path of --swd_every: the sliced Wasserstein distance (x 1000) between a fixed real set and
+    the samples of a fixed z, one value per Laplacian-pyramid level. `state` keeps both across evaluations;
+    the real set is drawn from `source` at the first one (ceil(n / B) batches)."""
+    n, patches = int(flags.swd_images), int(flags.swd_patches)
+    try:
+        R.check_swd(n, patches, cfg.output_size, ("--swd_images", "--swd_patches", "--output_size"))
+    except ValueError as e:
+        raise SystemExit(str(e))
+    if not state:
+        got = []
+        while sum(x.shape[0] for x in got) < n:
+            got.append(source.next().to(device, torch.float32))
+        state["real"] = torch.cat(got)[:n].contiguous()
+        gen = torch.Generator().manual_seed(int(flags.seed) + 4242)
+        state["z"] = (torch.rand(n, cfg.z_dim, generator=gen) * 2 - 1).to(device)
+    vals = engine.swd(state["real"], state["z"], patches, int(flags.seed), ema=_sample_ema(engine, flags))
+    sizes = R.swd_levels(cfg.output_size)
+    avg = sum(vals) / len(vals)
+    print("[SWD] step %d  %s  avg: %.2f" % (step, "  ".join("%d: %.2f" % sv for sv in zip(sizes, vals)), avg),
+          file=out, flush=True)
+    if writer is not None:
+        writer.add_summary_values([SummaryWriter.scalar("swd/%d" % s, v) for s, v in zip(sizes, vals)] +
+                                  [SummaryWriter.scalar("swd/avg", avg)], step)

@@ -134,6 +134,14 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                              "the final fraction, 0 < g_topk <= 1. 1 turns it off"),
     ("g_topk_steps", "int", 0, "length of the anneal of k in steps, 1..2^24; 0 = until the end of training "
                                "(max_steps after the --epoch cap)"),
+    ("swd_every", "int", 0, "every N steps, and at the end of training, the chief prints the sliced Wasserstein "
+                            "distance (x 1000) between --swd_images real and generated images per Laplacian-pyramid "
+                            "level (Karras et al. 2018). 0 turns it off. The real set is drawn once, from the sample "
+                            "source when there is one, else from the training source (advanced by "
+                            "ceil(swd_images / batch_size) batches)"),
+    ("swd_images", "int", 256, "images per set of the distance"),
+    ("swd_patches", "int", 128, "7x7 patches per image and level; --swd_images * --swd_patches must be a power of "
+                                "two in [16, 32768]"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -216,6 +224,14 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         parser.error("--g_ema_decay must satisfy 0 <= decay < 1, got %r" % (ns.g_ema_decay,))
     from ..ops.options import validate_flags  # (an open-ended --*_steps=0 stays open here: the trainer resolves it)
     validate_flags(ns, parser.error)
+    if int(ns.swd_every) < 0:
+        parser.error("--swd_every must be >= 0, got %r" % (ns.swd_every,))
+    if int(ns.swd_every) > 0 or any(a.split("=")[0] in ("--swd_images", "--swd_patches") for a in argv):
+        from ..ops.reference import check_swd
+        try:
+            check_swd(ns.swd_images, ns.swd_patches, ns.output_size, ("--swd_images", "--swd_patches", "--output_size"))
+        except ValueError as e:
+            parser.error(str(e))
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
