@@ -99,7 +99,7 @@ struct AccList {
 };
 
 // A DiffAugment stage on D's input as Program's two recorders of it (stage_fwd, stage_bwd) see it: they
-// are the same code for every stage. PT: the element type of its params rows [N][4]
+// are the same code for every stage. PT: the element type of its params rows [N][width]
 template <class PT>
 struct DStage {
   typedef int (*Launcher)(const elem_t*, elem_t*, PT*, int, int, int, int, int, uint64_t, const unsigned long long*,
@@ -109,11 +109,15 @@ struct DStage {
   const char* policies;       // ... spelled out for the message that rejects another
   Launcher launch[3];         // by the Program's element type: bf16, fp16, fp32
   bool probe_writes_params;   // the probe (step == 0) writes params as well as reading them
+  int width;                  // entries of a params row
+  size_t row_bytes() const { return (size_t)width * sizeof(PT); }
 };
 static const DStage<int> D_AUGMENT = {"d_augment", AUG_ALL, "translation (1) | cutout (2)",
-                                      {dcg_d_augment, dcg_d_augment_f16, dcg_d_augment_f32}, false};
+                                      {dcg_d_augment, dcg_d_augment_f16, dcg_d_augment_f32}, false, 4};
 static const DStage<float> D_COLOR = {"d_color", COLOR_ALL, "brightness (1) | saturation (2) | contrast (4)",
-                                      {dcg_d_color, dcg_d_color_f16, dcg_d_color_f32}, true};  // (color's probe: Mx)
+                                      {dcg_d_color, dcg_d_color_f16, dcg_d_color_f32}, true, 4};  // (color's probe: Mx)
+static const DStage<float> D_GEOM = {"d_geom", GEOM_ALL, "xflip (1) | rot90 (2) | scale (4) | rotate (8)",
+                                     {dcg_d_geom, dcg_d_geom_f16, dcg_d_geom_f32}, false, GEOM_PARAMS};
 
 class Program {
  public:
@@ -1216,14 +1220,14 @@ class Program {
     if (C < 1 || C > 4) throw std::runtime_error(o + ": C must satisfy 1 <= C <= 4, got " + std::to_string(C));
   }
   // a stage of x [N][S][S][C] -> y. step != 0: reads x and the 8-byte counter, writes y and the draws
-  // params [N][4]. step == 0 (the probe): reads x and params (and writes params where the stage says so),
+  // params [N][width]. step == 0 (the probe): reads x and params (and writes params where the stage says so),
   // writes y. gates != 0 (adaptive augmentation): the gated kernel. step != 0 also reads the 4 bytes of
   // p24 at ada_state and writes gates int32 [N]; the probe reads gates
   template <class PT>
   int stage_fwd(const DStage<PT>& st, std::string name, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C,
                 int policy, uint64_t seed, uintptr_t step, int stream, uintptr_t gates, uintptr_t ada_state) {
     stage_check(st, st.name, x, y, params, N, S, C, policy);
-    const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * 16, gbytes = (size_t)N * 4;
+    const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * st.row_bytes(), gbytes = (size_t)N * 4;
     const int mode = step ? 0 : 1;
     gate_check(st.name, gates, mode == 0 ? ada_state : 0, mode == 0, x, y, bytes, params, pbytes, gbytes);
     AccList acc;
@@ -1245,10 +1249,10 @@ class Program {
                 int C, int policy, int stream, uintptr_t gates) {
     const std::string o = std::string(st.name) + "_bwd";
     stage_check(st, o, gy, gx, params, N, S, C, policy);
-    const size_t bytes = (size_t)N * S * S * C * es_, gbytes = (size_t)N * 4;
-    gate_check(o.c_str(), gates, 0, false, gy, gx, bytes, params, (size_t)N * 16, gbytes);
+    const size_t bytes = (size_t)N * S * S * C * es_, pbytes = (size_t)N * st.row_bytes(), gbytes = (size_t)N * 4;
+    gate_check(o.c_str(), gates, 0, false, gy, gx, bytes, params, pbytes, gbytes);
     AccList acc;
-    acc.r(gy, bytes).r(params, (size_t)N * 16).w(gx, bytes);
+    acc.r(gy, bytes).r(params, pbytes).w(gx, bytes);
     if (gates) acc.r(gates, gbytes);
     const auto launch = st.launch[dt_];
     return add(name, stream, [=](hipStream_t s) {
@@ -1277,6 +1281,17 @@ class Program {
   int d_color_bwd(std::string name, uintptr_t gy, uintptr_t gx, uintptr_t params, int N, int S, int C, int policy,
                   int stream, uintptr_t gates) {
     return stage_bwd(D_COLOR, name, gy, gx, params, N, S, C, policy, stream, gates);
+  }
+  // ADA's geometric stage on D's input (dgeom.hip d_geom_kernel), params float [N][8] = (m00, m01, m10, m11, s,
+  // theta, flip, k): drawn from the Philox stream (seed, *step, GEOM_STREAM) and written; the probe reads the matrix
+  int d_geom(std::string name, uintptr_t x, uintptr_t y, uintptr_t params, int N, int S, int C, int policy,
+             uint64_t seed, uintptr_t step, int stream, uintptr_t gates, uintptr_t ada_state) {
+    return stage_fwd(D_GEOM, name, x, y, params, N, S, C, policy, seed, step, stream, gates, ada_state);
+  }
+  // its transpose (d_geom_bwd_kernel): the exact transposed resampling under the recorded matrices
+  int d_geom_bwd(std::string name, uintptr_t gy, uintptr_t gx, uintptr_t params, int N, int S, int C, int policy,
+                 int stream, uintptr_t gates) {
+    return stage_bwd(D_GEOM, name, gy, gx, params, N, S, C, policy, stream, gates);
   }
   // one step of the adaptive-augmentation controller (ada_update_kernel): reads the B fp32 real logits,
   // reads and writes the 32 bytes of state int32 [8] = (p24, acc, cnt, r_acc, windows, 0, 0, 0)
@@ -1630,6 +1645,11 @@ PYBIND11_MODULE(_dcgan_hip, m) {
            py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("seed"), py::arg("step"),
            py::arg("stream") = 0, py::arg("gates") = 0, py::arg("ada_state") = 0)
       .def("d_color_bwd", &Program::d_color_bwd, py::arg("name"), py::arg("gy"), py::arg("gx"), py::arg("params"),
+           py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("stream") = 0, py::arg("gates") = 0)
+      .def("d_geom", &Program::d_geom, py::arg("name"), py::arg("x"), py::arg("y"), py::arg("params"),
+           py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("seed"), py::arg("step"),
+           py::arg("stream") = 0, py::arg("gates") = 0, py::arg("ada_state") = 0)
+      .def("d_geom_bwd", &Program::d_geom_bwd, py::arg("name"), py::arg("gy"), py::arg("gx"), py::arg("params"),
            py::arg("N"), py::arg("S"), py::arg("C"), py::arg("policy"), py::arg("stream") = 0, py::arg("gates") = 0)
       .def("ada_update", &Program::ada_update, py::arg("name"), py::arg("logits"), py::arg("B"), py::arg("state"),
            py::arg("thr"), py::arg("target_n"), py::arg("delta24"), py::arg("interval"), py::arg("stream") = 0)

@@ -154,6 +154,23 @@ constexpr unsigned long long COLOR_STREAM = 3;
 //                     r_acc = acc; windows += 1; acc = cnt = 0
 constexpr unsigned long long AUG_GATE_STREAM = 4;
 constexpr unsigned long long COLOR_GATE_STREAM = 5;
+
+// ADA's geometric augmentations on D's input (dgeom.hip d_geom_kernel): x-flip, 90-degree turns, isotropic
+// scaling and arbitrary rotation, a bitmask of its own, applied between the color policy and AugPolicy's. Sample
+// n draws ONE Philox block, counter (n, step, GEOM_STREAM), of the step's z seed: flip = w0 >> 31, k = (w0 >> 29)
+// & 3, s = exp2(0.2 e) with e the even-lane Box-Muller normal of (w1, w2), theta = (float(w3 >> 8) 2^-24 - 0.5)
+// 2 pi -- always all four -- and records params float [8] = (m00, m01, m10, m11, s, theta, flip, k): M = F^flip
+// Q^k (1 / s) R(theta) over the effective policies, the map from output pixel to source point about the image's
+// centre, sampled bilinearly with reflected borders. Gates (ADA above): one block of GEOM_GATE_STREAM, bit i
+// on iff (w_i >> 8) < p24.
+enum GeomPolicy : int { GEOM_XFLIP = 1, GEOM_ROT90 = 2, GEOM_SCALE = 4, GEOM_ROTATE = 8, GEOM_ALL = 15 };
+constexpr unsigned long long GEOM_STREAM = 7;
+constexpr unsigned long long GEOM_GATE_STREAM = 8;
+constexpr int GEOM_PARAMS = 8;            // floats per params row
+constexpr float GEOM_LOG2_SIGMA = 0.2f;   // s = 2^(0.2 e): ADA's log-normal scale
+// the transpose enumerates reflection periods -GEOM_MAX_PERIODS..GEOM_MAX_PERIODS of the source plane: the
+// drawn matrices (1 / s <= 2.227, times sqrt 2 along a diagonal) stay inside -1..1
+constexpr int GEOM_MAX_PERIODS = 2;
 constexpr int ADA_ONE = 1 << 24;
 constexpr int ADA_MAX_INTERVAL = 1 << 16;
 constexpr int ADA_STATE_WORDS = 8;

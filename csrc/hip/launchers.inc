@@ -104,6 +104,14 @@ int DCG_API(dcg_d_augment)(const elem_t* x, elem_t* y, int* params, int N, int S
                            uint64_t seed, const unsigned long long* step, int* gates, const int* ada, hipStream_t s);
 int DCG_API(dcg_d_color)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy, int mode,
                          uint64_t seed, const unsigned long long* step, int* gates, const int* ada, hipStream_t s);
+// ADA's geometric augmentations (x-flip / 90-degree turns / scale / rotation, kernels.h GeomPolicy) of x
+// [N][S][S][C] into y, params float [N][8] = (m00, m01, m10, m11, s, theta, flip, k). mode 0: drawn from the
+// Philox stream (seed, *step, GEOM_STREAM) and written; 1: the matrix read from params as it is; 2: the exact
+// transpose of mode 1 (dcg_d_geom_bwd). gates / ada and -2 as above; a sample whose effective policy is 0 is copied
+int DCG_API(dcg_d_geom)(const elem_t* x, elem_t* y, float* params, int N, int S, int C, int policy, int mode,
+                        uint64_t seed, const unsigned long long* step, int* gates, const int* ada, hipStream_t s);
+int DCG_API(dcg_d_geom_bwd)(const elem_t* g, elem_t* gx, const float* params, const int* gates, int N, int S, int C,
+                            int policy, hipStream_t s);
 // one step of the ADA controller on state int32 [8] from the B real logits (fp32). -2: a null pointer, B < 1,
 // interval outside 1..2^16, B * interval >= 2^31, delta24 outside 1..2^24, |target_n| > B * interval, thr NaN
 int DCG_API(dcg_ada_update)(const float* logits, int B, int* state, float thr, int target_n, int delta24,

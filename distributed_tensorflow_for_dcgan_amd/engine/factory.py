@@ -103,7 +103,7 @@ class ReferenceEngine:
         B = self._real.shape[0]
         with torch.no_grad():
             out = self.step_impl.forward_losses(self._real, self._last_z, update_ema=False, record=rec, noise=False,
-                                                augment=False, color=False, topk=False)
+                                                augment=False, color=False, geom=False, topk=False)
         a = OrderedDict()
         a["z"] = self._last_z
         a["d"] = torch.sigmoid(out["logits_real"])
@@ -161,7 +161,7 @@ class ReferenceEngine:
         with torch.no_grad():
             out = self.step_impl.forward_losses(real.to(self.device, torch.float32), z.to(self.device),
                                                 update_ema=False, noise=False, augment=False, color=False,
-                                                topk=False)
+                                                geom=False, topk=False)
         return {"d_loss": float(out["d_loss"]), "g_loss": float(out["g_loss"])}
 
     def ada_status(self):

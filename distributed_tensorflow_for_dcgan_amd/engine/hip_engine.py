@@ -162,15 +162,18 @@ class _DStage(NamedTuple):
     # a DiffAugment stage: its Jacobian is not the identity, so the launch records what its transpose
     # (Program.<op>_bwd, recorded as <name>_bwd on the g_loss chain) replays for the fake half
     op: Optional[str] = None            # Program.<op>
-    params: Optional[str] = None        # its draws [2B][4] ...
+    params: Optional[str] = None        # its draws [2B][pwidth] ...
     pdtype: Optional[torch.dtype] = None  # ... of this type
     gates: Optional[str] = None         # under adaptive augmentation, its gate masks int32 [2B]
     grad: Optional[str] = None          # the image gradient [B] behind its transpose
+    pwidth: int = 4                     # entries of a row of its draws
 
 
-# in the order they run, the published one: color, then translation / cutout, then noise
+# in the order they run, the published one: color, then the geometric stages (ADA's resampling, DiffAugment's
+# translation / cutout), then noise
 D_STAGES = (
     _DStage("color", "d_colored", "d_color", "d_color", "color_params", torch.float32, "color_gates", "img_grad_c"),
+    _DStage("geom", "d_warped", "d_geom", "d_geom", "geom_params", torch.float32, "geom_gates", "img_grad_w", 8),
     _DStage("aug", "d_auged", "d_aug", "d_augment", "aug_params", torch.int32, "aug_gates", "img_grad_t"),
     _DStage("noise", "d_noisy", "d_noise"),
 )
@@ -231,7 +234,12 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # and writes the colored copy with (b, s, c, Mx); its Jacobian is a dense linear map per image,
         # which `d_color_bwd` applies transposed to the g_loss chain's image gradient, behind `d_aug_bwd`
         # and ahead of G's tanh backward.
-        # ada, adaptive augmentation probability (ops.reference.DAda): each selected policy of the two
+        # geom, ADA's geometric augmentations (ops.reference.DGeom), a third switch: D sees noise(translation_cutout(
+        # geom(color([real | fake])))). One recorded launch (`d_geom`) between `d_color` and `d_aug` draws (flip,
+        # k, s, theta) per sample from stream 7 of the step's z seed and the device step counter, and writes the
+        # resampled copy with the matrix it used; `d_geom_bwd` applies the exact transpose of that resampling to
+        # the g_loss chain's image gradient from the recorded matrices of the fake half.
+        # ada, adaptive augmentation probability (ops.reference.DAda): each selected policy of the three
         # switches above applies to a sample with probability p = p24 * 2^-24. `d_color` / `d_aug` are then
         # recorded as their gated kernels, which read p24 from the device state `ada_state` and record the
         # per-sample gate masks that the two `_bwd` ops replay. With a target, one more recorded launch per
@@ -338,8 +346,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         # layer 0 reads. ONE buffer for the sub-steps and the full step: each ends with its D chain (the
         # last reader) joined back into the main stream, where the next forward rewrites it
         # (schedule_check proves it: tests/test_instance_noise.py). A DiffAugment stage also keeps the
-        # draws [2B][4] its launch records -- int32 (ty, tx, oy, ox) of `d_aug`, float32 (b, s, c, Mx)
-        # of `d_color` -- and, under adaptive augmentation, the gate masks int32 [2B] its gated kernel
+        # draws its launch records -- int32 [2B][4] (ty, tx, oy, ox) of `d_aug`, float32 [2B][4] (b, s, c, Mx)
+        # of `d_color`, float32 [2B][8] (m00, m01, m10, m11, s, theta, flip, k) of `d_geom` -- and, under adaptive augmentation, the gate masks int32 [2B] its gated kernel
         # records (the effective policy per sample). Allocated last stage first, the controller's state
         # ahead of the gates: the order these buffers have always been allocated in, so that every buffer
         # of the process, this engine's and any later one's, keeps the address it had
@@ -347,7 +355,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
             on = getattr(self, st.opt).active
             setattr(self, st.out, torch.zeros_like(self.d_in) if on else None)
             if st.op:
-                setattr(self, st.params, t(B2, 4, dtype=st.pdtype, zero=True) if on else None)
+                setattr(self, st.params, t(B2, st.pwidth, dtype=st.pdtype, zero=True) if on else None)
         # adaptive augmentation: the controller's state int32 [8] = (p24, acc, cnt, r_acc, windows, 0, 0, 0)
         self.ada_state = None
         if self.ada.active:
@@ -816,7 +824,7 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         for st in self._d_stages() if noise else []:
             dst = getattr(self, st.out)
             if st.op:
-                # (adaptive augmentation: the gated kernels, gates from streams 5 / 4 against the live p24)
+                # (adaptive augmentation: the gated kernels, gates from streams 5 / 8 / 4 against the live p24)
                 gate = dict(gates=_p(getattr(self, st.gates)), ada_state=_p(self.ada_state)) if self.ada.active else {}
                 getattr(prog, st.op)(st.name, _p(prev), _p(dst), _p(getattr(self, st.params)), B2, cfg.output_size,
                                      cfg.c_dim, getattr(self, st.opt).mask, zseed, _p(self.step_counter), 0, **gate)
@@ -1092,7 +1100,8 @@ class HipEngine(HipDDPMixin, HipEngineAux):
         img_grad = self.img_grad
         for st in self._d_stages(transposed=True):
             # DiffAugment: dL/d(the stage's copy of the fake) -> dL/d(its input), the stage's transpose --
-            # the transposed gather of `d_aug`, the transposed color map under (s, c) of `d_color` -- over
+            # the transposed gather of `d_aug`, the transposed resampling of `d_geom`, the transposed color map
+            # under (s, c) of `d_color` -- over
             # the draws (and gates) the forward recorded for the fake half (rows B..2B-1)
             gx = getattr(self, st.grad)
             gate = dict(gates=_p(getattr(self, st.gates)[B:])) if self.ada.active else {}

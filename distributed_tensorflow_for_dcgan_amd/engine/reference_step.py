@@ -46,8 +46,11 @@ class ReferenceStep:
         # its color policy (ops.reference.DColor), ahead of translation / cutout: brightness, saturation,
         # contrast per sample, (b, s, c) from Philox stream 3 of the same seed at the global step
         self.color = o.color
+        # ADA's geometric stage (ops.reference.DGeom), between the two: x-flip, quarter turns, scale and
+        # rotation per sample as one bilinear resampling, its draws from Philox stream 7 of the same seed
+        self.geom = o.geom
         # adaptive augmentation probability (ops.reference.DAda): each selected policy applies to a sample
-        # iff its gate -- Philox streams 4 (translation, cutout) and 5 (color) of the same seed -- falls
+        # iff its gate -- Philox streams 4 (translation, cutout), 5 (color) and 8 (geometric) of the same seed -- falls
         # below p24; with a target, ``step`` steers p24 from its own real logits (ops.reference.ada_update),
         # `world` entering the step size only. D sub-steps gate with the live p24 and leave the state alone
         self.ada = o.ada
@@ -119,19 +122,30 @@ class ReferenceStep:
             return None
         return R.color_params(shape[0], R.substep_seed(self.noise_seed, sub), self.global_step)
 
+    def draw_geom(self, shape, sub: Optional[int] = None, gates=None) -> Optional[torch.Tensor]:
+        """The geometric stage's params float64 [2B, 8] = (m00, m01, m10, m11, s, theta, flip, k) over a [2B, S,
+        S, C] input at the current global step, the matrix that of the selected policies under `gates` (int
+        [2B] or None); None when the stage is off."""
+        if not self.geom.active:
+            return None
+        p = R.geom_params(shape[0], R.substep_seed(self.noise_seed, sub), self.global_step)
+        p[:, :4] = R.geom_matrix(p, self.geom, gates).reshape(-1, 4)
+        return p
+
     def draw_gates(self, n: int, sub: Optional[int] = None):
-        """(color gates, geometric gates), int32 [2B] each (None where that switch is off), at the current
-        global step and p24; None when no gate is active."""
+        """(color gates, translation / cutout gates, geometric-stage gates), int32 [2B] each (None where that
+        switch is off), at the current global step and p24; None when no gate is active."""
         if not self.ada.active:
             return None
         seed, p24 = R.substep_seed(self.noise_seed, sub), self.ada_state[0]
         cg = R.gate_masks(n, seed, self.global_step, R.COLOR_GATE_STREAM, p24, self.color.mask) if self.color.active else None
         ag = R.gate_masks(n, seed, self.global_step, R.AUG_GATE_STREAM, p24, self.aug.mask) if self.aug.active else None
-        return cg, ag
+        gg = R.gate_masks(n, seed, self.global_step, R.GEOM_GATE_STREAM, p24, self.geom.mask) if self.geom.active else None
+        return cg, ag, gg
 
     def forward_losses(self, real: torch.Tensor, z: torch.Tensor, Pg=None, Pd=None, update_ema=True,
                        record=None, update_ema_g=None, noise=None, sub: Optional[int] = None, augment=None,
-                       color=None, topk=None, gates=None):
+                       color=None, topk=None, gates=None, geom=None):
         """update_ema: D's BN moving averages; update_ema_g: G's (None = as D's). noise: the additive
         sigma * eps on D's input [2B, ...]; None = drawn (``draw_noise``, `sub` = the D sub-step) when
         instance noise is on; False = none (sample-time losses stay clean). augment: the params [2B, 4]
@@ -140,9 +154,11 @@ class ReferenceStep:
         (``draw_color``) when it is on; False = none. topk: the bool mask [B] of the fakes G learns from;
         None = the selection on this forward's own fake logits (``topk_k`` of them) when top-k is on; False
         = none. The result carries it as ``topk_sel`` (None when unused) beside ``g_loss_topk``, the mean
-        of G's loss over the selected (``g_loss`` itself when unused). gates: (color gates, geometric
-        gates) of adaptive augmentation, int [2B] each or None; None = drawn (``draw_gates``) when it is on;
-        False = none."""
+        of G's loss over the selected (``g_loss`` itself when unused). gates: (color gates, translation /
+        cutout gates[, geometric-stage gates]) of adaptive augmentation, int [2B] each or None; None = drawn
+        (``draw_gates``) when it is on; False = none. geom: the params [2B, 8] of the geometric stage with
+        their recorded matrix, applied between `color` and `augment`; None = drawn (``draw_geom``) when it
+        is on; False = none."""
         m = self.model
         if self.d_spectral_norm:  # D computes with W / sigma(W); autograd projects the gradient
             Pd = m.d_sn_weights(Pd)
@@ -152,11 +168,15 @@ class ReferenceStep:
         both = torch.cat([real, fake], 0)
         if gates is None:
             gates = self.draw_gates(both.shape[0], sub)
-        cg, ag = (None, None) if gates is None or gates is False else gates
+        cg, ag, gg = (None, None, None) if gates is None or gates is False else (tuple(gates) + (None,))[:3]
         if color is None:
             color = self.draw_color(both.shape, sub)
         if color is not None and color is not False:
             both = R.color_augment(both, color, self.color, gates=cg)
+        if geom is None:
+            geom = self.draw_geom(both.shape, sub, gg)
+        if geom is not None and geom is not False:
+            both = R.geom_augment(both, geom, self.geom, gates=gg)
         if augment is None:
             augment = self.draw_augment(both.shape, sub)
         if augment is not None and augment is not False:
@@ -180,14 +200,14 @@ class ReferenceStep:
                 "d_loss_fake": d_fake, "g_loss": g_loss, "d_loss": d_loss, "g_loss_topk": g_topk, "topk_sel": topk}
 
     def compute_grads(self, real: torch.Tensor, z: torch.Tensor, update_ema: bool = True, noise=None, augment=None,
-                      color=None, topk=None, gates=None):
+                      color=None, topk=None, gates=None, geom=None):
         """Returns (losses dict, flat D grads, flat G grads) without applying them. G's gradients are
         those of ``g_loss_topk`` (which is ``g_loss`` without a top-k selection)."""
         m = self.model
         Pg = {k: v.detach().clone().requires_grad_(True) for k, v in m.g.tensors.items()}
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
         out = self.forward_losses(real, z, Pg, Pd, update_ema=update_ema, noise=noise, augment=augment, color=color,
-                                  topk=topk, gates=gates)
+                                  topk=topk, gates=gates, geom=geom)
         d_names, g_names = m.d.names(), m.g.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], retain_graph=True,
                                  allow_unused=True)
@@ -203,14 +223,14 @@ class ReferenceStep:
         return out, gd_flat.flat, gg_flat.flat
 
     def compute_d_grads(self, real: torch.Tensor, z: torch.Tensor, noise=None, sub: Optional[int] = None,
-                        augment=None, color=None, gates=None):
+                        augment=None, color=None, gates=None, geom=None):
         """(losses dict, flat D grads) of a D sub-step: G's forward in training mode on batch
         statistics with its BN moving averages left alone, only d_loss differentiated, through D."""
         m = self.model
         Pd = {k: v.detach().clone().requires_grad_(True) for k, v in m.d.tensors.items()}
         out = self.forward_losses(real, z, None, Pd, update_ema=True, update_ema_g=False, noise=noise,
                                   sub=self._sub_k if sub is None else sub, augment=augment, color=color, topk=False,
-                                  gates=gates)
+                                  gates=gates, geom=geom)
         d_names = m.d.names()
         dg = torch.autograd.grad(out["d_loss"], [Pd[n] for n in d_names], allow_unused=True)
         gd_flat = m.d.like()
@@ -220,12 +240,13 @@ class ReferenceStep:
         return out, gd_flat.flat
 
     def d_step(self, real: torch.Tensor, z: torch.Tensor, noise=None, sub: Optional[int] = None,
-               augment=None, color=None, gates=None) -> Dict[str, float]:
+               augment=None, color=None, gates=None, geom=None) -> Dict[str, float]:
         """One D sub-step: a fresh z through G, D on [real | fake], the d_loss backward through D,
         TF-Adam(D) (D's beta powers advance) and the power step. Nothing of G changes -- parameters,
         Adam slots and powers, BN moving averages, weight EMA -- nor does the global step; D's BN
         moving averages (both slots) update as in a full step."""
-        out, gd = self.compute_d_grads(real, z, noise=noise, sub=sub, augment=augment, color=color, gates=gates)
+        out, gd = self.compute_d_grads(real, z, noise=noise, sub=sub, augment=augment, color=color, gates=gates,
+                                       geom=geom)
         self._sub_k += 1
         for s in range(2):
             self.model.d_bn.count_step(s)
@@ -248,10 +269,11 @@ class ReferenceStep:
                                       R.ada_delta24(self.ada_world, B, a.interval, a.kimg), a.interval)
 
     def step(self, real: torch.Tensor, z: torch.Tensor, noise=None, augment=None, color=None,
-             topk=None, gates=None) -> Dict[str, float]:
+             topk=None, gates=None, geom=None) -> Dict[str, float]:
         """topk: the mask of the fakes G learns from (an engine's recorded one); None = the reference's
         own selection when top-k is on; False = none."""
-        out, gd, gg = self.compute_grads(real, z, noise=noise, augment=augment, color=color, topk=topk, gates=gates)
+        out, gd, gg = self.compute_grads(real, z, noise=noise, augment=augment, color=color, topk=topk, gates=gates,
+                                         geom=geom)
         self.ada_step(out["logits_real"].detach())  # (follows the global step, whatever the update does)
         self._sub_k = 0
         for s in range(2):  # one EMA update per BN slot per step (as the HIP engine counts)

@@ -174,6 +174,7 @@ def check(cfg=None, batch_size: int = 8, dtype: str = "bf16", world: int = 1, sc
     ...: the d_noise op reads that counter too and writes the buffer D's layer 0 reads on two streams;
     d_augment: so does d_aug, whose recorded draws d_aug_bwd reads on the g_loss chain;
     d_color_augment: and d_color ahead of it, whose recorded (s, c) d_color_bwd reads behind d_aug_bwd;
+    d_geom_augment: and d_geom between the two, whose recorded matrices d_geom_bwd reads between theirs;
     g_topk, g_topk_steps: the g_topk op at the head of the G chain reads the logits, dl_g and that
     counter and writes the seed the g_loss chain starts from)."""
     import torch

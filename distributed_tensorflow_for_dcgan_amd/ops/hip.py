@@ -802,15 +802,22 @@ def _color_rows(op: str, params: torch.Tensor, params_out, N: int, device) -> to
     return p
 
 
+def _geom_rows(op: str, params: torch.Tensor, params_out, N: int, device) -> torch.Tensor:
+    if tuple(params.shape) != (N, 8) or not params.is_floating_point():
+        raise TypeError("%s: params must be a floating-point [N, 8]" % op)
+    return params.to(device=device, dtype=torch.float32).contiguous()
+
+
 class _DStage(NamedTuple):
     """A DiffAugment stage on D's input as the one-shot wrappers below see it: the draw and apply
     helpers read this and are the same code for every stage."""
     name: str           # of the wrappers in messages: <name>_draw, <name>_apply
     op: str             # Program.<op> / Program.<op>_bwd, recorded under the same names
-    dtype: torch.dtype  # of the params rows [N, 4]
+    dtype: torch.dtype  # of the params rows [N, width]
     check: str          # ops.reference's parser of a policy that is not yet the kernels' bitmask
     rows: object        # (op, params, params_out, N, device) -> the validated rows a probe / transpose reads
     gate_stream: int    # Philox stream of its gates (ops.reference.gate_masks)
+    width: int = 4      # entries of a params row
 
     def mask(self, policy) -> int:
         from . import reference as R
@@ -821,6 +828,7 @@ class _DStage(NamedTuple):
 
 _AUGMENT = _DStage("augment", "d_augment", torch.int32, "check_d_augment", _int_rows, 4)
 _COLOR = _DStage("color", "d_color", torch.float32, "check_d_color", _color_rows, 5)
+_GEOM = _DStage("geom", "d_geom", torch.float32, "check_d_geom", _geom_rows, 8, 8)
 
 
 def _stage_draw(st: _DStage, x, seed, step, policy, out, params_out, p24, gates_out):
@@ -832,9 +840,9 @@ def _stage_draw(st: _DStage, x, seed, step, policy, out, params_out, p24, gates_
     _check_step(op, step)
     N, S, C = x.shape[0], x.shape[1], x.shape[3]
     if params_out is None:
-        params_out = torch.empty(N, 4, device=x.device, dtype=st.dtype)
-    if params_out.dtype != st.dtype or tuple(params_out.shape) != (N, 4) or not params_out.is_contiguous():
-        raise TypeError("%s: params_out must be a contiguous %s [N, 4]" % (op, str(st.dtype).split(".")[-1]))
+        params_out = torch.empty(N, st.width, device=x.device, dtype=st.dtype)
+    if params_out.dtype != st.dtype or tuple(params_out.shape) != (N, st.width) or not params_out.is_contiguous():
+        raise TypeError("%s: params_out must be a contiguous %s [N, %d]" % (op, str(st.dtype).split(".")[-1], st.width))
     prog = ext().Program(_ELEM_DT[x.dtype])
     px, po = (_p(x), _p(out)) if x.numel() else (0, 0)
     record, pp = getattr(prog, st.op), _p(params_out) if N else 0
@@ -927,15 +935,44 @@ def color_apply(x: torch.Tensor, params: torch.Tensor, policy, transpose: bool =
     return _stage_apply(_COLOR, x, params, policy, transpose, out, params_out, gates)
 
 
+def geom_draw(x: torch.Tensor, seed: int, step, policy, out: Optional[torch.Tensor] = None,
+              params_out: Optional[torch.Tensor] = None, p24=None, gates_out: Optional[torch.Tensor] = None):
+    """ADA's geometric stage over x [N, S, S, C] as the training step runs it (d_geom_kernel): sample n draws
+    (flip, k, s, theta) from the Philox stream (seed, step, 7). Returns (y, params float32 [N, 8] = (m00, m01,
+    m10, m11, s, theta, flip, k)), the matrix that of the effective policies; policy: a DGeom, a policy list
+    ("xflip,rot90,scale,rotate") or the kernels' bitmask. Oracle: ops.reference.geom_augment on the recorded
+    matrix, ops.reference.geom_params / geom_matrix for the draws. p24: as ``augment_draw`` -- the gated
+    kernel, returns (y, params, gates int32 [N]) (oracle: ops.reference.gate_masks on stream 8)."""
+    return _stage_draw(_GEOM, x, seed, step, policy, out, params_out, p24, gates_out)
+
+
+def geom_params(n: int, seed: int, step, device="cuda") -> torch.Tensor:
+    """float32 [n, 8] as d_geom_kernel draws and records them for n samples under all four policies, over a
+    one-pixel dummy image of zeros (oracle: ops.reference.geom_params)."""
+    x = torch.zeros(int(n), 1, 1, 1, device=device, dtype=torch.bfloat16)
+    return geom_draw(x, seed, step, 15)[1]
+
+
+def geom_apply(x: torch.Tensor, params: torch.Tensor, geom, gates: Optional[torch.Tensor] = None,
+               transpose: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The geometric stage over x [N, S, S, C] under the matrices in columns 0..3 of given params [N, 8] (the
+    kernel's probe entry), or with transpose=True its exact transpose, the backward (d_geom_bwd). A sample whose
+    effective policy (`geom` & gates[n]) is 0 is copied. Oracles: ops.reference.geom_augment /
+    geom_augment_transpose."""
+    return _stage_apply(_GEOM, x, params, geom, transpose, out, None, gates)
+
+
 def gate_masks(n: int, seed: int, step, stream: int, p24, policy_mask: int, device="cuda") -> torch.Tensor:
     """int32 [n]: the gate masks the gated kernels record for n samples at p24 under `policy_mask` --
     stream 4: d_augment_kernel's (translation, cutout), stream 5: d_color_kernel's (brightness, saturation,
-    contrast) -- over dummy images of zeros. Oracle: ops.reference.gate_masks."""
-    for st in (_AUGMENT, _COLOR):
+    contrast), stream 8: d_geom_kernel's (xflip, rot90, scale, rotate) -- over dummy images of zeros. Oracle:
+    ops.reference.gate_masks."""
+    for st in (_AUGMENT, _COLOR, _GEOM):
         if st.gate_stream == int(stream):
             x = torch.zeros(int(n), 1, 1, 1, device=device, dtype=torch.bfloat16)
             return _stage_draw(st, x, seed, step, int(policy_mask), None, None, p24, None)[2]
-    raise ValueError("gate_masks: stream must be 4 (translation / cutout) or 5 (color), got %r" % (stream,))
+    raise ValueError("gate_masks: stream must be 4 (translation / cutout), 5 (color) or 8 (geometric), got %r"
+                     % (stream,))
 
 
 def ada_update(state: torch.Tensor, real_logits: torch.Tensor, thr: float, target_n: int, delta24: int,

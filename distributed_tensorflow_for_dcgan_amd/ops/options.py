@@ -82,7 +82,7 @@ TABLE: Dict[str, Group] = {g.fields[0]: g for g in (
     Group(("ada",), ("d_augment_p", "ada_target", "ada_interval", "ada_kimg"),
           ("DCGAN_D_AUGMENT_P", "DCGAN_ADA_TARGET", "DCGAN_ADA_INTERVAL", "DCGAN_ADA_KIMG"),
           (float, float, int, float), (-1.0, 0.0, 4, 500.0), R.check_ada, record=R.DAda,
-          context=lambda o, batch_size: {"augmented": o["aug"].active or o["color"].active,
+          context=lambda o, batch_size: {"augmented": o["aug"].active or o["color"].active or o["geom"].active,
                                          "batch_size": batch_size}),
     Group(("topk",), ("g_topk", "g_topk_steps"), ("DCGAN_G_TOPK", "DCGAN_G_TOPK_STEPS"), (float, int), (1.0, 0),
           R.check_g_topk, record=R.GTopK, steps="g_topk_steps", stand_in=lambda kw: 1),
@@ -93,9 +93,16 @@ TABLE: Dict[str, Group] = {g.fields[0]: g for g in (
           R.check_spectral_norm),
 )}
 
-KEYWORDS = frozenset(k for g in TABLE.values() for k in g.keywords)
-ENV_NAMES = tuple(n for g in TABLE.values() for n in g.env)
-ANNEALED = tuple(g for g in TABLE.values() if g.steps)
+# ADA's geometric stage, a row like TABLE's that every function below reads with them. It stands beside the
+# table: tests/test_options.py pins TABLE's keys to its own list of one non-default setting per row, and
+# tests/test_d_geom.py holds this row's. Resolved behind `color`, ahead of `ada`, whose check asks it.
+GEOM = Group(("geom",), ("d_geom_augment",), ("DCGAN_D_GEOM_AUGMENT",), (str,), ("",), R.check_d_geom)
+GROUPS: Tuple[Group, ...] = tuple(g for t in TABLE.values() for g in ((t, GEOM) if t.fields[0] == "color" else (t,)))
+BY_NAME: Dict[str, Group] = {g.fields[0]: g for g in GROUPS}
+
+KEYWORDS = frozenset(k for g in GROUPS for k in g.keywords)
+ENV_NAMES = tuple(n for g in GROUPS for n in g.env)
+ANNEALED = tuple(g for g in GROUPS if g.steps)
 
 
 class StepOptions(NamedTuple):
@@ -110,6 +117,7 @@ class StepOptions(NamedTuple):
     noise: R.InstanceNoise
     aug: R.DAugment
     color: R.DColor
+    geom: R.DGeom
     ada: R.DAda
     topk: R.GTopK
     g_ema_decay: float
@@ -129,7 +137,7 @@ def resolve(batch_size: Optional[int] = None, env: bool = True, lr: float = 2e-4
     its environment variable, then its default. Not env: one that is not given takes its default,
     and the environment is not read."""
     out: Dict[str, Any] = {"lr": float(lr), "beta1": float(beta1)}
-    for g in TABLE.values():
+    for g in GROUPS:
         res = g.resolve([keywords.pop(k, _UNSET) for k in g.keywords], env,
                         **(g.context(out, batch_size) if g.context else {}))
         out.update(zip(g.fields, res if len(g.fields) > 1 else (res,)))
@@ -139,8 +147,8 @@ def resolve(batch_size: Optional[int] = None, env: bool = True, lr: float = 2e-4
 
 
 def resolve_group(name: str, values, **context):
-    """One group of TABLE from the engines' arguments (None = the environment's default)."""
-    return TABLE[name].resolve(values, True, **context)
+    """One group of GROUPS from the engines' arguments (None = the environment's default)."""
+    return BY_NAME[name].resolve(values, True, **context)
 
 
 def open_ended(keywords: Dict[str, Any]) -> List[Group]:
@@ -152,7 +160,7 @@ def from_flags(flags, total_steps: Optional[int] = None) -> Dict[str, Any]:
     """The trainer's flags as engine keywords. An open-ended `*_steps` = 0 is resolved against
     `total_steps` when that is given; else it is left at 0 (see ``open_ended``)."""
     kw = {"lr": flags.learning_rate, "beta1": flags.beta1}
-    for g in TABLE.values():
+    for g in GROUPS:
         kw.update((k, getattr(flags, f)) for k, f in zip(g.keywords, g.flag_names))
     if total_steps is not None:
         for g in open_ended(kw):
@@ -164,7 +172,7 @@ def validate_flags(ns, error: Callable[[str], Any]) -> None:
     """Every group's validator over the parsed flags; a failure goes to `error` (which exits) as
     "--flag / --flag: message". An open-ended `*_steps` = 0 stays open: the trainer resolves it."""
     out: Dict[str, Any] = {"lr": ns.learning_rate}
-    for g in TABLE.values():
+    for g in GROUPS:
         context = g.context(out, ns.batch_size) if g.context else {}
         if g.steps:
             context["open_ended"] = True

@@ -767,6 +767,160 @@ def color_augment_transpose(g: torch.Tensor, params: torch.Tensor, color: DColor
     return v.to(g.dtype)
 
 
+# --------------------------------------------------------------------------- ADA's geometric augmentations
+GEOM_STREAM = 7       # Philox stream of the geometric draws (0..6 are taken)
+GEOM_GATE_STREAM = 8  # ... and of their gates: xflip (w0), rot90 (w1), scale (w2), rotate (w3)
+GEOM_POLICIES = ("xflip", "rot90", "scale", "rotate")  # bit i of the kernels' mask (kernels.h GeomPolicy)
+GEOM_LOG2_SIGMA = 0.2  # s = 2^(0.2 e), e ~ N(0, 1): ADA's log-normal isotropic scale
+GEOM_PARAMS = 8        # columns of a params row: (m00, m01, m10, m11, s, theta, flip, k)
+
+
+class DGeom(NamedTuple):
+    """The pixel blitting and general geometric transformations of ADA (Karras et al. 2020) on what D
+    sees, reals and fakes alike, between the color policy and translation / cutout: per sample an
+    x-flip, k quarter turns, an isotropic scale s (log-normal) and a rotation by theta (uniform), as
+    one bilinear resampling with reflected borders. Each is switched on its own."""
+    xflip: bool = False
+    rot90: bool = False
+    scale: bool = False
+    rotate: bool = False
+
+    @property
+    def active(self) -> bool:
+        return any(self)
+
+    @property
+    def mask(self) -> int:
+        """The kernels' policy bitmask."""
+        return sum(int(on) << i for i, on in enumerate(self))
+
+    def describe(self) -> str:
+        return ",".join(n for n, on in zip(GEOM_POLICIES, self) if on) or "off"
+
+
+def check_d_geom(spec="") -> DGeom:
+    """Validated DGeom from a comma-separated list of xflip, rot90, scale, rotate (any subset, any order);
+    "" and "none" mean off. Anything else is a ValueError naming the offending token."""
+    return _check_policy_list("d_geom_augment", DGeom, GEOM_POLICIES, spec)
+
+
+def resolve_d_geom(spec=None) -> DGeom:
+    """check_d_geom over the engines' argument: None = the environment default DCGAN_D_GEOM_AUGMENT,
+    then off. An explicit argument wins."""
+    from .options import resolve_group
+    return resolve_group("geom", (spec,))
+
+
+def geom_matrix(params: torch.Tensor, geom: DGeom, gates=None) -> torch.Tensor:
+    """float64 [N, 2, 2]: M = F^flip Q^k (1 / s) R(theta) of the draws in columns 4..7 of params [N, 8],
+    F = [[-1, 0], [0, 1]], Q = [[0, -1], [1, 0]], R = [[cos, -sin], [sin, cos]] -- the map from output
+    pixel to source point about the image's centre. A factor whose policy is off in ``geom.mask &
+    gates[n]`` (gates None: in ``geom.mask``) is the identity."""
+    p = torch.as_tensor(params).to(torch.float64)
+    if p.dim() != 2 or p.shape[1] != GEOM_PARAMS:
+        raise ValueError("geom_matrix: params must be [N, 8], got %s" % (tuple(p.shape),))
+    N = p.shape[0]
+    eff = torch.full((N,), geom.mask, dtype=torch.int64) if gates is None else _gate_rows(gates, N, geom.mask, "cpu")
+    on = [((eff >> i) & 1).bool().to(p.device) for i in range(4)]
+    s, theta, flip, k = p[:, 4], p[:, 5], p[:, 6], p[:, 7]
+    one, zero = torch.ones_like(s), torch.zeros_like(s)
+    a = torch.where(on[2], 1.0 / s, one)
+    th = torch.where(on[3], theta, zero)
+    M = a[:, None, None] * torch.stack([torch.cos(th), -torch.sin(th), torch.sin(th), torch.cos(th)], -1).view(N, 2, 2)
+    quarter = torch.where(on[1], k, zero).round().long() % 4   # Q^k = R(k pi / 2), in integers
+    qc = torch.tensor([1.0, 0.0, -1.0, 0.0], dtype=torch.float64, device=p.device)[quarter]
+    qs = torch.tensor([0.0, 1.0, 0.0, -1.0], dtype=torch.float64, device=p.device)[quarter]
+    M = torch.stack([qc, -qs, qs, qc], -1).view(N, 2, 2) @ M
+    fl = torch.where(on[0] & (flip != 0), -one, one)
+    return torch.stack([fl, zero, zero, one], -1).view(N, 2, 2) @ M
+
+
+def geom_params(n: int, seed: int, step: int) -> torch.Tensor:
+    """float64 [n, 8] = (m00, m01, m10, m11, s, theta, flip, k) of samples 0..n-1: sample i takes the words
+    w0..w3 of the Philox block at counter (i, step, GEOM_STREAM) under `seed`; flip = w0 >> 31, k = (w0 >>
+    29) & 3 quarter turns, s = 2^(0.2 e) with e the even-lane Box-Muller normal of (w1, w2) as
+    ``philox_normal`` forms it (|e| <= 5.77: s in [0.449, 2.226]), theta = (float(w3 >> 8) 2^-24 - 0.5) 2 pi.
+    All four are always drawn; the matrix columns are ``geom_matrix`` under all four policies."""
+    import numpy as np
+    w = philox_words(4 * int(n), seed, step, GEOM_STREAM)[:int(n)]
+    u0 = ((w[:, 1] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    u1 = (w[:, 2] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+    e = np.sqrt(-2.0 * np.log(u0)) * np.cos(2.0 * math.pi * u1)
+    out = np.zeros((int(n), GEOM_PARAMS), dtype=np.float64)
+    out[:, 4] = np.exp2(float(np.float32(GEOM_LOG2_SIGMA)) * e)
+    out[:, 5] = ((w[:, 3] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24 - 0.5) * (2.0 * math.pi)
+    out[:, 6] = (w[:, 0] >> np.uint32(31)).astype(np.float64)
+    out[:, 7] = ((w[:, 0] >> np.uint32(29)) & np.uint32(3)).astype(np.float64)
+    p = torch.from_numpy(out)
+    p[:, :4] = geom_matrix(p, DGeom(True, True, True, True)).reshape(-1, 4)
+    return p
+
+
+def _geom_taps(x: torch.Tensor, params, geom: DGeom, gates):
+    """(ct, n, y0, y1, x0, x1, fy, fx) of the resampling of x [N, S, S, C] under the RECORDED matrices in
+    columns 0..3 of params [N, 8] (the identity where ``geom.mask & gates[n]`` is 0): the taps int64 [N, S,
+    S] and weights [N, S, S, 1] in ct = x's dtype where that is fp32 / fp64, else fp32."""
+    if x.dim() != 4 or x.shape[1] != x.shape[2]:
+        raise ValueError("geom_augment: x must be [N, S, S, C], got %s" % (tuple(x.shape),))
+    N, S = x.shape[0], x.shape[1]
+    ct = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32
+    p = torch.as_tensor(params).to(device=x.device, dtype=ct)
+    if tuple(p.shape) != (N, GEOM_PARAMS):
+        raise ValueError("geom_augment: params must be [N, 8] = (m00, m01, m10, m11, s, theta, flip, k), got %s"
+                         % (tuple(p.shape),))
+    M = p[:, :4]
+    if gates is not None:
+        eye = torch.tensor([1.0, 0.0, 0.0, 1.0], dtype=ct, device=x.device)
+        M = torch.where((_gate_rows(gates, N, geom.mask, x.device) != 0)[:, None], M, eye)
+    c = (S - 1) / 2.0
+    a = torch.arange(S, device=x.device, dtype=ct) - c
+    u, v = a[None, None, :], a[None, :, None]
+
+    def axis(m0, m1):  # fold(m0 u + m1 v + c) and its two taps
+        s = m0[:, None, None] * u + m1[:, None, None] * v + c
+        T = 2.0 * (S - 1)
+        m = torch.remainder(s, T) if S > 1 else torch.zeros_like(s)
+        f = torch.where(m > S - 1, T - m, m).clamp(0, S - 1)
+        i0 = torch.floor(f)
+        return i0.long(), (i0.long() + 1).clamp(max=S - 1), (f - i0)[..., None]
+
+    x0, x1, fx = axis(M[:, 0], M[:, 1])
+    y0, y1, fy = axis(M[:, 2], M[:, 3])
+    return ct, torch.arange(N, device=x.device)[:, None, None], y0, y1, x0, x1, fy, fx
+
+
+def geom_augment(x: torch.Tensor, params: torch.Tensor, geom: DGeom, gates=None) -> torch.Tensor:
+    """The geometric stage over x [N, S, S, C] (NHWC) under params [N, 8], whose columns 0..3 hold the
+    matrix M as RECORDED (the device's exp2 / sincos are not the CPU's; ``geom_matrix`` checks the draw-to-
+    matrix step on its own). With c = (S - 1) / 2, output pixel (i, j) reads the source point
+
+        xs = m00 (j - c) + m01 (i - c) + c,   ys = m10 (j - c) + m11 (i - c) + c
+
+    folded by reflect-101 over any number of periods (m = x mod 2 (S - 1); m > S - 1 -> 2 (S - 1) - m) and
+    sampled bilinearly: x0 = floor, fx the fraction, x1 = min(x0 + 1, S - 1), the same in y; the result is
+    rounded once to x's dtype. A matrix of 0 and +-1 (xflip / rot90 alone) moves pixels bit for bit: k
+    quarter turns are ``torch.rot90(x, k, (1, 2))`` (counter-clockwise on the screen), after the flip
+    ``torch.flip(x, (2,))``. Index arithmetic throughout, so autograd gives the transpose. gates: int [N],
+    the recorded gate masks of adaptive augmentation: a sample with ``geom.mask & gates[n] == 0`` is the
+    identity. None: every sample under its matrix."""
+    ct, n, y0, y1, x0, x1, fy, fx = _geom_taps(x, params, geom, gates)
+    xc = x.to(ct)
+    top = (1 - fx) * xc[n, y0, x0] + fx * xc[n, y0, x1]
+    bot = (1 - fx) * xc[n, y1, x0] + fx * xc[n, y1, x1]
+    return ((1 - fy) * top + fy * bot).to(x.dtype)
+
+
+def geom_augment_transpose(g: torch.Tensor, params: torch.Tensor, geom: DGeom, gates=None) -> torch.Tensor:
+    """The transpose of ``geom_augment`` written out: every output pixel adds w * g to its four taps."""
+    ct, n, y0, y1, x0, x1, fy, fx = _geom_taps(g, params, geom, gates)
+    gc, out = g.to(ct), torch.zeros(g.shape, dtype=ct, device=g.device)
+    n = n.expand(y0.shape)
+    for yy, wy in ((y0, 1 - fy), (y1, fy)):
+        for xx, wx in ((x0, 1 - fx), (x1, fx)):
+            out.index_put_((n, yy, xx), wy * wx * gc, accumulate=True)
+    return out.to(g.dtype)
+
+
 # --------------------------------------------------------------------------- adaptive augmentation (ADA)
 AUG_GATE_STREAM = 4    # Philox stream of the gates of translation (w0) and cutout (w1)
 COLOR_GATE_STREAM = 5  # ... and of brightness (w0), saturation (w1), contrast (w2)
@@ -778,7 +932,7 @@ ADA_KEYS = ("p24", "acc", "cnt", "r_acc", "windows")  # the checkpoint's ada/<ke
 
 class DAda(NamedTuple):
     """Adaptive discriminator augmentation (Karras et al. 2020): every selected policy of DAugment /
-    DColor is applied to a sample with probability p, and p is steered by r_t = E[sign(D(real))] over
+    DColor / DGeom is applied to a sample with probability p, and p is steered by r_t = E[sign(D(real))] over
     windows of `interval` steps: up by a fixed step while r_t is above `target`, down while below,
     sized so that p can cross [0, 1] in `kimg` thousand real images. p is kept as the integer p24 = p *
     2^24, so the gate, the controller and a resume are exact. target = 0: a fixed p (p = 1: off, no
@@ -810,8 +964,9 @@ def check_ada(p=-1.0, target=0.0, interval=4, kimg=500.0, augmented: Optional[bo
               batch_size: Optional[int] = None) -> DAda:
     """Validated DAda; errors name the flag. p = -1 resolves to 1 without a target (off) and to 0 with
     one (the published start); else 0 <= p <= 1. 0 <= target < 1 (0 = no controller), interval in 1 ..
-    2^16, kimg > 0 and finite; batch_size (when given) * interval < 2^31. augmented=False: neither
-    d_augment nor d_color_augment selects a policy -- an error when a gate or the controller is on."""
+    2^16, kimg > 0 and finite; batch_size (when given) * interval < 2^31. augmented=False: none of
+    d_augment, d_color_augment and d_geom_augment selects a policy -- an error when a gate or the controller
+    is on."""
     if isinstance(p, DAda):
         p, target, interval, kimg = p
     try:
@@ -833,7 +988,8 @@ def check_ada(p=-1.0, target=0.0, interval=4, kimg=500.0, augmented: Optional[bo
         raise ValueError("ada_interval: batch_size * ada_interval must stay below 2^31, got %d * %d"
                          % (int(batch_size), interval))
     if ada.active and augmented is False:
-        raise ValueError("d_augment_p / ada_target need a policy to gate: set d_augment and / or d_color_augment")
+        raise ValueError("d_augment_p / ada_target need a policy to gate: set d_augment, d_color_augment and / or "
+                         "d_geom_augment")
     return ada
 
 
@@ -887,7 +1043,7 @@ def gate_masks(n: int, seed: int, step: int, stream: int, p24: int, policy_mask:
     import numpy as np
     w = philox_words(4 * int(n), seed, step, stream)[:int(n)].astype(np.int64) >> 8
     m = np.zeros(int(n), dtype=np.int64)
-    for k in range(3):
+    for k in range(4):
         m |= (w[:, k] < int(p24)).astype(np.int64) << k
     return torch.from_numpy((m & int(policy_mask)).astype(np.int32))
 

@@ -213,6 +213,10 @@ def run(flags: Flags, out=None) -> int:
         if color is not None and color.active:
             print("color augmentation of D's inputs: %s (reals and fakes, ahead of translation / cutout, a fresh "
                   "draw per sample and step)" % color.describe(), file=out, flush=True)
+        geom = getattr(engine, "geom", None)
+        if geom is not None and geom.active:
+            print("geometric augmentation of D's inputs: %s (reals and fakes, between color and translation / "
+                  "cutout, a fresh draw per sample and step)" % geom.describe(), file=out, flush=True)
         ada = getattr(engine, "ada", None)
         if ada is not None and ada.active:
             print("augmentation probability of D's inputs: %s (each selected policy gated per sample)"

@@ -121,7 +121,12 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
     ("d_color_augment", "str", "", "DiffAugment's color policy on the discriminator's inputs, ahead of --d_augment: "
                                       "a comma-separated list of brightness, saturation and contrast, each drawn per "
                                       "sample and step; empty or none turns it off"),
-    ("d_augment_p", "float", -1.0, "probability of each policy selected by --d_augment / --d_color_augment per sample, "
+    ("d_geom_augment", "str", "", "ADA's geometric augmentations of the discriminator's inputs, between "
+                                     "--d_color_augment and --d_augment: a comma-separated list of xflip, rot90, scale "
+                                     "(log-normal, isotropic) and rotate (uniform angle), one bilinear resampling with "
+                                     "reflected borders drawn per sample and step; empty or none turns it off"),
+    ("d_augment_p", "float", -1.0, "probability of each policy selected by --d_augment / --d_color_augment / "
+                                   "--d_geom_augment per sample, "
                                    "0 <= p <= 1. -1: 1 without --ada_target (every policy on every sample) and 0 with "
                                    "it (the start of the adaptive run); a value below 1 without --ada_target is a fixed p"),
     ("ada_target", "float", 0.0, "adaptive augmentation probability (ADA): the target for r_t = E[sign(D(real))], "
