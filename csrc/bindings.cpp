@@ -1424,6 +1424,17 @@ class Program {
                                    P<const float>(ref), P<double>(partial), N, J, st);
     }, AccList().r(src0, b).w(dst0, b).r(src1, b).w(dst1, b).r(ref, b).w(partial, (size_t)J * 8).v);
   }
+  // the same for N in (32768, 2^21], one column set: src sorted into dst (may be 0) by the global merge sort through
+  // the key buffers keys0, keys1 uint32 [J][N]; with the sorted columns `other`, partial double [J] = sum_i |sorted -
+  // other| through tilepart double [J][N / SWD_MERGE_TILE] (other, tilepart, partial: all or none)
+  int swd_sort_large(std::string name, uintptr_t src, uintptr_t dst, uintptr_t other, uintptr_t keys0, uintptr_t keys1,
+                     uintptr_t tilepart, uintptr_t partial, int N, int J, int stream) {
+    const size_t b = (size_t)J * N * 4, tb = (size_t)J * (N / SWD_MERGE_TILE) * 8;
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_swd_sort_large(P<const float>(src), P<float>(dst), P<const float>(other), P<uint32_t>(keys0),
+                                P<uint32_t>(keys1), P<double>(tilepart), P<double>(partial), N, J, st);
+    }, AccList().r(src, b).w(dst, b).r(other, b).w(keys0, b).w(keys1, b).w(tilepart, tb).w(partial, (size_t)J * 8).v);
+  }
   int swd_mean(std::string name, uintptr_t partial, uintptr_t out, int N, int J, int stream) {
     return add(name, stream, [=](hipStream_t st) { return dcg_swd_mean(P<const double>(partial), P<double>(out), N, J, st); },
                AccList().r(partial, (size_t)J * 8).w(out, 8).v);
@@ -1507,6 +1518,9 @@ PYBIND11_MODULE(_dcgan_hip, m) {
   });
   m.def("swd_kpad", &swd_kpad);  // k depth of the projection's theta' rows for C channels
   m.attr("SWD_FUSED_ROWS") = (int)SWD_FUSED_ROWS;
+  m.attr("SWD_GLOBAL_MAX_ROWS") = (int)SWD_GLOBAL_MAX_ROWS;  // N of swd_sort_large: (32768, 2^21]
+  m.attr("SWD_CHUNK_ROWS") = (int)SWD_CHUNK_ROWS;
+  m.attr("SWD_MERGE_TILE") = (int)SWD_MERGE_TILE;
   m.attr("OP_LAUNCH") = (int)OP_LAUNCH;
   m.attr("OP_RECORD") = (int)OP_RECORD;
   m.attr("OP_WAIT") = (int)OP_WAIT;
@@ -1669,5 +1683,6 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("swd_prepare", &Program::swd_prepare)
       .def("swd_project", &Program::swd_project)
       .def("swd_sort_distance", &Program::swd_sort_distance)
+      .def("swd_sort_large", &Program::swd_sort_large)
       .def("swd_mean", &Program::swd_mean);
 }

@@ -8,6 +8,9 @@
 constexpr unsigned long long SWD_STREAM = 6;      // Philox stream of the patch centres (0..5 are taken)
 constexpr int SWD_MIN_ROWS = 16, SWD_MAX_ROWS = 32768;  // N: descriptors per set and level (a power of two)
 constexpr int SWD_FUSED_ROWS = 16384;             // up to here two columns share the sort's LDS
+constexpr int SWD_GLOBAL_MAX_ROWS = 1 << 21;      // N of the global merge sort: above SWD_MAX_ROWS, a power of two
+constexpr int SWD_CHUNK_ROWS = 16384;             // its LDS-sorted runs: 64 KB, two workgroups per CU
+constexpr int SWD_MERGE_TILE = 4096;              // output keys per workgroup of a merge pass (256 threads x 16)
 constexpr int SWD_MAX_CH = 4;                     // channels
 constexpr int SWD_MAX_DIRS = 1024;                // J = repeats * dirs (a multiple of 128)
 constexpr int SWD_STAT_ROWS = 256;                // descriptors per block of the statistics' first pass
@@ -42,6 +45,12 @@ int dcg_swd_project(const float* l, const int* cen, const float* thetap, const f
 // partial[j] = sum_i |sorted0[i] - other[i]|, other = sorted1, else the sorted column ref[j] (partial may be null)
 int dcg_swd_sort_distance(const float* src0, float* dst0, const float* src1, float* dst1, const float* ref,
                           double* partial, int N, int J, hipStream_t st);
+// The same for N in (32768, 2^21]: runs of SWD_CHUNK_ROWS sorted in LDS, then log2(N / SWD_CHUNK_ROWS) merge-path
+// passes between the key buffers keys0, keys1 uint32 [J][N]. src[j] sorted -> dst[j] (dst may be null); with the
+// sorted columns `other` [J][N]: partial[j] = sum_i |sorted[i] - other[j][i]| through tilepart double
+// [J][N / SWD_MERGE_TILE] (other, tilepart and partial are given together or not at all). Buffers 16-byte aligned
+int dcg_swd_sort_large(const float* src, float* dst, const float* other, uint32_t* keys0, uint32_t* keys1,
+                       double* tilepart, double* partial, int N, int J, hipStream_t st);
 // out[0] = 1000 * sum_j partial[j] / (J * N), the partials added in index order
 int dcg_swd_mean(const double* partial, double* out, int N, int J, hipStream_t st);
 }

@@ -23,7 +23,15 @@
 //   swd_sort       one workgroup of 1024 threads per direction: the column through topk's monotone uint32
 //                  key into LDS, a bitonic network there, the sorted column kept; N <= 16384: two columns at
 //                  once. Then sum_i |a_i - b_i| against the second column or a stored sorted one, per-thread
-//                  strided fp64 sums and an LDS tree: a fixed order
+//                  strided fp64 sums and an LDS tree: a fixed order. N <= 32768, what one workgroup's LDS holds
+//   swd_sort_chunks, swd_merge, swd_tile_sum   N in (32768, 2^21]: runs of 16384 keys sorted by the same network
+//                  (64 KB of LDS, two workgroups per CU), then log2(N / 16384) merge passes between two key
+//                  buffers. A pass is split by merge path: a workgroup owns 4096 output keys of one pair of runs,
+//                  two of its waves find the tile's co-ranks by binary search in memory, the 4096 input keys go
+//                  to LDS, every thread finds its own co-rank there and merges 16 keys in registers (the left
+//                  run first among equals), and the tile leaves through LDS in 16-byte words. The last pass
+//                  stores floats (only if asked to) and sums |a - b| against the other sorted column: per
+//                  thread in index order, an LDS tree per tile, the tiles' partials added in index order
 //   swd_mean       1000 x the mean of the J partials, added in index order
 #include "common.h"
 #include "swd.h"
@@ -320,18 +328,9 @@ __device__ __forceinline__ float swd_unkey(uint32_t k) {
   return __builtin_bit_cast(float, k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
 
-__global__ __launch_bounds__(1024) void swd_sort_kernel(const float* __restrict__ src0, float* __restrict__ dst0,
-                                                        const float* __restrict__ src1, float* __restrict__ dst1,
-                                                        const float* __restrict__ ref, double* __restrict__ partial,
-                                                        int N) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t keys[];  // [1 or 2][N], then double red[1024]
-  const int tid = threadIdx.x, nset = src1 ? 2 : 1, half = N >> 1;
-  const size_t col = (size_t)blockIdx.x * N;
-  double* red = reinterpret_cast<double*>(keys + nset * N);
-  for (int i = tid; i < N; i += 1024) {
-    keys[i] = swd_key(src0[col + i]);
-    if (src1) keys[N + i] = swd_key(src1[col + i]);
-  }
+// the bitonic network over keys [nset][N] in LDS, 1024 threads; the caller synchronises before it reads the keys
+__device__ __forceinline__ void swd_bitonic(uint32_t* keys, int N, int nset, int tid) {
+  const int half = N >> 1;
   for (int k = 2; k <= N; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
       __syncthreads();
@@ -345,6 +344,21 @@ __global__ __launch_bounds__(1024) void swd_sort_kernel(const float* __restrict_
         }
       }
     }
+}
+
+__global__ __launch_bounds__(1024) void swd_sort_kernel(const float* __restrict__ src0, float* __restrict__ dst0,
+                                                        const float* __restrict__ src1, float* __restrict__ dst1,
+                                                        const float* __restrict__ ref, double* __restrict__ partial,
+                                                        int N) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t keys[];  // [1 or 2][N], then double red[1024]
+  const int tid = threadIdx.x, nset = src1 ? 2 : 1;
+  const size_t col = (size_t)blockIdx.x * N;
+  double* red = reinterpret_cast<double*>(keys + nset * N);
+  for (int i = tid; i < N; i += 1024) {
+    keys[i] = swd_key(src0[col + i]);
+    if (src1) keys[N + i] = swd_key(src1[col + i]);
+  }
+  swd_bitonic(keys, N, nset, tid);
   __syncthreads();
   double acc = 0.0;
   for (int i = tid; i < N; i += 1024) {
@@ -367,6 +381,130 @@ __global__ __launch_bounds__(1024) void swd_sort_kernel(const float* __restrict_
     __syncthreads();
   }
   if (tid == 0) partial[blockIdx.x] = red[0];
+}
+
+// ---------------------------------------------------------------- global merge sort (N > SWD_MAX_ROWS)
+// runs: workgroup (c, j) sorts keys [c T, (c + 1) T) of column j in LDS and writes them as uint32 keys
+__global__ __launch_bounds__(1024) void swd_sort_chunks_kernel(const float* __restrict__ src,
+                                                               uint32_t* __restrict__ keys_out, int N, int T) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t keys[];  // [T]
+  const int tid = threadIdx.x;
+  const size_t off = (size_t)blockIdx.y * N + (size_t)blockIdx.x * T;
+  for (int i = 4 * tid; i < T; i += 4096) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(src + off + i);
+    *reinterpret_cast<u32x4*>(keys + i) = (u32x4){swd_key(v[0]), swd_key(v[1]), swd_key(v[2]), swd_key(v[3])};
+  }
+  swd_bitonic(keys, T, 1, tid);
+  __syncthreads();
+  for (int i = 4 * tid; i < T; i += 4096)
+    *reinterpret_cast<u32x4*>(keys_out + off + i) = *reinterpret_cast<const u32x4*>(keys + i);
+}
+
+constexpr int SWD_MERGE_E = SWD_MERGE_TILE / 256;  // keys a thread merges serially
+// LDS word of key i while threads merge: thread t walks its two runs from about 8 t words on (E / 2 of either run
+// per thread on average), which alone would put a wave on 4 of the 32 banks; one pad word per 8 makes that
+// 9 t -- every lane of a half-wave on a bank of its own when the runs interleave evenly
+__device__ __forceinline__ int swd_pad_merge(int i) { return i + (i >> 3); }
+// ... and while the merged tile goes out: thread t stores its 16 keys as four 16-byte words from word 20 t on (4 pad
+// words per 16: eight lanes' 16-byte stores cover all 32 banks once), and reads 16-byte word v back at 4 v + 4 (v >> 2)
+__device__ __forceinline__ int swd_pad_out(int i) { return i + ((i >> 4) << 2); }
+constexpr int SWD_MERGE_LDS = SWD_MERGE_TILE + SWD_MERGE_TILE / 4;  // words: the larger of the two layouts
+
+// merge path: how many of the first d keys of merge(A [na], B [nb]) come from A, A first among equal keys.
+// Reads A[i] for i in [max(0, d - nb), min(d, na)) and B[d - 1 - i] only
+template <class FA, class FB>
+__device__ __forceinline__ int swd_corank(int d, int na, int nb, FA A, FB B) {
+  int lo = max(0, d - nb), hi = min(d, na);
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (A(mid) <= B(d - 1 - mid)) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// One pass: the sorted runs [2 q L, (2 q + 1) L) and [(2 q + 1) L, (2 q + 2) L) of column j of `in` merged; workgroup
+// (t, j) makes output keys [t M, (t + 1) M), M = SWD_MERGE_TILE. LAST (2 L = N): the keys go out as floats to dst (if
+// given) and, with `other`, tilepart[j][t] = sum |sorted - other| over the tile, per thread in index order, then a tree
+template <bool LAST>
+__global__ __launch_bounds__(256) void swd_merge_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                        float* __restrict__ dst, const float* __restrict__ other,
+                                                        double* __restrict__ tilepart, int N, int L) {
+  __shared__ __attribute__((aligned(16))) uint32_t buf[SWD_MERGE_LDS];
+  __shared__ int split[2];
+  constexpr int M = SWD_MERGE_TILE, E = SWD_MERGE_E;
+  const int tid = threadIdx.x;
+  const size_t col = (size_t)blockIdx.y * N;
+  const int pos = blockIdx.x * M, base = pos & ~(2 * L - 1), d0 = pos - base;
+  const uint32_t* __restrict__ A = in + col + base;
+  const uint32_t* __restrict__ B = A + L;
+  if (tid == 0 || tid == 64)  // the tile's two diagonals, each a chain of dependent global loads: one wave each
+    split[tid >> 6] = swd_corank(d0 + (tid ? M : 0), L, L, [&](int i) { return A[i]; }, [&](int i) { return B[i]; });
+  __syncthreads();
+  const int a0 = split[0], na = split[1] - a0, b0 = d0 - a0, nb = M - na;
+  for (int i = tid; i < M; i += 256) buf[swd_pad_merge(i)] = i < na ? A[a0 + i] : B[b0 + (i - na)];
+  __syncthreads();
+  auto la = [&](int i) { return buf[swd_pad_merge(i)]; };
+  auto lb = [&](int i) { return buf[swd_pad_merge(na + i)]; };
+  uint32_t r[E];
+  {
+    int i = swd_corank(tid * E, na, nb, la, lb), j = tid * E - i;
+    uint32_t ka = i < na ? la(i) : 0u, kb = j < nb ? lb(j) : 0u;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {  // (M - tid E >= E keys are left: the two runs never end together before e = E)
+      const bool ta = j >= nb || (i < na && ka <= kb);
+      r[e] = ta ? ka : kb;
+      if (ta) {
+        ++i;
+        ka = i < na ? la(i) : 0u;
+      } else {
+        ++j;
+        kb = j < nb ? lb(j) : 0u;
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < E / 4; ++q)
+    *reinterpret_cast<u32x4*>(buf + swd_pad_out(tid * E + 4 * q)) = (u32x4){r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]};
+  __syncthreads();
+  const size_t o = col + pos;
+  double acc = 0.0;
+#pragma unroll
+  for (int w = 0; w < M / 1024; ++w) {
+    const int v = 4 * (tid + 256 * w);
+    const u32x4 k = *reinterpret_cast<const u32x4*>(buf + swd_pad_out(v));
+    if (!LAST) {
+      *reinterpret_cast<u32x4*>(out + o + v) = k;
+    } else {
+      const f32x4 a = (f32x4){swd_unkey(k[0]), swd_unkey(k[1]), swd_unkey(k[2]), swd_unkey(k[3])};
+      if (dst) *reinterpret_cast<f32x4*>(dst + o + v) = a;
+      if (other) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(other + o + v);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc += (double)fabsf(a[q] - b[q]);
+      }
+    }
+  }
+  if (LAST && other) {
+    __shared__ double red[256];
+    red[tid] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+      if (tid < h) red[tid] += red[tid + h];
+      __syncthreads();
+    }
+    if (tid == 0) tilepart[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+  }
+}
+
+// partial[j] = the column's tile partials, added in index order
+__global__ __launch_bounds__(64) void swd_tile_sum_kernel(const double* __restrict__ tilepart, double* __restrict__ partial,
+                                                          int tiles, int J) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= J) return;
+  double s = 0.0;
+  for (int t = 0; t < tiles; ++t) s += tilepart[(size_t)j * tiles + t];
+  partial[j] = s;
 }
 
 __global__ __launch_bounds__(256) void swd_mean_kernel(const double* __restrict__ partial, double* __restrict__ out,
@@ -393,7 +531,7 @@ static bool swd_images_ok(int n, int s, int C, int halo, int rows) {
 
 static bool swd_rows_ok(int n, int P, int s, int C) {
   const long N = (long)n * P;
-  return n >= 1 && P >= 1 && N >= SWD_MIN_ROWS && N <= SWD_MAX_ROWS && (N & (N - 1)) == 0 && s >= 16 && C >= 1 &&
+  return n >= 1 && P >= 1 && N >= SWD_MIN_ROWS && N <= SWD_GLOBAL_MAX_ROWS && (N & (N - 1)) == 0 && s >= 16 && C >= 1 &&
          C <= SWD_MAX_CH && (double)n * s * s * C < 2147483648.0;
 }
 
@@ -473,6 +611,39 @@ extern "C" int dcg_swd_sort_distance(const float* src0, float* dst0, const float
   }
   const size_t shm = (size_t)(src1 ? 2 : 1) * N * sizeof(uint32_t) + 1024 * sizeof(double);
   hipLaunchKernelGGL(swd_sort_kernel, dim3(J), dim3(1024), shm, st, src0, dst0, src1, dst1, ref, partial, N);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_swd_sort_large(const float* src, float* dst, const float* other, uint32_t* keys0, uint32_t* keys1,
+                                  double* tilepart, double* partial, int N, int J, hipStream_t st) {
+  static_assert(SWD_MERGE_TILE % 1024 == 0 && SWD_MERGE_E % 4 == 0 && SWD_CHUNK_ROWS % 4096 == 0 &&
+                SWD_CHUNK_ROWS >= SWD_MERGE_TILE && SWD_CHUNK_ROWS <= SWD_MAX_ROWS, "swd: tile sizes");
+  if (!src || !keys0 || !keys1 || keys0 == keys1 || J < 1 || J > SWD_MAX_DIRS || N <= SWD_MAX_ROWS ||
+      N > SWD_GLOBAL_MAX_ROWS || (N & (N - 1)))
+    return -2;
+  if (!swd_al16(src) || !swd_al16(dst) || !swd_al16(other) || !swd_al16(keys0) || !swd_al16(keys1)) return -2;
+  if ((other != nullptr) != (partial != nullptr) || (other != nullptr) != (tilepart != nullptr) || (!dst && !other)) return -2;
+  constexpr int T = SWD_CHUNK_ROWS, M = SWD_MERGE_TILE;
+  static bool attr = false;
+  if (!attr) {
+    hipError_t e = hipFuncSetAttribute((const void*)swd_sort_chunks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       T * (int)sizeof(uint32_t));
+    if (e != hipSuccess) return (int)e;
+    attr = true;
+  }
+  hipLaunchKernelGGL(swd_sort_chunks_kernel, dim3(N / T, J), dim3(1024), (size_t)T * sizeof(uint32_t), st, src, keys0, N, T);
+  uint32_t *in = keys0, *out = keys1;
+  const dim3 grid(N / M, J);
+  for (int L = T; 2 * L < N; L <<= 1) {  // all passes but the last, between the two key buffers
+    hipLaunchKernelGGL(swd_merge_kernel<false>, grid, dim3(256), 0, st, (const uint32_t*)in, out, (float*)nullptr,
+                       (const float*)nullptr, (double*)nullptr, N, L);
+    uint32_t* t = in;
+    in = out;
+    out = t;
+  }
+  hipLaunchKernelGGL(swd_merge_kernel<true>, grid, dim3(256), 0, st, (const uint32_t*)in, (uint32_t*)nullptr, dst, other,
+                     tilepart, N, N / 2);
+  if (other) hipLaunchKernelGGL(swd_tile_sum_kernel, dim3((J + 63) / 64), dim3(64), 0, st, (const double*)tilepart, partial, N / M, J);
   return (int)hipGetLastError();
 }
 

@@ -148,13 +148,15 @@ class ReferenceEngine:
     def sampler(self, z: torch.Tensor, ema: Optional[bool] = None) -> torch.Tensor:
         return self.model.sampler(z.to(self.device), ema=ema)
 
-    def swd(self, real: torch.Tensor, z: torch.Tensor, patches: int, seed: int, ema: Optional[bool] = None):
+    def swd(self, real: torch.Tensor, z: torch.Tensor, patches: int, seed: int, ema: Optional[bool] = None,
+            max_rows: int = R.SWD_MAX_ROWS):
         """Sliced Wasserstein distance x 1000 between `real` and the samples of z per pyramid level: the
-        oracle (ops.reference.swd) in fp32 on this engine's device."""
+        oracle (ops.reference.swd) in fp32 on this engine's device. max_rows: the largest n * patches accepted."""
         B = self.batch_size
         with torch.no_grad():
             fake = torch.cat([self.sampler(z[i:i + B], ema=ema).float() for i in range(0, z.shape[0], B)])
-        return R.swd(real.to(self.device, torch.float32), fake, int(patches), int(seed), dtype=torch.float32)
+        return R.swd(real.to(self.device, torch.float32), fake, int(patches), int(seed), dtype=torch.float32,
+                     max_rows=max_rows)
 
     def eval_losses(self, real: torch.Tensor, z: torch.Tensor) -> Dict[str, float]:
         """Sample-time d_loss/g_loss (image_train.py:181-184) without mutating BN EMAs."""

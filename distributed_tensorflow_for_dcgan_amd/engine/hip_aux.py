@@ -12,6 +12,7 @@ import torch
 
 from ..models.config import same_pads
 from ..ops import hip as H
+from ..ops import reference as R
 
 RELU, TANH = 1, 3
 
@@ -160,14 +161,16 @@ class HipEngineAux:
 
     # ------------------------------------------------------------------ sliced Wasserstein distance
     def swd(self, real: Optional[torch.Tensor], z: torch.Tensor, patches: int, seed: int, ema: Optional[bool] = None,
-            refresh: bool = False) -> List[float]:
+            refresh: bool = False, max_rows: int = R.SWD_MAX_ROWS) -> List[float]:
         """Sliced Wasserstein distance x 1000 between `real` [n, S, S, C] and the n samples of z, per
         Laplacian-pyramid level, finest first (swd.hip; ops.hip.Swd). Programs of their own, recorded on
         first use: nothing of the training step is touched. The fakes come from ``sampler(z, ema=ema)`` in
         chunks of the batch size. The real side (its sorted projections per level) is computed on the first
         call and kept: later calls do not read `real` (None is fine) unless refresh is set or the set's
-        size, `patches` or `seed` changed."""
+        size, `patches` or `seed` changed. max_rows: the largest n * patches accepted, a power of two in
+        [32768, 2^21]; above 32768 the sorts are the global merge sort (ops.hip.Swd has the memory it takes)."""
         n, B = int(z.shape[0]), self.B
+        R.check_swd(n, patches, self.cfg.output_size, max_rows=R.check_swd_max_rows(max_rows))
         key = (n, int(patches), int(seed))
         sw = getattr(self, "_swd", None)
         if sw is None or self._swd_key != key or refresh:

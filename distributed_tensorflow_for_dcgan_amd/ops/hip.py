@@ -1239,7 +1239,7 @@ def swd_patch_centres(n: int, patches: int, s: int, level: int, seed: int, devic
     """int32 [n * patches, 2] = (cy, cx) of every descriptor of pyramid level `level` at size s, as the
     kernels draw them (oracle: ops.reference.swd_patch_centres)."""
     from . import reference as R
-    N = R.check_swd(n, patches, s)
+    N = R.check_swd(n, patches, s, max_rows=R.SWD_GLOBAL_MAX_ROWS)
     cen = torch.empty(N, 2, dtype=torch.int32, device=device)
     prog = ext().Program()
     prog.swd_centres("swd.centres", _p(cen), int(n), int(patches), int(s), int(level), int(seed) & (2 ** 64 - 1), 0)
@@ -1255,7 +1255,7 @@ def swd_project(l: torch.Tensor, centres: torch.Tensor, mean: torch.Tensor, std:
     from . import reference as R
     n, s, _, C = _f32_images("swd_project", l).shape
     N = centres.shape[0]
-    R.check_swd(n, N // n, s)
+    R.check_swd(n, N // n, s, max_rows=R.SWD_GLOBAL_MAX_ROWS)
     J = theta.shape[0]
     if centres.dtype != torch.int32 or tuple(centres.shape) != (N, 2) or N % n:
         raise TypeError("swd_project: centres must be int32 [N, 2], N a multiple of the image count")
@@ -1276,22 +1276,34 @@ def swd_project(l: torch.Tensor, centres: torch.Tensor, mean: torch.Tensor, std:
     return proj
 
 
+def _swd_large_scratch(J: int, N: int, device):
+    """The global merge sort's two key buffers uint32 [J, N] and its tile partials float64 [J, N / tile]."""
+    keys = [torch.empty(J, N, dtype=torch.int32, device=device) for _ in range(2)]
+    return keys[0], keys[1], torch.empty(J, N // ext().SWD_MERGE_TILE, dtype=torch.float64, device=device)
+
+
 def swd_sorted_distance(a: torch.Tensor, b: torch.Tensor):
     """(sort(a), sort(b), float64 mean_i |sort(a)[i] - sort(b)[i]|) of the columns a, b float32 [J, N] (row j = the
-    column of direction j), sorted by the monotone key (-0 < +0). N a power of two in [16, 32768]: up to
-    16384 both columns are sorted in one launch, above it each in a launch of its own."""
+    column of direction j), sorted by the monotone key (-0 < +0). N a power of two in [16, 2^21]: up to
+    16384 both columns are sorted in one launch, up to 32768 each in a launch of its own, above that each by
+    the global merge sort (swd_sort_large)."""
+    from . import reference as R
     if a.dtype != torch.float32 or a.dim() != 2 or b.dtype != a.dtype or b.shape != a.shape:
         raise TypeError("swd_sorted_distance: a and b must be float32 [J, N] of one shape")
     J, N = a.shape
-    if N < 16 or N > 32768 or N & (N - 1) or not 1 <= J <= 1024:
-        raise ValueError("swd_sorted_distance: N must be a power of two in [16, 32768] and J at most 1024, got "
-                         "[%d, %d]" % (J, N))
+    if N < 16 or N > ext().SWD_GLOBAL_MAX_ROWS or N & (N - 1) or not 1 <= J <= 1024:
+        raise ValueError("swd_sorted_distance: N must be a power of two in [16, %d] and J at most 1024, got "
+                         "[%d, %d]" % (ext().SWD_GLOBAL_MAX_ROWS, J, N))
     a, b = a.contiguous(), b.contiguous()
     sa, sb = torch.empty_like(a), torch.empty_like(b)
     part = torch.empty(J, dtype=torch.float64, device=a.device)
     prog = ext().Program()
     if N <= ext().SWD_FUSED_ROWS:
         prog.swd_sort_distance("swd.sort2", _p(b), _p(sb), _p(a), _p(sa), 0, _p(part), N, J, 0)
+    elif N > R.SWD_MAX_ROWS:
+        k0, k1, tp = _swd_large_scratch(J, N, a.device)
+        prog.swd_sort_large("swd.sort_large", _p(a), _p(sa), 0, _p(k0), _p(k1), 0, 0, N, J, 0)
+        prog.swd_sort_large("swd.sort_large_dist", _p(b), _p(sb), _p(sa), _p(k0), _p(k1), _p(tp), _p(part), N, J, 0)
     else:
         prog.swd_sort_distance("swd.sort", _p(a), _p(sa), 0, 0, 0, 0, N, J, 0)
         prog.swd_sort_distance("swd.sort_dist", _p(b), _p(sb), 0, 0, _p(sa), _p(part), N, J, 0)
@@ -1303,12 +1315,14 @@ class Swd:
     """The sliced Wasserstein distance of image sets [n, S, S, C] against one real set, on the device
     (swd.hip; oracle: ops.reference.swd). ``set_real`` projects the real set and keeps its sorted columns
     per level -- the reals, the patch centres and the directions never change -- so every ``distance`` costs
-    the evaluated set's side only. Everything is recorded once: the side's Program and the two sort Programs."""
+    the evaluated set's side only. Everything is recorded once: the side's Program and the two sort Programs.
+    n * patches: a power of two up to 2^21; above 32768 the sorts are the global merge sort, through one pair
+    of key buffers [J, N] that all levels share."""
 
     def __init__(self, n: int, S: int, C: int, patches: int, seed: int, repeats: int = 4, dirs: int = 128,
                  device="cuda"):
         from . import reference as R
-        self.N = N = R.check_swd(n, patches, S)
+        self.N = N = R.check_swd(n, patches, S, max_rows=R.SWD_GLOBAL_MAX_ROWS)
         self.J = J = int(repeats) * int(dirs)
         if J % 128 or not 128 <= J <= 1024 or not 1 <= C <= 4:
             raise ValueError("swd: repeats * dirs must be a multiple of 128 up to 1024 and C at most 4")
@@ -1346,14 +1360,23 @@ class Swd:
         run(init)
         if self.fused:
             self.real_proj = [new(J, N) for _ in sizes]
+        large = N > R.SWD_MAX_ROWS
+        if large:
+            self.keys0, self.keys1, self.tilepart = k0, k1, tp = _swd_large_scratch(J, N, device)
         for k, s in enumerate(sizes):
-            if self.fused:  # the first distance: both sets' columns in one launch, the reals' kept
+            if large:       # the global merge sort: the reals' sorted columns kept, the fakes' never stored
+                first.swd_sort_large("swd.sort_large%d" % s, _p(self.proj[k]), _p(self.real_sorted[k]), 0, _p(k0), _p(k1),
+                                     0, 0, N, J, 0)
+                cached.swd_sort_large("swd.sort_large_dist%d" % s, _p(self.proj[k]), 0, _p(self.real_sorted[k]), _p(k0),
+                                      _p(k1), _p(tp), _p(self.partial[k]), N, J, 0)
+            elif self.fused:  # the first distance: both sets' columns in one launch, the reals' kept
                 first.swd_sort_distance("swd.sort2_%d" % s, _p(self.proj[k]), 0, _p(self.real_proj[k]),
                                         _p(self.real_sorted[k]), 0, _p(self.partial[k]), N, J, 0)
             else:           # the reals' columns, sorted when they are set
                 first.swd_sort_distance("swd.sort%d" % s, _p(self.proj[k]), _p(self.real_sorted[k]), 0, 0, 0, 0, N, J, 0)
-            cached.swd_sort_distance("swd.sort_dist%d" % s, _p(self.proj[k]), 0, 0, 0, _p(self.real_sorted[k]),
-                                     _p(self.partial[k]), N, J, 0)
+            if not large:
+                cached.swd_sort_distance("swd.sort_dist%d" % s, _p(self.proj[k]), 0, 0, 0, _p(self.real_sorted[k]),
+                                         _p(self.partial[k]), N, J, 0)
         for p in (first, cached) if self.fused else (cached,):
             for k in range(nl):
                 p.swd_mean("swd.mean%d" % sizes[k], _p(self.partial[k]), _p(self.out[k]), N, J, 0)

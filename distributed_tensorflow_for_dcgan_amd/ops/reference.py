@@ -1296,6 +1296,7 @@ def check_spectral_norm(flag) -> bool:
 SWD_STREAM = 6             # Philox stream of the patch centres and directions (0..5 are taken)
 SWD_DIR_STEP = 1 << 16     # counter word 2 of the directions of repeat r: 2^16 + r (the levels use 0, 1, ...)
 SWD_MIN_ROWS, SWD_MAX_ROWS = 16, 32768  # descriptors per set and level the device sort holds in LDS
+SWD_GLOBAL_MAX_ROWS = 1 << 21           # ... and what its global merge sort takes (--swd_max_rows opts in)
 SWD_TAPS = (1.0, 4.0, 6.0, 4.0, 1.0)   # / 16
 
 
@@ -1307,14 +1308,24 @@ def swd_levels(S: int):
     return out
 
 
-def check_swd(n: int, patches: int, S: int, names=("n", "patches", "output size")) -> int:
-    """Validated N = n * patches descriptors per set: a power of two in [16, 32768], S >= 16. `names`: how
-    the caller spells the three in its message (the flag parser passes its flags)."""
-    n, patches, S = int(n), int(patches), int(S)
+def check_swd_max_rows(max_rows: int, name: str = "max_rows") -> int:
+    """Validated upper bound of N: a power of two in [32768, 2^21]."""
+    m = int(max_rows)
+    if m < SWD_MAX_ROWS or m > SWD_GLOBAL_MAX_ROWS or m & (m - 1):
+        raise ValueError("%s must be a power of two in [%d, %d], got %d" % (name, SWD_MAX_ROWS, SWD_GLOBAL_MAX_ROWS, m))
+    return m
+
+
+def check_swd(n: int, patches: int, S: int, names=("n", "patches", "output size"), max_rows: int = SWD_MAX_ROWS) -> int:
+    """Validated N = n * patches descriptors per set: a power of two in [16, max_rows], S >= 16. max_rows: 32768,
+    what the one-workgroup sort holds, unless the caller opts in to the global merge sort (up to 2^21).
+    `names`: how the caller spells the three in its message (the flag parser passes its flags)."""
+    n, patches, S, max_rows = int(n), int(patches), int(S), int(max_rows)
     N = n * patches
-    if n < 1 or patches < 1 or N < SWD_MIN_ROWS or N > SWD_MAX_ROWS or N & (N - 1):
-        raise ValueError("%s * %s must be a power of two in [%d, %d] (larger sets need a global merge sort), got "
-                         "%d * %d" % (names[0], names[1], SWD_MIN_ROWS, SWD_MAX_ROWS, n, patches))
+    if n < 1 or patches < 1 or N < SWD_MIN_ROWS or N > max_rows or N & (N - 1):
+        why = "larger sets need a global merge sort" if max_rows == SWD_MAX_ROWS else "the bound is --swd_max_rows"
+        raise ValueError("%s * %s must be a power of two in [%d, %d] (%s), got "
+                         "%d * %d" % (names[0], names[1], SWD_MIN_ROWS, max_rows, why, n, patches))
     if S < 16:
         raise ValueError("%s must be at least 16 for the sliced Wasserstein distance, got %d" % (names[2], S))
     return N
@@ -1402,14 +1413,14 @@ def swd_sorted_distance(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 
 def swd(A: torch.Tensor, B: torch.Tensor, patches: int, seed: int, repeats: int = 4, dirs: int = 128,
-        dtype=torch.float64):
+        dtype=torch.float64, max_rows: int = SWD_MAX_ROWS):
     """Sliced Wasserstein distance x 1000 between the image sets A (real) and B (fake), both [n, S, S, C] in
     [-1, 1], per pyramid level (a list of floats, finest level first). A channel that is constant over a
-    set has sigma = 0 and makes that level non-finite."""
+    set has sigma = 0 and makes that level non-finite. max_rows: the largest n * patches accepted."""
     if A.shape != B.shape or A.dim() != 4 or A.shape[1] != A.shape[2]:
         raise ValueError("swd: A and B must share a shape [n, S, S, C], got %s and %s" % (tuple(A.shape), tuple(B.shape)))
     n, S, _, C = A.shape
-    check_swd(n, patches, S)
+    check_swd(n, patches, S, max_rows=check_swd_max_rows(max_rows))
     theta = swd_directions(49 * C, seed, repeats, dirs, dtype).to(A.device)
     out = []
     for k, (la, lb) in enumerate(zip(swd_laplacian(A, dtype), swd_laplacian(B, dtype))):

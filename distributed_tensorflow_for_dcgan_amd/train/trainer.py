@@ -474,7 +474,8 @@ def _swd(engine, flags, state, source, cfg, device, step, out, writer) -> None:
     the real set is drawn from `source` at the first one (ceil(n / B) batches)."""
     n, patches = int(flags.swd_images), int(flags.swd_patches)
     try:
-        R.check_swd(n, patches, cfg.output_size, ("--swd_images", "--swd_patches", "--output_size"))
+        R.check_swd(n, patches, cfg.output_size, ("--swd_images", "--swd_patches", "--output_size"),
+                    max_rows=int(flags.swd_max_rows))
     except ValueError as e:
         raise SystemExit(str(e))
     if not state:
@@ -484,7 +485,8 @@ def _swd(engine, flags, state, source, cfg, device, step, out, writer) -> None:
         state["real"] = torch.cat(got)[:n].contiguous()
         gen = torch.Generator().manual_seed(int(flags.seed) + 4242)
         state["z"] = (torch.rand(n, cfg.z_dim, generator=gen) * 2 - 1).to(device)
-    vals = engine.swd(state["real"], state["z"], patches, int(flags.seed), ema=_sample_ema(engine, flags))
+    vals = engine.swd(state["real"], state["z"], patches, int(flags.seed), ema=_sample_ema(engine, flags),
+                      max_rows=int(flags.swd_max_rows))
     sizes = R.swd_levels(cfg.output_size)
     avg = sum(vals) / len(vals)
     print("[SWD] step %d  %s  avg: %.2f" % (step, "  ".join("%d: %.2f" % sv for sv in zip(sizes, vals)), avg),

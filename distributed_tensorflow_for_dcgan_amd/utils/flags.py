@@ -146,7 +146,11 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                             "ceil(swd_images / batch_size) batches)"),
     ("swd_images", "int", 256, "images per set of the distance"),
     ("swd_patches", "int", 128, "7x7 patches per image and level; --swd_images * --swd_patches must be a power of "
-                                "two in [16, 32768]"),
+                                "two in [16, --swd_max_rows]"),
+    ("swd_max_rows", "int", 32768, "largest --swd_images * --swd_patches accepted: a power of two in [32768, 2^21]. "
+                                   "Above 32768 the HIP engine sorts with its global merge sort and holds two "
+                                   "float32 [512, N] buffers per pyramid level plus two key buffers (34.6 GiB at "
+                                   "the paper's 16384 x 128 and 64x64x3)"),
 ]
 
 ALL_FLAGS = REFERENCE_FLAGS + EXTRA_FLAGS
@@ -231,12 +235,14 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
     validate_flags(ns, parser.error)
     if int(ns.swd_every) < 0:
         parser.error("--swd_every must be >= 0, got %r" % (ns.swd_every,))
-    if int(ns.swd_every) > 0 or any(a.split("=")[0] in ("--swd_images", "--swd_patches") for a in argv):
-        from ..ops.reference import check_swd
-        try:
-            check_swd(ns.swd_images, ns.swd_patches, ns.output_size, ("--swd_images", "--swd_patches", "--output_size"))
-        except ValueError as e:
-            parser.error(str(e))
+    from ..ops.reference import check_swd, check_swd_max_rows
+    try:
+        check_swd_max_rows(ns.swd_max_rows, "--swd_max_rows")
+        if int(ns.swd_every) > 0 or any(a.split("=")[0] in ("--swd_images", "--swd_patches") for a in argv):
+            check_swd(ns.swd_images, ns.swd_patches, ns.output_size, ("--swd_images", "--swd_patches", "--output_size"),
+                      max_rows=ns.swd_max_rows)
+    except ValueError as e:
+        parser.error(str(e))
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
