@@ -1,0 +1,85 @@
+"""Time of ``engine.nn_metric`` on the HIP engine: the first evaluation (real side, its leave-one-out search, fake
+side and the three blocks that involve it) and a cached one (fake side only), in HIP events around each call, and in
+the same process ``torch.cdist`` + ``min`` over the same four blocks of the same feature matrices as the yardstick.
+
+    python benchmarks/bench_nn.py [--images 1024] [--output_size 64] [--nn_size 0] [--iters 10] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributed_tensorflow_for_dcgan_amd.engine.hip_engine import HipEngine  # noqa: E402
+from distributed_tensorflow_for_dcgan_amd.models.config import DCGANConfig  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=1024)
+    ap.add_argument("--output_size", type=int, default=64)
+    ap.add_argument("--nn_size", type=int, default=0)
+    ap.add_argument("--c_dim", type=int, default=3)
+    ap.add_argument("--batch_size", type=int, default=64)
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--out", default=None, help="also append the result line to this file")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_nn.py needs a GPU"
+    dev = torch.device("cuda", 0)
+    cfg = DCGANConfig(output_size=a.output_size, c_dim=a.c_dim)
+    eng = HipEngine(cfg, a.batch_size, dev, dtype=a.dtype, graph=False)
+    g = torch.Generator().manual_seed(0)
+    eng.set_synthetic_batch((torch.rand(a.batch_size, a.output_size, a.output_size, a.c_dim, generator=g) * 2 - 1).to(dev))
+    for _ in range(3):
+        eng.train_step()
+    n = a.images
+    real = (torch.rand(n, a.output_size, a.output_size, a.c_dim, generator=g) * 2 - 1).to(dev)
+    z = (torch.rand(n, cfg.z_dim, generator=g) * 2 - 1).to(dev)
+    eng.sampler(z[:a.batch_size])  # (the sampler's program and code objects are not the metric's cost)
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        r = fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1), r
+    cold, res = timed(lambda: eng.nn_metric(real, z, a.nn_size, refresh=True))  # records the programs: reported apart
+    first = sorted(timed(lambda: eng.nn_metric(real, z, a.nn_size, refresh=True))[0] for _ in range(a.iters))
+    cached = sorted(timed(lambda: eng.nn_metric(None, z, a.nn_size))[0] for _ in range(a.iters))
+    nn = eng._nn
+    FA, FB = nn._keep[2][1], nn._keep[3][1]  # the centred feature matrices the kernels searched
+
+    def yard():
+        out = []
+        for X, Y, loo in ((FA, FA, True), (FA, FB, False), (FB, FA, False), (FB, FB, True)):
+            D = torch.cdist(X, Y)
+            if loo:
+                D.fill_diagonal_(float("inf"))
+            out.append(D.min(1))
+        return out
+    timed(yard)
+    cd = sorted(timed(yard)[0] for _ in range(a.iters))
+    K = nn.K
+    med = lambda v: round(v[len(v) // 2], 3)  # noqa: E731
+    out = {"metric": "nn_eval_ms", "images": n, "shape": [a.output_size, a.output_size, a.c_dim], "K": K, "dtype": a.dtype,
+           "iters": a.iters, "cold_first_ms": round(cold, 3), "first_ms_median": med(first),
+           "first_ms_min_max": [round(first[0], 3), round(first[-1], 3)], "cached_ms_median": med(cached),
+           "cached_ms_min_max": [round(cached[0], 3), round(cached[-1], 3)], "cdist_min_4_blocks_ms_median": med(cd),
+           "cdist_min_max": [round(cd[0], 3), round(cd[-1], 3)],
+           "gemm_flop_first": 4 * 2.0 * n * n * nn._keep[2][1].shape[1],
+           "result": {k: (round(v, 4) if isinstance(v, float) else None) for k, v in res.items() if k != "nearest"}}
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -35,6 +35,7 @@
 #include "hip/kernels.h"
 #include "comm.h"
 #include "hip/swd.h"
+#include "hip/nn.h"
 extern "C" {
 #include "hip/narrow2.inc"
 }
@@ -1440,6 +1441,42 @@ class Program {
                AccList().r(partial, (size_t)J * 8).w(out, 8).v);
   }
 
+  // ---- 1-nearest-neighbour search (nn.hip, nn.h): fp32 whatever the Program's element type. Feature rows
+  // F [M][Kp], Kp = nn_kpad(K); an argument out of range fails the run (-2)
+  // x [n][K] -> F = x - mu, norm [n] = |F_i|^2; compute_mu: mu [K] is first set to the rows' mean (the fp64 partials
+  // are the Program's); mu may be 0 (no centring)
+  int nn_features(std::string name, uintptr_t x, int n, int K, uintptr_t mu, int compute_mu, uintptr_t F, uintptr_t norm,
+                  int stream) {
+    const size_t pb = compute_mu ? nn_mean_part_bytes(n, K) : 0;
+    double* part = pb ? reinterpret_cast<double*>(dev_alloc(pb)) : nullptr;
+    AccList a;
+    a.r(x, (size_t)n * K * 4).w(F, (size_t)n * nn_kpad(K) * 4).w(norm, (size_t)n * 4);
+    if (compute_mu) a.w(mu, (size_t)K * 4).w((uintptr_t)part, pb); else a.r(mu, (size_t)K * 4);
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_features(P<const float>(x), n, K, P<float>(mu), part, compute_mu, P<float>(F), P<float>(norm), st);
+    }, a.v);
+  }
+  // part uint64 [splits][Mx]: per row of X and column chunk the smallest (key(d) << 32 | column)
+  int nn_top1(std::string name, uintptr_t X, uintptr_t nx, uintptr_t Y, uintptr_t ny, uintptr_t part, int Mx, int My,
+              int Kp, int loo, int splits, int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_top1(P<const float>(X), P<const float>(nx), P<const float>(Y), P<const float>(ny), P<uint64_t>(part),
+                         Mx, My, Kp, loo, splits, st);
+    }, AccList().r(X, (size_t)Mx * Kp * 4).r(nx, (size_t)Mx * 4).r(Y, (size_t)My * Kp * 4).r(ny, (size_t)My * 4)
+           .w(part, (size_t)splits * Mx * 8).v);
+  }
+  int nn_merge(std::string name, uintptr_t part, uintptr_t idx, int Mx, int splits, int stream) {
+    return add(name, stream, [=](hipStream_t st) { return dcg_nn_merge(P<const uint64_t>(part), P<int>(idx), Mx, splits, st); },
+               AccList().r(part, (size_t)splits * Mx * 8).w(idx, (size_t)Mx * 4).v);
+  }
+  // dist double [Mx] = |x0_i - y0_idx[i]|^2 from the uncentred rows x0 [Mx][K], y0 [My][K]
+  int nn_refine(std::string name, uintptr_t x0, uintptr_t y0, uintptr_t idx, uintptr_t dist, int Mx, int My, int K,
+                int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_refine(P<const float>(x0), P<const float>(y0), P<const int>(idx), P<double>(dist), Mx, My, K, st);
+    }, AccList().r(x0, (size_t)Mx * K * 4).r(y0, (size_t)My * K * 4).r(idx, (size_t)Mx * 4).w(dist, (size_t)Mx * 8).v);
+  }
+
  private:
   int add(const std::string& name, int stream, std::function<int(hipStream_t)> fn, std::vector<Acc> acc,
           int kind = OP_LAUNCH, int ev = -1) {
@@ -1517,6 +1554,8 @@ PYBIND11_MODULE(_dcgan_hip, m) {
     return py::make_tuple(p.nrb, p.rpb, p.nct, p.ncb, p.ws_floats);
   });
   m.def("swd_kpad", &swd_kpad);  // k depth of the projection's theta' rows for C channels
+  m.def("nn_kpad", &nn_kpad);  // row length of the feature matrix for K features
+  m.attr("NN_TILE") = (int)NN_TILE;
   m.attr("SWD_FUSED_ROWS") = (int)SWD_FUSED_ROWS;
   m.attr("SWD_GLOBAL_MAX_ROWS") = (int)SWD_GLOBAL_MAX_ROWS;  // N of swd_sort_large: (32768, 2^21]
   m.attr("SWD_CHUNK_ROWS") = (int)SWD_CHUNK_ROWS;
@@ -1684,5 +1723,9 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("swd_project", &Program::swd_project)
       .def("swd_sort_distance", &Program::swd_sort_distance)
       .def("swd_sort_large", &Program::swd_sort_large)
-      .def("swd_mean", &Program::swd_mean);
+      .def("swd_mean", &Program::swd_mean)
+      .def("nn_features", &Program::nn_features)
+      .def("nn_top1", &Program::nn_top1)
+      .def("nn_merge", &Program::nn_merge)
+      .def("nn_refine", &Program::nn_refine);
 }

@@ -1,0 +1,37 @@
+// 1-nearest-neighbour search between two sets of feature rows (nn.hip): limits and host launchers. Everything
+// is fp32 whatever the engine's element type, so the file is built once and its launchers carry no suffix.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+constexpr int NN_TILE = 128;        // rows and columns of G = X Y^T that one workgroup owns at a time
+constexpr int NN_BK = 32;           // k depth of one LDS stage
+constexpr int NN_PITCH = NN_BK + 4; // floats between LDS rows: 36 r mod 64 is distinct for 16 rows (see nn.hip)
+constexpr int NN_MEAN_ROWS = 64;    // rows per fp64 partial sum of the mean
+constexpr int NN_FEAT_ROWS = 4;     // rows per workgroup of nn_features
+constexpr int NN_MAX_ROWS = 1 << 20;
+constexpr int NN_MAX_K = 1 << 20;
+
+// K padded with zeros to the k depth of four 16x16x4 MFMAs
+static inline int nn_kpad(int K) { return (K + 15) & ~15; }
+static inline int nn_col_tiles(int My) { return (My + NN_TILE - 1) / NN_TILE; }
+// fp64 partials of the mean: [ceil(n / NN_MEAN_ROWS)][K]
+static inline size_t nn_mean_part_bytes(int n, int K) {
+  return (size_t)((n + NN_MEAN_ROWS - 1) / NN_MEAN_ROWS) * (size_t)K * sizeof(double);
+}
+
+extern "C" {
+// Every launcher: -2 = an argument out of range (null pointer, size, alignment)
+// x [n][K] -> F [n][Kp] = x - mu (zeros from K on), norm [n] = |F_i|^2. mu [K] may be null (no centring). With
+// compute_mu, mu is first set to the mean over the n rows: fp64 partials `part` per 64 rows, added in index order
+int dcg_nn_features(const float* x, int n, int K, float* mu, double* part, int compute_mu, float* F, float* norm,
+                    hipStream_t st);
+// part [splits][Mx] = per row i of X and column chunk c the smallest (key(d) << 32 | j), d = nx_i + ny_j - 2 x_i.y_j
+// over the columns j of the chunk (j != i with loo). X [Mx][Kp], Y [My][Kp], Kp a multiple of 16, 16-byte aligned
+int dcg_nn_top1(const float* X, const float* nx, const float* Y, const float* ny, uint64_t* part, int Mx, int My, int Kp,
+                int loo, int splits, hipStream_t st);
+// idx [Mx] = the column of the smallest of part [splits][Mx] over the chunks, in chunk order
+int dcg_nn_merge(const uint64_t* part, int* idx, int Mx, int splits, hipStream_t st);
+// dist [Mx] = sum_k (x0[i][k] - y0[idx[i]][k])^2 from the uncentred rows: fp32 differences and squares, fp64 sums
+int dcg_nn_refine(const float* x0, const float* y0, const int* idx, double* dist, int Mx, int My, int K, hipStream_t st);
+}

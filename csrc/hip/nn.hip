@@ -1,0 +1,291 @@
+// dcg-variants: bf16
+// 1-nearest-neighbour search between two sets of feature rows: the hot path of the leave-one-out 1-NN
+// two-sample test (Lopez-Paz & Oquab 2017) and of the nearest-training-image distance. fp32 throughout,
+// whatever the engine's element type (one build, nn.h): bf16's 2^-8 is the size of the gaps being compared.
+// It runs beside the training step, never inside it.
+//
+// X [Mx][K], Y [My][K] are pyramid levels (swd_down's output, or the images) flattened per image:
+//   nn_features  F [M][Kp] = x - mu, zero-filled from K to Kp = K rounded up to 16, and norm [M] = |F_i|^2. mu is
+//                the real set's per-feature mean, from fp64 partial sums per 64 rows added in index order (no
+//                atomics). Centring changes no distance; it shrinks the norms and with them the cancellation
+//                in d = |x|^2 + |y|^2 - 2 x.y. A workgroup owns 4 rows; a row's norm is summed by wave
+//                shuffles, then through LDS in wave order: a fixed order
+//   nn_top1      G = X Y^T on v_mfma_f32_16x16x4_f32 with the selection fused into its epilogue. A workgroup of
+//                256 threads owns 128 rows of X and walks the 128-column tiles of its chunk of Y (grid.y
+//                chunks, so that a small My still fills the GPU). Both operand tiles stream through LDS in k
+//                steps of 32, double-buffered: the 16-byte global loads of step t + 1 are issued into
+//                registers before the MFMAs of step t and stored to the other buffer after them, one barrier
+//                per step. LDS rows sit 36 floats apart: the fragment read of lane (fr, fq) is the 16 bytes at
+//                row fr, float 4 fq, and 36 fr mod 64 takes 16 distinct multiples of 4 -- the 16 lanes of a
+//                quarter-wave cover all 64 banks once (and any 8 consecutive rows all of 32). Each wave owns
+//                64 x 64 of the tile: 4 A and 4 B fragments feed 64 MFMAs per 16 k. Per tile the epilogue forms
+//                d = nx_i + ny_j - 2 g, masks the diagonal (loo) and the columns past My, packs
+//                (topk's monotone key of d) << 32 | j and folds it into the lane's running minimum of its 16
+//                rows: one 64-bit min is "smallest d, then smallest j". At the end of the chunk the minima
+//                are reduced across the 16 lanes of a column group by shuffles and across the two column
+//                waves through LDS, and go to part [chunk][row]. No atomics, no dependence between workgroups
+//   nn_merge     idx [Mx] = the column of the minimum of part over the chunks, in chunk order
+//   nn_refine    the Gram form is only good enough to choose. The winner's distance is recomputed from the
+//                uncentred rows, (x_k - y_k)^2 in fp32 summed in fp64: one wave per row, every lane its k in
+//                index order, then a shuffle tree -- a fixed order; a bitwise duplicate reports exactly 0
+// Every index into a feature matrix is 64-bit: n Kp passes 2^31 at 128x128x3.
+#include "common.h"
+#include "nn.h"
+
+namespace dcg {
+
+// ---------------------------------------------------------------- mean and features
+// thread k of row block b: the fp64 sum of x[r][k] over the block's rows, in index order
+__global__ __launch_bounds__(256) void nn_mean_part_kernel(const float* __restrict__ x, int n, int K,
+                                                           double* __restrict__ part) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= K) return;
+  const int r0 = blockIdx.y * NN_MEAN_ROWS, r1 = min(n, r0 + NN_MEAN_ROWS);
+  double s = 0.0;
+  for (int r = r0; r < r1; ++r) s += (double)x[(size_t)r * K + k];
+  part[(size_t)blockIdx.y * K + k] = s;
+}
+
+__global__ __launch_bounds__(256) void nn_mean_final_kernel(const double* __restrict__ part, int blocks, int K,
+                                                            double count, float* __restrict__ mu) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= K) return;
+  double s = 0.0;
+  for (int b = 0; b < blocks; ++b) s += part[(size_t)b * K + k];
+  mu[k] = (float)(s / count);
+}
+
+__global__ __launch_bounds__(256) void nn_features_kernel(const float* __restrict__ x, const float* __restrict__ mu,
+                                                          float* __restrict__ F, float* __restrict__ norm, int n, int K,
+                                                          int Kp) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int q = 0; q < NN_FEAT_ROWS; ++q) {
+    const int r = blockIdx.x * NN_FEAT_ROWS + q;
+    if (r >= n) break;  // (the same for every thread of the workgroup)
+    const float* src = x + (size_t)r * K;
+    float* dst = F + (size_t)r * Kp;
+    float s = 0.f;
+    for (int k = tid; k < Kp; k += 256) {
+      float v = 0.f;
+      if (k < K) v = mu ? src[k] - mu[k] : src[k];
+      dst[k] = v;
+      s = __builtin_fmaf(v, v, s);
+    }
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (tid == 0) norm[r] = ((red[0] + red[1]) + red[2]) + red[3];
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------- the distance GEMM with its selection
+// topk's key (misc.hip topk_key): uint32, monotone in x, -0 < +0
+__device__ __forceinline__ uint32_t nn_key(float x) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, x);
+  return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+constexpr unsigned long long NN_NONE = ~0ull;  // no candidate: above every (key, column)
+constexpr int NN_TILE_F = NN_TILE * NN_PITCH;  // floats of one operand tile in LDS
+constexpr size_t NN_TOP1_LDS = (size_t)4 * NN_TILE_F * sizeof(float) + (size_t)2 * NN_TILE * sizeof(unsigned long long);
+
+__device__ __forceinline__ unsigned long long nn_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+
+// two waves per SIMD (248 VGPRs, no scratch): two workgroups per CU, the second one's MFMAs cover this one's barrier
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void nn_top1_kernel(const float* __restrict__ X, const float* __restrict__ nx, const float* __restrict__ Y,
+                    const float* __restrict__ ny, unsigned long long* __restrict__ part, int Mx, int My, int Kp, int loo,
+                    int nct) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [2 buffers][X tile, Y tile][128][36], then red
+  unsigned long long* red = reinterpret_cast<unsigned long long*>(lds + 4 * NN_TILE_F);  // [2 column waves][128]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int m0 = blockIdx.x * NN_TILE, chunk = blockIdx.y, splits = gridDim.y;
+  const int t0 = (int)((long long)chunk * nct / splits), t1 = (int)((long long)(chunk + 1) * nct / splits);
+  const int nk = (Kp + NN_BK - 1) / NN_BK, steps = (t1 - t0) * nk;
+  const int lr = tid >> 3, lq = tid & 7;  // the loader's rows lr + 32 p, its 16-byte word lq of the 32 k
+  const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 sx[4], sy[4];
+
+  auto fetch = [&](int it) {  // rows past the ends and k past Kp read as zeros
+    const int ct = t0 + it / nk, k0 = (it % nk) * NN_BK + 4 * lq;
+    const bool kok = k0 < Kp;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int rx = m0 + lr + 32 * p, ry = ct * NN_TILE + lr + 32 * p;
+      sx[p] = (kok && rx < Mx) ? *reinterpret_cast<const f32x4*>(X + (size_t)rx * Kp + k0) : zero;
+      sy[p] = (kok && ry < My) ? *reinterpret_cast<const f32x4*>(Y + (size_t)ry * Kp + k0) : zero;
+    }
+  };
+  auto stash = [&](int buf) {
+    float* bx = lds + buf * 2 * NN_TILE_F + lr * NN_PITCH + 4 * lq;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      *reinterpret_cast<f32x4*>(bx + 32 * p * NN_PITCH) = sx[p];
+      *reinterpret_cast<f32x4*>(bx + NN_TILE_F + 32 * p * NN_PITCH) = sy[p];
+    }
+  };
+
+  float nxr[4][4];               // |x|^2 of the lane's rows: wr * 64 + i * 16 + 4 fq + r
+  unsigned long long best[4][4];
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = m0 + wr * 64 + i * 16 + 4 * fq + r;
+      nxr[i][r] = row < Mx ? nx[row] : 0.f;
+      best[i][r] = NN_NONE;
+    }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = zero;
+
+  fetch(0);
+  stash(0);
+  __syncthreads();
+  for (int it = 0; it < steps; ++it) {
+    const int buf = it & 1;
+    const bool more = it + 1 < steps;
+    if (more) fetch(it + 1);
+    const float* bx = lds + buf * 2 * NN_TILE_F + (wr * 64 + fr) * NN_PITCH + 4 * fq;
+    const float* by = lds + buf * 2 * NN_TILE_F + NN_TILE_F + (wc * 64 + fr) * NN_PITCH + 4 * fq;
+#pragma unroll
+    for (int kk = 0; kk < NN_BK; kk += 16) {  // lane group fq supplies k = kk + 4 fq + e to MFMA e, for A and B alike
+      f32x4 a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const f32x4*>(bx + i * 16 * NN_PITCH + kk);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const f32x4*>(by + j * 16 * NN_PITCH + kk);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
+    }
+    if (more) stash(buf ^ 1);  // (last read in step it - 1, before that step's barrier)
+    if ((it + 1) % nk == 0) {  // the tile is complete. C fragment: rows 4 fq + r of column fr
+      const int cbase = (t0 + it / nk) * NN_TILE + wc * 64;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = cbase + j * 16 + fr;
+        const bool cok = col < My;
+        const float nyv = cok ? ny[col] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = m0 + wr * 64 + i * 16 + 4 * fq + r;
+            const float d = __builtin_fmaf(-2.f, acc[i][j][r], nxr[i][r] + nyv);
+            unsigned long long key = ((unsigned long long)nn_key(d) << 32) | (unsigned)col;
+            if (!cok || (loo && col == row)) key = NN_NONE;
+            best[i][r] = nn_min(best[i][r], key);
+          }
+        acc[0][j] = zero; acc[1][j] = zero; acc[2][j] = zero; acc[3][j] = zero;
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      unsigned long long v = best[i][r];
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) v = nn_min(v, __shfl_xor(v, o, 64));
+      if (fr == 0) red[wc * NN_TILE + wr * 64 + i * 16 + 4 * fq + r] = v;
+    }
+  __syncthreads();
+  if (tid < NN_TILE && m0 + tid < Mx) part[(size_t)chunk * Mx + m0 + tid] = nn_min(red[tid], red[NN_TILE + tid]);
+}
+
+__global__ __launch_bounds__(256) void nn_merge_kernel(const unsigned long long* __restrict__ part, int* __restrict__ idx,
+                                                       int Mx, int splits) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Mx) return;
+  unsigned long long b = part[i];
+  for (int c = 1; c < splits; ++c) b = nn_min(b, part[(size_t)c * Mx + i]);
+  idx[i] = (int)(unsigned)b;  // (-1: no candidate)
+}
+
+// ---------------------------------------------------------------- the winner's distance, recomputed
+__global__ __launch_bounds__(256) void nn_refine_kernel(const float* __restrict__ x0, const float* __restrict__ y0,
+                                                        const int* __restrict__ idx, double* __restrict__ dist, int Mx,
+                                                        int My, int K) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= Mx) return;
+  const int j = idx[row];
+  double s = __builtin_inf();
+  if (j >= 0 && j < My) {
+    const float* x = x0 + (size_t)row * K;
+    const float* y = y0 + (size_t)j * K;
+    s = 0.0;
+    for (int k = lane; k < K; k += 64) {
+      const float df = x[k] - y[k];
+      const float sq = df * df;
+      s += (double)sq;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  }
+  if (lane == 0) dist[row] = s;
+}
+
+static inline bool nn_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool nn_shape_ok(int M, int K) { return M >= 1 && M <= NN_MAX_ROWS && K >= 1 && K <= NN_MAX_K; }
+
+}  // namespace dcg
+
+using namespace dcg;
+
+extern "C" int dcg_nn_features(const float* x, int n, int K, float* mu, double* part, int compute_mu, float* F,
+                               float* norm, hipStream_t st) {
+  if (!x || !F || !norm || !nn_shape_ok(n, K) || (compute_mu && (!mu || !part))) return -2;
+  if (compute_mu) {
+    const int blocks = (n + NN_MEAN_ROWS - 1) / NN_MEAN_ROWS;
+    hipLaunchKernelGGL(nn_mean_part_kernel, dim3((K + 255) / 256, blocks), dim3(256), 0, st, x, n, K, part);
+    hipLaunchKernelGGL(nn_mean_final_kernel, dim3((K + 255) / 256), dim3(256), 0, st, (const double*)part, blocks, K,
+                       (double)n, mu);
+  }
+  hipLaunchKernelGGL(nn_features_kernel, dim3((n + NN_FEAT_ROWS - 1) / NN_FEAT_ROWS), dim3(256), 0, st, x,
+                     (const float*)mu, F, norm, n, K, nn_kpad(K));
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_top1(const float* X, const float* nx, const float* Y, const float* ny, uint64_t* part, int Mx,
+                           int My, int Kp, int loo, int splits, hipStream_t st) {
+  static_assert(NN_BK % 16 == 0 && NN_PITCH % 4 == 0 && NN_TILE == 128, "nn: tile sizes");
+  if (!X || !nx || !Y || !ny || !part || !nn_shape_ok(Mx, Kp) || !nn_shape_ok(My, Kp) || Kp % 16 || !nn_al16(X) ||
+      !nn_al16(Y))
+    return -2;
+  const int nct = nn_col_tiles(My);
+  if (splits < 1 || splits > nct || splits > 65535 || (loo && (Mx != My || My < 2))) return -2;
+  static bool attr = false;
+  if (!attr) {  // 74 KB: two workgroups per CU
+    hipError_t e = hipFuncSetAttribute((const void*)nn_top1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)NN_TOP1_LDS);
+    if (e != hipSuccess) return (int)e;
+    attr = true;
+  }
+  hipLaunchKernelGGL(nn_top1_kernel, dim3((Mx + NN_TILE - 1) / NN_TILE, splits), dim3(256), NN_TOP1_LDS, st, X, nx, Y, ny,
+                     reinterpret_cast<unsigned long long*>(part), Mx, My, Kp, loo ? 1 : 0, nct);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_merge(const uint64_t* part, int* idx, int Mx, int splits, hipStream_t st) {
+  if (!part || !idx || Mx < 1 || Mx > NN_MAX_ROWS || splits < 1) return -2;
+  hipLaunchKernelGGL(nn_merge_kernel, dim3((Mx + 255) / 256), dim3(256), 0, st,
+                     reinterpret_cast<const unsigned long long*>(part), idx, Mx, splits);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_refine(const float* x0, const float* y0, const int* idx, double* dist, int Mx, int My, int K,
+                             hipStream_t st) {
+  if (!x0 || !y0 || !idx || !dist || !nn_shape_ok(Mx, K) || !nn_shape_ok(My, K)) return -2;
+  hipLaunchKernelGGL(nn_refine_kernel, dim3((Mx + 3) / 4), dim3(256), 0, st, x0, y0, idx, dist, Mx, My, K);
+  return (int)hipGetLastError();
+}

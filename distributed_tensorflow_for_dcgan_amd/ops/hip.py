@@ -1417,3 +1417,155 @@ def swd(A: torch.Tensor, B: torch.Tensor, patches: int, seed: int, repeats: int 
     sw = Swd(n, S, C, int(patches), seed, repeats, dirs, device=A.device)
     sw.set_real(A)
     return sw.distance(B)
+
+
+# --------------------------------------------------------------------------- 1-NN two-sample test
+def _nn_levels(prog, x: torch.Tensor, size: int, tag: str):
+    """Record x's Gaussian pyramid down to side `size` (swd_down launches): the levels [x, ..., [n, size, size, C]],
+    which the caller keeps for as long as the Program."""
+    n, S, _, C = x.shape
+    g = [x]
+    while g[-1].shape[1] != size:
+        s = g[-1].shape[1]
+        g.append(torch.empty(n, s // 2, s // 2, C, dtype=torch.float32, device=x.device))
+        prog.swd_down("nn.%s.down%d" % (tag, s), _p(g[-2]), _p(g[-1]), n, s, C, 0)
+    return g
+
+
+def nn_splits(Mx: int, My: int) -> int:
+    """Column chunks of one nn_top1 launch: enough workgroups for two per CU of a 256-CU device, at most one
+    chunk per 128-column tile."""
+    T = ext().NN_TILE
+    return max(1, min((My + T - 1) // T, -(-512 // ((Mx + T - 1) // T))))
+
+
+class _NnSearch:
+    """The recorded ops of one block: nn_top1 of the rows (F, norm) of `x` against those of `y`, merge, refine."""
+
+    def __init__(self, prog, tag, x, y, idx, dist, loo, splits=None):
+        (X0, FX, nX), (Y0, FY, nY) = x, y
+        Mx, My, K, Kp = X0.shape[0], Y0.shape[0], X0.shape[1], FX.shape[1]
+        sp = nn_splits(Mx, My) if splits is None else int(splits)
+        if not 1 <= sp <= (My + ext().NN_TILE - 1) // ext().NN_TILE:
+            raise ValueError("nn_top1: splits must be in [1, %d], got %d" % ((My + ext().NN_TILE - 1) // ext().NN_TILE, sp))
+        self.part = torch.empty(sp, Mx, dtype=torch.int64, device=X0.device)
+        prog.nn_top1("nn.top1." + tag, _p(FX), _p(nX), _p(FY), _p(nY), _p(self.part), Mx, My, Kp, int(bool(loo)), sp, 0)
+        prog.nn_merge("nn.merge." + tag, _p(self.part), _p(idx), Mx, sp, 0)
+        prog.nn_refine("nn.refine." + tag, _p(X0), _p(Y0), _p(idx), _p(dist), Mx, My, K, 0)
+
+
+def _nn_side(prog, tag, x0: torch.Tensor, mu, compute_mu: bool):
+    """Record nn_features of the rows x0 [M, K]: (x0, F [M, Kp], norm [M])."""
+    M, K = x0.shape
+    F = torch.empty(M, ext().nn_kpad(K), dtype=torch.float32, device=x0.device)
+    norm = torch.empty(M, dtype=torch.float32, device=x0.device)
+    prog.nn_features("nn.features." + tag, _p(x0), M, K, 0 if mu is None else _p(mu), int(compute_mu), _p(F), _p(norm), 0)
+    return x0, F, norm
+
+
+def _nn_rows(op: str, X: torch.Tensor) -> torch.Tensor:
+    if X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous() or X.shape[0] < 1 or X.shape[1] < 1:
+        raise TypeError("%s: rows must be a contiguous float32 matrix [M, K], got %s %s" % (op, X.dtype, tuple(X.shape)))
+    return X
+
+
+def nn_features(x: torch.Tensor, size: Optional[int] = None, mu: Optional[torch.Tensor] = None):
+    """(F [n, Kp], norm [n], mu [K]) of the images x [n, S, S, C] float32 at pyramid side `size` (None: S): the
+    level minus `mu` -- None: the level's own mean over the n rows, which is returned -- zero-filled to Kp = K
+    rounded up to 16, and every row's squared norm (oracle: ops.reference.nn_features, uncentred)."""
+    from . import reference as R
+    n, S, _, C = _f32_images("nn_features", x).shape
+    if C > 4:
+        raise ValueError("nn_features: at most 4 channels, got %d" % C)
+    size = R.check_nn(n, size, S)
+    prog = ext().Program()
+    levels = _nn_levels(prog, x, size, "x")
+    lvl = levels[-1].view(n, -1)
+    own = mu is None
+    mu = torch.empty(lvl.shape[1], dtype=torch.float32, device=x.device) if own else mu.to(x.device, torch.float32).contiguous()
+    if mu.shape != (lvl.shape[1],):
+        raise ValueError("nn_features: mu must hold K = %d values" % lvl.shape[1])
+    _, F, norm = _nn_side(prog, "x", lvl, mu, own)
+    run(prog)
+    del levels
+    return F, norm, mu
+
+
+def nn_top1(X: torch.Tensor, Y: torch.Tensor, loo: bool = False, splits: Optional[int] = None, out=None):
+    """(index int32 [Mx], distance float64 [Mx]): per row of X [Mx, K] its nearest row of Y [My, K] in squared L2
+    distance, chosen by the MFMA Gram form with no centring, and that distance recomputed from the differences
+    (oracle: ops.reference.nn_top1). loo: X is Y and a row is not its own neighbour. splits: column chunks of the
+    launch (None: nn_splits). out: the (index, distance) tensors to write."""
+    _nn_rows("nn_top1", X), _nn_rows("nn_top1", Y)
+    if X.shape[1] != Y.shape[1] or (loo and X.shape != Y.shape) or Y.shape[0] < 1 + bool(loo):
+        raise ValueError("nn_top1: X [Mx, K] and Y [My, K] (one shape with loo, at least 2 rows), got %s and %s"
+                         % (tuple(X.shape), tuple(Y.shape)))
+    Mx = X.shape[0]
+    idx, dist = out if out is not None else (torch.empty(Mx, dtype=torch.int32, device=X.device),
+                                             torch.empty(Mx, dtype=torch.float64, device=X.device))
+    if idx.dtype != torch.int32 or dist.dtype != torch.float64 or idx.shape != (Mx,) or dist.shape != (Mx,):
+        raise TypeError("nn_top1: out must be (int32 [Mx], float64 [Mx])")
+    prog = ext().Program()
+    x = _nn_side(prog, "x", X, None, False)
+    y = x if loo else _nn_side(prog, "y", Y, None, False)
+    keep = _NnSearch(prog, "xy", x, y, idx, dist, loo, splits)
+    run(prog)
+    del keep
+    return idx, dist
+
+
+class NnMetric:
+    """The leave-one-out 1-NN two-sample test of image sets [n, S, S, C] against one real set, on the device
+    (nn.hip; oracle: ops.reference.nn_two_sample on nn_features). ``set_real`` computes the real set's level, its
+    mean, centred features and the (A, A) block once; every call costs the fake side and the three blocks that
+    involve it. Everything is recorded once: one Program per side."""
+
+    def __init__(self, n: int, S: int, C: int, size: Optional[int] = None, device="cuda"):
+        from . import reference as R
+        if not 1 <= int(C) <= 4:
+            raise ValueError("nn_two_sample: at most 4 channels, got %d" % C)
+        self.size = size = R.check_nn(n, size, S)
+        self.n, self.K = n, size * size * C
+        new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=device)  # noqa: E731
+        self.xa, self.x = new(n, S, S, C), new(n, S, S, C)  # the real set; the set under evaluation
+        self.mu = new(self.K)
+        # rows 0..n-1: the reals, n..2n-1: the evaluated set; A = nearest real, B = nearest fake
+        self.dA, self.dB = new(2 * n, dt=torch.float64), new(2 * n, dt=torch.float64)
+        self.jA, self.jB = new(2 * n, dt=torch.int32), new(2 * n, dt=torch.int32)
+        self.prog_real, self.prog_fake = ext().Program(), ext().Program()
+        la, lb = _nn_levels(self.prog_real, self.xa, size, "a"), _nn_levels(self.prog_fake, self.x, size, "b")
+        a = _nn_side(self.prog_real, "a", la[-1].view(n, -1), self.mu, True)
+        b = _nn_side(self.prog_fake, "b", lb[-1].view(n, -1), self.mu, False)
+        self._keep = [la, lb, a, b,
+                      _NnSearch(self.prog_real, "aa", a, a, self.jA[:n], self.dA[:n], True),
+                      _NnSearch(self.prog_fake, "ab", a, b, self.jB[:n], self.dB[:n], False),
+                      _NnSearch(self.prog_fake, "ba", b, a, self.jA[n:], self.dA[n:], False),
+                      _NnSearch(self.prog_fake, "bb", b, b, self.jB[n:], self.dB[n:], True)]
+        self.has_real = False
+
+    def set_real(self, real: torch.Tensor) -> None:
+        self.xa.copy_(real)
+        run(self.prog_real)
+        self.has_real = True
+
+    def __call__(self, x: Optional[torch.Tensor] = None):
+        """ops.reference.NnResult of x -- None: of what the caller wrote into ``self.x`` -- against the real set. The
+        label, the counts and the medians are torch on the device over the four [2n] arrays."""
+        from . import reference as R
+        if not self.has_real:
+            raise RuntimeError("nn_two_sample: set_real() first")
+        if x is not None:
+            self.x.copy_(x)
+        run(self.prog_fake)
+        return R.nn_summary(self.dA.clone(), self.jA.long(), self.dB.clone(), self.jB.long(), self.K)
+
+
+def nn_two_sample(A: torch.Tensor, B: torch.Tensor, size: Optional[int] = None):
+    """The 1-NN two-sample test between the image sets A (real) and B (fake), float32 [n, S, S, C] on the device,
+    in the pixels of pyramid level `size` (None: S): an ops.reference.NnResult."""
+    n, S, _, C = _f32_images("nn_two_sample", A).shape
+    if _f32_images("nn_two_sample", B).shape != A.shape:
+        raise ValueError("nn_two_sample: A and B must share a shape")
+    m = NnMetric(n, S, C, size, device=A.device)
+    m.set_real(A)
+    return m(B)

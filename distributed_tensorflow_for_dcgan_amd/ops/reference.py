@@ -1432,3 +1432,88 @@ def swd(A: torch.Tensor, B: torch.Tensor, patches: int, seed: int, repeats: int 
             proj.append((((d.reshape(-1, 49, C) - mu) / sigma).reshape(d.shape) @ theta.t()).t())
         out.append(1000.0 * float(swd_sorted_distance(proj[0], proj[1]).mean()))
     return out
+
+
+# --------------------------------------------------------------------------- 1-NN two-sample test
+# The leave-one-out 1-nearest-neighbour two-sample test (Lopez-Paz & Oquab 2017; Xu et al. 2018) between a real
+# and a generated image set, in the pixels of a Gaussian-pyramid level, and the nearest-training-image distance.
+class NnResult(NamedTuple):
+    dA: torch.Tensor      # [2n] squared distance to the nearest real row (rows 0..n-1: the reals, then the fakes)
+    jA: torch.Tensor      # [2n] ... and its index in the real set
+    dB: torch.Tensor      # [2n] squared distance to the nearest fake row
+    jB: torch.Tensor      # [2n] ... and its index in the fake set
+    counts: Tuple[int, int, int]  # reals called real, fakes called fake, rows
+    acc: float
+    acc_real: float
+    acc_fake: float
+    dist_fr: float
+    dist_rr: float
+
+
+def check_nn(n: int, size: int, S: int, names=("n", "size", "output size")) -> int:
+    """Validated feature side of the 1-NN test: `size` (0 or None = S) must be a level of swd_levels(S), n >= 2."""
+    n, size, S = int(n), int(size or 0) or int(S), int(S)
+    if n < 2:
+        raise ValueError("%s must be at least 2 for the 1-NN two-sample test, got %d" % (names[0], n))
+    if size not in swd_levels(S):
+        raise ValueError("%s must be one of the pyramid sizes %s of %s %d, got %d" % (names[1], swd_levels(S), names[2], S, size))
+    return size
+
+
+def nn_features(x: torch.Tensor, size: Optional[int] = None, dtype=torch.float64) -> torch.Tensor:
+    """[n, s * s * C]: the Gaussian-pyramid level of side s = size (None: S, the pixels) of x [n, S, S, C]."""
+    if x.dim() != 4 or x.shape[1] != x.shape[2] or x.shape[3] > 4:
+        raise ValueError("nn_features: images must be [n, S, S, C] with C <= 4, got %s" % (tuple(x.shape),))
+    size = check_nn(x.shape[0], size, x.shape[1])
+    g = x.to(dtype)
+    while g.shape[1] != size:
+        g = swd_down(g)
+    return g.reshape(g.shape[0], -1)
+
+
+def nn_distances(X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    """D [Mx, My] = sum_k (x_k - y_k)^2, from the differences (equal rows give exactly 0)."""
+    rows = max(1, (1 << 24) // max(1, Y.shape[0] * Y.shape[1]))
+    return torch.cat([((X[i:i + rows, None, :] - Y[None, :, :]) ** 2).sum(-1) for i in range(0, X.shape[0], rows)])
+
+
+def nn_top1(X: torch.Tensor, Y: torch.Tensor, loo: bool = False):
+    """(d [Mx], j [Mx]): per row of X its smallest squared distance to a row of Y and that row's index; equal
+    distances -> the smallest j. loo: X is Y, and a row is not its own neighbour."""
+    if X.dim() != 2 or Y.dim() != 2 or X.shape[1] != Y.shape[1] or (loo and X.shape != Y.shape) or Y.shape[0] < 1 + bool(loo):
+        raise ValueError("nn_top1: X [Mx, K] and Y [My, K] (one shape with loo, at least 2 rows), got %s and %s"
+                         % (tuple(X.shape), tuple(Y.shape)))
+    D = nn_distances(X, Y)
+    if loo:
+        D.fill_diagonal_(float("inf"))
+    d = D.min(1).values
+    cols = torch.arange(Y.shape[0], device=D.device).expand_as(D)
+    j = torch.where(D == d[:, None], cols, Y.shape[0]).min(1).values
+    return d, j
+
+
+def nn_summary(dA, jA, dB, jB, K: int) -> NnResult:
+    """The labels, counts, accuracies and median distances from the four [2n] arrays (torch, on their device)."""
+    n = dA.shape[0] // 2
+    real = dA <= dB  # a tie goes to real
+    cr, cf = int(real[:n].sum()), int((~real[n:]).sum())
+    rms = (dA.double() / K).sqrt()
+    return NnResult(dA, jA, dB, jB, (cr, cf, 2 * n), (cr + cf) / (2.0 * n), cr / float(n), cf / float(n),
+                    float(rms[n:].median()), float(rms[:n].median()))  # (torch's median is the lower one)
+
+
+def nn_two_sample(A: torch.Tensor, B: torch.Tensor) -> NnResult:
+    """The leave-one-out 1-NN two-sample test between the feature rows A (real) and B (fake), both [n, K]."""
+    if A.shape != B.shape or A.dim() != 2 or A.shape[0] < 2:
+        raise ValueError("nn_two_sample: A and B must share a shape [n, K] with n >= 2, got %s and %s"
+                         % (tuple(A.shape), tuple(B.shape)))
+    aa, ab, ba, bb = nn_top1(A, A, True), nn_top1(A, B), nn_top1(B, A), nn_top1(B, B, True)
+    return nn_summary(torch.cat([aa[0], ba[0]]), torch.cat([aa[1], ba[1]]), torch.cat([ab[0], bb[0]]),
+                      torch.cat([ab[1], bb[1]]), A.shape[1])
+
+
+def nn_report(r: NnResult) -> dict:
+    """What the engines' nn_metric returns: the five numbers and, per fake, the index of its nearest real image."""
+    n = r.dA.shape[0] // 2
+    return {"acc": r.acc, "acc_real": r.acc_real, "acc_fake": r.acc_fake, "dist_fr": r.dist_fr, "dist_rr": r.dist_rr,
+            "nearest": [int(j) for j in r.jA[n:].tolist()]}

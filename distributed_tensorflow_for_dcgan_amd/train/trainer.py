@@ -282,6 +282,7 @@ def run(flags: Flags, out=None) -> int:
     last_rate_t, last_rate_step = start_time, step
     losslog = AsyncLossLog(engine, device)
     swd_every, swd_at, swd_state = int(flags.swd_every), -1, {}
+    nn_every, nn_at, nn_state = int(flags.nn_every), -1, swd_state  # (one real draw for both metrics)
 
     def emit(entries):
         for (st, t, ips), L in entries:
@@ -359,6 +360,9 @@ def run(flags: Flags, out=None) -> int:
             if chief and swd_every > 0 and step % swd_every == 0:
                 swd_at = step
                 _swd(engine, flags, swd_state, sample_source or source, cfg, device, step, out, writer)
+            if chief and nn_every > 0 and step % nn_every == 0:
+                nn_at = step
+                _nn(engine, flags, nn_state, sample_source or source, cfg, device, step, out, writer)
             if int(flags.check_sync_every) > 0 and world > 1 and step % int(flags.check_sync_every) == 0:
                 tens = (engine.sync_check_tensors() if hasattr(engine, "sync_check_tensors")
                         else [engine.model.g.flat, engine.model.d.flat])
@@ -374,6 +378,8 @@ def run(flags: Flags, out=None) -> int:
             engine.sync_bn_state()
         if chief and swd_every > 0 and swd_at != step:  # once at the end of training
             _swd(engine, flags, swd_state, sample_source or source, cfg, device, step, out, writer)
+        if chief and nn_every > 0 and nn_at != step:
+            _nn(engine, flags, nn_state, sample_source or source, cfg, device, step, out, writer)
         if chief:
             path = ckpt.save(engine)
             print("saved %s" % path, file=out)
@@ -438,6 +444,13 @@ def _test_mode(engine, flags, cfg, B, device, info, chief, out) -> int:
             _swd(engine, flags, {}, src, cfg, device, step, out, None)
         finally:
             src.close()
+    if flags.explicitly_set("nn_images") and (flags.synthetic or os.path.isdir(flags.data_dir)):
+        shape = (cfg.output_size, cfg.output_size, cfg.c_dim)  # the restored checkpoint's 1-NN test
+        src = make_source(flags, B, shape, device, rank=0, world=1, engine_dtype=getattr(engine, "dtype_name", None))
+        try:
+            _nn(engine, flags, {}, src, cfg, device, step, out, None)
+        finally:
+            src.close()
     if flags.visualize:
         base = (torch.rand(1, cfg.z_dim, generator=gen) * 2 - 1).repeat(B, 1)
         sweep = torch.linspace(-1.0, 1.0, B)
@@ -478,14 +491,11 @@ def _swd(engine, flags, state, source, cfg, device, step, out, writer) -> None:
                     max_rows=int(flags.swd_max_rows))
     except ValueError as e:
         raise SystemExit(str(e))
-    if not state:
-        got = []
-        while sum(x.shape[0] for x in got) < n:
-            got.append(source.next().to(device, torch.float32))
-        state["real"] = torch.cat(got)[:n].contiguous()
+    real = _metric_reals(flags, state, source, device)[:n]
+    if "z" not in state:
         gen = torch.Generator().manual_seed(int(flags.seed) + 4242)
         state["z"] = (torch.rand(n, cfg.z_dim, generator=gen) * 2 - 1).to(device)
-    vals = engine.swd(state["real"], state["z"], patches, int(flags.seed), ema=_sample_ema(engine, flags),
+    vals = engine.swd(real, state["z"], patches, int(flags.seed), ema=_sample_ema(engine, flags),
                       max_rows=int(flags.swd_max_rows))
     sizes = R.swd_levels(cfg.output_size)
     avg = sum(vals) / len(vals)
@@ -494,3 +504,52 @@ def _swd(engine, flags, state, source, cfg, device, step, out, writer) -> None:
     if writer is not None:
         writer.add_summary_values([SummaryWriter.scalar("swd/%d" % s, v) for s, v in zip(sizes, vals)] +
                                   [SummaryWriter.scalar("swd/avg", avg)], step)
+
+
+def _metric_reals(flags, state, source, device) -> torch.Tensor:
+    """The fixed real set of --swd_every and --nn_every, drawn from `source` at the first evaluation of either
+    (ceil(n / B) batches): as many images as the larger of the metrics that are on asks for."""
+    if "real" not in state:
+        n = max([int(flags.swd_images)] * (int(flags.swd_every) > 0 or not int(flags.nn_every) > 0) +
+                [int(flags.nn_images)] * (int(flags.nn_every) > 0 or flags.explicitly_set("nn_images")))
+        got = []
+        while sum(x.shape[0] for x in got) < n:
+            got.append(source.next().to(device, torch.float32))
+        state["real"] = torch.cat(got)[:n].contiguous()
+    return state["real"]
+
+
+def _nn(engine, flags, state, source, cfg, device, step, out, writer) -> None:
+    """Chief side path of --nn_every: the leave-one-out 1-NN two-sample test between a fixed real set and the
+    samples of a fixed z, and with --nn_grid the first fakes beside their nearest real images."""
+    n, g = int(flags.nn_images), int(flags.nn_grid)
+    try:
+        size = R.check_nn(n, flags.nn_size, cfg.output_size, ("--nn_images", "--nn_size", "--output_size"))
+    except ValueError as e:
+        raise SystemExit(str(e))
+    real = _metric_reals(flags, state, source, device)[:n].contiguous()
+    if real.shape[0] < n:
+        raise SystemExit("--nn_images=%d needs %d real images, the metrics' draw holds %d" % (n, n, real.shape[0]))
+    if "nn_z" not in state:
+        gen = torch.Generator().manual_seed(int(flags.seed) + 4243)
+        state["nn_z"] = (torch.rand(n, cfg.z_dim, generator=gen) * 2 - 1).to(device)
+    ema = _sample_ema(engine, flags)
+    r = engine.nn_metric(real, state["nn_z"], size, ema=ema)
+    print("[NN] step %d  1nn: %.3f (real %.3f  fake %.3f)  fake->real %.4f  real->real %.4f"
+          % (step, r["acc"], r["acc_real"], r["acc_fake"], r["dist_fr"], r["dist_rr"]), file=out, flush=True)
+    if writer is not None:
+        writer.add_summary_values([SummaryWriter.scalar("nn/" + k, r[v]) for k, v in (
+            ("acc", "acc"), ("acc_real", "acc_real"), ("acc_fake", "acc_fake"), ("dist_fake_real", "dist_fr"),
+            ("dist_real_real", "dist_rr"))], step)
+    if g > 0:
+        g = min(g, n)
+        z, B, fake = state["nn_z"], int(getattr(engine, "B", 0) or engine.batch_size), []
+        for i in range(0, g, B):  # (whole batches: the HIP sampler's programs are recorded for B rows)
+            zc = z[i:i + B] if i + B <= n else torch.cat([z[i:], z.new_zeros(i + B - n, z.shape[1])])
+            fake.append(engine.sampler(zc, ema=ema).detach().float())
+        fake = torch.cat(fake)[:g]
+        near = real[torch.tensor(r["nearest"][:g], device=real.device)]
+        pairs = torch.stack([fake.to(real.device), near], 1).reshape(2 * g, *real.shape[1:])
+        os.makedirs(flags.sample_dir, exist_ok=True)
+        IM.save_images(pairs.cpu().numpy(), (g, 2), os.path.join(flags.sample_dir, "nn_%d.png" % step))
+

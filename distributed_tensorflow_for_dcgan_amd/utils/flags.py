@@ -147,6 +147,16 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
     ("swd_images", "int", 256, "images per set of the distance"),
     ("swd_patches", "int", 128, "7x7 patches per image and level; --swd_images * --swd_patches must be a power of "
                                 "two in [16, --swd_max_rows]"),
+    ("nn_every", "int", 0, "every N steps, and at the end of training, the chief prints the leave-one-out 1-NN two-sample "
+                           "test between --nn_images real and generated images: its accuracy per class (0.5 / 0.5 is the "
+                           "goal; fake -> 1: collapse; both -> 0: memorisation) and the median RMS distance of a "
+                           "generated image to its nearest real one beside that of the real set itself. 0 turns it "
+                           "off. The real set is drawn as --swd_every draws its own (one draw when both are on)"),
+    ("nn_images", "int", 1024, "images per set of the 1-NN test, at least 2"),
+    ("nn_size", "int", 0, "side of the Gaussian-pyramid level whose pixels are compared: --output_size halved while "
+                          "even and at least 16. 0 = --output_size, the images themselves"),
+    ("nn_grid", "int", 0, "with --nn_every: also write nn_<step>.png into --sample_dir, the first g generated images, "
+                          "each beside its nearest real one. 0 = none"),
     ("swd_max_rows", "int", 32768, "largest --swd_images * --swd_patches accepted: a power of two in [32768, 2^21]. "
                                    "Above 32768 the HIP engine sorts with its global merge sort and holds two "
                                    "float32 [512, N] buffers per pyramid level plus two key buffers (34.6 GiB at "
@@ -243,6 +253,16 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
                       max_rows=ns.swd_max_rows)
     except ValueError as e:
         parser.error(str(e))
+    if int(ns.nn_every) < 0 or int(ns.nn_grid) < 0:
+        parser.error("--nn_every and --nn_grid must be >= 0, got %r and %r" % (ns.nn_every, ns.nn_grid))
+    if int(ns.nn_every) > 0 or any(a.split("=")[0] in ("--nn_images", "--nn_size", "--nn_grid") for a in argv):
+        from ..ops.reference import check_nn
+        try:
+            check_nn(ns.nn_images, ns.nn_size, ns.output_size, ("--nn_images", "--nn_size", "--output_size"))
+        except ValueError as e:
+            parser.error(str(e))
+        if int(ns.nn_grid) > int(ns.nn_images):
+            parser.error("--nn_grid must be at most --nn_images, got %r" % (ns.nn_grid,))
     names = {n for n, _, _, _ in ALL_FLAGS}
     explicit = set()
     for tok in argv:
