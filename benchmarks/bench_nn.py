@@ -1,8 +1,11 @@
 """Time of ``engine.nn_metric`` on the HIP engine: the first evaluation (real side, its leave-one-out search, fake
 side and the three blocks that involve it) and a cached one (fake side only), in HIP events around each call, and in
 the same process ``torch.cdist`` + ``min`` over the same four blocks of the same feature matrices as the yardstick.
+With ``--k`` the same for the metric with the k-NN manifold estimates next to the k = 0 numbers of the same run, the
+nn_topk kernel against nn_top1 and nn_count on the (A, A) block alone, and ``torch.cdist`` + ``topk`` + the comparison
+against the radii as the yardstick.
 
-    python benchmarks/bench_nn.py [--images 1024] [--output_size 64] [--nn_size 0] [--iters 10] [--out FILE]
+    python benchmarks/bench_nn.py [--images 1024] [--output_size 64] [--nn_size 0] [--k 0] [--iters 10] [--out FILE]
 """
 import argparse
 import json
@@ -24,6 +27,7 @@ def main():
     ap.add_argument("--c_dim", type=int, default=3)
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
+    ap.add_argument("--k", type=int, default=0, help="also time the metric with precision / recall / density / coverage")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None, help="also append the result line to this file")
     a = ap.parse_args()
@@ -73,6 +77,45 @@ def main():
            "cdist_min_max": [round(cd[0], 3), round(cd[-1], 3)],
            "gemm_flop_first": 4 * 2.0 * n * n * nn._keep[2][1].shape[1],
            "result": {k: (round(v, 4) if isinstance(v, float) else None) for k, v in res.items() if k != "nearest"}}
+    if a.k > 0:
+        from distributed_tensorflow_for_dcgan_amd.ops import hip as H
+        timed(lambda: eng.nn_metric(real, z, a.nn_size, refresh=True, k=a.k))
+        first_k = sorted(timed(lambda: eng.nn_metric(real, z, a.nn_size, refresh=True, k=a.k))[0] for _ in range(a.iters))
+        cached_k = sorted(timed(lambda: eng.nn_metric(None, z, a.nn_size, k=a.k))[0] for _ in range(a.iters))
+        res_k = eng.nn_metric(None, z, a.nn_size, k=a.k)
+        nk = eng._nn
+        (_, FA, nA), (_, FB, nB) = nk._keep[2], nk._keep[3]
+        Kp, sp, e, p = FA.shape[1], H.nn_splits(n, n), H.ext(), H._p
+        part = torch.empty(sp, n, a.k, dtype=torch.int64, device=dev)
+        cpart, cnt = torch.empty(sp, n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        progs = {"top1": e.Program(), "topk": e.Program(), "count": e.Program()}  # the (A, A) block's GEMM kernel alone
+        progs["top1"].nn_top1("top1", p(FA), p(nA), p(FA), p(nA), p(part), n, n, Kp, 1, sp, 0)
+        progs["topk"].nn_topk("topk", p(FA), p(nA), p(FA), p(nA), p(part), n, n, Kp, 1, sp, a.k, 0)
+        progs["count"].nn_count("count", p(FA), p(nA), p(FA), p(nA), p(nk.rad[:n]), p(cpart), p(cnt), n, n, Kp, sp, 0)
+        kern = {}
+        for name, prog in progs.items():
+            timed(lambda: H.run(prog))
+            kern[name] = sorted(timed(lambda: H.run(prog))[0] for _ in range(a.iters))
+
+        def yard_k():
+            r, res = {}, []
+            for X, Y, loo in ((FA, FA, True), (FB, FB, True), (FA, FB, False), (FB, FA, False)):
+                D = torch.cdist(X, Y)
+                if loo:
+                    D.fill_diagonal_(float("inf"))
+                    r[id(X)] = D.topk(a.k, dim=1, largest=False).values[:, -1]
+                    res.append(r[id(X)])
+                else:
+                    res += [D.min(1), (D <= r[id(Y)][None, :]).sum(1)]
+            return res
+        timed(yard_k)
+        cdk = sorted(timed(yard_k)[0] for _ in range(a.iters))
+        out.update({"k": a.k, "first_k_ms_median": med(first_k), "first_k_ms_min_max": [round(first_k[0], 3), round(first_k[-1], 3)],
+                    "cached_k_ms_median": med(cached_k), "cached_k_ms_min_max": [round(cached_k[0], 3), round(cached_k[-1], 3)],
+                    "aa_kernel_ms_median": {m: med(v) for m, v in kern.items()},
+                    "aa_kernel_ms_min_max": {m: [round(v[0], 3), round(v[-1], 3)] for m, v in kern.items()},
+                    "cdist_topk_count_ms_median": med(cdk), "cdist_topk_count_min_max": [round(cdk[0], 3), round(cdk[-1], 3)],
+                    "result_k": {m: round(v, 4) for m, v in res_k.items() if m in ("precision", "recall", "density", "coverage")}})
     line = json.dumps(out)
     print(line)
     if a.out:

@@ -1476,6 +1476,38 @@ class Program {
       return dcg_nn_refine(P<const float>(x0), P<const float>(y0), P<const int>(idx), P<double>(dist), Mx, My, K, st);
     }, AccList().r(x0, (size_t)Mx * K * 4).r(y0, (size_t)My * K * 4).r(idx, (size_t)Mx * 4).w(dist, (size_t)Mx * 8).v);
   }
+  // part uint64 [splits][Mx][k]: per row of X and column chunk its k smallest (key(d) << 32 | column), ascending
+  int nn_topk(std::string name, uintptr_t X, uintptr_t nx, uintptr_t Y, uintptr_t ny, uintptr_t part, int Mx, int My,
+              int Kp, int loo, int splits, int k, int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_topk(P<const float>(X), P<const float>(nx), P<const float>(Y), P<const float>(ny), P<uint64_t>(part),
+                         Mx, My, Kp, loo, splits, k, st);
+    }, AccList().r(X, (size_t)Mx * Kp * 4).r(nx, (size_t)Mx * 4).r(Y, (size_t)My * Kp * 4).r(ny, (size_t)My * 4)
+           .w(part, (size_t)splits * Mx * k * 8).v);
+  }
+  int nn_merge_k(std::string name, uintptr_t part, uintptr_t idx, int Mx, int splits, int k, int stream) {
+    return add(name, stream,
+               [=](hipStream_t st) { return dcg_nn_merge_k(P<const uint64_t>(part), P<int>(idx), Mx, splits, k, st); },
+               AccList().r(part, (size_t)splits * Mx * k * 8).w(idx, (size_t)Mx * k * 4).v);
+  }
+  // dist double [Mx][k] = nn_refine's distance of every candidate idx [Mx][k]; rad float [Mx] = the row's largest
+  int nn_radius(std::string name, uintptr_t x0, uintptr_t y0, uintptr_t idx, uintptr_t dist, uintptr_t rad, int Mx, int My,
+                int K, int k, int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_radius(P<const float>(x0), P<const float>(y0), P<const int>(idx), P<double>(dist), P<float>(rad), Mx,
+                           My, K, k, st);
+    }, AccList().r(x0, (size_t)Mx * K * 4).r(y0, (size_t)My * K * 4).r(idx, (size_t)Mx * k * 4)
+           .w(dist, (size_t)Mx * k * 8).w(rad, (size_t)Mx * 4).v);
+  }
+  // cnt int32 [Mx] = per row of X the columns of Y whose ball rad [My] it lies in; part int32 [splits][Mx]
+  int nn_count(std::string name, uintptr_t X, uintptr_t nx, uintptr_t Y, uintptr_t ny, uintptr_t rad, uintptr_t part,
+               uintptr_t cnt, int Mx, int My, int Kp, int splits, int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_count(P<const float>(X), P<const float>(nx), P<const float>(Y), P<const float>(ny), P<const float>(rad),
+                          P<int>(part), P<int>(cnt), Mx, My, Kp, splits, st);
+    }, AccList().r(X, (size_t)Mx * Kp * 4).r(nx, (size_t)Mx * 4).r(Y, (size_t)My * Kp * 4).r(ny, (size_t)My * 4)
+           .r(rad, (size_t)My * 4).w(part, (size_t)splits * Mx * 4).w(cnt, (size_t)Mx * 4).v);
+  }
 
  private:
   int add(const std::string& name, int stream, std::function<int(hipStream_t)> fn, std::vector<Acc> acc,
@@ -1556,6 +1588,7 @@ PYBIND11_MODULE(_dcgan_hip, m) {
   m.def("swd_kpad", &swd_kpad);  // k depth of the projection's theta' rows for C channels
   m.def("nn_kpad", &nn_kpad);  // row length of the feature matrix for K features
   m.attr("NN_TILE") = (int)NN_TILE;
+  m.attr("NN_MAX_KNN") = (int)NN_MAX_KNN;
   m.attr("SWD_FUSED_ROWS") = (int)SWD_FUSED_ROWS;
   m.attr("SWD_GLOBAL_MAX_ROWS") = (int)SWD_GLOBAL_MAX_ROWS;  // N of swd_sort_large: (32768, 2^21]
   m.attr("SWD_CHUNK_ROWS") = (int)SWD_CHUNK_ROWS;
@@ -1727,5 +1760,9 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("nn_features", &Program::nn_features)
       .def("nn_top1", &Program::nn_top1)
       .def("nn_merge", &Program::nn_merge)
-      .def("nn_refine", &Program::nn_refine);
+      .def("nn_refine", &Program::nn_refine)
+      .def("nn_topk", &Program::nn_topk)
+      .def("nn_merge_k", &Program::nn_merge_k)
+      .def("nn_radius", &Program::nn_radius)
+      .def("nn_count", &Program::nn_count);
 }

@@ -1,4 +1,4 @@
-// 1-nearest-neighbour search between two sets of feature rows (nn.hip): limits and host launchers. Everything
+// 1- and k-nearest-neighbour search between two sets of feature rows (nn.hip): limits and host launchers. Everything
 // is fp32 whatever the engine's element type, so the file is built once and its launchers carry no suffix.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@ constexpr int NN_MEAN_ROWS = 64;    // rows per fp64 partial sum of the mean
 constexpr int NN_FEAT_ROWS = 4;     // rows per workgroup of nn_features
 constexpr int NN_MAX_ROWS = 1 << 20;
 constexpr int NN_MAX_K = 1 << 20;
+constexpr int NN_MAX_KNN = 16;      // neighbours per row of nn_topk: one per lane of the 16 that share a row
 
 // K padded with zeros to the k depth of four 16x16x4 MFMAs
 static inline int nn_kpad(int K) { return (K + 15) & ~15; }
@@ -34,4 +35,16 @@ int dcg_nn_top1(const float* X, const float* nx, const float* Y, const float* ny
 int dcg_nn_merge(const uint64_t* part, int* idx, int Mx, int splits, hipStream_t st);
 // dist [Mx] = sum_k (x0[i][k] - y0[idx[i]][k])^2 from the uncentred rows: fp32 differences and squares, fp64 sums
 int dcg_nn_refine(const float* x0, const float* y0, const int* idx, double* dist, int Mx, int My, int K, hipStream_t st);
+// part [splits][Mx][k] = per row and column chunk the k smallest keys of dcg_nn_top1's kind, ascending, ~0 where the
+// chunk has fewer than k columns. 1 <= k <= NN_MAX_KNN, k <= My (My - 1 with loo); bitwise independent of splits
+int dcg_nn_topk(const float* X, const float* nx, const float* Y, const float* ny, uint64_t* part, int Mx, int My, int Kp,
+                int loo, int splits, int k, hipStream_t st);
+// idx [Mx][k] = the columns of the k smallest of part [splits][Mx][k] over the chunks, ascending by key; -1: none
+int dcg_nn_merge_k(const uint64_t* part, int* idx, int Mx, int splits, int k, hipStream_t st);
+// dist [Mx][k] = dcg_nn_refine's distance of every candidate idx [Mx][k]; rad [Mx] = the fp32 value of the row's largest
+int dcg_nn_radius(const float* x0, const float* y0, const int* idx, double* dist, float* rad, int Mx, int My, int K, int k,
+                  hipStream_t st);
+// cnt [Mx] = #{j < My : nx_i + ny_j - 2 x_i.y_j <= rad_j}, through the chunks' counts part int [splits][Mx] in chunk order
+int dcg_nn_count(const float* X, const float* nx, const float* Y, const float* ny, const float* rad, int* part, int* cnt,
+                 int Mx, int My, int Kp, int splits, hipStream_t st);
 }

@@ -1,6 +1,7 @@
 // dcg-variants: bf16
-// 1-nearest-neighbour search between two sets of feature rows: the hot path of the leave-one-out 1-NN
-// two-sample test (Lopez-Paz & Oquab 2017) and of the nearest-training-image distance. fp32 throughout,
+// Nearest-neighbour search between two sets of feature rows: the hot path of the leave-one-out 1-NN two-sample
+// test (Lopez-Paz & Oquab 2017), of the nearest-training-image distance and of the k-NN manifold estimates
+// (precision / recall, Kynkaanniemi et al. 2019; density / coverage, Naeem et al. 2020). fp32 throughout,
 // whatever the engine's element type (one build, nn.h): bf16's 2^-8 is the size of the gaps being compared.
 // It runs beside the training step, never inside it.
 //
@@ -28,6 +29,24 @@
 //   nn_refine    the Gram form is only good enough to choose. The winner's distance is recomputed from the
 //                uncentred rows, (x_k - y_k)^2 in fp32 summed in fp64: one wave per row, every lane its k in
 //                index order, then a shuffle tree -- a fixed order; a bitwise duplicate reports exactly 0
+//   nn_topk      the same GEMM (nn_gemm_tiles: one main loop for nn_topk and nn_count) with a k-smallest selection,
+//                k <= 16, in its epilogue. The packed keys of one row are distinct, so "the k smallest keys of a
+//                set" does not depend on the order they are met in. A row's list lies across the 16 lanes that
+//                share the row (all fr of one fq): lane fr < k holds the fr-th smallest so far, in the registers
+//                that hold nn_top1's minima; lane k - 1 holds the row's threshold. Per tile a lane tests its 4 new
+//                keys of the row against the threshold (one broadcast shuffle); only if some lane of the wave has
+//                one below it does the wave re-select: k rounds of "smallest key above the last one extracted"
+//                over the group's 16 x (4 new + 1 listed) keys, each round a 4-step shuffle minimum, round p
+//                landing in lane p. Once the lists have filled a row triggers about k ln(My) times in all. The
+//                two column waves' lists meet once per chunk in LDS (the operand tiles' space) and merge by two
+//                pointers into part [chunk][row][k], NN_NONE where the chunk has fewer than k columns
+//   nn_merge_k   idx [Mx][k] = the columns of the k smallest keys of part over the chunks, ascending, -1 where
+//                there is none: one wave per row, k rounds of the same extraction over the row's splits * k keys
+//   nn_radius    nn_refine for all k candidates of a row, one wave per candidate, and rad = the fp32 value of
+//                the largest: the squared radius of the row's k-NN ball
+//   nn_count     the same GEMM with an integer epilogue: cnt [row] = #{col : nx + ny - 2 g <= rad [col]}, 16
+//                counters per lane where nn_top1 holds its minima, summed across the 16 lanes by shuffles, across
+//                the two column waves through LDS and across the chunks in chunk order. Integers only
 // Every index into a feature matrix is 64-bit: n Kp passes 2^31 at 128x128x3.
 #include "common.h"
 #include "nn.h"
@@ -80,7 +99,7 @@ __global__ __launch_bounds__(256) void nn_features_kernel(const float* __restric
   }
 }
 
-// ---------------------------------------------------------------- the distance GEMM with its selection
+// ---------------------------------------------------------------- the distance GEMM with its epilogues
 // topk's key (misc.hip topk_key): uint32, monotone in x, -0 < +0
 __device__ __forceinline__ uint32_t nn_key(float x) {
   const uint32_t u = __builtin_bit_cast(uint32_t, x);
@@ -88,9 +107,81 @@ __device__ __forceinline__ uint32_t nn_key(float x) {
 }
 constexpr unsigned long long NN_NONE = ~0ull;  // no candidate: above every (key, column)
 constexpr int NN_TILE_F = NN_TILE * NN_PITCH;  // floats of one operand tile in LDS
-constexpr size_t NN_TOP1_LDS = (size_t)4 * NN_TILE_F * sizeof(float) + (size_t)2 * NN_TILE * sizeof(unsigned long long);
+constexpr size_t NN_GEMM_LDS = (size_t)4 * NN_TILE_F * sizeof(float);
+constexpr size_t NN_TOP1_LDS = NN_GEMM_LDS + (size_t)2 * NN_TILE * sizeof(unsigned long long);
+constexpr int NN_LIST_PITCH = NN_MAX_KNN + 1;  // 64-bit words between two rows' lists in LDS: odd, so rows spread over banks
+static_assert((size_t)2 * NN_TILE * NN_LIST_PITCH * sizeof(unsigned long long) <= NN_GEMM_LDS, "nn: lists fit the tiles");
 
 __device__ __forceinline__ unsigned long long nn_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+
+// nn_top1's main loop for nn_topk and nn_count (nn_top1_kernel keeps its own copy below: built on this function it
+// takes 250 VGPRs for its 248): the workgroup's 128 rows from m0 against the column tiles [t0, t1) of Y. Whenever a tile's sums are complete, epi(first column of the wave's 64, acc) consumes and clears
+// them: C fragment acc[i][j][r] = row wr * 64 + i * 16 + 4 fq + r, column j * 16 + fr. The last epilogue is followed
+// by a barrier, after which the operand tiles in LDS are free
+template <class Epi>
+__device__ __forceinline__ void nn_gemm_tiles(const float* __restrict__ X, const float* __restrict__ Y, float* lds, int Mx,
+                                              int My, int Kp, int m0, int t0, int t1, Epi epi) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int nk = (Kp + NN_BK - 1) / NN_BK, steps = (t1 - t0) * nk;
+  const int lr = tid >> 3, lq = tid & 7;  // the loader's rows lr + 32 p, its 16-byte word lq of the 32 k
+  const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 sx[4], sy[4];
+
+  auto fetch = [&](int it) {  // rows past the ends and k past Kp read as zeros
+    const int ct = t0 + it / nk, k0 = (it % nk) * NN_BK + 4 * lq;
+    const bool kok = k0 < Kp;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int rx = m0 + lr + 32 * p, ry = ct * NN_TILE + lr + 32 * p;
+      sx[p] = (kok && rx < Mx) ? *reinterpret_cast<const f32x4*>(X + (size_t)rx * Kp + k0) : zero;
+      sy[p] = (kok && ry < My) ? *reinterpret_cast<const f32x4*>(Y + (size_t)ry * Kp + k0) : zero;
+    }
+  };
+  auto stash = [&](int buf) {
+    float* bx = lds + buf * 2 * NN_TILE_F + lr * NN_PITCH + 4 * lq;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      *reinterpret_cast<f32x4*>(bx + 32 * p * NN_PITCH) = sx[p];
+      *reinterpret_cast<f32x4*>(bx + NN_TILE_F + 32 * p * NN_PITCH) = sy[p];
+    }
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = zero;
+
+  fetch(0);
+  stash(0);
+  __syncthreads();
+  for (int it = 0; it < steps; ++it) {
+    const int buf = it & 1;
+    const bool more = it + 1 < steps;
+    if (more) fetch(it + 1);
+    const float* bx = lds + buf * 2 * NN_TILE_F + (wr * 64 + fr) * NN_PITCH + 4 * fq;
+    const float* by = lds + buf * 2 * NN_TILE_F + NN_TILE_F + (wc * 64 + fr) * NN_PITCH + 4 * fq;
+#pragma unroll
+    for (int kk = 0; kk < NN_BK; kk += 16) {  // lane group fq supplies k = kk + 4 fq + e to MFMA e, for A and B alike
+      f32x4 a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const f32x4*>(bx + i * 16 * NN_PITCH + kk);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const f32x4*>(by + j * 16 * NN_PITCH + kk);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
+    }
+    if (more) stash(buf ^ 1);  // (last read in step it - 1, before that step's barrier)
+    if ((it + 1) % nk == 0) epi((t0 + it / nk) * NN_TILE + wc * 64, acc);  // the tile is complete
+    __syncthreads();
+  }
+}
 
 // two waves per SIMD (248 VGPRs, no scratch): two workgroups per CU, the second one's MFMAs cover this one's barrier
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -212,7 +303,128 @@ __global__ __launch_bounds__(256) void nn_merge_kernel(const unsigned long long*
   idx[i] = (int)(unsigned)b;  // (-1: no candidate)
 }
 
+// ---------------------------------------------------------------- the k smallest per row
+// list[i][r] of lane (fr, fq): the fr-th smallest key so far of row wr * 64 + i * 16 + 4 fq + r (NN_NONE from lane k on)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void nn_topk_kernel(const float* __restrict__ X, const float* __restrict__ nx, const float* __restrict__ Y,
+                    const float* __restrict__ ny, unsigned long long* __restrict__ part, int Mx, int My, int Kp, int loo,
+                    int nct, int k) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [2 buffers][X tile, Y tile][128][36]; at the end the lists
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int m0 = blockIdx.x * NN_TILE, chunk = blockIdx.y, splits = gridDim.y;
+  const int t0 = (int)((long long)chunk * nct / splits), t1 = (int)((long long)(chunk + 1) * nct / splits);
+  const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  float nxr[4][4];
+  unsigned long long list[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = m0 + wr * 64 + i * 16 + 4 * fq + r;
+      nxr[i][r] = row < Mx ? nx[row] : 0.f;
+      list[i][r] = NN_NONE;
+    }
+
+  nn_gemm_tiles(X, Y, lds, Mx, My, Kp, m0, t0, t1, [&](int cbase, f32x4 (&acc)[4][4]) {
+    float nyv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) nyv[j] = cbase + j * 16 + fr < My ? ny[cbase + j * 16 + fr] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = m0 + wr * 64 + i * 16 + 4 * fq + r;
+        unsigned long long c[4];  // the lane's new keys of this row
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int col = cbase + j * 16 + fr;
+          const float d = __builtin_fmaf(-2.f, acc[i][j][r], nxr[i][r] + nyv[j]);
+          c[j] = ((unsigned long long)nn_key(d) << 32) | (unsigned)col;
+          if (col >= My || (loo && col == row)) c[j] = NN_NONE;
+        }
+        const unsigned long long thr = __shfl(list[i][r], k - 1, 16);
+        const unsigned long long low = nn_min(nn_min(c[0], c[1]), nn_min(c[2], c[3]));
+        if (__any(low < thr)) {  // (wave-uniform) some row of the wave's four groups gains a key
+          unsigned long long prev = 0, mine = NN_NONE;
+          for (int p = 0; p < k; ++p) {  // round p: the smallest key above round p - 1's, into lane p
+            unsigned long long m = (p == 0 || list[i][r] > prev) ? list[i][r] : NN_NONE;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (p == 0 || c[j] > prev) m = nn_min(m, c[j]);
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) m = nn_min(m, __shfl_xor(m, o, 64));
+            if (fr == p) mine = m;
+            prev = m;  // (NN_NONE once the keys are used up: nothing lies above it)
+          }
+          list[i][r] = mine;
+        }
+      }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = zero;
+  });
+
+  unsigned long long* red = reinterpret_cast<unsigned long long*>(lds);  // [2 column waves][128][NN_LIST_PITCH]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      red[(size_t)(wc * NN_TILE + wr * 64 + i * 16 + 4 * fq + r) * NN_LIST_PITCH + fr] = list[i][r];
+  __syncthreads();
+  if (tid < NN_TILE && m0 + tid < Mx) {  // two ascending lists -> the k smallest of both
+    const unsigned long long* a = red + (size_t)tid * NN_LIST_PITCH;
+    const unsigned long long* b = red + (size_t)(NN_TILE + tid) * NN_LIST_PITCH;
+    unsigned long long* dst = part + ((size_t)chunk * Mx + m0 + tid) * k;
+    int ia = 0, ib = 0;
+    for (int p = 0; p < k; ++p) {  // (ia + ib = p < k <= 16: inside the lists)
+      const unsigned long long va = a[ia], vb = b[ib];
+      const bool fa = va <= vb;
+      dst[p] = fa ? va : vb;
+      ia += fa ? 1 : 0;
+      ib += fa ? 0 : 1;
+    }
+  }
+}
+
+// one wave per row: round p takes the smallest of the row's splits * k keys above round p - 1's
+__global__ __launch_bounds__(256) void nn_merge_k_kernel(const unsigned long long* __restrict__ part, int* __restrict__ idx,
+                                                         int Mx, int splits, int k) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= Mx) return;
+  unsigned long long prev = 0;
+  for (int p = 0; p < k; ++p) {
+    unsigned long long m = NN_NONE;
+    for (int c = 0; c < splits; ++c) {
+      const unsigned long long* src = part + ((size_t)c * Mx + row) * k;
+      for (int q = lane; q < k; q += 64) {
+        const unsigned long long e = src[q];
+        if (p == 0 || e > prev) m = nn_min(m, e);
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = nn_min(m, __shfl_xor(m, o, 64));
+    if (lane == 0) idx[(size_t)row * k + p] = (int)(unsigned)m;  // (-1: no candidate)
+    prev = m;
+  }
+}
+
 // ---------------------------------------------------------------- the winner's distance, recomputed
+// sum_k (x_k - y_k)^2 over the wave: fp32 differences and squares, every lane its k in index order in fp64, a shuffle tree
+__device__ __forceinline__ double nn_wave_dist(const float* __restrict__ x, const float* __restrict__ y, int K, int lane) {
+  double s = 0.0;
+  for (int k = lane; k < K; k += 64) {
+    const float df = x[k] - y[k];
+    const float sq = df * df;
+    s += (double)sq;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+
 __global__ __launch_bounds__(256) void nn_refine_kernel(const float* __restrict__ x0, const float* __restrict__ y0,
                                                         const int* __restrict__ idx, double* __restrict__ dist, int Mx,
                                                         int My, int K) {
@@ -220,23 +432,111 @@ __global__ __launch_bounds__(256) void nn_refine_kernel(const float* __restrict_
   if (row >= Mx) return;
   const int j = idx[row];
   double s = __builtin_inf();
-  if (j >= 0 && j < My) {
-    const float* x = x0 + (size_t)row * K;
-    const float* y = y0 + (size_t)j * K;
-    s = 0.0;
-    for (int k = lane; k < K; k += 64) {
-      const float df = x[k] - y[k];
-      const float sq = df * df;
-      s += (double)sq;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  }
+  if (j >= 0 && j < My) s = nn_wave_dist(x0 + (size_t)row * K, y0 + (size_t)j * K, K, lane);
   if (lane == 0) dist[row] = s;
+}
+
+// a workgroup per row, a wave per candidate (p = wave, wave + 4, ...); rad = the largest of the row's k distances
+__global__ __launch_bounds__(256) void nn_radius_kernel(const float* __restrict__ x0, const float* __restrict__ y0,
+                                                        const int* __restrict__ idx, double* __restrict__ dist,
+                                                        float* __restrict__ rad, int Mx, int My, int K, int k) {
+  __shared__ double top[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, row = blockIdx.x;
+  double most = 0.0;
+  for (int p = wave; p < k; p += 4) {
+    const int j = idx[(size_t)row * k + p];
+    double s = __builtin_inf();
+    if (j >= 0 && j < My) s = nn_wave_dist(x0 + (size_t)row * K, y0 + (size_t)j * K, K, lane);
+    if (lane == 0) dist[(size_t)row * k + p] = s;
+    most = s > most ? s : most;
+  }
+  if (lane == 0) top[wave] = most;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) most = top[w] > most ? top[w] : most;
+    rad[row] = (float)most;
+  }
+}
+
+// ---------------------------------------------------------------- the balls a row falls into
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void nn_count_kernel(const float* __restrict__ X, const float* __restrict__ nx, const float* __restrict__ Y,
+                     const float* __restrict__ ny, const float* __restrict__ rad, int* __restrict__ part, int Mx, int My,
+                     int Kp, int nct) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [2 buffers][X tile, Y tile][128][36]; at the end the counts
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int m0 = blockIdx.x * NN_TILE, chunk = blockIdx.y, splits = gridDim.y;
+  const int t0 = (int)((long long)chunk * nct / splits), t1 = (int)((long long)(chunk + 1) * nct / splits);
+  const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  float nxr[4][4];
+  int cnt[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = m0 + wr * 64 + i * 16 + 4 * fq + r;
+      nxr[i][r] = row < Mx ? nx[row] : 0.f;
+      cnt[i][r] = 0;
+    }
+
+  nn_gemm_tiles(X, Y, lds, Mx, My, Kp, m0, t0, t1, [&](int cbase, f32x4 (&acc)[4][4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int col = cbase + j * 16 + fr;
+      const bool cok = col < My;
+      const float nyv = cok ? ny[col] : 0.f, rv = cok ? rad[col] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float d = __builtin_fmaf(-2.f, acc[i][j][r], nxr[i][r] + nyv);
+          cnt[i][r] += (cok && d <= rv) ? 1 : 0;
+        }
+      acc[0][j] = zero; acc[1][j] = zero; acc[2][j] = zero; acc[3][j] = zero;
+    }
+  });
+
+  int* red = reinterpret_cast<int*>(lds);  // [2 column waves][128]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int v = cnt[i][r];
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
+      if (fr == 0) red[wc * NN_TILE + wr * 64 + i * 16 + 4 * fq + r] = v;
+    }
+  __syncthreads();
+  if (tid < NN_TILE && m0 + tid < Mx) part[(size_t)chunk * Mx + m0 + tid] = red[tid] + red[NN_TILE + tid];
+}
+
+__global__ __launch_bounds__(256) void nn_count_sum_kernel(const int* __restrict__ part, int* __restrict__ cnt, int Mx,
+                                                           int splits) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Mx) return;
+  int s = part[i];
+  for (int c = 1; c < splits; ++c) s += part[(size_t)c * Mx + i];
+  cnt[i] = s;
 }
 
 static inline bool nn_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline bool nn_shape_ok(int M, int K) { return M >= 1 && M <= NN_MAX_ROWS && K >= 1 && K <= NN_MAX_K; }
+// the operands and the chunking of one distance GEMM
+static inline bool nn_gemm_ok(const float* X, const float* nx, const float* Y, const float* ny, int Mx, int My, int Kp,
+                              int splits) {
+  return X && nx && Y && ny && nn_shape_ok(Mx, Kp) && nn_shape_ok(My, Kp) && Kp % 16 == 0 && nn_al16(X) && nn_al16(Y) &&
+         splits >= 1 && splits <= nn_col_tiles(My) && splits <= 65535;
+}
+// more than 64 KB of dynamic LDS has to be asked for, once per kernel
+template <class Kernel>
+static inline hipError_t nn_big_lds(Kernel kernel, size_t bytes, bool* done) {
+  if (*done) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  *done = e == hipSuccess;
+  return e;
+}
 
 }  // namespace dcg
 
@@ -287,5 +587,45 @@ extern "C" int dcg_nn_refine(const float* x0, const float* y0, const int* idx, d
                              hipStream_t st) {
   if (!x0 || !y0 || !idx || !dist || !nn_shape_ok(Mx, K) || !nn_shape_ok(My, K)) return -2;
   hipLaunchKernelGGL(nn_refine_kernel, dim3((Mx + 3) / 4), dim3(256), 0, st, x0, y0, idx, dist, Mx, My, K);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_topk(const float* X, const float* nx, const float* Y, const float* ny, uint64_t* part, int Mx,
+                           int My, int Kp, int loo, int splits, int k, hipStream_t st) {
+  if (!part || !nn_gemm_ok(X, nx, Y, ny, Mx, My, Kp, splits) || (loo && Mx != My) || k < 1 || k > NN_MAX_KNN ||
+      k > My - (loo ? 1 : 0))
+    return -2;
+  static bool attr = false;
+  const hipError_t e = nn_big_lds(nn_topk_kernel, NN_GEMM_LDS, &attr);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(nn_topk_kernel, dim3((Mx + NN_TILE - 1) / NN_TILE, splits), dim3(256), NN_GEMM_LDS, st, X, nx, Y, ny,
+                     reinterpret_cast<unsigned long long*>(part), Mx, My, Kp, loo ? 1 : 0, nn_col_tiles(My), k);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_merge_k(const uint64_t* part, int* idx, int Mx, int splits, int k, hipStream_t st) {
+  if (!part || !idx || Mx < 1 || Mx > NN_MAX_ROWS || splits < 1 || k < 1 || k > NN_MAX_KNN) return -2;
+  hipLaunchKernelGGL(nn_merge_k_kernel, dim3((Mx + 3) / 4), dim3(256), 0, st,
+                     reinterpret_cast<const unsigned long long*>(part), idx, Mx, splits, k);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_radius(const float* x0, const float* y0, const int* idx, double* dist, float* rad, int Mx, int My,
+                             int K, int k, hipStream_t st) {
+  if (!x0 || !y0 || !idx || !dist || !rad || !nn_shape_ok(Mx, K) || !nn_shape_ok(My, K) || k < 1 || k > NN_MAX_KNN)
+    return -2;
+  hipLaunchKernelGGL(nn_radius_kernel, dim3(Mx), dim3(256), 0, st, x0, y0, idx, dist, rad, Mx, My, K, k);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_count(const float* X, const float* nx, const float* Y, const float* ny, const float* rad, int* part,
+                            int* cnt, int Mx, int My, int Kp, int splits, hipStream_t st) {
+  if (!rad || !part || !cnt || !nn_gemm_ok(X, nx, Y, ny, Mx, My, Kp, splits)) return -2;
+  static bool attr = false;
+  const hipError_t e = nn_big_lds(nn_count_kernel, NN_GEMM_LDS, &attr);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(nn_count_kernel, dim3((Mx + NN_TILE - 1) / NN_TILE, splits), dim3(256), NN_GEMM_LDS, st, X, nx, Y, ny,
+                     rad, part, Mx, My, Kp, nn_col_tiles(My));
+  hipLaunchKernelGGL(nn_count_sum_kernel, dim3((Mx + 255) / 256), dim3(256), 0, st, (const int*)part, cnt, Mx, splits);
   return (int)hipGetLastError();
 }

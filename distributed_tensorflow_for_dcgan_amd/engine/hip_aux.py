@@ -188,21 +188,22 @@ class HipEngineAux:
 
     # ------------------------------------------------------------------ 1-NN two-sample test
     def nn_metric(self, real: Optional[torch.Tensor], z: torch.Tensor, size: Optional[int] = None,
-                  ema: Optional[bool] = None, refresh: bool = False) -> dict:
+                  ema: Optional[bool] = None, refresh: bool = False, k: int = 0) -> dict:
         """The leave-one-out 1-NN two-sample test between `real` [n, S, S, C] and the n samples of z in the pixels
         of pyramid level `size` (None or 0: the images), and the nearest-real distances (nn.hip; ops.hip.NnMetric):
         {"acc", "acc_real", "acc_fake", "dist_fr", "dist_rr", "nearest"}, `nearest` the index of every fake's
         nearest real image. Programs of their own, recorded on first use: nothing of the training step is
         touched. The fakes come from ``sampler(z, ema=ema)`` in chunks of the batch size. The real side (features,
         mean and its own leave-one-out search) is computed on the first call and kept: later calls do not read
-        `real` (None is fine) unless refresh is set or the set's size or `size` changed."""
+        `real` (None is fine) unless refresh is set or the set's size, `size` or k changed. k > 0 adds the k-NN
+        manifold estimates "precision", "recall", "density", "coverage" and "k" (ops.hip.NnMetric.prdc)."""
         n, B = int(z.shape[0]), self.B
-        key = (n, R.check_nn(n, size, self.cfg.output_size))
+        key = (n, R.check_nn(n, size, self.cfg.output_size), R.check_nn_k(k, n, least=0))
         nn = getattr(self, "_nn", None)
         if nn is None or self._nn_key != key or refresh:
             if real is None or int(real.shape[0]) != n:
                 raise ValueError("nn_metric: the first evaluation needs the n = %d real images" % n)
-            nn = H.NnMetric(n, self.cfg.output_size, self.cfg.c_dim, key[1], device=self.device)
+            nn = H.NnMetric(n, self.cfg.output_size, self.cfg.c_dim, key[1], device=self.device, k=key[2])
             nn.set_real(real.to(self.device, torch.float32))
             self._nn, self._nn_key = nn, key
         z = z.to(self.device, torch.float32)
@@ -210,7 +211,10 @@ class HipEngineAux:
             m = min(B, n - i)
             zc = z[i:i + m] if m == B else torch.cat([z[i:], z.new_zeros(B - m, z.shape[1])])
             nn.x[i:i + m].copy_(self.sampler(zc, ema=ema)[:m])
-        return R.nn_report(nn())
+        out = R.nn_report(nn())
+        if key[2]:
+            out.update(R.nn_prdc_report(nn.prdc()))
+        return out
 
     def placement(self) -> List[str]:
         """--log_device_placement lines: every recorded op of the step runs on this rank's HIP

@@ -1454,6 +1454,38 @@ class _NnSearch:
         prog.nn_refine("nn.refine." + tag, _p(X0), _p(Y0), _p(idx), _p(dist), Mx, My, K, 0)
 
 
+def _nn_chunks(op: str, Mx: int, My: int, splits) -> int:
+    sp, tiles = nn_splits(Mx, My) if splits is None else int(splits), (My + ext().NN_TILE - 1) // ext().NN_TILE
+    if not 1 <= sp <= tiles:
+        raise ValueError("%s: splits must be in [1, %d], got %d" % (op, tiles, sp))
+    return sp
+
+
+class _NnSearchK:
+    """The recorded ops of one block's k nearest: nn_topk of the rows (F, norm) of `x` against those of `y`, merge_k,
+    radius. idx int32 [Mx, k], dist float64 [Mx, k] (ascending by the Gram form's key), rad float32 [Mx]."""
+
+    def __init__(self, prog, tag, x, y, idx, dist, rad, loo, k, splits=None):
+        (X0, FX, nX), (Y0, FY, nY) = x, y
+        Mx, My, K, Kp = X0.shape[0], Y0.shape[0], X0.shape[1], FX.shape[1]
+        sp = _nn_chunks("nn_topk", Mx, My, splits)
+        self.part = torch.empty(sp, Mx, k, dtype=torch.int64, device=X0.device)
+        prog.nn_topk("nn.topk." + tag, _p(FX), _p(nX), _p(FY), _p(nY), _p(self.part), Mx, My, Kp, int(bool(loo)), sp, k, 0)
+        prog.nn_merge_k("nn.merge_k." + tag, _p(self.part), _p(idx), Mx, sp, k, 0)
+        prog.nn_radius("nn.radius." + tag, _p(X0), _p(Y0), _p(idx), _p(dist), _p(rad), Mx, My, K, k, 0)
+
+
+class _NnCount:
+    """The recorded op of one count block: cnt int32 [Mx] = per row of `x` the rows of `y` whose ball rad [My] holds it."""
+
+    def __init__(self, prog, tag, x, y, rad, cnt, splits=None):
+        (X0, FX, nX), (Y0, FY, nY) = x, y
+        Mx, My, Kp = X0.shape[0], Y0.shape[0], FX.shape[1]
+        sp = _nn_chunks("nn_count", Mx, My, splits)
+        self.part = torch.empty(sp, Mx, dtype=torch.int32, device=X0.device)
+        prog.nn_count("nn.count." + tag, _p(FX), _p(nX), _p(FY), _p(nY), _p(rad), _p(self.part), _p(cnt), Mx, My, Kp, sp, 0)
+
+
 def _nn_side(prog, tag, x0: torch.Tensor, mu, compute_mu: bool):
     """Record nn_features of the rows x0 [M, K]: (x0, F [M, Kp], norm [M])."""
     M, K = x0.shape
@@ -1514,17 +1546,69 @@ def nn_top1(X: torch.Tensor, Y: torch.Tensor, loo: bool = False, splits: Optiona
     return idx, dist
 
 
+def nn_topk(X: torch.Tensor, Y: torch.Tensor, k: int, loo: bool = False, splits: Optional[int] = None, out=None):
+    """(index int32 [Mx, k], distance float64 [Mx, k]): per row of X [Mx, K] its k nearest rows of Y [My, K] in squared
+    L2 distance, 1 <= k <= 16, chosen and ordered by the MFMA Gram form with no centring (equal distances -> the
+    smaller index first), and their distances recomputed from the differences (oracle: ops.reference.nn_topk). loo: X
+    is Y and a row is not its own neighbour. splits: column chunks of the launch (None: nn_splits); the result does not
+    depend on it. out: the (index, distance) tensors to write, or (index, distance, radius float32 [Mx]): the fp32
+    value of every row's largest distance."""
+    from . import reference as R
+    _nn_rows("nn_topk", X), _nn_rows("nn_topk", Y)
+    if X.shape[1] != Y.shape[1] or (loo and X.shape != Y.shape):
+        raise ValueError("nn_topk: X [Mx, K] and Y [My, K] (one shape with loo), got %s and %s" % (tuple(X.shape), tuple(Y.shape)))
+    k = R.check_nn_k(k, Y.shape[0] + (0 if loo else 1), ("k", "the candidates + 1"))
+    Mx = X.shape[0]
+    new = lambda dt, *s: torch.empty(*s, dtype=dt, device=X.device)  # noqa: E731
+    idx, dist = out[:2] if out is not None else (new(torch.int32, Mx, k), new(torch.float64, Mx, k))
+    rad = out[2] if out is not None and len(out) > 2 else new(torch.float32, Mx)
+    if (idx.dtype, dist.dtype, rad.dtype) != (torch.int32, torch.float64, torch.float32) or \
+            idx.shape != (Mx, k) or dist.shape != (Mx, k) or rad.shape != (Mx,) or not (idx.is_contiguous() and dist.is_contiguous()):
+        raise TypeError("nn_topk: out must be contiguous (int32 [Mx, k], float64 [Mx, k][, float32 [Mx]])")
+    prog = ext().Program()
+    x = _nn_side(prog, "x", X, None, False)
+    y = x if loo else _nn_side(prog, "y", Y, None, False)
+    keep = _NnSearchK(prog, "xy", x, y, idx, dist, rad, loo, k, splits)
+    run(prog)
+    del keep
+    return idx, dist
+
+
+def nn_count(X: torch.Tensor, Y: torch.Tensor, rad: torch.Tensor, splits: Optional[int] = None, out=None):
+    """int32 [Mx]: per row of X [Mx, K] the rows j of Y [My, K] with |x - y_j|^2 <= rad_j (float32 [My], squared
+    radii; a tie is inside), the distance in the MFMA Gram form with no centring (oracle: ops.reference.nn_count).
+    splits: column chunks of the launch (None: nn_splits). out: the tensor to write."""
+    _nn_rows("nn_count", X), _nn_rows("nn_count", Y)
+    if X.shape[1] != Y.shape[1] or rad.dtype != torch.float32 or rad.shape != (Y.shape[0],) or not rad.is_contiguous():
+        raise ValueError("nn_count: X [Mx, K], Y [My, K] and rad float32 [My], got %s, %s and %s %s"
+                         % (tuple(X.shape), tuple(Y.shape), rad.dtype, tuple(rad.shape)))
+    Mx = X.shape[0]
+    cnt = out if out is not None else torch.empty(Mx, dtype=torch.int32, device=X.device)
+    if cnt.dtype != torch.int32 or cnt.shape != (Mx,):
+        raise TypeError("nn_count: out must be int32 [Mx]")
+    prog = ext().Program()
+    keep = _NnCount(prog, "xy", _nn_side(prog, "x", X, None, False), _nn_side(prog, "y", Y, None, False), rad, cnt, splits)
+    run(prog)
+    del keep
+    return cnt
+
+
 class NnMetric:
     """The leave-one-out 1-NN two-sample test of image sets [n, S, S, C] against one real set, on the device
     (nn.hip; oracle: ops.reference.nn_two_sample on nn_features). ``set_real`` computes the real set's level, its
     mean, centred features and the (A, A) block once; every call costs the fake side and the three blocks that
-    involve it. Everything is recorded once: one Program per side."""
+    involve it. Everything is recorded once: one Program per side.
 
-    def __init__(self, n: int, S: int, C: int, size: Optional[int] = None, device="cuda"):
+    k > 0 adds the k-NN manifold estimates (``prdc``; oracle: ops.reference.nn_prdc). The (A, A) and (B, B) blocks
+    are then searched once, for k neighbours (nn_topk; the 1-NN test reads column 0), which gives every row's ball,
+    and two count blocks follow: the fakes against the reals' balls and the reals against the fakes'."""
+
+    def __init__(self, n: int, S: int, C: int, size: Optional[int] = None, device="cuda", k: int = 0):
         from . import reference as R
         if not 1 <= int(C) <= 4:
             raise ValueError("nn_two_sample: at most 4 channels, got %d" % C)
         self.size = size = R.check_nn(n, size, S)
+        self.k = k = R.check_nn_k(k, n, least=0)
         self.n, self.K = n, size * size * C
         new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=device)  # noqa: E731
         self.xa, self.x = new(n, S, S, C), new(n, S, S, C)  # the real set; the set under evaluation
@@ -1536,17 +1620,43 @@ class NnMetric:
         la, lb = _nn_levels(self.prog_real, self.xa, size, "a"), _nn_levels(self.prog_fake, self.x, size, "b")
         a = _nn_side(self.prog_real, "a", la[-1].view(n, -1), self.mu, True)
         b = _nn_side(self.prog_fake, "b", lb[-1].view(n, -1), self.mu, False)
+        if k:  # the k nearest inside either set, its balls' squared radii, and per row the other set's balls it lies in
+            self.kj, self.kd = new(2 * n, k, dt=torch.int32), new(2 * n, k, dt=torch.float64)
+            self.rad, self.hits = new(2 * n), new(2 * n, dt=torch.int32)
+            own = lambda p, tag, s, r: _NnSearchK(p, tag, s, s, self.kj[r], self.kd[r], self.rad[r], True, k)  # noqa: E731
+        else:
+            own = lambda p, tag, s, r: _NnSearch(p, tag, s, s, (self.jA if s is a else self.jB)[r],  # noqa: E731
+                                                 (self.dA if s is a else self.dB)[r], True)
         self._keep = [la, lb, a, b,
-                      _NnSearch(self.prog_real, "aa", a, a, self.jA[:n], self.dA[:n], True),
+                      own(self.prog_real, "aa", a, slice(0, n)),
                       _NnSearch(self.prog_fake, "ab", a, b, self.jB[:n], self.dB[:n], False),
                       _NnSearch(self.prog_fake, "ba", b, a, self.jA[n:], self.dA[n:], False),
-                      _NnSearch(self.prog_fake, "bb", b, b, self.jB[n:], self.dB[n:], True)]
+                      own(self.prog_fake, "bb", b, slice(n, 2 * n))]
+        if k:
+            self._keep += [_NnCount(self.prog_fake, "ab", a, b, self.rad[n:], self.hits[:n]),
+                           _NnCount(self.prog_fake, "ba", b, a, self.rad[:n], self.hits[n:])]
         self.has_real = False
+
+    def _first_of_k(self, rows: slice, j: torch.Tensor, d: torch.Tensor) -> None:
+        j[rows].copy_(self.kj[rows, 0])
+        d[rows].copy_(self.kd[rows, 0])
 
     def set_real(self, real: torch.Tensor) -> None:
         self.xa.copy_(real)
         run(self.prog_real)
+        if self.k:
+            self._first_of_k(slice(0, self.n), self.jA, self.dA)
         self.has_real = True
+
+    def prdc(self):
+        """ops.reference.NnPrdc of the last evaluated set (k > 0): the counts are the device's, the four ratios torch
+        on the device. Coverage reads the (A, B) 1-NN block: a real is covered when its nearest fake is in its ball."""
+        from . import reference as R
+        if not self.k:
+            raise RuntimeError("nn_prdc: the metric was built with k = 0")
+        n = self.n
+        return R.nn_prdc_summary(self.hits[:n].clone(), self.hits[n:].clone(), self.dB[:n] <= self.rad[:n].double(), self.k,
+                                 self.rad[:n].clone(), self.rad[n:].clone())
 
     def __call__(self, x: Optional[torch.Tensor] = None):
         """ops.reference.NnResult of x -- None: of what the caller wrote into ``self.x`` -- against the real set. The
@@ -1557,7 +1667,22 @@ class NnMetric:
         if x is not None:
             self.x.copy_(x)
         run(self.prog_fake)
+        if self.k:
+            self._first_of_k(slice(self.n, 2 * self.n), self.jB, self.dB)
         return R.nn_summary(self.dA.clone(), self.jA.long(), self.dB.clone(), self.jB.long(), self.K)
+
+
+def nn_prdc(A: torch.Tensor, B: torch.Tensor, size: Optional[int] = None, k: int = 5):
+    """Precision, recall, density and coverage of the image set B (fake) against A (real), float32 [n, S, S, C] on
+    the device, from k-NN balls in the pixels of pyramid level `size` (None: S): an ops.reference.NnPrdc."""
+    from . import reference as R
+    n, S, _, C = _f32_images("nn_prdc", A).shape
+    if _f32_images("nn_prdc", B).shape != A.shape:
+        raise ValueError("nn_prdc: A and B must share a shape")
+    m = NnMetric(n, S, C, size, device=A.device, k=R.check_nn_k(k, n))
+    m.set_real(A)
+    m(B)
+    return m.prdc()
 
 
 def nn_two_sample(A: torch.Tensor, B: torch.Tensor, size: Optional[int] = None):

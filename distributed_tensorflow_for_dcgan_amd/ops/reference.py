@@ -1517,3 +1517,68 @@ def nn_report(r: NnResult) -> dict:
     n = r.dA.shape[0] // 2
     return {"acc": r.acc, "acc_real": r.acc_real, "acc_fake": r.acc_fake, "dist_fr": r.dist_fr, "dist_rr": r.dist_rr,
             "nearest": [int(j) for j in r.jA[n:].tolist()]}
+
+
+# The k-NN manifold estimates on the same feature rows: improved precision and recall (Kynkaanniemi et al. 2019) and
+# density and coverage (Naeem et al. 2020). A row's ball reaches to its k-th nearest neighbour inside its own set.
+NN_MAX_KNN = 16
+
+
+class NnPrdc(NamedTuple):
+    precision: float      # fakes inside some real ball
+    recall: float         # reals inside some fake ball
+    density: float        # real balls per fake, over k: may exceed 1
+    coverage: float       # reals whose own ball holds a fake
+    k: int
+    hitsA: torch.Tensor   # [n] per real the fake balls it lies in
+    hitsB: torch.Tensor   # [n] per fake the real balls it lies in
+    rA: torch.Tensor      # [n] squared radius of every real's ball
+    rB: torch.Tensor      # [n] ... of every fake's
+
+
+def check_nn_k(k: int, n: int, names=("k", "n"), least: int = 1) -> int:
+    """Validated neighbour count: `least` <= k <= min(16, n - 1) (the flag and the engines pass least = 0: off)."""
+    k, n = int(k), int(n)
+    if not least <= k <= min(NN_MAX_KNN, n - 1):
+        raise ValueError("%s must be in [%d, min(%d, %s - 1)], got %d with %s = %d"
+                         % (names[0], least, NN_MAX_KNN, names[1], k, names[1], n))
+    return k
+
+
+def nn_topk(X: torch.Tensor, Y: torch.Tensor, k: int, loo: bool = False):
+    """(d [Mx, k], j [Mx, k]): per row of X its k smallest squared distances to rows of Y and those rows' indices,
+    ordered by (d, j): equal distances -> the smaller j first. loo: X is Y, and a row is not its own neighbour."""
+    if X.dim() != 2 or Y.dim() != 2 or X.shape[1] != Y.shape[1] or (loo and X.shape != Y.shape):
+        raise ValueError("nn_topk: X [Mx, K] and Y [My, K] (one shape with loo), got %s and %s" % (tuple(X.shape), tuple(Y.shape)))
+    k = check_nn_k(k, Y.shape[0] + (0 if loo else 1), ("k", "the candidates + 1"))
+    D = nn_distances(X, Y)
+    if loo:
+        D.fill_diagonal_(float("inf"))
+    d, j = D.sort(dim=1, stable=True)
+    return d[:, :k].contiguous(), j[:, :k].contiguous()
+
+
+def nn_count(X: torch.Tensor, Y: torch.Tensor, rad: torch.Tensor) -> torch.Tensor:
+    """[Mx]: per row of X the rows j of Y with D(x, y_j) <= rad_j (a tie is inside)."""
+    return (nn_distances(X, Y) <= rad.to(X.dtype)[None, :]).sum(1)
+
+
+def nn_prdc_summary(hitsA, hitsB, covered, k: int, rA=None, rB=None) -> NnPrdc:
+    """The four ratios from the per-row counts and the coverage mask (torch, on their device)."""
+    n = hitsA.shape[0]
+    return NnPrdc(int((hitsB > 0).sum()) / float(n), int((hitsA > 0).sum()) / float(n),
+                  int(hitsB.sum()) / float(int(k) * n), int(covered.sum()) / float(n), int(k), hitsA, hitsB, rA, rB)
+
+
+def nn_prdc(A: torch.Tensor, B: torch.Tensor, k: int) -> NnPrdc:
+    """Precision, recall, density and coverage between the feature rows A (real) and B (fake), both [n, K]."""
+    if A.shape != B.shape or A.dim() != 2:
+        raise ValueError("nn_prdc: A and B must share a shape [n, K], got %s and %s" % (tuple(A.shape), tuple(B.shape)))
+    k = check_nn_k(k, A.shape[0])
+    rA, rB = nn_topk(A, A, k, True)[0][:, -1], nn_topk(B, B, k, True)[0][:, -1]
+    return nn_prdc_summary(nn_count(A, B, rB), nn_count(B, A, rA), nn_top1(A, B)[0] <= rA, k, rA, rB)
+
+
+def nn_prdc_report(p: NnPrdc) -> dict:
+    """What the engines' nn_metric adds to nn_report with k > 0."""
+    return {"precision": p.precision, "recall": p.recall, "density": p.density, "coverage": p.coverage, "k": p.k}

@@ -157,6 +157,9 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                           "even and at least 16. 0 = --output_size, the images themselves"),
     ("nn_grid", "int", 0, "with --nn_every: also write nn_<step>.png into --sample_dir, the first g generated images, "
                           "each beside its nearest real one. 0 = none"),
+    ("nn_k", "int", 0, "with --nn_every: also print precision, recall, density and coverage of the generated set from "
+                       "k-NN balls in the same features (Kynkaanniemi et al. 2019 use k = 3, Naeem et al. 2020 k = 5): "
+                       "high precision with low recall = good images of few kinds. 1..min(16, --nn_images - 1); 0 = off"),
     ("swd_max_rows", "int", 32768, "largest --swd_images * --swd_patches accepted: a power of two in [32768, 2^21]. "
                                    "Above 32768 the HIP engine sorts with its global merge sort and holds two "
                                    "float32 [512, N] buffers per pyramid level plus two key buffers (34.6 GiB at "
@@ -255,10 +258,11 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         parser.error(str(e))
     if int(ns.nn_every) < 0 or int(ns.nn_grid) < 0:
         parser.error("--nn_every and --nn_grid must be >= 0, got %r and %r" % (ns.nn_every, ns.nn_grid))
-    if int(ns.nn_every) > 0 or any(a.split("=")[0] in ("--nn_images", "--nn_size", "--nn_grid") for a in argv):
-        from ..ops.reference import check_nn
+    if int(ns.nn_every) > 0 or any(a.split("=")[0] in ("--nn_images", "--nn_size", "--nn_grid", "--nn_k") for a in argv):
+        from ..ops.reference import check_nn, check_nn_k
         try:
             check_nn(ns.nn_images, ns.nn_size, ns.output_size, ("--nn_images", "--nn_size", "--output_size"))
+            check_nn_k(ns.nn_k, ns.nn_images, ("--nn_k", "--nn_images"), least=0)
         except ValueError as e:
             parser.error(str(e))
         if int(ns.nn_grid) > int(ns.nn_images):
