@@ -3,9 +3,11 @@ side and the three blocks that involve it) and a cached one (fake side only), in
 the same process ``torch.cdist`` + ``min`` over the same four blocks of the same feature matrices as the yardstick.
 With ``--k`` the same for the metric with the k-NN manifold estimates next to the k = 0 numbers of the same run, the
 nn_topk kernel against nn_top1 and nn_count on the (A, A) block alone, and ``torch.cdist`` + ``topk`` + the comparison
-against the radii as the yardstick.
+against the radii as the yardstick. With ``--mmd`` the metric with the kernel MMD, its triangular Gram kernel alone (full
+and without the (A, A) pairs) against three nn_count launches over (A, A), (A, B), (B, B), and ``torch.cdist`` + ``exp``
++ ``sum`` over the same three blocks as the yardstick.
 
-    python benchmarks/bench_nn.py [--images 1024] [--output_size 64] [--nn_size 0] [--k 0] [--iters 10] [--out FILE]
+    python benchmarks/bench_nn.py [--images 1024] [--output_size 64] [--nn_size 0] [--k 0] [--mmd] [--iters 10] [--out FILE]
 """
 import argparse
 import json
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--k", type=int, default=0, help="also time the metric with precision / recall / density / coverage")
+    ap.add_argument("--mmd", action="store_true", help="also time the metric with the kernel MMD and its Gram kernel alone")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None, help="also append the result line to this file")
     a = ap.parse_args()
@@ -116,6 +119,42 @@ def main():
                     "aa_kernel_ms_min_max": {m: [round(v[0], 3), round(v[-1], 3)] for m, v in kern.items()},
                     "cdist_topk_count_ms_median": med(cdk), "cdist_topk_count_min_max": [round(cdk[0], 3), round(cdk[-1], 3)],
                     "result_k": {m: round(v, 4) for m, v in res_k.items() if m in ("precision", "recall", "density", "coverage")}})
+    if a.mmd:
+        from distributed_tensorflow_for_dcgan_amd.ops import hip as H
+        timed(lambda: eng.nn_metric(real, z, a.nn_size, refresh=True, mmd=True))
+        first_m = sorted(timed(lambda: eng.nn_metric(real, z, a.nn_size, refresh=True, mmd=True))[0] for _ in range(a.iters))
+        cached_m = sorted(timed(lambda: eng.nn_metric(None, z, a.nn_size, mmd=True))[0] for _ in range(a.iters))
+        res_m = eng.nn_metric(None, z, a.nn_size, mmd=True)
+        nm = eng._nn
+        (_, FA, nA), (_, FB, nB) = nm._keep[2], nm._keep[3]
+        Kp, sp, e, p = FA.shape[1], H.nn_splits(n, n), H.ext(), H._p
+        part = torch.empty(e.nn_mmd_pairs(n, n, 0), 3, dtype=torch.float64, device=dev)
+        rad, cpart, cnt = torch.zeros(n, device=dev), torch.empty(sp, n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        # the Gram kernel alone: the triangle of [A; B] (about 2 n^2 pairs) against nn_count over (A, A), (A, B), (B, B) (3 n^2)
+        progs = {"triangle": e.Program(), "triangle_skip_aa": e.Program(), "count_3_blocks": e.Program()}
+        progs["triangle"].nn_mmd("mmd", p(FA), p(nA), p(FB), p(nB), p(nm.bw), p(part), n, n, Kp, 0, 0)
+        progs["triangle_skip_aa"].nn_mmd("mmd", p(FA), p(nA), p(FB), p(nB), p(nm.bw), p(part), n, n, Kp, 1, 0)
+        for tag, (X, nX), (Y, nY) in (("aa", (FA, nA), (FA, nA)), ("ab", (FA, nA), (FB, nB)), ("bb", (FB, nB), (FB, nB))):
+            progs["count_3_blocks"].nn_count("count." + tag, p(X), p(nX), p(Y), p(nY), p(rad), p(cpart), p(cnt), n, n, Kp, sp, 0)
+        kern = {}
+        for name, prog in progs.items():
+            timed(lambda: H.run(prog))
+            kern[name] = sorted(timed(lambda: H.run(prog))[0] for _ in range(a.iters))
+        c4h = float(nm.bw[0]) * 4.0
+
+        def yard_m():
+            return [sum(torch.exp(-(2.0 ** m) * q) for m in range(5)).sum()
+                    for q in (torch.cdist(X, Y).square_() / c4h for X, Y in ((FA, FA), (FA, FB), (FB, FB)))]
+        timed(yard_m)
+        cdm = sorted(timed(yard_m)[0] for _ in range(a.iters))
+        mm = lambda v: [round(v[0], 3), round(v[-1], 3)]  # noqa: E731
+        out.update({"first_mmd_ms_median": med(first_m), "first_mmd_ms_min_max": mm(first_m),
+                    "cached_mmd_ms_median": med(cached_m), "cached_mmd_ms_min_max": mm(cached_m),
+                    "mmd_workgroups": [e.nn_mmd_pairs(n, n, 0), e.nn_mmd_pairs(n, n, 1)],
+                    "gram_kernel_ms_median": {m: med(v) for m, v in kern.items()},
+                    "gram_kernel_ms_min_max": {m: mm(v) for m, v in kern.items()},
+                    "cdist_exp_sum_3_blocks_ms_median": med(cdm), "cdist_exp_sum_min_max": mm(cdm),
+                    "result_mmd": {m: round(res_m[m], 5) for m in ("mmd2", "k_rr", "k_ff", "k_rf", "h")}})
     line = json.dumps(out)
     print(line)
     if a.out:

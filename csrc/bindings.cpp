@@ -1508,6 +1508,30 @@ class Program {
     }, AccList().r(X, (size_t)Mx * Kp * 4).r(nx, (size_t)Mx * 4).r(Y, (size_t)My * Kp * 4).r(ny, (size_t)My * 4)
            .r(rad, (size_t)My * 4).w(part, (size_t)splits * Mx * 4).w(cnt, (size_t)Mx * 4).v);
   }
+  // bw float [2] = {h, log2(e) / (4 h)}: the kernel MMD's bandwidth from the n centred rows' squared norms
+  int nn_mmd_bw(std::string name, uintptr_t norm, int n, uintptr_t bw, int stream) {
+    return add(name, stream, [=](hipStream_t st) { return dcg_nn_mmd_bw(P<const float>(norm), n, P<float>(bw), st); },
+               AccList().r(norm, (size_t)n * 4).w(bw, 8).v);
+  }
+  // part double [nn_mmd_pairs(Mx, My, skip_aa)][3]: the Gaussian-mixture sums per tile pair of the upper triangle of
+  // the Gram of [X; Y] and per class AA, AB, BB
+  int nn_mmd(std::string name, uintptr_t X, uintptr_t nx, uintptr_t Y, uintptr_t ny, uintptr_t bw, uintptr_t part, int Mx,
+             int My, int Kp, int skip_aa, int stream) {
+    const size_t pairs = Mx >= 1 && My >= 0 ? (size_t)nn_mmd_pairs(Mx, My, skip_aa) : 0;
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_mmd(P<const float>(X), P<const float>(nx), P<const float>(Y), P<const float>(ny), P<const float>(bw),
+                        P<double>(part), Mx, My, Kp, skip_aa, st);
+    }, AccList().r(X, (size_t)Mx * Kp * 4).r(nx, (size_t)Mx * 4).r(Y, (size_t)My * Kp * 4).r(ny, (size_t)My * 4).r(bw, 8)
+           .w(part, pairs * 3 * 8).v);
+  }
+  // out double [8] = {S_AA, S_BB, S_AB, k_rr, k_ff, k_rf, mmd2, h}; saa: the cached S_AA of a skip_aa launch (0: none)
+  int nn_mmd_final(std::string name, uintptr_t part, int pairs, uintptr_t saa, int skip_aa, int Mx, int My, uintptr_t bw,
+                   uintptr_t out, int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_mmd_final(P<const double>(part), pairs, P<const double>(saa), skip_aa, Mx, My, P<const float>(bw),
+                              P<double>(out), st);
+    }, AccList().r(part, (size_t)(pairs > 0 ? pairs : 0) * 3 * 8).r(saa, 8).r(bw, 8).w(out, 64).v);
+  }
 
  private:
   int add(const std::string& name, int stream, std::function<int(hipStream_t)> fn, std::vector<Acc> acc,
@@ -1589,6 +1613,7 @@ PYBIND11_MODULE(_dcgan_hip, m) {
   m.def("nn_kpad", &nn_kpad);  // row length of the feature matrix for K features
   m.attr("NN_TILE") = (int)NN_TILE;
   m.attr("NN_MAX_KNN") = (int)NN_MAX_KNN;
+  m.def("nn_mmd_pairs", &nn_mmd_pairs);  // workgroups of nn_mmd = rows of its part [pairs][3]
   m.attr("SWD_FUSED_ROWS") = (int)SWD_FUSED_ROWS;
   m.attr("SWD_GLOBAL_MAX_ROWS") = (int)SWD_GLOBAL_MAX_ROWS;  // N of swd_sort_large: (32768, 2^21]
   m.attr("SWD_CHUNK_ROWS") = (int)SWD_CHUNK_ROWS;
@@ -1764,5 +1789,8 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("nn_topk", &Program::nn_topk)
       .def("nn_merge_k", &Program::nn_merge_k)
       .def("nn_radius", &Program::nn_radius)
-      .def("nn_count", &Program::nn_count);
+      .def("nn_count", &Program::nn_count)
+      .def("nn_mmd_bw", &Program::nn_mmd_bw)
+      .def("nn_mmd", &Program::nn_mmd)
+      .def("nn_mmd_final", &Program::nn_mmd_final);
 }

@@ -16,6 +16,12 @@ constexpr int NN_MAX_KNN = 16;      // neighbours per row of nn_topk: one per la
 // K padded with zeros to the k depth of four 16x16x4 MFMAs
 static inline int nn_kpad(int K) { return (K + 15) & ~15; }
 static inline int nn_col_tiles(int My) { return (My + NN_TILE - 1) / NN_TILE; }
+// workgroups of nn_mmd: the 128 x 128 tiles (I, J), I <= J, of the upper triangle of the Gram of Mx + My stacked rows,
+// with skip_aa from the first tile column that holds a row past Mx (at least one: My >= 1 then)
+static inline int nn_mmd_pairs(int Mx, int My, int skip_aa) {
+  const int T = nn_col_tiles(Mx + My), J0 = skip_aa ? Mx / NN_TILE : 0;
+  return T * (T + 1) / 2 - J0 * (J0 + 1) / 2;
+}
 // fp64 partials of the mean: [ceil(n / NN_MEAN_ROWS)][K]
 static inline size_t nn_mean_part_bytes(int n, int K) {
   return (size_t)((n + NN_MEAN_ROWS - 1) / NN_MEAN_ROWS) * (size_t)K * sizeof(double);
@@ -47,4 +53,16 @@ int dcg_nn_radius(const float* x0, const float* y0, const int* idx, double* dist
 // cnt [Mx] = #{j < My : nx_i + ny_j - 2 x_i.y_j <= rad_j}, through the chunks' counts part int [splits][Mx] in chunk order
 int dcg_nn_count(const float* X, const float* nx, const float* Y, const float* ny, const float* rad, int* part, int* cnt,
                  int Mx, int My, int Kp, int splits, hipStream_t st);
+// The kernel MMD (a mixture of 5 Gaussians, 2 sigma^2 = 4h .. h/4). bw float [2] = {h, c}: h = 2 / (n - 1) * sum_i
+// norm_i, the mean squared distance between two of the n centred rows whose squared norms are norm; c = log2(e) / (4 h)
+int dcg_nn_mmd_bw(const float* norm, int n, float* bw, hipStream_t st);
+// part double [nn_mmd_pairs(Mx, My, skip_aa)][3]: per tile pair of the upper triangle of the Gram of Z = [X; Y] and
+// per class (row >= Mx) + (col >= Mx) the sum over row < col of sum_m exp2(-2^m d c), m = 0..4, c = bw [1]. My = 0:
+// X alone (Y, ny may be null). skip_aa: no pair of two rows of X, and no tile that holds only such pairs
+int dcg_nn_mmd(const float* X, const float* nx, const float* Y, const float* ny, const float* bw, double* part, int Mx,
+               int My, int Kp, int skip_aa, hipStream_t st);
+// out double [8] = {S_AA, S_BB, S_AB, k_rr, k_ff, k_rf, mmd2, h} from part in a fixed order, the sums with the
+// mixture's 1/5. With skip_aa, S_AA is *saa (null: 0); a mean over no pair is 0
+int dcg_nn_mmd_final(const double* part, int pairs, const double* saa, int skip_aa, int Mx, int My, const float* bw,
+                     double* out, hipStream_t st);
 }

@@ -47,6 +47,15 @@
 //   nn_count     the same GEMM with an integer epilogue: cnt [row] = #{col : nx + ny - 2 g <= rad [col]}, 16
 //                counters per lane where nn_top1 holds its minima, summed across the 16 lanes by shuffles, across
 //                the two column waves through LDS and across the chunks in chunk order. Integers only
+//   nn_mmd_bw    the kernel MMD's bandwidth h = 2 / (n - 1) * sum_i norm_i of the centred reals, fp64 in a fixed order,
+//                and c = log2(e) / (4 h), left on the device for nn_mmd
+//   nn_mmd       the Gaussian-mixture kernel summed over the upper triangle of the Gram of Z = [X; Y]: one workgroup
+//                per 128 x 128 tile (I, J), I <= J, in one launch, so the symmetric blocks cost half a rectangle's
+//                MFMAs. The same main loop on one tile, every loader row from the matrix that holds it. Epilogue:
+//                d = max(nx + ny - 2 g, 0), e1 = exp2(-d c), the other four Gaussians by squaring, three fp32
+//                partials per lane by class (A, A), (A, B), (B, B) over row < col, then fp64: shuffles, the four
+//                waves through LDS in order, part [pair][3]. No atomics; bitwise reproducible
+//   nn_mmd_final the pairs' sums added in a fixed order, the three means and mmd2 = k_rr + k_ff - 2 k_rf
 // Every index into a feature matrix is 64-bit: n Kp passes 2^31 at 128x128x3.
 #include "common.h"
 #include "nn.h"
@@ -521,6 +530,192 @@ __global__ __launch_bounds__(256) void nn_count_sum_kernel(const int* __restrict
   cnt[i] = s;
 }
 
+// ---------------------------------------------------------------- kernel MMD over the upper triangle of one Gram
+__device__ __forceinline__ double nn_wave_sum(double s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+
+// h = 2 / (n - 1) * sum_i norm_i, c = log2(e) / (4 h): every thread its rows in index order in fp64, a shuffle tree,
+// the four waves in order
+__global__ __launch_bounds__(256) void nn_mmd_bw_kernel(const float* __restrict__ norm, int n, float* __restrict__ bw) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double s = 0.0;
+  for (int i = tid; i < n; i += 256) s += (double)norm[i];
+  s = nn_wave_sum(s);
+  if (lane == 0) red[wave] = s;
+  __syncthreads();
+  if (tid == 0) {
+    const double h = 2.0 / (double)(n - 1) * (((red[0] + red[1]) + red[2]) + red[3]);
+    bw[0] = (float)h;
+    bw[1] = (float)(1.4426950408889634 / (4.0 * h));  // (h = 0: inf, and the sums come out non-finite)
+  }
+}
+
+// One workgroup per 128 x 128 tile (I, J), I <= J, of the Gram of Z = [X; Y]: pair p = J (J + 1) / 2 + I, so that
+// neighbours share the tile column J. nn_gemm_tiles does not serve: it addresses its operands as X + row * Kp and
+// Y + row * Kp, while a tile of Z may straddle row Mx and takes every row from the matrix that holds it; and with
+// exactly one tile per workgroup the epilogue leaves the loop, so the loader's registers are dead when it runs. The
+// loop itself (staging, pitch, one barrier per step, MFMA order) is nn_gemm_tiles'. Rows past M are read from row
+// M - 1: their sums only reach masked elements, and every load stays inside the matrices
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void nn_mmd_kernel(const float* __restrict__ X, const float* __restrict__ nx, const float* __restrict__ Y,
+                   const float* __restrict__ ny, const float* __restrict__ bw, double* __restrict__ part, int Mx, int My,
+                   int Kp, int p0, int skip_aa) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [2 buffers][I tile, J tile][128][36]; at the end the sums
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int M = Mx + My, p = p0 + (int)blockIdx.x;  // (at most 8192 tile rows: p < 2^26)
+  int J = (int)((__builtin_sqrtf(8.f * (float)p + 1.f) - 1.f) * 0.5f);
+  while (J * (J + 1) / 2 > p) --J;  // the float root is one step off at the most
+  while ((J + 1) * (J + 2) / 2 <= p) ++J;
+  const int I = p - J * (J + 1) / 2;
+  const int nk = (Kp + NN_BK - 1) / NN_BK;
+  const int lr = tid >> 3, lq = tid & 7;  // the loader's rows lr + 32 p, its 16-byte word lq of the 32 k
+  const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const float* pi[4];
+  const float* pj[4];
+  f32x4 si[4], sj[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int zi = min(I * NN_TILE + lr + 32 * q, M - 1), zj = min(J * NN_TILE + lr + 32 * q, M - 1);
+    pi[q] = (zi < Mx ? X + (size_t)zi * Kp : Y + (size_t)(zi - Mx) * Kp) + 4 * lq;
+    pj[q] = (zj < Mx ? X + (size_t)zj * Kp : Y + (size_t)(zj - Mx) * Kp) + 4 * lq;
+  }
+
+  auto fetch = [&](int it) {  // k past Kp reads as zeros
+    const int k0 = it * NN_BK;
+    const bool kok = k0 + 4 * lq < Kp;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      si[q] = kok ? *reinterpret_cast<const f32x4*>(pi[q] + k0) : zero;
+      sj[q] = kok ? *reinterpret_cast<const f32x4*>(pj[q] + k0) : zero;
+    }
+  };
+  auto stash = [&](int buf) {
+    float* bx = lds + buf * 2 * NN_TILE_F + lr * NN_PITCH + 4 * lq;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      *reinterpret_cast<f32x4*>(bx + 32 * q * NN_PITCH) = si[q];
+      *reinterpret_cast<f32x4*>(bx + NN_TILE_F + 32 * q * NN_PITCH) = sj[q];
+    }
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = zero;
+
+  fetch(0);
+  stash(0);
+  __syncthreads();
+  for (int it = 0; it < nk; ++it) {
+    const int buf = it & 1;
+    const bool more = it + 1 < nk;
+    if (more) fetch(it + 1);
+    const float* bx = lds + buf * 2 * NN_TILE_F + (wr * 64 + fr) * NN_PITCH + 4 * fq;
+    const float* by = lds + buf * 2 * NN_TILE_F + NN_TILE_F + (wc * 64 + fr) * NN_PITCH + 4 * fq;
+#pragma unroll
+    for (int kk = 0; kk < NN_BK; kk += 16) {  // lane group fq supplies k = kk + 4 fq + e to MFMA e, for A and B alike
+      f32x4 a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const f32x4*>(bx + i * 16 * NN_PITCH + kk);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const f32x4*>(by + j * 16 * NN_PITCH + kk);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
+    }
+    if (more) stash(buf ^ 1);  // (last read in step it - 1, before that step's barrier)
+    __syncthreads();
+  }
+
+  // C fragment acc[i][j][r] = row I 128 + wr 64 + i 16 + 4 fq + r, column J 128 + wc 64 + j 16 + fr. One exp2 per
+  // pair; the bandwidths lie a factor 2 apart, so the other four Gaussians are its repeated squares
+  const float c = bw[1];
+  const int r0 = I * NN_TILE + wr * 64 + 4 * fq, c0 = J * NN_TILE + wc * 64 + fr;
+  float nr[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int z = min(r0 + i * 16 + r, M - 1);
+      nr[i][r] = z < Mx ? nx[z] : ny[z - Mx];
+    }
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;  // the lane's sums per class (row >= Mx) + (col >= Mx): AA, AB, BB
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = c0 + j * 16, z = min(col, M - 1);
+    const float nc = z < Mx ? nx[z] : ny[z - Mx];
+    const bool cok = col < M && !(skip_aa && col < Mx);  // (row < col: with col in X the pair is (A, A))
+    const int cc = col >= Mx ? 1 : 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = r0 + i * 16 + r;
+        const float d = fmaxf(__builtin_fmaf(-2.f, acc[i][j][r], nr[i][r] + nc), 0.f);
+        const float e1 = __builtin_amdgcn_exp2f(-d * c), e2 = e1 * e1, e4 = e2 * e2, e8 = e4 * e4, e16 = e8 * e8;
+        const float t = (((e1 + e2) + e4) + e8) + e16;
+        const bool ok = cok && row < col;  // strictly above the diagonal
+        const int cls = (row >= Mx ? 1 : 0) + cc;
+        s0 += (ok && cls == 0) ? t : 0.f;
+        s1 += (ok && cls == 1) ? t : 0.f;
+        s2 += (ok && cls == 2) ? t : 0.f;
+      }
+  }
+  double* red = reinterpret_cast<double*>(lds);  // [4 waves][3] (the tiles are free after the loop's last barrier)
+  const double v0 = nn_wave_sum((double)s0), v1 = nn_wave_sum((double)s1), v2 = nn_wave_sum((double)s2);
+  if (lane == 0) {
+    red[wave * 3 + 0] = v0;
+    red[wave * 3 + 1] = v1;
+    red[wave * 3 + 2] = v2;
+  }
+  __syncthreads();
+  if (tid < 3) part[(size_t)blockIdx.x * 3 + tid] = ((red[tid] + red[3 + tid]) + red[6 + tid]) + red[9 + tid];
+}
+
+// out = {S_AA, S_BB, S_AB, k_rr, k_ff, k_rf, mmd2, h}. A fixed order: thread t adds the pairs t, t + 256, ... in index
+// order per class, then a shuffle tree and the four waves in order. With skip_aa, S_AA is the cached *saa (null: 0)
+__global__ __launch_bounds__(256) void nn_mmd_final_kernel(const double* __restrict__ part, int pairs,
+                                                           const double* __restrict__ saa, int skip_aa, int Mx, int My,
+                                                           const float* __restrict__ bw, double* __restrict__ out) {
+  __shared__ double red[12];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int p = tid; p < pairs; p += 256) {
+    s0 += part[(size_t)p * 3 + 0];
+    s1 += part[(size_t)p * 3 + 1];
+    s2 += part[(size_t)p * 3 + 2];
+  }
+  s0 = nn_wave_sum(s0), s1 = nn_wave_sum(s1), s2 = nn_wave_sum(s2);
+  if (lane == 0) {
+    red[wave * 3 + 0] = s0;
+    red[wave * 3 + 1] = s1;
+    red[wave * 3 + 2] = s2;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double raw[3];
+    for (int q = 0; q < 3; ++q) raw[q] = (((red[q] + red[3 + q]) + red[6 + q]) + red[9 + q]) / 5.0;
+    const double na = (double)Mx, nb = (double)My;
+    const double saa_v = skip_aa ? (saa ? *saa : 0.0) : raw[0], sab = raw[1], sbb = raw[2];
+    const double krr = Mx > 1 ? 2.0 * saa_v / (na * (na - 1.0)) : 0.0, kff = My > 1 ? 2.0 * sbb / (nb * (nb - 1.0)) : 0.0;
+    const double krf = My > 0 ? sab / (na * nb) : 0.0;
+    out[0] = saa_v, out[1] = sbb, out[2] = sab;
+    out[3] = krr, out[4] = kff, out[5] = krf;
+    out[6] = krr + kff - 2.0 * krf;
+    out[7] = (double)bw[0];
+  }
+}
+
 static inline bool nn_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline bool nn_shape_ok(int M, int K) { return M >= 1 && M <= NN_MAX_ROWS && K >= 1 && K <= NN_MAX_K; }
 // the operands and the chunking of one distance GEMM
@@ -627,5 +822,34 @@ extern "C" int dcg_nn_count(const float* X, const float* nx, const float* Y, con
   hipLaunchKernelGGL(nn_count_kernel, dim3((Mx + NN_TILE - 1) / NN_TILE, splits), dim3(256), NN_GEMM_LDS, st, X, nx, Y, ny,
                      rad, part, Mx, My, Kp, nn_col_tiles(My));
   hipLaunchKernelGGL(nn_count_sum_kernel, dim3((Mx + 255) / 256), dim3(256), 0, st, (const int*)part, cnt, Mx, splits);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_mmd_bw(const float* norm, int n, float* bw, hipStream_t st) {
+  if (!norm || !bw || n < 2 || n > NN_MAX_ROWS) return -2;
+  hipLaunchKernelGGL(nn_mmd_bw_kernel, dim3(1), dim3(256), 0, st, norm, n, bw);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_mmd(const float* X, const float* nx, const float* Y, const float* ny, const float* bw, double* part,
+                          int Mx, int My, int Kp, int skip_aa, hipStream_t st) {
+  if (!X || !nx || !bw || !part || !nn_shape_ok(Mx, Kp) || My < 0 || My > NN_MAX_ROWS - Mx || Kp % 16 || !nn_al16(X) ||
+      (My > 0 && (!Y || !ny || !nn_al16(Y))) || (skip_aa && My < 1))
+    return -2;
+  const int pairs = nn_mmd_pairs(Mx, My, skip_aa);
+  static bool attr = false;
+  const hipError_t e = nn_big_lds(nn_mmd_kernel, NN_GEMM_LDS, &attr);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(nn_mmd_kernel, dim3(pairs), dim3(256), NN_GEMM_LDS, st, X, nx, Y, ny, bw, part, Mx, My, Kp,
+                     nn_mmd_pairs(Mx, My, 0) - pairs, skip_aa ? 1 : 0);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_mmd_final(const double* part, int pairs, const double* saa, int skip_aa, int Mx, int My,
+                                const float* bw, double* out, hipStream_t st) {
+  if (!part || !bw || !out || Mx < 1 || My < 0 || Mx > NN_MAX_ROWS || My > NN_MAX_ROWS - Mx || (skip_aa && My < 1) ||
+      pairs != nn_mmd_pairs(Mx, My, skip_aa))
+    return -2;
+  hipLaunchKernelGGL(nn_mmd_final_kernel, dim3(1), dim3(256), 0, st, part, pairs, saa, skip_aa ? 1 : 0, Mx, My, bw, out);
   return (int)hipGetLastError();
 }

@@ -159,11 +159,11 @@ class ReferenceEngine:
                      max_rows=max_rows)
 
     def nn_metric(self, real: torch.Tensor, z: torch.Tensor, size: Optional[int] = None, ema: Optional[bool] = None,
-                  refresh: bool = False, k: int = 0) -> dict:
+                  refresh: bool = False, k: int = 0, mmd: bool = False) -> dict:
         """The 1-NN two-sample test between `real` and the samples of z at pyramid level `size`: the oracle
         (ops.reference.nn_two_sample on nn_features) in fp32 on this engine's device. k > 0 adds the k-NN manifold
-        estimates (ops.reference.nn_prdc)."""
-        k = R.check_nn_k(k, z.shape[0], least=0)
+        estimates (ops.reference.nn_prdc), mmd the kernel MMD (ops.reference.nn_mmd)."""
+        k, mmd = R.check_nn_k(k, z.shape[0], least=0), R.check_nn_mmd(mmd, z.shape[0])
         B = self.batch_size
         with torch.no_grad():
             fake = torch.cat([self.sampler(z[i:i + B], ema=ema).float() for i in range(0, z.shape[0], B)])
@@ -172,6 +172,8 @@ class ReferenceEngine:
         out = R.nn_report(R.nn_two_sample(A, Bf))
         if k:
             out.update(R.nn_prdc_report(R.nn_prdc(A, Bf, k)))
+        if mmd:
+            out.update(R.nn_mmd_report(R.nn_mmd(A, Bf)))
         return out
 
     def eval_losses(self, real: torch.Tensor, z: torch.Tensor) -> Dict[str, float]:

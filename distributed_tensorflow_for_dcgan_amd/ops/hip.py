@@ -12,6 +12,7 @@ The training engine records its whole step into persistent programs instead
 from __future__ import annotations
 
 import importlib
+import math
 import os
 from typing import NamedTuple, Optional, Sequence, Tuple
 
@@ -1486,6 +1487,20 @@ class _NnCount:
         prog.nn_count("nn.count." + tag, _p(FX), _p(nX), _p(FY), _p(nY), _p(rad), _p(self.part), _p(cnt), Mx, My, Kp, sp, 0)
 
 
+class _NnMmd:
+    """The recorded ops of one pass of the kernel MMD over the upper triangle of the Gram of [x; y] (y None: x alone):
+    nn_mmd with the bandwidth it reads from bw float32 [2], and its finalize into out float64 [8]. skip_aa: the pairs
+    inside x are left out and their sum is read from saa float64 [1] (None: 0)."""
+
+    def __init__(self, prog, tag, x, y, bw, out, skip_aa=False, saa=None):
+        (_, FX, nX), (_, FY, nY) = x, (y if y is not None else (None, None, None))
+        Mx, My, Kp, skip = FX.shape[0], 0 if y is None else FY.shape[0], FX.shape[1], int(bool(skip_aa))
+        pairs = ext().nn_mmd_pairs(Mx, My, skip)
+        self.part = torch.empty(pairs, 3, dtype=torch.float64, device=FX.device)
+        prog.nn_mmd("nn.mmd." + tag, _p(FX), _p(nX), _p(FY), _p(nY), _p(bw), _p(self.part), Mx, My, Kp, skip, 0)
+        prog.nn_mmd_final("nn.mmd_final." + tag, _p(self.part), pairs, _p(saa), skip, Mx, My, _p(bw), _p(out), 0)
+
+
 def _nn_side(prog, tag, x0: torch.Tensor, mu, compute_mu: bool):
     """Record nn_features of the rows x0 [M, K]: (x0, F [M, Kp], norm [M])."""
     M, K = x0.shape
@@ -1593,6 +1608,26 @@ def nn_count(X: torch.Tensor, Y: torch.Tensor, rad: torch.Tensor, splits: Option
     return cnt
 
 
+def nn_mmd_sums(X: torch.Tensor, Y: torch.Tensor, h: float, skip_aa: bool = False, out=None):
+    """float64 [3] = (S_AA, S_BB, S_AB): the Gaussian-mixture kernel of bandwidth unit h (its fp32 value is used) summed
+    over the pairs i < j inside X [Mx, K], inside Y [My, K], and over all pairs of a row of X and a row of Y, from one
+    pass over the upper triangle of the MFMA Gram of [X; Y] with no centring (oracle: ops.reference.nn_mmd_sums).
+    skip_aa: the pairs inside X are left out, S_AA = 0. out: float64 [8] to write, the sums in its first three slots."""
+    _nn_rows("nn_mmd_sums", X), _nn_rows("nn_mmd_sums", Y)
+    if X.shape[1] != Y.shape[1]:
+        raise ValueError("nn_mmd_sums: X [Mx, K] and Y [My, K], got %s and %s" % (tuple(X.shape), tuple(Y.shape)))
+    res = out if out is not None else torch.empty(8, dtype=torch.float64, device=X.device)
+    if res.dtype != torch.float64 or res.shape != (8,):
+        raise TypeError("nn_mmd_sums: out must be float64 [8]")
+    h32 = float(torch.tensor(float(h), dtype=torch.float32))
+    bw = torch.tensor([h32, math.log2(math.e) / (4.0 * h32) if h32 else math.inf], dtype=torch.float32).to(X.device)
+    prog = ext().Program()
+    keep = _NnMmd(prog, "xy", _nn_side(prog, "x", X, None, False), _nn_side(prog, "y", Y, None, False), bw, res, skip_aa)
+    run(prog)
+    del keep
+    return res[:3]
+
+
 class NnMetric:
     """The leave-one-out 1-NN two-sample test of image sets [n, S, S, C] against one real set, on the device
     (nn.hip; oracle: ops.reference.nn_two_sample on nn_features). ``set_real`` computes the real set's level, its
@@ -1601,14 +1636,19 @@ class NnMetric:
 
     k > 0 adds the k-NN manifold estimates (``prdc``; oracle: ops.reference.nn_prdc). The (A, A) and (B, B) blocks
     are then searched once, for k neighbours (nn_topk; the 1-NN test reads column 0), which gives every row's ball,
-    and two count blocks follow: the fakes against the reals' balls and the reals against the fakes'."""
+    and two count blocks follow: the fakes against the reals' balls and the reals against the fakes'.
 
-    def __init__(self, n: int, S: int, C: int, size: Optional[int] = None, device="cuda", k: int = 0):
+    mmd adds the kernel MMD (``mmd``; oracle: ops.reference.nn_mmd). ``set_real`` computes the bandwidth and the
+    (A, A) sum from the triangle over the reals alone; every call runs the triangle over [A; B] without its (A, A)
+    pairs. With k = 0 and mmd off the recorded ops and buffers are those of the 1-NN test alone."""
+
+    def __init__(self, n: int, S: int, C: int, size: Optional[int] = None, device="cuda", k: int = 0, mmd: bool = False):
         from . import reference as R
         if not 1 <= int(C) <= 4:
             raise ValueError("nn_two_sample: at most 4 channels, got %d" % C)
         self.size = size = R.check_nn(n, size, S)
         self.k = k = R.check_nn_k(k, n, least=0)
+        self.has_mmd = R.check_nn_mmd(mmd, n)
         self.n, self.K = n, size * size * C
         new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=device)  # noqa: E731
         self.xa, self.x = new(n, S, S, C), new(n, S, S, C)  # the real set; the set under evaluation
@@ -1635,6 +1675,11 @@ class NnMetric:
         if k:
             self._keep += [_NnCount(self.prog_fake, "ab", a, b, self.rad[n:], self.hits[:n]),
                            _NnCount(self.prog_fake, "ba", b, a, self.rad[:n], self.hits[n:])]
+        if self.has_mmd:  # bw = {h, c} and mmd_real[0] = S_AA stay from set_real on; mmd_out is the evaluated set's
+            self.bw, self.mmd_real, self.mmd_out = new(2), new(8, dt=torch.float64), new(8, dt=torch.float64)
+            self.prog_real.nn_mmd_bw("nn.mmd_bw.a", _p(a[2]), n, _p(self.bw), 0)
+            self._keep += [_NnMmd(self.prog_real, "aa", a, None, self.bw, self.mmd_real),
+                           _NnMmd(self.prog_fake, "ab", a, b, self.bw, self.mmd_out, True, self.mmd_real[:1])]
         self.has_real = False
 
     def _first_of_k(self, rows: slice, j: torch.Tensor, d: torch.Tensor) -> None:
@@ -1657,6 +1702,14 @@ class NnMetric:
         n = self.n
         return R.nn_prdc_summary(self.hits[:n].clone(), self.hits[n:].clone(), self.dB[:n] <= self.rad[:n].double(), self.k,
                                  self.rad[:n].clone(), self.rad[n:].clone())
+
+    def mmd(self):
+        """ops.reference.NnMmd of the last evaluated set (mmd on): one copy of the device's eight doubles."""
+        from . import reference as R
+        if not self.has_mmd:
+            raise RuntimeError("nn_mmd: the metric was built with mmd off")
+        o = self.mmd_out.tolist()
+        return R.NnMmd(o[7], o[3], o[4], o[5], o[6])
 
     def __call__(self, x: Optional[torch.Tensor] = None):
         """ops.reference.NnResult of x -- None: of what the caller wrote into ``self.x`` -- against the real set. The
@@ -1683,6 +1736,18 @@ def nn_prdc(A: torch.Tensor, B: torch.Tensor, size: Optional[int] = None, k: int
     m.set_real(A)
     m(B)
     return m.prdc()
+
+
+def nn_mmd(A: torch.Tensor, B: torch.Tensor, size: Optional[int] = None):
+    """The unbiased kernel MMD^2 estimate of the image set B (fake) against A (real), float32 [n, S, S, C] on the
+    device, in the pixels of pyramid level `size` (None: S): an ops.reference.NnMmd."""
+    n, S, _, C = _f32_images("nn_mmd", A).shape
+    if _f32_images("nn_mmd", B).shape != A.shape:
+        raise ValueError("nn_mmd: A and B must share a shape")
+    m = NnMetric(n, S, C, size, device=A.device, mmd=True)
+    m.set_real(A)
+    m(B)
+    return m.mmd()
 
 
 def nn_two_sample(A: torch.Tensor, B: torch.Tensor, size: Optional[int] = None):

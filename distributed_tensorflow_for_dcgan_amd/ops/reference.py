@@ -1582,3 +1582,65 @@ def nn_prdc(A: torch.Tensor, B: torch.Tensor, k: int) -> NnPrdc:
 def nn_prdc_report(p: NnPrdc) -> dict:
     """What the engines' nn_metric adds to nn_report with k > 0."""
     return {"precision": p.precision, "recall": p.recall, "density": p.density, "coverage": p.coverage, "k": p.k}
+
+
+# The kernel maximum mean discrepancy on the same feature rows (Gretton et al. 2012; recommended beside the 1-NN test by
+# Xu et al. 2018): the unbiased estimate of MMD^2 under a mixture of 5 Gaussians whose bandwidths, a factor 2 apart,
+# are set by the real set's mean squared distance h. A smooth function of the samples: it has no steps of 1 / n.
+NN_MMD_SCALES = 5
+
+
+class NnMmd(NamedTuple):
+    h: float      # mean of D(A_i, A_j) over i != j: the bandwidth unit, from the real set alone
+    k_rr: float   # mean kernel value between two different reals
+    k_ff: float   # ... between two different fakes
+    k_rf: float   # ... between a real and a fake
+    mmd2: float   # k_rr + k_ff - 2 k_rf: unbiased, so it may be negative
+
+
+def check_nn_mmd(on, n: int, names=("mmd", "n")) -> bool:
+    """Validated switch of the kernel MMD: a boolean, and n >= 2 when it is on (k_rr and k_ff average over i != j)."""
+    if not isinstance(on, (bool, int)) or int(on) not in (0, 1):
+        raise ValueError("%s must be a boolean, got %r" % (names[0], on))
+    if on and int(n) < 2:
+        raise ValueError("%s needs %s to be at least 2, got %d" % (names[0], names[1], int(n)))
+    return bool(on)
+
+
+def nn_mmd_bandwidth(FA: torch.Tensor) -> float:
+    """h = the mean of D(A_i, A_j) over i != j = 2 / (n - 1) * sum_i |A_i - mean(A)|^2."""
+    if FA.dim() != 2 or FA.shape[0] < 2:
+        raise ValueError("nn_mmd_bandwidth: rows [n, K] with n >= 2, got %s" % (tuple(FA.shape),))
+    return 2.0 / (FA.shape[0] - 1) * float(((FA - FA.mean(0, keepdim=True)) ** 2).sum())
+
+
+def nn_mmd_kernel(D: torch.Tensor, h: float) -> torch.Tensor:
+    """k = 1/5 sum_{m = 0..4} exp(-2^m D / (4 h)): Gaussians with 2 sigma^2 = 4h, 2h, h, h/2, h/4."""
+    q = D / torch.as_tensor(4.0 * h, dtype=D.dtype, device=D.device)  # (h = 0: non-finite, reported as it is)
+    return sum(torch.exp(-(2.0 ** m) * q) for m in range(NN_MMD_SCALES)) / NN_MMD_SCALES
+
+
+def nn_mmd_sums(X: torch.Tensor, Y: torch.Tensor, h: float, skip_aa: bool = False):
+    """(S_AA, S_BB, S_AB) over the stacked rows [X; Y]: the kernel summed over i < j inside X, over i < j inside Y
+    (0 rows are fine) and over every pair of a row of X and a row of Y. skip_aa: S_AA is not computed and is 0."""
+    if X.dim() != 2 or Y.dim() != 2 or X.shape[1] != Y.shape[1] or X.shape[0] < 1:
+        raise ValueError("nn_mmd_sums: X [Mx, K] and Y [My, K], got %s and %s" % (tuple(X.shape), tuple(Y.shape)))
+    upper = lambda Z: float(nn_mmd_kernel(nn_distances(Z, Z), h).triu(1).sum()) if Z.shape[0] > 1 else 0.0  # noqa: E731
+    return (0.0 if skip_aa else upper(X), upper(Y),
+            float(nn_mmd_kernel(nn_distances(X, Y), h).sum()) if Y.shape[0] else 0.0)
+
+
+def nn_mmd(FA: torch.Tensor, FB: torch.Tensor) -> NnMmd:
+    """The unbiased MMD^2 estimate between the feature rows FA (real) and FB (fake), both [n, K]."""
+    if FA.shape != FB.shape or FA.dim() != 2 or FA.shape[0] < 2:
+        raise ValueError("nn_mmd: A and B must share a shape [n, K] with n >= 2, got %s and %s"
+                         % (tuple(FA.shape), tuple(FB.shape)))
+    n, h = FA.shape[0], nn_mmd_bandwidth(FA)
+    s_aa, s_bb, s_ab = nn_mmd_sums(FA, FB, h)
+    k_rr, k_ff, k_rf = 2.0 * s_aa / (n * (n - 1)), 2.0 * s_bb / (n * (n - 1)), s_ab / float(n * n)
+    return NnMmd(h, k_rr, k_ff, k_rf, k_rr + k_ff - 2.0 * k_rf)
+
+
+def nn_mmd_report(m: NnMmd) -> dict:
+    """What the engines' nn_metric adds to nn_report with mmd on."""
+    return {"mmd2": m.mmd2, "k_rr": m.k_rr, "k_ff": m.k_ff, "k_rf": m.k_rf, "h": m.h}

@@ -160,6 +160,10 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
     ("nn_k", "int", 0, "with --nn_every: also print precision, recall, density and coverage of the generated set from "
                        "k-NN balls in the same features (Kynkaanniemi et al. 2019 use k = 3, Naeem et al. 2020 k = 5): "
                        "high precision with low recall = good images of few kinds. 1..min(16, --nn_images - 1); 0 = off"),
+    ("nn_mmd", "bool", False, "with --nn_every: also print the unbiased kernel MMD^2 estimate between the two sets in the "
+                              "same features (a mixture of 5 Gaussians whose bandwidths follow the real set's mean "
+                              "squared distance h), with the mean kernel values it is made of. Smooth in the samples: "
+                              "it has no steps of 1 / --nn_images. 0 = the sets agree; it may come out slightly negative"),
     ("swd_max_rows", "int", 32768, "largest --swd_images * --swd_patches accepted: a power of two in [32768, 2^21]. "
                                    "Above 32768 the HIP engine sorts with its global merge sort and holds two "
                                    "float32 [512, N] buffers per pyramid level plus two key buffers (34.6 GiB at "
@@ -258,11 +262,13 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         parser.error(str(e))
     if int(ns.nn_every) < 0 or int(ns.nn_grid) < 0:
         parser.error("--nn_every and --nn_grid must be >= 0, got %r and %r" % (ns.nn_every, ns.nn_grid))
-    if int(ns.nn_every) > 0 or any(a.split("=")[0] in ("--nn_images", "--nn_size", "--nn_grid", "--nn_k") for a in argv):
-        from ..ops.reference import check_nn, check_nn_k
+    if int(ns.nn_every) > 0 or any(a.split("=")[0] in ("--nn_images", "--nn_size", "--nn_grid", "--nn_k", "--nn_mmd")
+                                   for a in argv):
+        from ..ops.reference import check_nn, check_nn_k, check_nn_mmd
         try:
             check_nn(ns.nn_images, ns.nn_size, ns.output_size, ("--nn_images", "--nn_size", "--output_size"))
             check_nn_k(ns.nn_k, ns.nn_images, ("--nn_k", "--nn_images"), least=0)
+            check_nn_mmd(ns.nn_mmd, ns.nn_images, ("--nn_mmd", "--nn_images"))
         except ValueError as e:
             parser.error(str(e))
         if int(ns.nn_grid) > int(ns.nn_images):
