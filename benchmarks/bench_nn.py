@@ -5,9 +5,11 @@ With ``--k`` the same for the metric with the k-NN manifold estimates next to th
 nn_topk kernel against nn_top1 and nn_count on the (A, A) block alone, and ``torch.cdist`` + ``topk`` + the comparison
 against the radii as the yardstick. With ``--mmd`` the metric with the kernel MMD, its triangular Gram kernel alone (full
 and without the (A, A) pairs) against three nn_count launches over (A, A), (A, B), (B, B), and ``torch.cdist`` + ``exp``
-+ ``sum`` over the same three blocks as the yardstick.
++ ``sum`` over the same three blocks as the yardstick. With ``--fd`` the metric with the Frechet distance (``--fd_iters``
+steps of the polar iteration), one launch of the cross-Gram, of P = X X^T and of the step alone, ``torch.linalg.svdvals``
+of the same C where the build has it, and the distance of a second real draw against the first: the floor to compare with.
 
-    python benchmarks/bench_nn.py [--images 1024] [--output_size 64] [--nn_size 0] [--k 0] [--mmd] [--iters 10] [--out FILE]
+    python benchmarks/bench_nn.py [--images 1024] [--output_size 64] [--nn_size 0] [--k 0] [--mmd] [--fd] [--iters 10] [--out FILE]
 """
 import argparse
 import json
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--k", type=int, default=0, help="also time the metric with precision / recall / density / coverage")
     ap.add_argument("--mmd", action="store_true", help="also time the metric with the kernel MMD and its Gram kernel alone")
+    ap.add_argument("--fd", action="store_true", help="also time the metric with the Frechet distance and its GEMM launches alone")
+    ap.add_argument("--fd_iters", type=int, default=40)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None, help="also append the result line to this file")
     a = ap.parse_args()
@@ -155,6 +159,41 @@ def main():
                     "gram_kernel_ms_min_max": {m: mm(v) for m, v in kern.items()},
                     "cdist_exp_sum_3_blocks_ms_median": med(cdm), "cdist_exp_sum_min_max": mm(cdm),
                     "result_mmd": {m: round(res_m[m], 5) for m in ("mmd2", "k_rr", "k_ff", "k_rf", "h")}})
+    if a.fd:
+        from distributed_tensorflow_for_dcgan_amd.ops import hip as H
+        timed(lambda: eng.nn_metric(real, z, a.nn_size, refresh=True, fd=a.fd_iters))
+        first_f = sorted(timed(lambda: eng.nn_metric(real, z, a.nn_size, refresh=True, fd=a.fd_iters))[0] for _ in range(a.iters))
+        cached_f = sorted(timed(lambda: eng.nn_metric(None, z, a.nn_size, fd=a.fd_iters))[0] for _ in range(a.iters))
+        nf = eng._nn
+        it, FA, FB, e, p = nf._keep[-1], nf._keep[2][1], nf._keep[3][1], H.ext(), H._p
+        progs = {"gram": e.Program(), "ppt": e.Program(), "step": e.Program()}  # one launch each, on the metric's buffers
+        progs["ppt"].nn_fd_ppt("ppt", p(it.X[0]), p(it.P), n, 0)
+        progs["step"].nn_fd_step("step", p(it.P), p(it.X[0]), p(it.X[1]), n, 0)
+        progs["gram"].nn_fd_gram("gram", p(FA), p(FB), p(nf.fd_c), n, FA.shape[1], 0)
+        kern = {}
+        for name, prog in progs.items():
+            timed(lambda: H.run(prog))
+            kern[name] = sorted(timed(lambda: H.run(prog))[0] for _ in range(a.iters))
+        mm = lambda v: [round(v[0], 3), round(v[-1], 3)]  # noqa: E731
+        res_f = eng.nn_metric(None, z, a.nn_size, fd=a.fd_iters)  # (fd_c is again this set's centred C)
+        Cc = nf.fd_c[:, :n].contiguous()
+        try:
+            timed(lambda: torch.linalg.svdvals(Cc))
+            sv = sorted(timed(lambda: torch.linalg.svdvals(Cc))[0] for _ in range(a.iters))
+            svd = {"svdvals_ms_median": med(sv), "svdvals_ms_min_max": mm(sv),
+                   "svdvals_nuc": float(torch.linalg.svdvals(Cc).double().sum())}
+        except Exception as ex:  # (a build without a device SVD)
+            svd = {"svdvals": "unavailable: %s" % type(ex).__name__}
+        real2 = (torch.rand(n, a.output_size, a.output_size, a.c_dim, generator=g) * 2 - 1).to(dev)
+        floor = H.nn_frechet(real, real2, a.nn_size or None, a.fd_iters)  # a second real draw: the floor of the distance
+        out.update({"fd_iters": a.fd_iters, "first_fd_ms_median": med(first_f), "first_fd_ms_min_max": mm(first_f),
+                    "cached_fd_ms_median": med(cached_f), "cached_fd_ms_min_max": mm(cached_f),
+                    "fd_workgroups": {"ppt": e.nn_fd_ppt_groups(n), "step": e.nn_fd_step_groups(n)},
+                    "fd_kernel_ms_median": {m: med(v) for m, v in kern.items()},
+                    "fd_kernel_ms_min_max": {m: mm(v) for m, v in kern.items()},
+                    "result_fd": {m: res_f[m] for m in ("fd", "fd_mean2", "fd_tr", "fd_nuc", "fd_tail")},
+                    "real_real_floor": floor._asdict(),
+                    "fp32_resolution": n * 2.0 ** -24 * (floor.tr_a + floor.tr_b)}, **svd)
     line = json.dumps(out)
     print(line)
     if a.out:

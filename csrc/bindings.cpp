@@ -1532,6 +1532,58 @@ class Program {
                               P<double>(out), st);
     }, AccList().r(part, (size_t)(pairs > 0 ? pairs : 0) * 3 * 8).r(saa, 8).r(bw, 8).w(out, 64).v);
   }
+  // ---- the Frechet distance through the polar iteration: square fp32 matrices [n][nn_fd_ld(n)]
+  static size_t fd_sq(int n) { return n > 0 ? (size_t)n * nn_fd_ld(n) * 4 : 0; }
+  static size_t fd_blocks(int n) { return n > 0 ? (size_t)(n + NN_MEAN_ROWS - 1) / NN_MEAN_ROWS : 0; }
+  int nn_fd_gram(std::string name, uintptr_t FA, uintptr_t FB, uintptr_t C, int n, int Kp, int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_fd_gram(P<const float>(FA), P<const float>(FB), P<float>(C), n, Kp, st);
+    }, AccList().r(FA, (size_t)n * Kp * 4).r(FB, (size_t)n * Kp * 4).w(C, fd_sq(n)).v);
+  }
+  // C is centred in place (center) and X = C / alpha, al double [2] = {alpha, 1 / alpha}; the workspaces are the Program's
+  int nn_fd_scale(std::string name, uintptr_t C, int n, int center, uintptr_t al, uintptr_t X, int stream) {
+    const size_t nb = n > 0 ? (size_t)n * 8 : 0, cb = fd_blocks(n) * nb;
+    double* rmean = nb ? reinterpret_cast<double*>(dev_alloc(2 * nb + cb)) : nullptr;
+    double* rabs = rmean ? rmean + n : nullptr;
+    double* cpart = rmean ? rmean + 2 * (size_t)n : nullptr;
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_fd_scale(P<float>(C), n, center, rmean, rabs, cpart, P<double>(al), P<float>(X), st);
+    }, AccList().w(C, fd_sq(n)).w((uintptr_t)rmean, 2 * nb + cb).w(al, 16).w(X, fd_sq(n)).v);
+  }
+  int nn_fd_ppt(std::string name, uintptr_t X, uintptr_t Pm, int n, int stream) {
+    return add(name, stream, [=](hipStream_t st) { return dcg_nn_fd_ppt(P<const float>(X), P<float>(Pm), n, st); },
+               AccList().r(X, fd_sq(n)).w(Pm, fd_sq(n)).v);
+  }
+  int nn_fd_step(std::string name, uintptr_t Pm, uintptr_t X, uintptr_t Xn, int n, int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_fd_step(P<const float>(Pm), P<const float>(X), P<float>(Xn), n, st);
+    }, AccList().r(Pm, fd_sq(n)).r(X, fd_sq(n)).w(Xn, fd_sq(n)).v);
+  }
+  int nn_fd_trace(std::string name, uintptr_t X, uintptr_t C, int n, uintptr_t part, int stream) {
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_fd_trace(P<const float>(X), P<const float>(C), n, P<double>(part), st);
+    }, AccList().r(X, fd_sq(n)).r(C, fd_sq(n)).w(part, n > 0 ? (size_t)nn_fd_parts(n) * 8 : 0).v);
+  }
+  int nn_fd_tr(std::string name, uintptr_t norm, int n, uintptr_t out, int stream) {
+    return add(name, stream, [=](hipStream_t st) { return dcg_nn_fd_tr(P<const float>(norm), n, P<double>(out), st); },
+               AccList().r(norm, (size_t)(n > 0 ? n : 0) * 4).w(out, 8).v);
+  }
+  // mpart double [ceil(n / 64)][Kp]: the column sums of FB [n][Kp] per 64 rows
+  int nn_fd_mean(std::string name, uintptr_t FB, int n, int Kp, uintptr_t mpart, int stream) {
+    const size_t kp = Kp > 0 ? (size_t)Kp : 0;
+    return add(name, stream, [=](hipStream_t st) { return dcg_nn_fd_mean(P<const float>(FB), n, Kp, P<double>(mpart), st); },
+               AccList().r(FB, (size_t)(n > 0 ? n : 0) * kp * 4).w(mpart, fd_blocks(n) * kp * 8).v);
+  }
+  // out double [8] = {fd, mean2, tr_a, tr_b, nuc, tail, alpha, iters}. mpart (nn_fd_mean's), norm_b, tra: 0 for the
+  // nuclear norm of a bare C
+  int nn_fd_final(std::string name, uintptr_t tprev, uintptr_t tlast, uintptr_t al, uintptr_t mpart, int Kp, uintptr_t norm_b,
+                  uintptr_t tra, int n, int iters, uintptr_t out, int stream) {
+    const size_t mb = mpart && Kp > 0 ? fd_blocks(n) * (size_t)Kp * 8 : 0, tb = n > 0 ? (size_t)nn_fd_parts(n) * 8 : 0;
+    return add(name, stream, [=](hipStream_t st) {
+      return dcg_nn_fd_final(P<const double>(tprev), P<const double>(tlast), P<const double>(al), P<const double>(mpart), Kp,
+                             P<const float>(norm_b), P<const double>(tra), n, iters, P<double>(out), st);
+    }, AccList().r(tprev, tb).r(tlast, tb).r(al, 16).r(mpart, mb).r(norm_b, (size_t)(n > 0 ? n : 0) * 4).r(tra, 8).w(out, 64).v);
+  }
 
  private:
   int add(const std::string& name, int stream, std::function<int(hipStream_t)> fn, std::vector<Acc> acc,
@@ -1614,6 +1666,13 @@ PYBIND11_MODULE(_dcgan_hip, m) {
   m.attr("NN_TILE") = (int)NN_TILE;
   m.attr("NN_MAX_KNN") = (int)NN_MAX_KNN;
   m.def("nn_mmd_pairs", &nn_mmd_pairs);  // workgroups of nn_mmd = rows of its part [pairs][3]
+  m.def("nn_fd_ld", &nn_fd_ld);        // row length of the Frechet distance's square matrices of n rows
+  m.def("nn_fd_parts", &nn_fd_parts);  // fp64 partials of nn_fd_trace
+  m.def("nn_fd_ppt_groups", &nn_fd_ppt_groups);    // workgroups of P = X X^T ...
+  m.def("nn_fd_step_groups", &nn_fd_step_groups);  // ... and of the step
+  m.attr("NN_MEAN_ROWS") = (int)NN_MEAN_ROWS;  // rows per fp64 partial sum of a mean (nn_fd_mean's mpart)
+  m.attr("NN_FD_MAX_ROWS") = (int)NN_FD_MAX_ROWS;
+  m.attr("NN_FD_MAX_ITERS") = (int)NN_FD_MAX_ITERS;
   m.attr("SWD_FUSED_ROWS") = (int)SWD_FUSED_ROWS;
   m.attr("SWD_GLOBAL_MAX_ROWS") = (int)SWD_GLOBAL_MAX_ROWS;  // N of swd_sort_large: (32768, 2^21]
   m.attr("SWD_CHUNK_ROWS") = (int)SWD_CHUNK_ROWS;
@@ -1792,5 +1851,13 @@ PYBIND11_MODULE(_dcgan_hip, m) {
       .def("nn_count", &Program::nn_count)
       .def("nn_mmd_bw", &Program::nn_mmd_bw)
       .def("nn_mmd", &Program::nn_mmd)
-      .def("nn_mmd_final", &Program::nn_mmd_final);
+      .def("nn_mmd_final", &Program::nn_mmd_final)
+      .def("nn_fd_gram", &Program::nn_fd_gram)
+      .def("nn_fd_scale", &Program::nn_fd_scale)
+      .def("nn_fd_ppt", &Program::nn_fd_ppt)
+      .def("nn_fd_step", &Program::nn_fd_step)
+      .def("nn_fd_trace", &Program::nn_fd_trace)
+      .def("nn_fd_tr", &Program::nn_fd_tr)
+      .def("nn_fd_mean", &Program::nn_fd_mean)
+      .def("nn_fd_final", &Program::nn_fd_final);
 }

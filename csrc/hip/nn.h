@@ -22,6 +22,17 @@ static inline int nn_mmd_pairs(int Mx, int My, int skip_aa) {
   const int T = nn_col_tiles(Mx + My), J0 = skip_aa ? Mx / NN_TILE : 0;
   return T * (T + 1) / 2 - J0 * (J0 + 1) / 2;
 }
+// The Frechet distance's square matrices [n][nn_fd_ld(n)]: a row is padded with zeros to a multiple of 16 columns, so
+// that it serves as the k range of a GEMM. Below NN_FD_SMALL rows the tiles are 64 x 64, so that a launch fills the device
+constexpr int NN_FD_MAX_ROWS = 8192;
+constexpr int NN_FD_MAX_ITERS = 256;
+constexpr int NN_FD_SMALL = 2048;
+static inline int nn_fd_ld(int n) { return (n + 15) & ~15; }
+static inline int nn_fd_tile(int n) { return n < NN_FD_SMALL ? 64 : NN_TILE; }
+static inline int nn_fd_parts(int n) { return (n + 3) / 4; }  // fp64 partials of nn_fd_trace: one per 4 rows
+// workgroups of P = X X^T (the tiles of the upper triangle) and of the step X' = 1.5 X - 0.5 P X
+static inline int nn_fd_ppt_groups(int n) { const int T = (n + nn_fd_tile(n) - 1) / nn_fd_tile(n); return T * (T + 1) / 2; }
+static inline int nn_fd_step_groups(int n) { const int T = (n + nn_fd_tile(n) - 1) / nn_fd_tile(n); return T * T; }
 // fp64 partials of the mean: [ceil(n / NN_MEAN_ROWS)][K]
 static inline size_t nn_mean_part_bytes(int n, int K) {
   return (size_t)((n + NN_MEAN_ROWS - 1) / NN_MEAN_ROWS) * (size_t)K * sizeof(double);
@@ -65,4 +76,25 @@ int dcg_nn_mmd(const float* X, const float* nx, const float* Y, const float* ny,
 // mixture's 1/5. With skip_aa, S_AA is *saa (null: 0); a mean over no pair is 0
 int dcg_nn_mmd_final(const double* part, int pairs, const double* saa, int skip_aa, int Mx, int My, const float* bw,
                      double* out, hipStream_t st);
+// The Frechet distance through the polar iteration (nn.hip). 2 <= n <= NN_FD_MAX_ROWS; C, X, Xn, P are [n][nn_fd_ld(n)]
+// C = FA FB^T / (n - 1), FA and FB [n][Kp]
+int dcg_nn_fd_gram(const float* FA, const float* FB, float* C, int n, int Kp, hipStream_t st);
+// center: C <- C - rowmean(C) in place. al double [2] = {alpha, 1 / alpha}, alpha = sqrt(max_i sum_j |c_ij| * max_j
+// sum_i |c_ij|); X = C / alpha. Workspaces: rmean, rabs double [n], cpart double [ceil(n / NN_MEAN_ROWS)][n]
+int dcg_nn_fd_scale(float* C, int n, int center, double* rmean, double* rabs, double* cpart, double* al, float* X,
+                    hipStream_t st);
+// P = X X^T, over the tiles of the upper triangle, each stored to both halves
+int dcg_nn_fd_ppt(const float* X, float* P, int n, hipStream_t st);
+// Xn = 1.5 X - 0.5 P X; Xn is neither X nor P
+int dcg_nn_fd_step(const float* P, const float* X, float* Xn, int n, hipStream_t st);
+// part double [nn_fd_parts(n)]: sum_ij X_ij C_ij per 4 rows
+int dcg_nn_fd_trace(const float* X, const float* C, int n, double* part, hipStream_t st);
+// out double [1] = sum_i norm_i / (n - 1)
+int dcg_nn_fd_tr(const float* norm, int n, double* out, hipStream_t st);
+// mpart double [ceil(n / NN_MEAN_ROWS)][Kp]: the column sums of FB per 64 rows
+int dcg_nn_fd_mean(const float* FB, int n, int Kp, double* mpart, hipStream_t st);
+// out double [8] = {fd, mean2, tr_a, tr_b, nuc, tail, alpha, iters} from the traces of the last two iterates; mpart,
+// norm_b and tra may be null (their terms are then 0: the nuclear norm of a bare C)
+int dcg_nn_fd_final(const double* tprev, const double* tlast, const double* al, const double* mpart, int Kp,
+                    const float* norm_b, const double* tra, int n, int iters, double* out, hipStream_t st);
 }

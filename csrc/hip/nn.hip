@@ -56,6 +56,35 @@
 //                partials per lane by class (A, A), (A, B), (B, B) over row < col, then fp64: shuffles, the four
 //                waves through LDS in order, part [pair][3]. No atomics; bitwise reproducible
 //   nn_mmd_final the pairs' sums added in a fixed order, the three means and mmd2 = k_rr + k_ff - 2 k_rf
+// The Frechet distance of the two sets' Gaussians, FD = |d|^2 + tr S_A + tr S_B - 2 tr (S_A S_B)^(1/2), through its dual
+// (Mathiasen & Hvilshoj 2020): tr (S_A S_B)^(1/2) = ||C||_*, C = Xc Yc^T / (n - 1) [n][n], and ||C||_* = tr(U^T C) for the
+// polar factor U of C, which the Newton-Schulz iteration X <- 1.5 X - 0.5 (X X^T) X reaches by GEMMs alone. Square
+// matrices [n][ld], ld = n rounded up to 16, columns n..ld-1 zero, so that a row is a k range for the loaders above:
+//   nn_fd_nt     out = scale A B^T, the main loop above with a store epilogue. As the cross-Gram C' = F_A F_B^T / (n - 1)
+//                over all tiles; as P = X X^T over the tiles (I, J), I <= J, of the upper triangle (nn_mmd's pair
+//                index), an off-diagonal tile also stored transposed: the four rows 4 fq + r of a C fragment are four
+//                consecutive columns of the mirror image, one 16-byte store
+//   nn_fd_rows .. nn_fd_x0  the scale. F_B is centred by the real mean, F_B = Yc + 1 d^T, and F_A's columns sum to zero,
+//                so C = C' - rowmean(C'): per row the fp64 mean and the sum of |c - mean| (one wave per row, every lane
+//                its columns in index order, a shuffle tree), per column the same sum through fp64 partials per 64
+//                rows, alpha = sqrt(max row sum * max column sum) >= sigma_max (a maximum has no order), and one
+//                pass that leaves C centred in place and X_0 = C / alpha: singular values in [0, 1]
+//   nn_fd_step   X' = 1.5 X - 0.5 P X. P's rows are the row-major operand as above; X is the k-major one, element (k, j),
+//                read from its rows with no transposed copy in memory: per stage of 32 k a thread takes 16-byte loads
+//                along j and stores them as they are into a tile [32 k][TILE + 4]. The B fragment of lane (fr, fq) for
+//                MFMA e is the float at row kk + 4 fq + e, column 16 j + fr: with a pitch of TILE + 4 = 132 (or 68)
+//                floats, 4 fq pitch mod 64 = 16 fq, so the bank is 16 fq + fr + a constant -- the wave's 64 lanes read
+//                64 different banks (and either half-wave 32 different ones mod 32). The 16-byte stores of 16
+//                consecutive lanes cover 64 consecutive floats of one k row: every bank once. A transpose in the
+//                stash would buy 16-byte fragment reads at the price of 4-way conflicts on every store; [k][col] with
+//                this pitch has none on either side. The 1.5 X term comes from the output tile's own rows of X in the
+//                epilogue. Two X buffers alternate, so the last two iterates are both there at the end
+//   nn_fd_trace  part [4 rows] = sum X_ij C_ij in fp64: a wave per row in index order, the four waves in order
+//   nn_fd_final  v = tr(X^T C) of the last two iterates from nn_fd_trace's parts in a fixed order, |d|^2 from the fp64
+//                column sums of F_B (nn_fd_mean: nn_mean_part on F_B), tr S_B from its norms:
+//                out = {fd, mean2, tr_a, tr_b, nuc = v_k, tail = v_k - v_{k-1}, alpha, iters}
+// Tiles are 128 x 128 as above or, below 2048 rows, 64 x 64 (a wave owns 32 x 32): at n = 1024 that is 136 workgroups
+// for P and 256 for the step instead of 36 and 64. No atomics; every dependency between workgroups is a launch boundary.
 // Every index into a feature matrix is 64-bit: n Kp passes 2^31 at 128x128x3.
 #include "common.h"
 #include "nn.h"
@@ -716,6 +745,326 @@ __global__ __launch_bounds__(256) void nn_mmd_final_kernel(const double* __restr
   }
 }
 
+// ---------------------------------------------------------------- Frechet distance: the polar iteration on C [n][n]
+// tile pair p -> (I, J), I <= J, p = J (J + 1) / 2 + I (nn_mmd's order)
+__device__ __forceinline__ void nn_tri_pair(int p, int& I, int& J) {
+  J = (int)((__builtin_sqrtf(8.f * (float)p + 1.f) - 1.f) * 0.5f);
+  while (J * (J + 1) / 2 > p) --J;  // the float root is one step off at the most
+  while ((J + 1) * (J + 2) / 2 <= p) ++J;
+  I = p - J * (J + 1) / 2;
+}
+
+// out [M][ld] = scale A B^T, A and B [M][Kp] (Kp a multiple of 16): one workgroup per tile of 32 FR rows and columns,
+// a wave 16 FR x 16 FR. SYM (A is B): blockIdx.x is a pair of the upper triangle, and an off-diagonal tile goes to both
+// halves. Rows past M read as zeros, so the columns M..ld-1 of out are written as zeros
+template <int FR, bool SYM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, FR == 4 ? 2 : 4)))
+void nn_fd_nt_kernel(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ out, int M, int Kp,
+                     int ld, float scale) {
+  constexpr int TILE = 32 * FR, TF = TILE * NN_PITCH;
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [2 buffers][A tile, B tile][TILE][36]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  int I, J;
+  if (SYM) nn_tri_pair((int)blockIdx.x, I, J); else I = (int)blockIdx.y, J = (int)blockIdx.x;
+  const int nk = (Kp + NN_BK - 1) / NN_BK;
+  const int lr = tid >> 3, lq = tid & 7;  // the loader's rows lr + 32 p, its 16-byte word lq of the 32 k
+  const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 sa[FR], sb[FR];
+
+  auto fetch = [&](int it) {
+    const int k0 = it * NN_BK + 4 * lq;
+    const bool kok = k0 < Kp;
+#pragma unroll
+    for (int p = 0; p < FR; ++p) {
+      const int ra = I * TILE + lr + 32 * p, rb = J * TILE + lr + 32 * p;
+      sa[p] = (kok && ra < M) ? *reinterpret_cast<const f32x4*>(A + (size_t)ra * Kp + k0) : zero;
+      sb[p] = (kok && rb < M) ? *reinterpret_cast<const f32x4*>(B + (size_t)rb * Kp + k0) : zero;
+    }
+  };
+  auto stash = [&](int buf) {
+    float* bx = lds + buf * 2 * TF + lr * NN_PITCH + 4 * lq;
+#pragma unroll
+    for (int p = 0; p < FR; ++p) {
+      *reinterpret_cast<f32x4*>(bx + 32 * p * NN_PITCH) = sa[p];
+      *reinterpret_cast<f32x4*>(bx + TF + 32 * p * NN_PITCH) = sb[p];
+    }
+  };
+
+  f32x4 acc[FR][FR];
+#pragma unroll
+  for (int i = 0; i < FR; ++i)
+#pragma unroll
+    for (int j = 0; j < FR; ++j) acc[i][j] = zero;
+
+  fetch(0);
+  stash(0);
+  __syncthreads();
+  for (int it = 0; it < nk; ++it) {
+    const int buf = it & 1;
+    const bool more = it + 1 < nk;
+    if (more) fetch(it + 1);
+    const float* bx = lds + buf * 2 * TF + (wr * 16 * FR + fr) * NN_PITCH + 4 * fq;
+    const float* by = lds + buf * 2 * TF + TF + (wc * 16 * FR + fr) * NN_PITCH + 4 * fq;
+#pragma unroll
+    for (int kk = 0; kk < NN_BK; kk += 16) {  // lane group fq supplies k = kk + 4 fq + e to MFMA e, for A and B alike
+      f32x4 a[FR], b[FR];
+#pragma unroll
+      for (int i = 0; i < FR; ++i) a[i] = *reinterpret_cast<const f32x4*>(bx + i * 16 * NN_PITCH + kk);
+#pragma unroll
+      for (int j = 0; j < FR; ++j) b[j] = *reinterpret_cast<const f32x4*>(by + j * 16 * NN_PITCH + kk);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < FR; ++i)
+#pragma unroll
+          for (int j = 0; j < FR; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
+    }
+    if (more) stash(buf ^ 1);  // (last read in step it - 1, before that step's barrier)
+    __syncthreads();
+  }
+
+  // C fragment acc[i][j][r] = row I TILE + wr 16 FR + 16 i + 4 fq + r, column J TILE + wc 16 FR + 16 j + fr. In the
+  // mirror image the four r are four consecutive columns from a multiple of 4: inside the row's ld, 16-byte aligned
+  const bool mirror = SYM && I != J;
+#pragma unroll
+  for (int i = 0; i < FR; ++i)
+#pragma unroll
+    for (int j = 0; j < FR; ++j) {
+      const int row0 = I * TILE + wr * 16 * FR + 16 * i + 4 * fq, col = J * TILE + wc * 16 * FR + 16 * j + fr;
+      f32x4 v = acc[i][j];
+      v[0] *= scale, v[1] *= scale, v[2] *= scale, v[3] *= scale;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (row0 + r < M && col < ld) out[(size_t)(row0 + r) * ld + col] = v[r];
+      if (mirror && col < M && row0 < ld) *reinterpret_cast<f32x4*>(out + (size_t)col * ld + row0) = v;
+    }
+}
+
+// Xn = 1.5 X - 0.5 P X, all [M][ld]. P's rows are the row-major operand (nn_fd_nt's A); X is the k-major one
+template <int FR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, FR == 4 ? 2 : 4)))
+void nn_fd_step_kernel(const float* __restrict__ P, const float* __restrict__ X, float* __restrict__ Xn, int M, int ld) {
+  constexpr int TILE = 32 * FR, TF = TILE * NN_PITCH, PB = TILE + 4, BF = NN_BK * PB;
+  constexpr int CW = TILE / 4, KR = 256 / CW;  // 16-byte words per k row of the X tile; k rows per pass of the loader
+  static_assert(KR * FR == NN_BK && (4 * PB) % 64 == 16, "nn_fd_step: the X tile's loader and pitch");
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [2 buffers][TILE][36] of P, then [2 buffers][32][PB] of X
+  float* ldx = lds + 2 * TF;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int I = (int)blockIdx.y, J = (int)blockIdx.x;
+  const int nk = (M + NN_BK - 1) / NN_BK;
+  const int lr = tid >> 3, lq = tid & 7;     // P: rows lr + 32 p, 16-byte word lq of the 32 k
+  const int lk = tid / CW, lc = tid % CW;    // X: k rows lk + KR p, 16-byte word lc of the TILE columns
+  const int xc = J * TILE + 4 * lc;
+  const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 sp[FR], sx[FR];
+
+  auto fetch = [&](int it) {  // P: rows past M and k past ld read as zeros; X: k rows past M and columns past ld
+    const int k0 = it * NN_BK + 4 * lq;
+#pragma unroll
+    for (int p = 0; p < FR; ++p) {
+      const int rp = I * TILE + lr + 32 * p, kx = it * NN_BK + lk + KR * p;
+      sp[p] = (k0 < ld && rp < M) ? *reinterpret_cast<const f32x4*>(P + (size_t)rp * ld + k0) : zero;
+      sx[p] = (kx < M && xc < ld) ? *reinterpret_cast<const f32x4*>(X + (size_t)kx * ld + xc) : zero;
+    }
+  };
+  auto stash = [&](int buf) {
+    float* bp = lds + buf * TF + lr * NN_PITCH + 4 * lq;
+    float* bx = ldx + buf * BF + lk * PB + 4 * lc;
+#pragma unroll
+    for (int p = 0; p < FR; ++p) {
+      *reinterpret_cast<f32x4*>(bp + 32 * p * NN_PITCH) = sp[p];
+      *reinterpret_cast<f32x4*>(bx + KR * p * PB) = sx[p];
+    }
+  };
+
+  f32x4 acc[FR][FR];
+#pragma unroll
+  for (int i = 0; i < FR; ++i)
+#pragma unroll
+    for (int j = 0; j < FR; ++j) acc[i][j] = zero;
+
+  fetch(0);
+  stash(0);
+  __syncthreads();
+  for (int it = 0; it < nk; ++it) {
+    const int buf = it & 1;
+    const bool more = it + 1 < nk;
+    if (more) fetch(it + 1);
+    const float* bp = lds + buf * TF + (wr * 16 * FR + fr) * NN_PITCH + 4 * fq;
+    const float* bx = ldx + buf * BF + 4 * fq * PB + wc * 16 * FR + fr;
+#pragma unroll
+    for (int kk = 0; kk < NN_BK; kk += 16) {  // lane group fq supplies k = kk + 4 fq + e to MFMA e, for P and X alike
+      f32x4 a[FR];
+      float b[FR][4];
+#pragma unroll
+      for (int i = 0; i < FR; ++i) a[i] = *reinterpret_cast<const f32x4*>(bp + i * 16 * NN_PITCH + kk);
+#pragma unroll
+      for (int j = 0; j < FR; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) b[j][e] = bx[(kk + e) * PB + 16 * j];
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < FR; ++i)
+#pragma unroll
+          for (int j = 0; j < FR; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
+    }
+    if (more) stash(buf ^ 1);  // (last read in step it - 1, before that step's barrier)
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int i = 0; i < FR; ++i)
+#pragma unroll
+    for (int j = 0; j < FR; ++j) {
+      const int row0 = I * TILE + wr * 16 * FR + 16 * i + 4 * fq, col = J * TILE + wc * 16 * FR + 16 * j + fr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (row0 + r < M && col < ld) {
+          const size_t o = (size_t)(row0 + r) * ld + col;
+          Xn[o] = __builtin_fmaf(-0.5f, acc[i][j][r], 1.5f * X[o]);
+        }
+    }
+}
+
+// the sum of a double over the workgroup's 256 threads in a fixed order: a shuffle tree, then the four waves in order
+__device__ __forceinline__ double nn_block_sum(double s, double* red) {
+  s = nn_wave_sum(s);
+  __syncthreads();  // (red is free again)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+__device__ __forceinline__ double nn_block_max(double s, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s = fmax(s, __shfl_xor(s, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+// one wave per row: rmean = the row's mean over its n columns (0 without center), rabs = sum_j |c - rmean|
+__global__ __launch_bounds__(256) void nn_fd_rows_kernel(const float* __restrict__ C, int n, int ld, int center,
+                                                         double* __restrict__ rmean, double* __restrict__ rabs) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const float* c = C + (size_t)row * ld;
+  double m = 0.0;
+  if (center) {
+    double s = 0.0;
+    for (int j = lane; j < n; j += 64) s += (double)c[j];
+    m = nn_wave_sum(s) / (double)n;
+  }
+  double a = 0.0;
+  for (int j = lane; j < n; j += 64) a += fabs((double)c[j] - m);
+  a = nn_wave_sum(a);
+  if (lane == 0) rmean[row] = m, rabs[row] = a;
+}
+
+// thread j of row block b: sum_r |c[r][j] - rmean[r]| over the block's 64 rows in index order
+__global__ __launch_bounds__(256) void nn_fd_cols_kernel(const float* __restrict__ C, int n, int ld,
+                                                         const double* __restrict__ rmean, double* __restrict__ cpart) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int r0 = blockIdx.y * NN_MEAN_ROWS, r1 = min(n, r0 + NN_MEAN_ROWS);
+  double s = 0.0;
+  for (int r = r0; r < r1; ++r) s += fabs((double)C[(size_t)r * ld + j] - rmean[r]);
+  cpart[(size_t)blockIdx.y * n + j] = s;
+}
+
+// al = {alpha, 1 / alpha (0 when alpha is 0: C = 0 has X = 0 and a nuclear norm of 0)}
+__global__ __launch_bounds__(256) void nn_fd_alpha_kernel(const double* __restrict__ rabs, const double* __restrict__ cpart,
+                                                          int n, int blocks, double* __restrict__ al) {
+  __shared__ double red[4];
+  double mr = 0.0, mc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    mr = fmax(mr, rabs[i]);
+    double s = 0.0;
+    for (int b = 0; b < blocks; ++b) s += cpart[(size_t)b * n + i];
+    mc = fmax(mc, s);
+  }
+  mr = nn_block_max(mr, red);
+  mc = nn_block_max(mc, red);
+  if (threadIdx.x == 0) {
+    const double alpha = sqrt(mr * mc);
+    al[0] = alpha;
+    al[1] = alpha > 0.0 ? 1.0 / alpha : 0.0;
+  }
+}
+
+// a workgroup per row: C <- C - rmean in place (columns n..ld-1: 0), X = C / alpha
+__global__ __launch_bounds__(256) void nn_fd_x0_kernel(float* __restrict__ C, int n, int ld, const double* __restrict__ rmean,
+                                                       const double* __restrict__ al, float* __restrict__ X) {
+  const int row = blockIdx.x;
+  const double m = rmean[row], alpha = al[0];
+  for (int j = threadIdx.x; j < ld; j += 256) {
+    const size_t o = (size_t)row * ld + j;
+    const float c = j < n ? (float)((double)C[o] - m) : 0.f;
+    C[o] = c;
+    X[o] = alpha > 0.0 ? (float)((double)c / alpha) : 0.f;
+  }
+}
+
+// part [workgroup] = sum_ij X_ij C_ij over the workgroup's 4 rows: a wave per row in index order, the waves in order
+__global__ __launch_bounds__(256) void nn_fd_trace_kernel(const float* __restrict__ X, const float* __restrict__ C, int n,
+                                                          int ld, double* __restrict__ part) {
+  __shared__ double red[4];
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  double s = 0.0;
+  if (row < n)
+    for (int j = lane; j < n; j += 64) s += (double)X[(size_t)row * ld + j] * (double)C[(size_t)row * ld + j];
+  s = nn_block_sum(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// out [0] = sum_i norm_i / (n - 1): the trace of the covariance of n rows centred by their own mean
+__global__ __launch_bounds__(256) void nn_fd_tr_kernel(const float* __restrict__ norm, int n, double* __restrict__ out) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)norm[i];
+  s = nn_block_sum(s, red);
+  if (threadIdx.x == 0) out[0] = s / (double)(n - 1);
+}
+
+// out = {fd, mean2, tr_a, tr_b, nuc, tail, alpha, iters}. tprev, tlast: nn_fd_trace's parts of the last two iterates.
+// mpart [mblocks][Kp]: nn_mean_part's sums of F_B's rows, d = their mean; norm_b [n] = |F_B i|^2; tra: tr S_A. Without
+// them (the probe on a bare C) the three terms are 0
+__global__ __launch_bounds__(256) void nn_fd_final_kernel(const double* __restrict__ tprev, const double* __restrict__ tlast,
+                                                          int nparts, const double* __restrict__ al,
+                                                          const double* __restrict__ mpart, int mblocks, int Kp,
+                                                          const float* __restrict__ norm_b, const double* __restrict__ tra,
+                                                          int n, int iters, double* __restrict__ out) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  double v0 = 0.0, v1 = 0.0, m2 = 0.0, sb = 0.0;
+  for (int p = tid; p < nparts; p += 256) v0 += tprev[p], v1 += tlast[p];
+  if (mpart)
+    for (int k = tid; k < Kp; k += 256) {
+      double s = 0.0;
+      for (int b = 0; b < mblocks; ++b) s += mpart[(size_t)b * Kp + k];
+      s /= (double)n;
+      m2 += s * s;
+    }
+  if (norm_b)
+    for (int i = tid; i < n; i += 256) sb += (double)norm_b[i];
+  v0 = nn_block_sum(v0, red), v1 = nn_block_sum(v1, red), m2 = nn_block_sum(m2, red), sb = nn_block_sum(sb, red);
+  if (tid == 0) {
+    const double alpha = al[0], nuc = v1;
+    const double tr_a = tra ? tra[0] : 0.0, tr_b = norm_b ? (sb - (double)n * m2) / (double)(n - 1) : 0.0;
+    out[0] = m2 + tr_a + tr_b - 2.0 * nuc;
+    out[1] = m2, out[2] = tr_a, out[3] = tr_b;
+    out[4] = nuc;
+    out[5] = v1 - v0;
+    out[6] = alpha;
+    out[7] = (double)iters;
+  }
+}
+
 static inline bool nn_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline bool nn_shape_ok(int M, int K) { return M >= 1 && M <= NN_MAX_ROWS && K >= 1 && K <= NN_MAX_K; }
 // the operands and the chunking of one distance GEMM
@@ -851,5 +1200,92 @@ extern "C" int dcg_nn_mmd_final(const double* part, int pairs, const double* saa
       pairs != nn_mmd_pairs(Mx, My, skip_aa))
     return -2;
   hipLaunchKernelGGL(nn_mmd_final_kernel, dim3(1), dim3(256), 0, st, part, pairs, saa, skip_aa ? 1 : 0, Mx, My, bw, out);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- Frechet distance: launchers
+static inline bool nn_fd_ok(int n) { return n >= 2 && n <= NN_FD_MAX_ROWS; }
+
+template <int FR, bool SYM>
+static int nn_fd_nt_launch(const float* A, const float* B, float* out, int M, int Kp, int ld, float scale, hipStream_t st) {
+  constexpr int TILE = 32 * FR;
+  constexpr size_t bytes = (size_t)4 * TILE * NN_PITCH * sizeof(float);
+  static bool attr = false;
+  const hipError_t e = nn_big_lds(nn_fd_nt_kernel<FR, SYM>, bytes, &attr);
+  if (e != hipSuccess) return (int)e;
+  const int T = (M + TILE - 1) / TILE;
+  hipLaunchKernelGGL((nn_fd_nt_kernel<FR, SYM>), SYM ? dim3(T * (T + 1) / 2) : dim3(T, T), dim3(256), bytes, st, A, B, out, M,
+                     Kp, ld, scale);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_fd_gram(const float* FA, const float* FB, float* C, int n, int Kp, hipStream_t st) {
+  if (!FA || !FB || !C || !nn_fd_ok(n) || Kp < 16 || Kp > NN_MAX_K || Kp % 16 || !nn_al16(FA) || !nn_al16(FB) || !nn_al16(C))
+    return -2;
+  const float scale = 1.f / (float)(n - 1);
+  return nn_fd_tile(n) == 64 ? nn_fd_nt_launch<2, false>(FA, FB, C, n, Kp, nn_fd_ld(n), scale, st)
+                             : nn_fd_nt_launch<4, false>(FA, FB, C, n, Kp, nn_fd_ld(n), scale, st);
+}
+
+extern "C" int dcg_nn_fd_scale(float* C, int n, int center, double* rmean, double* rabs, double* cpart, double* al, float* X,
+                               hipStream_t st) {
+  if (!C || !rmean || !rabs || !cpart || !al || !X || !nn_fd_ok(n) || !nn_al16(C) || !nn_al16(X)) return -2;
+  const int ld = nn_fd_ld(n), blocks = (n + NN_MEAN_ROWS - 1) / NN_MEAN_ROWS;
+  hipLaunchKernelGGL(nn_fd_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, st, (const float*)C, n, ld, center ? 1 : 0, rmean, rabs);
+  hipLaunchKernelGGL(nn_fd_cols_kernel, dim3((n + 255) / 256, blocks), dim3(256), 0, st, (const float*)C, n, ld,
+                     (const double*)rmean, cpart);
+  hipLaunchKernelGGL(nn_fd_alpha_kernel, dim3(1), dim3(256), 0, st, (const double*)rabs, (const double*)cpart, n, blocks, al);
+  hipLaunchKernelGGL(nn_fd_x0_kernel, dim3(n), dim3(256), 0, st, C, n, ld, (const double*)rmean, (const double*)al, X);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_fd_ppt(const float* X, float* P, int n, hipStream_t st) {
+  if (!X || !P || X == P || !nn_fd_ok(n) || !nn_al16(X) || !nn_al16(P)) return -2;
+  const int ld = nn_fd_ld(n);
+  return nn_fd_tile(n) == 64 ? nn_fd_nt_launch<2, true>(X, X, P, n, ld, ld, 1.f, st)
+                             : nn_fd_nt_launch<4, true>(X, X, P, n, ld, ld, 1.f, st);
+}
+
+template <int FR>
+static int nn_fd_step_launch(const float* P, const float* X, float* Xn, int n, hipStream_t st) {
+  constexpr int TILE = 32 * FR;
+  constexpr size_t bytes = (size_t)2 * (TILE * NN_PITCH + NN_BK * (TILE + 4)) * sizeof(float);
+  static bool attr = false;
+  const hipError_t e = nn_big_lds(nn_fd_step_kernel<FR>, bytes, &attr);
+  if (e != hipSuccess) return (int)e;
+  const int T = (n + TILE - 1) / TILE;
+  hipLaunchKernelGGL((nn_fd_step_kernel<FR>), dim3(T, T), dim3(256), bytes, st, P, X, Xn, n, nn_fd_ld(n));
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_fd_step(const float* P, const float* X, float* Xn, int n, hipStream_t st) {
+  if (!P || !X || !Xn || X == Xn || P == Xn || !nn_fd_ok(n) || !nn_al16(P) || !nn_al16(X) || !nn_al16(Xn)) return -2;
+  return nn_fd_tile(n) == 64 ? nn_fd_step_launch<2>(P, X, Xn, n, st) : nn_fd_step_launch<4>(P, X, Xn, n, st);
+}
+
+extern "C" int dcg_nn_fd_trace(const float* X, const float* C, int n, double* part, hipStream_t st) {
+  if (!X || !C || !part || !nn_fd_ok(n)) return -2;
+  hipLaunchKernelGGL(nn_fd_trace_kernel, dim3(nn_fd_parts(n)), dim3(256), 0, st, X, C, n, nn_fd_ld(n), part);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_fd_tr(const float* norm, int n, double* out, hipStream_t st) {
+  if (!norm || !out || !nn_fd_ok(n)) return -2;
+  hipLaunchKernelGGL(nn_fd_tr_kernel, dim3(1), dim3(256), 0, st, norm, n, out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_fd_mean(const float* FB, int n, int Kp, double* mpart, hipStream_t st) {
+  if (!FB || !mpart || !nn_fd_ok(n) || Kp < 1 || Kp > NN_MAX_K) return -2;
+  hipLaunchKernelGGL(nn_mean_part_kernel, dim3((Kp + 255) / 256, (n + NN_MEAN_ROWS - 1) / NN_MEAN_ROWS), dim3(256), 0, st, FB, n,
+                     Kp, mpart);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dcg_nn_fd_final(const double* tprev, const double* tlast, const double* al, const double* mpart, int Kp,
+                               const float* norm_b, const double* tra, int n, int iters, double* out, hipStream_t st) {
+  if (!tprev || !tlast || !al || !out || !nn_fd_ok(n) || iters < 1 || iters > NN_FD_MAX_ITERS || (mpart && Kp < 1)) return -2;
+  hipLaunchKernelGGL(nn_fd_final_kernel, dim3(1), dim3(256), 0, st, tprev, tlast, nn_fd_parts(n), al, mpart,
+                     (n + NN_MEAN_ROWS - 1) / NN_MEAN_ROWS, Kp, norm_b, tra, n, iters, out);
   return (int)hipGetLastError();
 }

@@ -159,11 +159,12 @@ class ReferenceEngine:
                      max_rows=max_rows)
 
     def nn_metric(self, real: torch.Tensor, z: torch.Tensor, size: Optional[int] = None, ema: Optional[bool] = None,
-                  refresh: bool = False, k: int = 0, mmd: bool = False) -> dict:
+                  refresh: bool = False, k: int = 0, mmd: bool = False, fd: int = 0) -> dict:
         """The 1-NN two-sample test between `real` and the samples of z at pyramid level `size`: the oracle
         (ops.reference.nn_two_sample on nn_features) in fp32 on this engine's device. k > 0 adds the k-NN manifold
-        estimates (ops.reference.nn_prdc), mmd the kernel MMD (ops.reference.nn_mmd)."""
-        k, mmd = R.check_nn_k(k, z.shape[0], least=0), R.check_nn_mmd(mmd, z.shape[0])
+        estimates (ops.reference.nn_prdc), mmd the kernel MMD (ops.reference.nn_mmd), fd > 0 the Frechet distance from fd
+        steps of the polar iteration (ops.reference.nn_frechet)."""
+        k, mmd, fd = R.check_nn_k(k, z.shape[0], least=0), R.check_nn_mmd(mmd, z.shape[0]), R.check_nn_fd(fd, z.shape[0])
         B = self.batch_size
         with torch.no_grad():
             fake = torch.cat([self.sampler(z[i:i + B], ema=ema).float() for i in range(0, z.shape[0], B)])
@@ -174,6 +175,8 @@ class ReferenceEngine:
             out.update(R.nn_prdc_report(R.nn_prdc(A, Bf, k)))
         if mmd:
             out.update(R.nn_mmd_report(R.nn_mmd(A, Bf)))
+        if fd:
+            out.update(R.nn_fd_report(R.nn_frechet(A, Bf, fd)))
         return out
 
     def eval_losses(self, real: torch.Tensor, z: torch.Tensor) -> Dict[str, float]:

@@ -188,23 +188,26 @@ class HipEngineAux:
 
     # ------------------------------------------------------------------ 1-NN two-sample test
     def nn_metric(self, real: Optional[torch.Tensor], z: torch.Tensor, size: Optional[int] = None,
-                  ema: Optional[bool] = None, refresh: bool = False, k: int = 0, mmd: bool = False) -> dict:
+                  ema: Optional[bool] = None, refresh: bool = False, k: int = 0, mmd: bool = False, fd: int = 0) -> dict:
         """The leave-one-out 1-NN two-sample test between `real` [n, S, S, C] and the n samples of z in the pixels
         of pyramid level `size` (None or 0: the images), and the nearest-real distances (nn.hip; ops.hip.NnMetric):
         {"acc", "acc_real", "acc_fake", "dist_fr", "dist_rr", "nearest"}, `nearest` the index of every fake's
         nearest real image. Programs of their own, recorded on first use: nothing of the training step is
         touched. The fakes come from ``sampler(z, ema=ema)`` in chunks of the batch size. The real side (features,
         mean and its own leave-one-out search) is computed on the first call and kept: later calls do not read
-        `real` (None is fine) unless refresh is set or the set's size, `size`, k or mmd changed. k > 0 adds the k-NN
+        `real` (None is fine) unless refresh is set or the set's size, `size`, k, mmd or fd changed. k > 0 adds the k-NN
         manifold estimates "precision", "recall", "density", "coverage" and "k" (ops.hip.NnMetric.prdc); mmd adds the
-        kernel MMD's "mmd2", "k_rr", "k_ff", "k_rf" and "h" (ops.hip.NnMetric.mmd)."""
+        kernel MMD's "mmd2", "k_rr", "k_ff", "k_rf" and "h" (ops.hip.NnMetric.mmd); fd > 0 adds the Frechet distance's
+        "fd", "fd_mean2", "fd_tr", "fd_nuc" and "fd_tail" from fd steps of the polar iteration (ops.hip.NnMetric.frechet)."""
         n, B = int(z.shape[0]), self.B
-        key = (n, R.check_nn(n, size, self.cfg.output_size), R.check_nn_k(k, n, least=0), R.check_nn_mmd(mmd, n))
+        key = (n, R.check_nn(n, size, self.cfg.output_size), R.check_nn_k(k, n, least=0), R.check_nn_mmd(mmd, n),
+               R.check_nn_fd(fd, n))
         nn = getattr(self, "_nn", None)
         if nn is None or self._nn_key != key or refresh:
             if real is None or int(real.shape[0]) != n:
                 raise ValueError("nn_metric: the first evaluation needs the n = %d real images" % n)
-            nn = H.NnMetric(n, self.cfg.output_size, self.cfg.c_dim, key[1], device=self.device, k=key[2], mmd=key[3])
+            nn = H.NnMetric(n, self.cfg.output_size, self.cfg.c_dim, key[1], device=self.device, k=key[2], mmd=key[3],
+                            fd=key[4])
             nn.set_real(real.to(self.device, torch.float32))
             self._nn, self._nn_key = nn, key
         z = z.to(self.device, torch.float32)
@@ -217,6 +220,8 @@ class HipEngineAux:
             out.update(R.nn_prdc_report(nn.prdc()))
         if key[3]:
             out.update(R.nn_mmd_report(nn.mmd()))
+        if key[4]:
+            out.update(R.nn_fd_report(nn.frechet()))
         return out
 
     def placement(self) -> List[str]:

@@ -1501,6 +1501,57 @@ class _NnMmd:
         prog.nn_mmd_final("nn.mmd_final." + tag, _p(self.part), pairs, _p(saa), skip, Mx, My, _p(bw), _p(out), 0)
 
 
+class _NnFd:
+    """The recorded ops of the Frechet distance's last term on C float32 [n, nn_fd_ld(n)] (nn.hip): the scale (with
+    `center` the row means are taken out first), `iters` steps X <- 1.5 X - 0.5 (X X^T) X between two X buffers, the
+    traces of the last two iterates and the finalize into out float64 [8]. y = (_, FB, norm_b) and tra float64 [1] give
+    the other three terms; without them out holds the nuclear norm of C alone."""
+
+    def __init__(self, prog, tag, C, n, iters, out, center=False, y=None, tra=None):
+        from . import reference as R
+        e = ext()
+        if (e.NN_FD_MAX_ROWS, e.NN_FD_MAX_ITERS) != (R.NN_FD_MAX_ROWS, R.NN_FD_MAX_ITERS):  # (nn.h and the oracle: one pair)
+            raise RuntimeError("nn_fd: the extension's limits %r differ from ops.reference's" % ((e.NN_FD_MAX_ROWS, e.NN_FD_MAX_ITERS),))
+        new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=C.device)  # noqa: E731
+        self.X, self.P = [new(n, e.nn_fd_ld(n)), new(n, e.nn_fd_ld(n))], new(n, e.nn_fd_ld(n))
+        self.al, self.t = new(2, dt=torch.float64), new(2, e.nn_fd_parts(n), dt=torch.float64)
+        prog.nn_fd_scale("nn.fd_scale." + tag, _p(C), n, int(bool(center)), _p(self.al), _p(self.X[0]), 0)
+        for k in range(iters):
+            cur, nxt = self.X[k & 1], self.X[(k + 1) & 1]
+            prog.nn_fd_ppt("nn.fd_ppt.%s.%d" % (tag, k), _p(cur), _p(self.P), n, 0)
+            prog.nn_fd_step("nn.fd_step.%s.%d" % (tag, k), _p(self.P), _p(cur), _p(nxt), n, 0)
+        for q, k in enumerate((iters - 1, iters)):  # X_k lies in buffer k & 1
+            prog.nn_fd_trace("nn.fd_trace.%s.%d" % (tag, q), _p(self.X[k & 1]), _p(C), n, _p(self.t[q]), 0)
+        FB, nB = (y[1], y[2]) if y is not None else (None, None)
+        self.mpart = None if FB is None else new(-(-n // e.NN_MEAN_ROWS), FB.shape[1], dt=torch.float64)  # F_B's column sums per 64 rows
+        if FB is not None:
+            prog.nn_fd_mean("nn.fd_mean." + tag, _p(FB), n, FB.shape[1], _p(self.mpart), 0)
+        prog.nn_fd_final("nn.fd_final." + tag, _p(self.t[0]), _p(self.t[1]), _p(self.al), _p(self.mpart),
+                         0 if FB is None else FB.shape[1], _p(nB), _p(tra), n, iters, _p(out), 0)
+
+
+def nn_polar_nuclear(C: torch.Tensor, iters: int, out=None):
+    """(nuc, tail, alpha) of the square float32 matrix C on the device: the sum of its singular values from `iters`
+    steps of the Newton-Schulz polar iteration on MFMA GEMMs, the last step's gain, and the scale (oracle:
+    ops.reference.nn_polar_nuclear). out: float64 [8] to write (nuc, tail, alpha in slots 4..6)."""
+    from . import reference as R
+    if C.dtype != torch.float32 or C.dim() != 2 or C.shape[0] != C.shape[1]:
+        raise TypeError("nn_polar_nuclear: C must be a square float32 matrix, got %s %s" % (C.dtype, tuple(C.shape)))
+    n = C.shape[0]
+    if R.check_nn_fd(iters, n, ("iters", "n")) < 1:
+        raise ValueError("nn_polar_nuclear: iters must be at least 1")
+    res = out if out is not None else torch.empty(8, dtype=torch.float64, device=C.device)
+    if res.dtype != torch.float64 or res.shape != (8,):
+        raise TypeError("nn_polar_nuclear: out must be float64 [8]")
+    Cp = torch.zeros(n, ext().nn_fd_ld(n), dtype=torch.float32, device=C.device)
+    Cp[:, :n].copy_(C)
+    prog = ext().Program()
+    keep = _NnFd(prog, "c", Cp, n, int(iters), res)
+    run(prog)
+    del keep
+    return tuple(res[4:7].tolist())
+
+
 def _nn_side(prog, tag, x0: torch.Tensor, mu, compute_mu: bool):
     """Record nn_features of the rows x0 [M, K]: (x0, F [M, Kp], norm [M])."""
     M, K = x0.shape
@@ -1640,15 +1691,21 @@ class NnMetric:
 
     mmd adds the kernel MMD (``mmd``; oracle: ops.reference.nn_mmd). ``set_real`` computes the bandwidth and the
     (A, A) sum from the triangle over the reals alone; every call runs the triangle over [A; B] without its (A, A)
-    pairs. With k = 0 and mmd off the recorded ops and buffers are those of the 1-NN test alone."""
+    pairs.
 
-    def __init__(self, n: int, S: int, C: int, size: Optional[int] = None, device="cuda", k: int = 0, mmd: bool = False):
+    fd > 0 adds the Frechet distance with fd steps of the polar iteration (``frechet``; oracle:
+    ops.reference.nn_frechet). ``set_real`` keeps tr S_A; every call takes the cross-Gram of the two feature matrices
+    and iterates on it. With k = 0, mmd off and fd = 0 the recorded ops and buffers are those of the 1-NN test alone."""
+
+    def __init__(self, n: int, S: int, C: int, size: Optional[int] = None, device="cuda", k: int = 0, mmd: bool = False,
+                 fd: int = 0):
         from . import reference as R
         if not 1 <= int(C) <= 4:
             raise ValueError("nn_two_sample: at most 4 channels, got %d" % C)
         self.size = size = R.check_nn(n, size, S)
         self.k = k = R.check_nn_k(k, n, least=0)
         self.has_mmd = R.check_nn_mmd(mmd, n)
+        self.fd = fd = R.check_nn_fd(fd, n)
         self.n, self.K = n, size * size * C
         new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=device)  # noqa: E731
         self.xa, self.x = new(n, S, S, C), new(n, S, S, C)  # the real set; the set under evaluation
@@ -1680,6 +1737,12 @@ class NnMetric:
             self.prog_real.nn_mmd_bw("nn.mmd_bw.a", _p(a[2]), n, _p(self.bw), 0)
             self._keep += [_NnMmd(self.prog_real, "aa", a, None, self.bw, self.mmd_real),
                            _NnMmd(self.prog_fake, "ab", a, b, self.bw, self.mmd_out, True, self.mmd_real[:1])]
+        if fd:  # fd_tra = tr S_A stays from set_real on; fd_c is the cross-Gram, centred in place by the scale
+            self.fd_tra, self.fd_out = new(1, dt=torch.float64), new(8, dt=torch.float64)
+            self.fd_c = new(n, ext().nn_fd_ld(n))
+            self.prog_real.nn_fd_tr("nn.fd_tr.a", _p(a[2]), n, _p(self.fd_tra), 0)
+            self.prog_fake.nn_fd_gram("nn.fd_gram.ab", _p(a[1]), _p(b[1]), _p(self.fd_c), n, a[1].shape[1], 0)
+            self._keep.append(_NnFd(self.prog_fake, "ab", self.fd_c, n, fd, self.fd_out, True, b, self.fd_tra))
         self.has_real = False
 
     def _first_of_k(self, rows: slice, j: torch.Tensor, d: torch.Tensor) -> None:
@@ -1710,6 +1773,14 @@ class NnMetric:
             raise RuntimeError("nn_mmd: the metric was built with mmd off")
         o = self.mmd_out.tolist()
         return R.NnMmd(o[7], o[3], o[4], o[5], o[6])
+
+    def frechet(self):
+        """ops.reference.NnFd of the last evaluated set (fd > 0): one copy of the device's eight doubles."""
+        from . import reference as R
+        if not self.fd:
+            raise RuntimeError("nn_frechet: the metric was built with fd = 0")
+        o = self.fd_out.tolist()
+        return R.NnFd(*o[:7], int(o[7]))
 
     def __call__(self, x: Optional[torch.Tensor] = None):
         """ops.reference.NnResult of x -- None: of what the caller wrote into ``self.x`` -- against the real set. The
@@ -1748,6 +1819,21 @@ def nn_mmd(A: torch.Tensor, B: torch.Tensor, size: Optional[int] = None):
     m.set_real(A)
     m(B)
     return m.mmd()
+
+
+def nn_frechet(A: torch.Tensor, B: torch.Tensor, size: Optional[int] = None, iters: int = 40):
+    """The Frechet distance of the image set B (fake) against A (real), float32 [n, S, S, C] on the device, between
+    the Gaussians fitted to the pixels of pyramid level `size` (None: S), with `iters` steps of the polar iteration:
+    an ops.reference.NnFd."""
+    n, S, _, C = _f32_images("nn_frechet", A).shape
+    if _f32_images("nn_frechet", B).shape != A.shape:
+        raise ValueError("nn_frechet: A and B must share a shape")
+    if int(iters) < 1:
+        raise ValueError("nn_frechet: iters must be at least 1, got %r" % (iters,))
+    m = NnMetric(n, S, C, size, device=A.device, fd=iters)
+    m.set_real(A)
+    m(B)
+    return m.frechet()
 
 
 def nn_two_sample(A: torch.Tensor, B: torch.Tensor, size: Optional[int] = None):

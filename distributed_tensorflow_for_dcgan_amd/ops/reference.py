@@ -1644,3 +1644,78 @@ def nn_mmd(FA: torch.Tensor, FB: torch.Tensor) -> NnMmd:
 def nn_mmd_report(m: NnMmd) -> dict:
     """What the engines' nn_metric adds to nn_report with mmd on."""
     return {"mmd2": m.mmd2, "k_rr": m.k_rr, "k_ff": m.k_ff, "k_rf": m.k_rf, "h": m.h}
+
+
+# The Frechet distance between the Gaussians fitted to the two sets in the same feature rows (Heusel et al. 2017 take
+# Inception features; the distance is defined for any). With n <= K samples the last term has an exact dual (Mathiasen &
+# Hvilshoj 2020): tr (S_A S_B)^(1/2) = ||C||_*, C = Xc Yc^T / (n - 1) [n, n], the sum of C's singular values, and
+# ||C||_* = tr(U^T C) for the polar factor U of C, which the Newton-Schulz iteration reaches by matrix products alone.
+NN_FD_ITERS = 40        # growth of the smallest singular value by 1.5 per step: enough for sigma_min / alpha >= 1e-5
+NN_FD_MAX_ITERS = 256
+NN_FD_MAX_ROWS = 8192   # the dual's matrices are [n, n]
+
+
+class NnFd(NamedTuple):
+    fd: float     # mean2 + tr_a + tr_b - 2 nuc
+    mean2: float  # |mu_A - mu_B|^2
+    tr_a: float   # tr S_A, the real set's covariance (1 / (n - 1))
+    tr_b: float   # tr S_B
+    nuc: float    # ||C||_* = tr (S_A S_B)^(1/2)
+    tail: float   # the last step's gain in nuc: >= 0 in exact arithmetic, and small once the iteration count was enough;
+                  # converged in fp32 it is rounding noise of either sign (0: exact svdvals)
+    alpha: float  # the iteration's scale >= sigma_max(C) (0: exact svdvals)
+    iters: int    # steps of the polar iteration (0: exact svdvals)
+
+
+def check_nn_fd(iters, n: int, names=("fd", "n")) -> int:
+    """Validated iteration count of the Frechet distance: 0 = off, else 1..256 with 2 <= n <= 8192."""
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= NN_FD_MAX_ITERS:
+        raise ValueError("%s must be an integer in [0, %d], got %r" % (names[0], NN_FD_MAX_ITERS, iters))
+    if iters and not 2 <= int(n) <= NN_FD_MAX_ROWS:
+        raise ValueError("%s needs %s to be in [2, %d], got %d" % (names[0], names[1], NN_FD_MAX_ROWS, int(n)))
+    return iters
+
+
+def check_nn_fd_flags(on, iters, n: int, names=("--nn_fd", "--nn_fd_iters", "--nn_images")) -> int:
+    """The `fd` of nn_metric from the switch and the iteration count: `on` a boolean, 1 <= iters <= 256 whether on or
+    off, and 2 <= n <= 8192 when on. Returns iters, or 0 when off."""
+    if not isinstance(on, (bool, int)) or int(on) not in (0, 1):
+        raise ValueError("%s must be a boolean, got %r" % (names[0], on))
+    if check_nn_fd(iters, n if on else 2, names[1:]) < 1:
+        raise ValueError("%s must be at least 1, got %r" % (names[1], iters))
+    return iters if on else 0
+
+
+def nn_polar_nuclear(C: torch.Tensor, iters: int):
+    """(nuc, tail, alpha): alpha = sqrt(max row sum * max column sum of |C|) >= sigma_max, X_0 = C / alpha,
+    X <- 1.5 X - 0.5 X X^T X `iters` times, v_k = sum X_k C = alpha * sum X_k X_0; nuc = v_iters rises to ||C||_*, tail = v_iters -
+    v_(iters - 1). In C's dtype."""
+    if C.dim() != 2 or C.shape[0] != C.shape[1] or not 1 <= int(iters) <= NN_FD_MAX_ITERS:
+        raise ValueError("nn_polar_nuclear: C [n, n] and 1 <= iters <= %d, got %s and %r" % (NN_FD_MAX_ITERS, tuple(C.shape), iters))
+    alpha = float((C.abs().sum(1).max() * C.abs().sum(0).max()).sqrt())
+    X = C / alpha if alpha > 0 else torch.zeros_like(C)
+    prev = 0.0
+    for _ in range(int(iters)):
+        prev, X = float((X * C).sum()), 1.5 * X - 0.5 * (X @ X.T) @ X
+    nuc = float((X * C).sum())
+    return nuc, nuc - prev, alpha
+
+
+def nn_frechet(FA: torch.Tensor, FB: torch.Tensor, iters: int = 0) -> NnFd:
+    """The Frechet distance between the feature rows FA (real) and FB (fake), both [n, K], through the dual form.
+    iters = 0: ||C||_* from torch.linalg.svdvals; else from nn_polar_nuclear."""
+    if FA.shape != FB.shape or FA.dim() != 2 or FA.shape[0] < 2:
+        raise ValueError("nn_frechet: A and B must share a shape [n, K] with n >= 2, got %s and %s"
+                         % (tuple(FA.shape), tuple(FB.shape)))
+    n = FA.shape[0]
+    Xc, Yc = FA - FA.mean(0, keepdim=True), FB - FB.mean(0, keepdim=True)
+    C = Xc @ Yc.T / (n - 1)
+    mean2 = float(((FA.mean(0) - FB.mean(0)) ** 2).sum())
+    tr_a, tr_b = float((Xc ** 2).sum()) / (n - 1), float((Yc ** 2).sum()) / (n - 1)
+    nuc, tail, alpha = nn_polar_nuclear(C, iters) if iters else (float(torch.linalg.svdvals(C).sum()), 0.0, 0.0)
+    return NnFd(mean2 + tr_a + tr_b - 2.0 * nuc, mean2, tr_a, tr_b, nuc, tail, alpha, int(iters))
+
+
+def nn_fd_report(f: NnFd) -> dict:
+    """What the engines' nn_metric adds to nn_report with fd > 0."""
+    return {"fd": f.fd, "fd_mean2": f.mean2, "fd_tr": f.tr_a + f.tr_b, "fd_nuc": f.nuc, "fd_tail": f.tail}

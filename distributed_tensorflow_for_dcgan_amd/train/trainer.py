@@ -537,9 +537,10 @@ def _nn(engine, flags, state, source, cfg, device, step, out, writer) -> None:
     try:
         nn_k = R.check_nn_k(flags.nn_k, n, ("--nn_k", "--nn_images"), least=0)
         nn_mmd = R.check_nn_mmd(flags.nn_mmd, n, ("--nn_mmd", "--nn_images"))
+        nn_fd = R.check_nn_fd_flags(flags.nn_fd, int(flags.nn_fd_iters), n)
     except ValueError as e:
         raise SystemExit(str(e))
-    r = engine.nn_metric(real, state["nn_z"], size, ema=ema, k=nn_k, mmd=nn_mmd)
+    r = engine.nn_metric(real, state["nn_z"], size, ema=ema, k=nn_k, mmd=nn_mmd, fd=nn_fd)
     print("[NN] step %d  1nn: %.3f (real %.3f  fake %.3f)  fake->real %.4f  real->real %.4f"
           % (step, r["acc"], r["acc_real"], r["acc_fake"], r["dist_fr"], r["dist_rr"]), file=out, flush=True)
     prdc = ("precision", "recall", "density", "coverage") if nn_k else ()
@@ -549,10 +550,14 @@ def _nn(engine, flags, state, source, cfg, device, step, out, writer) -> None:
     if nn_mmd:
         print("[MMD] step %d  mmd2 %.5f  k_rr %.4f  k_ff %.4f  k_rf %.4f  h %.1f"
               % (step, r["mmd2"], r["k_rr"], r["k_ff"], r["k_rf"], r["h"]), file=out, flush=True)
+    fd = ("fd", "fd_mean2", "fd_tr", "fd_tail") if nn_fd else ()
+    if nn_fd:
+        print("[FD] step %d  fd %.4f  mean2 %.4f  tr %.4f  nuc %.4f  tail %.2e"
+              % (step, r["fd"], r["fd_mean2"], r["fd_tr"], r["fd_nuc"], r["fd_tail"]), file=out, flush=True)
     if writer is not None:
         writer.add_summary_values([SummaryWriter.scalar("nn/" + k, r[v]) for k, v in (
             ("acc", "acc"), ("acc_real", "acc_real"), ("acc_fake", "acc_fake"), ("dist_fake_real", "dist_fr"),
-            ("dist_real_real", "dist_rr")) + tuple((m, m) for m in prdc + mmd)], step)
+            ("dist_real_real", "dist_rr")) + tuple((m, m) for m in prdc + mmd + fd)], step)
     if g > 0:
         g = min(g, n)
         z, B, fake = state["nn_z"], int(getattr(engine, "B", 0) or engine.batch_size), []

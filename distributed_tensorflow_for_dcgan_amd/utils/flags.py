@@ -164,6 +164,12 @@ EXTRA_FLAGS: List[Tuple[str, str, Any, str]] = [
                               "same features (a mixture of 5 Gaussians whose bandwidths follow the real set's mean "
                               "squared distance h), with the mean kernel values it is made of. Smooth in the samples: "
                               "it has no steps of 1 / --nn_images. 0 = the sets agree; it may come out slightly negative"),
+    ("nn_fd", "bool", False, "with --nn_every: also print the Frechet distance between the Gaussians fitted to the two sets "
+                             "in the same features, |mu_r - mu_f|^2 + tr S_r + tr S_f - 2 tr (S_r S_f)^(1/2), with its parts. "
+                             "Needs no pretrained network; 0 = the sets' first two moments agree"),
+    ("nn_fd_iters", "int", 40, "steps of the polar iteration behind --nn_fd's last term, 1..256. In exact arithmetic the "
+                               "distance is approached from above; the printed tail is the last step's gain and tells "
+                               "whether this was enough (converged in fp32: rounding noise of either sign)"),
     ("swd_max_rows", "int", 32768, "largest --swd_images * --swd_patches accepted: a power of two in [32768, 2^21]. "
                                    "Above 32768 the HIP engine sorts with its global merge sort and holds two "
                                    "float32 [512, N] buffers per pyramid level plus two key buffers (34.6 GiB at "
@@ -262,13 +268,15 @@ def parse_flags(argv: Optional[Sequence[str]] = None,
         parser.error(str(e))
     if int(ns.nn_every) < 0 or int(ns.nn_grid) < 0:
         parser.error("--nn_every and --nn_grid must be >= 0, got %r and %r" % (ns.nn_every, ns.nn_grid))
-    if int(ns.nn_every) > 0 or any(a.split("=")[0] in ("--nn_images", "--nn_size", "--nn_grid", "--nn_k", "--nn_mmd")
+    if int(ns.nn_every) > 0 or any(a.split("=")[0] in ("--nn_images", "--nn_size", "--nn_grid", "--nn_k", "--nn_mmd", "--nn_fd",
+                                                           "--nn_fd_iters")
                                    for a in argv):
-        from ..ops.reference import check_nn, check_nn_k, check_nn_mmd
+        from ..ops.reference import check_nn, check_nn_fd_flags, check_nn_k, check_nn_mmd
         try:
             check_nn(ns.nn_images, ns.nn_size, ns.output_size, ("--nn_images", "--nn_size", "--output_size"))
             check_nn_k(ns.nn_k, ns.nn_images, ("--nn_k", "--nn_images"), least=0)
             check_nn_mmd(ns.nn_mmd, ns.nn_images, ("--nn_mmd", "--nn_images"))
+            check_nn_fd_flags(ns.nn_fd, ns.nn_fd_iters, ns.nn_images)
         except ValueError as e:
             parser.error(str(e))
         if int(ns.nn_grid) > int(ns.nn_images):
